@@ -1,6 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the pyratslam hot path on MI355X (BASELINE.json metric).
 
+A plain run sets up, warms up and times the headline steps only, and prints
+``value`` with its ``config`` and ``roofline``; every leg from
+``library_sharded`` down, and the default-path and PCIe-inclusive rates of the
+headline, run with ``--full``.  ``--dump-outputs DIR`` writes the (index, score)
+arrays the last timed step returned as DIR/index.npy and DIR/score.npy.
+
 One JSON line on rank 0:
   value        template compares/s of the whole job (all ranks).  A step is one
                ``rs_vt_match_stream`` call over `--batches-per-step` distinct
@@ -23,7 +29,7 @@ One JSON line on rank 0:
   cpu_baseline the oracle (C/OpenMP restatement of the reference) on this
                host's cores, bounded sample, rank 0 at N=1.
 
-Usage: python bench.py [--gpus N --steps K --warmup W].  N > 1 launches its own
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  N > 1 launches its own
 N rank processes (pyratslam_amd.launch) unless a launcher such as
 torch.distributed.run already set RANK / WORLD_SIZE; the control plane is
 pyratslam_amd.dist (TCP, no PyTorch), the data path RCCL.
@@ -89,6 +95,13 @@ def parse():
     ap.add_argument('--cpu-seconds', type=float, default=6.0, help='CPU baseline budget per leg')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--traffic-json', default=os.path.join(ROOT, 'profiles', 'pmc_traffic.json'))
+    ap.add_argument('--full', action='store_true',
+                    help='also run every other leg (default-path and PCIe-inclusive rates, '
+                         'configs[2..4], pose cells, replay, CPU baselines); without it only the '
+                         'headline template-matching steps are set up, warmed up and timed')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (index.npy, score.npy, '
+                         'float64, shaped (batches, queries)) into DIR')
     return ap.parse_args()
 
 
@@ -112,11 +125,13 @@ def _sharded_library(args, d, T):
                                                 device=d.dev, capacity=T), 'host-tcp-min')
 
 
-def bench_templates(args, d, per_gpu=None, total=None, steps=None, warmup=None, bps=None):
+def bench_templates(args, d, per_gpu=None, total=None, steps=None, warmup=None, bps=None, full=True):
     """Frozen-library template matching.  ``per_gpu`` templates on every rank
     (weak scaling), or a fixed library of ``total`` sharded over the ranks
     (strong scaling).  A step = one rs_vt_match_stream call over ``bps``
-    distinct HBM-resident batches of ``args.queries`` queries."""
+    distinct HBM-resident batches of ``args.queries`` queries.  ``full`` adds the
+    default-path and PCIe-inclusive rates after the timed steps.  ``last_outputs``
+    of the result holds the (index, score) arrays the last timed step returned."""
     import ctypes
 
     from pyratslam_amd import _lib, synthetic
@@ -227,6 +242,48 @@ def bench_templates(args, d, per_gpu=None, total=None, steps=None, warmup=None, 
     t1 = time.perf_counter()
     d.barrier()
     dt = d.max(t1 - t0)
+    # what the last timed step handed its caller (--dump-outputs)
+    if pipeline == 'stream':
+        last_outputs = results[-1][0] if results else None
+    else:
+        last_outputs = (idx.copy(), score.copy()) if steps > 0 else None
+    kernel_ms = [m for m in kernel_ms if m is not None and m >= 0]
+    compares = float(total) * Q
+    res = {
+        'value': compares * steps * bpc / dt,
+        'ms_per_step': 1e3 * dt / steps,
+        'batches_per_step': bpc,
+        'timed_batches': steps * bpc,
+        'timed_region_s': dt,
+        'scan_ms': float(np.mean(kernel_ms)) if kernel_ms else float('nan'),
+        'scan_ms_min': float(np.min(kernel_ms)) if kernel_ms else float('nan'),
+        'kernel': SCAN_KERNELS.get(vts.scan_form(), vts.scan_form()),
+        'compares_per_launch': float(len(range(d.rank, total, n))) * Q * bpc,
+        'queries_per_launch': Q * bpc,
+        'templates_per_launch': len(range(d.rank, total, n)),
+        'reduce': reduce_kind,
+        'pipeline': pipeline,
+        'templates_total': total,
+        'last_outputs': last_outputs,
+    }
+
+    def known_answers(correct):
+        """the indices the steps so far returned against their queries' sources"""
+        for (sidx, _), c in results:
+            for b in range(bpc):
+                s_ = srcs[c * bpc + b]
+                correct = correct and bool(np.all(sidx[b][s_ >= 0] == s_[s_ >= 0]))
+        return correct
+
+    if not full:
+        # a plain run ends here: no further launches, only the host-side look at what
+        # the timed steps already returned
+        if pipeline == 'stream':
+            correct = known_answers(correct)
+            bufs.close()
+        res['hits_correct'] = correct
+        vts.close()
+        return res
     # The same K steps again on the library's default path (scan timing off): the call
     # polls its keys in pinned host memory and the scan's last block exports them, with
     # no HIP events around the scan -- what a caller of match_stream gets.  Reported
@@ -243,14 +300,9 @@ def bench_templates(args, d, per_gpu=None, total=None, steps=None, warmup=None, 
     d.barrier()
     dt_default = d.max(u1 - u0)
     if pipeline == 'stream':
-        for (sidx, _), c in results:
-            for b in range(bpc):
-                s_ = srcs[c * bpc + b]
-                correct = correct and bool(np.all(sidx[b][s_ >= 0] == s_[s_ >= 0]))
+        correct = known_answers(correct)
         bufs.close()
         match(staged=False)                  # stage one batch again for the PCIe-inclusive rate
-    kernel_ms = [m for m in kernel_ms if m is not None and m >= 0]
-    compares = float(total) * Q
     # PCIe-inclusive rates (queries uploaded from host memory), not the value: the
     # stream call over a step's batches from a pageable host array (uploaded in groups
     # behind the scan, rs_vt_match_stream), and one batch per rs_vt_match_batch call
@@ -277,27 +329,13 @@ def bench_templates(args, d, per_gpu=None, total=None, steps=None, warmup=None, 
     p1 = time.perf_counter()
     d.barrier()
     dtp = d.max(p1 - p0)
-    res = {
-        'value': compares * steps * bpc / dt,
-        'ms_per_step': 1e3 * dt / steps,
+    res.update({
         'default_path_value': compares * steps * bpc / dt_default,
         'default_path_ms_per_step': 1e3 * dt_default / steps,
-        'batches_per_step': bpc,
-        'timed_batches': steps * bpc,
-        'timed_region_s': dt,
         'pcie_inclusive_value': pcie_stream if pcie_stream is not None else compares * npcie / dtp,
         'pcie_inclusive_per_batch_value': compares * npcie / dtp,
-        'scan_ms': float(np.mean(kernel_ms)) if kernel_ms else float('nan'),
-        'scan_ms_min': float(np.min(kernel_ms)) if kernel_ms else float('nan'),
-        'kernel': SCAN_KERNELS.get(vts.scan_form(), vts.scan_form()),
-        'compares_per_launch': float(len(range(d.rank, total, n))) * Q * bpc,
-        'queries_per_launch': Q * bpc,
-        'templates_per_launch': len(range(d.rank, total, n)),
-        'reduce': reduce_kind,
-        'pipeline': pipeline,
         'hits_correct': correct,
-        'templates_total': total,
-    }
+    })
     vts.close()
     return res
 
@@ -705,51 +743,9 @@ def bench_replay(args, d):
                     '(the node publishes after every step); synthetic stand-in for dataset_10Hz.bag'}
 
 
-def main():
-    args = parse()
-    if args.gpus > 1 and not launch.under_launcher():
-        # our own N ranks, started before this process touches the GPU
-        sys.exit(launch.spawn(args.gpus, [os.path.abspath(__file__)] + sys.argv[1:]))
-    d = Dist(args.gpus)
-    # the GPU of this rank; --same-device puts every rank on GPU 0 (a test aid for
-    # 1-GPU boxes: RCCL refuses two ranks on one GPU, so the host reducer is used)
-    d.dev = 0 if args.same_device else d.local
-    tv = bench_templates(args, d, per_gpu=args.templates_per_gpu)
-    lib100 = None
-    if args.library_total > 0:
-        lib100 = bench_templates(args, d, total=args.library_total, steps=args.library_steps,
-                                 warmup=1, bps=2)
-    pc = bench_posecells(args, d)
-    pc['node_step'] = bench_node_step(args, d)
-    pc['other_grids'] = bench_other_grids(args, d)
-    pcs, st = None, None
-    if not args.no_pc_stress:
-        pcs = bench_posecell_stress(args, d)
-        if args.stress_templates > 0:
-            st = bench_templates(args, d, per_gpu=args.stress_templates, steps=4, warmup=1, bps=5)
-    rp = None if args.no_replay else bench_replay(args, d)
-    if d.rank != 0:
-        d.close()
-        return
-    tj = _traffic()
-    roof = scan_roofline(tv, tj, 'headline')
-    tj_pc = tj.get('pose_cell', {})
-    for leg in (pc, pcs):
-        if leg and leg['step_form'] in tj_pc:
-            rec = tj_pc[leg['step_form']]
-            if rec.get('shape') in (None, leg['shape']):
-                leg['roofline']['traffic'] = rec.get('hbm_bytes_per_step')
-                leg['roofline']['traffic_kernels'] = rec.get('kernels')
-                # the profiles' per-kernel trace medians, with the record they come from
-                # and whether their sum exceeds the wall time per step beside them (a
-                # profiled run's kernels need not be the timed steps' kernels)
-                kus = rec.get('kernel_us_rocprof')
-                if kus:
-                    leg['kernel_us_per_step_rocprof'] = kus
-                    leg['kernel_us_rocprof_source'] = rec.get('kernel_us_source')
-                    leg['kernel_us_rocprof_exceeds_wall'] = sum(kus.values()) > leg['us_per_step']
-                    leg['roofline']['kernels'] = pc_kernel_rooflines(leg['shape'], kus, rec)
-    out = {
+def headline_fields(args, d, tv, tj):
+    """The result line's fields of the headline leg (all a plain run prints)."""
+    return {
         'metric': METRIC,
         'value': tv['value'],
         'unit': 'compares/s',
@@ -774,11 +770,80 @@ def main():
             'timed_batches': tv['timed_batches'],
             'timed_region_s': tv['timed_region_s'],
             'template_shape': [64, 32],
-            'pose_cell_grid': pc['shape'],
+            'pose_cell_grid': [int(s) for s in args.pc_shape.split(',')],
             'parallelism': 'library sharded over %d GPU(s), %s; pose cells replicated'
                            % (d.world, tv['reduce']),
         },
-        'roofline': roof,
+        'roofline': scan_roofline(tv, tj, 'headline'),
+        'known_answer_hits_correct': tv['hits_correct'],
+    }
+
+
+def dump_outputs(path, last_outputs):
+    """--dump-outputs: the (index, score) arrays of the last timed step, each
+    (batches, queries), as float64 (template indices and scores are integers far
+    below 2^53, so the conversion is exact)."""
+    if last_outputs is None:
+        raise SystemExit('--dump-outputs needs at least one timed step')
+    os.makedirs(path, exist_ok=True)
+    for name, a in zip(('index', 'score'), last_outputs):
+        np.save(os.path.join(path, name + '.npy'), np.asarray(a).astype(np.float64))
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and not launch.under_launcher():
+        # our own N ranks, started before this process touches the GPU
+        sys.exit(launch.spawn(args.gpus, [os.path.abspath(__file__)] + sys.argv[1:]))
+    d = Dist(args.gpus)
+    # the GPU of this rank; --same-device puts every rank on GPU 0 (a test aid for
+    # 1-GPU boxes: RCCL refuses two ranks on one GPU, so the host reducer is used)
+    d.dev = 0 if args.same_device else d.local
+    tv = bench_templates(args, d, per_gpu=args.templates_per_gpu, full=args.full)
+    last_outputs = tv.pop('last_outputs')
+    if args.dump_outputs and d.rank == 0:
+        dump_outputs(args.dump_outputs, last_outputs)
+    if not args.full:
+        # a plain run: the headline leg alone (every other leg is behind --full)
+        if d.rank == 0:
+            print(json.dumps(headline_fields(args, d, tv, _traffic())), flush=True)
+        d.close()
+        return
+    lib100 = None
+    if args.library_total > 0:
+        lib100 = bench_templates(args, d, total=args.library_total, steps=args.library_steps,
+                                 warmup=1, bps=2)
+    pc = bench_posecells(args, d)
+    pc['node_step'] = bench_node_step(args, d)
+    pc['other_grids'] = bench_other_grids(args, d)
+    pcs, st = None, None
+    if not args.no_pc_stress:
+        pcs = bench_posecell_stress(args, d)
+        if args.stress_templates > 0:
+            st = bench_templates(args, d, per_gpu=args.stress_templates, steps=4, warmup=1, bps=5)
+    rp = None if args.no_replay else bench_replay(args, d)
+    if d.rank != 0:
+        d.close()
+        return
+    tj = _traffic()
+    tj_pc = tj.get('pose_cell', {})
+    for leg in (pc, pcs):
+        if leg and leg['step_form'] in tj_pc:
+            rec = tj_pc[leg['step_form']]
+            if rec.get('shape') in (None, leg['shape']):
+                leg['roofline']['traffic'] = rec.get('hbm_bytes_per_step')
+                leg['roofline']['traffic_kernels'] = rec.get('kernels')
+                # the profiles' per-kernel trace medians, with the record they come from
+                # and whether their sum exceeds the wall time per step beside them (a
+                # profiled run's kernels need not be the timed steps' kernels)
+                kus = rec.get('kernel_us_rocprof')
+                if kus:
+                    leg['kernel_us_per_step_rocprof'] = kus
+                    leg['kernel_us_rocprof_source'] = rec.get('kernel_us_source')
+                    leg['kernel_us_rocprof_exceeds_wall'] = sum(kus.values()) > leg['us_per_step']
+                    leg['roofline']['kernels'] = pc_kernel_rooflines(leg['shape'], kus, rec)
+    out = headline_fields(args, d, tv, tj)
+    out.update({
         'library_sharded': None if lib100 is None else {
             'workload': 'configs[2]: %d stored 64x32 u8 templates in total, sharded round-robin '
                         'over %d GPU(s), %d-query batches resident in HBM' % (
@@ -812,7 +877,7 @@ def main():
                                                  'rounds 1-4 quoted the per-batch figure, kept below',
                           'pcie_inclusive_per_batch_compares_per_s': tv['pcie_inclusive_per_batch_value'],
                           'known_answer_hits_correct': tv['hits_correct']},
-    }
+    })
     if pcs is not None and st is not None:
         pcs['templates'] = {
             'workload': 'configs[3]: %d stored 64x32 u8 templates per GPU, %d-query batches '

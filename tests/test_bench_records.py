@@ -24,6 +24,26 @@ def test_scan_records_name_the_64x32_instantiation():
         assert core <= rec['valu_insts_per_launch'] <= 1.2 * core, (key, core, rec['valu_insts_per_launch'])
 
 
+def test_plain_run_is_the_default_and_dump_is_float64(monkeypatch, tmp_path):
+    """--full is off unless asked for, and --dump-outputs stores the integer results
+    of the last timed step exactly, as float64."""
+    import sys
+
+    import numpy as np
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 7
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', str(tmp_path / 'o')])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == str(tmp_path / 'o')
+    idx = np.array([[3, 0], [999, 7]], dtype=np.int64)
+    score = np.array([[0, 64 * 32 * 255], [5, 6]], dtype=np.uint64)
+    bench.dump_outputs(args.dump_outputs, (idx, score))
+    for name, a in (('index', idx), ('score', score)):
+        got = np.load(tmp_path / 'o' / (name + '.npy'))
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+
+
 def test_scan_roofline_fraction_is_physical():
     tj = _traffic()
     rec = tj['scans']['headline']

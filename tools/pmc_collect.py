@@ -211,7 +211,7 @@ def main():
         rec['counter_source'] = f'profiles/{a.tag}/{cfg}_counters.csv'
     bench = trace_stats(os.path.join(a.dir, 'bench_trace'))
     if bench:
-        summary['bench_command'] = {'command': 'python bench.py', 'kernels': bench}
+        summary['bench_command'] = {'command': 'python bench.py --full', 'kernels': bench}
     os.makedirs(a.out, exist_ok=True)
     with open(os.path.join(a.out, f'{a.tag}_pmc_summary.json'), 'w') as fh:
         json.dump(summary, fh, indent=1)
@@ -235,7 +235,7 @@ def main():
                 if ws else '-'))
         lines.append('')
     if bench:
-        lines += ['## bench command (`python bench.py`, kernel trace + stats)', '',
+        lines += ['## bench command (`python bench.py --full`, kernel trace + stats)', '',
                   '| kernel | calls | avg us | min us | max us | % time |', '|---|---|---|---|---|---|']
         for k, t in sorted(bench.items(), key=lambda kv: -kv[1]['pct']):
             lines.append('| %s | %d | %.2f | %.2f | %.2f | %.1f |' % (

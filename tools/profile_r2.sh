@@ -25,7 +25,7 @@ SQ="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU
 for c in "${configs[@]}"; do
   if [ "$c" = bench ]; then
     timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/bench_trace" -o run \
-        -- python bench.py > "$out/bench.json" 2> "$out/bench.err" || { echo "bench trace failed: $?"; exit 1; }
+        -- python bench.py --full > "$out/bench.json" 2> "$out/bench.err" || { echo "bench trace failed: $?"; exit 1; }
     continue
   fi
   args=${CMD[$c]}
