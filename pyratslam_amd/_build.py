@@ -18,7 +18,10 @@ SOURCES = ['rs_common.cpp', 'posecell.hip', 'view_templates.hip']
 # The pose-cell stencils keep scalar FMAs: SLP packing into v_pk_fma_f32 pairs the
 # filter taps into register pairs and doubles the VGPRs of the conv_xy passes
 # (pc_fused_rows 90 -> 220, pc_path_rows<128> 85 -> 146), halving occupancy.
-EXTRA = {'view_templates.hip': ['-mllvm', '-amdgpu-atomic-optimizer-strategy=None'],
+# The plane scan is scheduled for ILP: its query-plane reads, issued a row ahead, then
+# land a few planes into the row before instead of next to their use.
+EXTRA = {'view_templates.hip': ['-mllvm', '-amdgpu-atomic-optimizer-strategy=None',
+                                '-mllvm', '-amdgpu-sched-strategy=max-ilp'],
          # pc_step_halo's first 9 arguments (the union image's addresses, the partial sums) preloaded
          # into scalar registers (posecell.hip, before pc_step_halo)
          'posecell.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-kernarg-preload-count=9']}

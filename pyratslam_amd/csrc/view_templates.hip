@@ -508,47 +508,120 @@ struct PlaneRange {
     static constexpr int JLO = ja(SA), JHI = jb(SB), NUH = JHI - JLO + 1;
 };
 
+// The walk over a wave's start rows [SA, SB] goes one residue class of S mod 4 at
+// a time: a start row S meets offsets o = 4J - S only, so one class touches 3 or 4
+// of the 2M-1 offsets ({-4,0,4}, {-5,-1,3,7}, {-6,-2,2,6}, {-7,-3,1,5} at M = 8)
+// and only that many counters are live at once (ascending S kept all 2M-1 live for
+// the whole query).  A class's counts are flushed into the LDS partial sums when
+// the class ends, packed as u16 pairs taken within the class.  Offset index
+// x = o + M - 1 belongs to class (M-1-x) mod 4, where it is counter x / 4.
+constexpr int PL_NO = 2 * FAST_M - 1;
+constexpr int PL_NA = (PL_NO + 3) / 4;   // counters of the largest class
+constexpr int pl_class(int x) { return ((FAST_M - 1 - x) % 4 + 4) % 4; }
+constexpr int pl_class_n(int rho) {      // offsets of class rho
+    const int base = ((FAST_M - 1 - rho) % 4 + 4) % 4;
+    return base < PL_NO ? (PL_NO - 1 - base) / 4 + 1 : 0;
+}
+constexpr int pl_class_slot(int rho) {   // first partial-count slot of class rho
+    int s = 0;
+    for (int r = 0; r < rho; ++r) s += (pl_class_n(r) + 1) / 2;
+    return s;
+}
+constexpr int pl_slot(int x) { return pl_class_slot(pl_class(x)) + x / 8; }
+constexpr int pl_half(int x) { return (x / 4) & 1; }
+
+struct QRow {   // the 8 planes of one query unit
+    uint32_t v[8];
+};
+
+template <int H, int HALF>
+struct PlaneWalk {
+    using R = PlaneRange<H, HALF>;
+    static constexpr int NR = R::SB - R::SA + 1;
+    static constexpr int first(int rho) { return R::SA + ((rho - R::SA) % 4 + 4) % 4; }
+    static constexpr int rows(int rho) { return first(rho) <= R::SB ? (R::SB - first(rho)) / 4 + 1 : 0; }
+    static constexpr int row(int i) {   // start row of step i
+        for (int rho = 0; rho < 4; ++rho) {
+            if (i < rows(rho)) return first(rho) + 4 * i;
+            i -= rows(rho);
+        }
+        return -1;
+    }
+    static constexpr bool last(int i) { return i + 1 == NR || (row(i + 1) & 3) != (row(i) & 3); }
+    static constexpr bool units_ok() {
+        for (int s = R::SA; s <= R::SB; ++s) {
+            const int nj = R::jb(s) - R::ja(s) + 1;
+            if (nj < 1 || nj > PL_NA || R::ja(s) < R::JLO || R::jb(s) > R::JHI) return false;
+        }
+        return true;
+    }
+    static_assert(units_ok(), "units per query row");
+    static_assert(rows(0) && rows(1) && rows(2) && rows(3), "every class has a row");
+};
+
 // One query start row S against the template units it meets (o = 4J - S within
 // +-(M-1): 3 or 4 units).  The borrow chains of those units are interleaved
 // plane by plane, so consecutive bitop3s are independent (a single chain would
 // stall on every instruction).  All indices are compile-time.
 template <int H, int HALF, int S>
 __device__ __forceinline__ void plane_row(const uint32_t (&P)[PlaneRange<H, HALF>::NUH][8],
-                                          const uint32_t* q, uint32_t (&acc)[2 * FAST_M - 1]) {
+                                          const QRow& q, uint32_t (&a)[PL_NA]) {
     using R = PlaneRange<H, HALF>;
-    constexpr int M = FAST_M, JA = R::ja(S), JB = R::jb(S), NJ = JB - JA + 1;
-    static_assert(NJ >= 1 && NJ <= 4 && JA >= R::JLO && JB <= R::JHI, "units per query row");
+    constexpr int M = FAST_M, JA = R::ja(S), NJ = R::jb(S) - JA + 1;
     uint32_t b[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) b[j] = __builtin_amdgcn_bitop3_b32(P[JA - R::JLO + j][0], q[0], 0u, 0x8E);
-#pragma unroll
-    for (int k = 1; k < 8; ++k)
+    for (int k = 0; k < 8; ++k)
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
-            b[j] = __builtin_amdgcn_bitop3_b32(P[JA - R::JLO + j][k], q[k], b[j], 0x8E);
+            b[j] = __builtin_amdgcn_bitop3_b32(P[JA - R::JLO + j][k], q.v[k], k ? b[j] : 0u, 0x8E);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         // v_bcnt's own accumulator (asm keeps the compiler from re-associating
         // the counts into half-rate v_add3_u32)
-        uint32_t& a = acc[4 * (JA + j) - S + M - 1];
-        asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(a) : "v"(b[j]), "v"(a));
+        uint32_t& c = a[(4 * (JA + j) - S + M - 1) / 4];
+        asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(c) : "v"(b[j]), "v"(c));
     }
+}
+
+template <int H, int HALF, int S>
+__device__ __forceinline__ QRow plane_read(const uint32_t* sq) {
+    using R = PlaneRange<H, HALF>;
+    const uint4 lo = *reinterpret_cast<const uint4*>(sq + (S - R::S0) * 8);
+    const uint4 hi = *reinterpret_cast<const uint4*>(sq + (S - R::S0) * 8 + 4);
+    return QRow{{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
 }
 
 // Query planes are staged per batch in LDS and read as wave-uniform
 // ds_read_b128 broadcasts into VGPRs: on gfx950 a VALU instruction with an SGPR
 // operand issues at about half the all-VGPR rate (tools/ubench_chain.hip:
 // 0.23 vs 0.36-0.41 wave-instructions per SIMD-cycle), so the chains take both
-// operands from VGPRs.
-template <int H, int HALF, int S>
-__device__ __forceinline__ void plane_rows(const uint32_t (&P)[PlaneRange<H, HALF>::NUH][8],
-                                           const uint32_t* sq, uint32_t (&acc)[2 * FAST_M - 1]) {
-    using R = PlaneRange<H, HALF>;
-    const uint4 lo = *reinterpret_cast<const uint4*>(sq + (S - R::S0) * 8);
-    const uint4 hi = *reinterpret_cast<const uint4*>(sq + (S - R::S0) * 8 + 4);
-    const uint32_t q[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    plane_row<H, HALF, S>(P, q, acc);
-    if constexpr (S < R::SB) plane_rows<H, HALF, S + 1>(P, sq, acc);
+// operands from VGPRs.  Step I of the walk: q holds its row's planes on entry and
+// the next step's on return (after the last step, the first row of the next
+// query, from sqn).  The next row's reads are issued ahead of this row's chains,
+// in the registers the class order freed; the scheduling barrier keeps them from
+// sinking back to their use (built with the max-ILP scheduler, _build.py, they end
+// up a few planes into the row before, when that row's first planes are dead).
+template <int H, int HALF, int I>
+__device__ __forceinline__ void plane_walk(const uint32_t (&P)[PlaneRange<H, HALF>::NUH][8],
+                                           const uint32_t* sq, const uint32_t* sqn, QRow& q,
+                                           uint32_t (&a)[PL_NA], uint32_t (&part)[pl_class_slot(4)][64],
+                                           int lane) {
+    using WK = PlaneWalk<H, HALF>;
+    constexpr int S = WK::row(I);
+    constexpr bool wrap = I + 1 == WK::NR;
+    const QRow qn = plane_read<H, HALF, WK::row(wrap ? 0 : I + 1)>(wrap ? sqn : sq);
+    __builtin_amdgcn_sched_barrier(0);
+    plane_row<H, HALF, S>(P, q, a);
+    if constexpr (WK::last(I)) {
+        constexpr int rho = S & 3, n = pl_class_n(rho);
+#pragma unroll
+        for (int k = 0; k < (n + 1) / 2; ++k)
+            atomicAdd(&part[pl_class_slot(rho) + k][lane], a[2 * k] | (2 * k + 1 < n ? a[2 * k + 1] << 16 : 0u));
+#pragma unroll
+        for (int k = 0; k < PL_NA; ++k) a[k] = 0u;
+    }
+    q = qn;
+    if constexpr (!wrap) plane_walk<H, HALF, I + 1>(P, sq, sqn, q, a, part, lane);
 }
 
 
@@ -570,6 +643,7 @@ struct PlaneLds {
 // flight through this batch's compute.
 constexpr int PL_NK = PlaneLds<64>::NK;   // the same for every H (it depends on max_offset only)
 static_assert(PlaneLds<32>::NK == PL_NK, "partial-count slots independent of H");
+static_assert(pl_class_slot(4) == PL_NK, "the classes' u16 pairs fill the same slots");
 // the staged query planes, sized per template height (a kernel allocates only the
 // instances it names: the H = 32 scan, the ROS node's geometry, does not carry the
 // H = 64 buffers)
@@ -661,15 +735,16 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
                     (__attribute__((address_space(3))) void*)(qnxt + i0), 16, 0, 0);
         }
     }
+    const uint32_t* sq0 = reinterpret_cast<const uint32_t*>(qcur) + cg * NS * 8;
+    QRow q = plane_read<H, HALF, PlaneWalk<H, HALF>::row(0)>(sq0);
 #pragma unroll 1
     for (int b = 0; b < nb; ++b) {
-        uint32_t acc[NO];
+        uint32_t a[PL_NA];
 #pragma unroll
-        for (int o = 0; o < NO; ++o) acc[o] = 0u;
-        plane_rows<H, HALF, R::SA>(P, reinterpret_cast<const uint32_t*>(qcur) + (b * PL_CG + cg) * NS * 8, acc);
-#pragma unroll
-        for (int k = 0; k < NK; ++k)
-            atomicAdd(&part[b][k][lane], acc[2 * k] | (2 * k + 1 < NO ? acc[2 * k + 1] << 16 : 0u));
+        for (int k = 0; k < PL_NA; ++k) a[k] = 0u;
+        // (the last query of the batch reads its own first rows again)
+        plane_walk<H, HALF, 0>(P, sq0 + b * (PL_CG * NS * 8), sq0 + min(b + 1, nb - 1) * (PL_CG * NS * 8), q, a,
+                               part[b], lane);
     }
     // every wave's DMA into qnxt has landed before any wave passes the barrier and
     // reads it (explicit: nothing else guarantees this wait stays in front of it)
@@ -677,14 +752,15 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
     __syncthreads();
     if (wave < nb) {  // wave w finishes query qb + w of the batch
         const int qi = qb + wave;
-        uint32_t best = 0xFFFFFFFFu;
+        uint32_t best = 0xFFFFFFFFu, t[NK];
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
-            const uint32_t t = part[wave][k][lane];
+            t[k] = part[wave][k][lane];
             part[wave][k][lane] = 0u;
-            best = min(best, vt_pl_ts[2 * k][lane] + 256u * (t & 0xFFFFu));
-            if (2 * k + 1 < NO) best = min(best, vt_pl_ts[2 * k + 1][lane] + 256u * (t >> 16));
         }
+#pragma unroll
+        for (int x = 0; x < NO; ++x)   // each count with its own TS(o)
+            best = min(best, vt_pl_ts[x][lane] + 256u * (pl_half(x) ? t[pl_slot(x)] >> 16 : t[pl_slot(x)] & 0xFFFFu));
         emit_score<MATRIX>(out, slot, count, qi, nq, best - qsum[qi], rank, nranks, lane == 0);
     }
     bi = bn;

@@ -8,7 +8,7 @@ name=$1; src=${2:-pyratslam_amd/csrc/view_templates.hip}; shift; shift || true
 mkdir -p tools/ab
 H=/opt/rocm/bin/hipcc
 $H --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Ipyratslam_amd/csrc -x hip \
-   -mllvm -amdgpu-atomic-optimizer-strategy=None "$@" -c "$src" -o tools/ab/$name.vt.o
+   -mllvm -amdgpu-atomic-optimizer-strategy=None -mllvm -amdgpu-sched-strategy=max-ilp "$@" -c "$src" -o tools/ab/$name.vt.o
 $H --offload-arch=gfx950 -shared -fPIC -o tools/ab/$name.so pyratslam_amd/build/rs_common.o \
    pyratslam_amd/build/posecell.o tools/ab/$name.vt.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 echo tools/ab/$name.so

@@ -18,7 +18,7 @@ open('abtmp/%s_vt.hip' % name, 'w').write(s)
 PY
 H=/opt/rocm/bin/hipcc
 $H --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Ipyratslam_amd/csrc -x hip \
-   -mllvm -amdgpu-atomic-optimizer-strategy=None -c abtmp/${name}_vt.hip -o tools/ab/$name.vt.o
+   -mllvm -amdgpu-atomic-optimizer-strategy=None -mllvm -amdgpu-sched-strategy=max-ilp -c abtmp/${name}_vt.hip -o tools/ab/$name.vt.o
 $H --offload-arch=gfx950 -shared -fPIC -o abtmp/$name.so pyratslam_amd/build/rs_common.o \
    pyratslam_amd/build/posecell.o tools/ab/$name.vt.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 echo abtmp/$name.so
