@@ -39,6 +39,14 @@
  *   rs_vt_read      ViewTemplate.template         view_templates.py:11
  *   rs_vt_scores    ViewTemplate.match per pair   view_templates.py:16-28 (uint8, wrapping)
  *   rs_sad_scores   ViewTemplate.match per pair   view_templates.py:16-28 (float32/float64)
+ *   rs_vtf_create   ViewTemplates.__init__ for float frames  view_templates.py:42-57
+ *   rs_vtf_add / rs_vtf_append_staged  templates.append(...)  view_templates.py:68-70
+ *   rs_vtf_read     ViewTemplate.template         view_templates.py:11
+ *   rs_vtf_scores   ViewTemplate.match per pair   view_templates.py:16-28 (float, resident)
+ *   rs_vtf_scan     the match_val list, its min and np.argmin  view_templates.py:65-67,73
+ *                   (the threshold decision of :67 stays with the caller)
+ *   rs_sad_plan_sum np.sum inside ViewTemplate.match  view_templates.py:24 (host, the
+ *                   summation plan the float kernels execute)
  *   rs_vt_set_threshold  the `min(match_val) > match_threshold` rule, view_templates.py:67
  *   rs_vt_set_subsample / rs_vt_match_frames
  *                   input[self.mask].reshape(...) view_templates.py:48-57,64 (on device)
@@ -307,6 +315,59 @@ int rs_vt_set_threshold(rs_vt* h, double threshold);
 #define RS_DT_F64 1
 int rs_sad_scores(int device, int dtype, int H, int W, int max_offset, int64_t nt,
                   const void* templates, int nq, const void* queries, void* scores);
+
+/* ------------------------------------------------------------------------ */
+/* Device-resident float view-template library                               */
+/* ------------------------------------------------------------------------ */
+/* The float arithmetic of rs_sad_scores against a library that stays in HBM: a
+ * camera pipeline whose frames are float32 / float64 (normalised to [0, 1], say)
+ * uploads a template once and each match uploads only its queries.  Scores are
+ * bit-identical to numpy's: the host lowers numpy's pairwise summation of the
+ * (H - 2*max_offset) * W window into a plan (leaves of <= 128 elements with 8
+ * strided accumulator chains, the fixed combine ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)),
+ * the sequential tail, the postfix tree over the leaves) and the scan kernel runs
+ * one chain per lane, combining by cross-lane exchange in the plan's order.
+ * All templates, queries and scores of a handle have its dtype (RS_DT_F32 / F64;
+ * another value: RS_ERR_TYPE); any H > 2*max_offset, W >= 1, 1 <= max_offset <= 16. */
+typedef struct rs_vtf rs_vtf;
+
+/* ViewTemplates.__init__ (view_templates.py:42-57) for float frames: an empty library
+ * of H x W templates on `device`; capacity = initial slots (grows by doubling) */
+int rs_vtf_create(int H, int W, int max_offset, int dtype, int64_t capacity, int device,
+                  rs_vtf** out);
+int rs_vtf_destroy(rs_vtf* h);
+int rs_vtf_count(const rs_vtf* h, int64_t* count);
+/* templates.append(...) (view_templates.py:68-70), unconditionally, n host templates */
+int rs_vtf_add(rs_vtf* h, int n, const void* templates, int64_t* first_index);
+/* ViewTemplate.template (view_templates.py:11): template `index` back to the host */
+int rs_vtf_read(rs_vtf* h, int64_t index, void* out);
+/* ViewTemplate.match per pair (view_templates.py:16-28): nq host queries against
+ * templates [t0, t0+nt), scores[q*nt + t] as rs_vt_scores */
+int rs_vtf_scores(rs_vtf* h, int nq, const void* queries, int64_t t0, int64_t nt, void* scores);
+/* The scan of ViewTemplates.match (view_templates.py:65-67,73) for nq host queries
+ * against the library as it stands (nothing is appended): best_score[i] = the
+ * minimum of query i's match_val list, best_index[i] = np.argmin of it (the first
+ * minimum); +inf / -1 for an empty library.  A score is never NaN (a NaN sum is
+ * never taken, as `diff < mindiff` never takes it): an all-NaN pair scores +inf.
+ * want_inbatch != 0 also fills inbatch[i*nq + j] for j < i with the score of staged
+ * query i against staged query j as the template (not symmetric; entries with
+ * j >= i are +inf), which is what a caller needs to resolve a batch with the
+ * semantics of successive ViewTemplates.match calls.  The queries stay staged on
+ * the device for rs_vtf_append_staged. */
+int rs_vtf_scan(rs_vtf* h, int nq, const void* queries, int want_inbatch, void* best_score,
+                int64_t* best_index, void* inbatch);
+/* templates.append(...) (view_templates.py:68-70) for staged queries which[0..n)
+ * of the last rs_vtf_scan / rs_vtf_scores, in that order, device to device */
+int rs_vtf_append_staged(rs_vtf* h, int n, const int32_t* which, int64_t* first_index);
+/* HIP events around the scan and its argmin reduction (default off), and their time
+ * for the last rs_vtf_scan in ms; -1 when it ran untimed or the library was empty */
+int rs_vtf_set_timing(rs_vtf* h, int enable);
+int rs_vtf_last_ms(rs_vtf* h, double* ms);
+/* np.sum of view_templates.py:24 on the host alone (no handle, no device): the sum
+ * of values[0..n) of dtype RS_DT_F32 / F64 evaluated through the very plan the scan
+ * kernel executes for a window of n elements, lane for lane, in that precision.
+ * Equal to numpy's np.sum bit for bit; checks the summation order without a GPU. */
+int rs_sad_plan_sum(int dtype, int64_t n, const void* values, void* out);
 
 /* Multi-GPU: one process per GPU, library sharded round-robin (template g lives
  * on rank g % nranks at slot g / nranks); per query the local first-argmin keys

@@ -116,6 +116,18 @@ SIGNATURES = {
     'rs_vt_set_threshold': (ctypes.c_int, [_vp, ctypes.c_double]),
     'rs_sad_scores': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp]),
+    'rs_vtf_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int64, ctypes.c_int, ctypes.POINTER(_vp)]),
+    'rs_vtf_destroy': (ctypes.c_int, [_vp]),
+    'rs_vtf_count': (ctypes.c_int, [_vp, _i64p]),
+    'rs_vtf_add': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _i64p]),
+    'rs_vtf_read': (ctypes.c_int, [_vp, ctypes.c_int64, _vp]),
+    'rs_vtf_scores': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int64, _vp]),
+    'rs_vtf_scan': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _i64p, _vp]),
+    'rs_vtf_append_staged': (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i64p]),
+    'rs_vtf_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'rs_vtf_last_ms': (ctypes.c_int, [_vp, _f64p]),
+    'rs_sad_plan_sum': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, _vp]),
     'rs_comm_unique_id': (ctypes.c_int, [_u8p]),
     'rs_vt_attach_comm': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _u8p]),
     'rs_vt_set_shard': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),

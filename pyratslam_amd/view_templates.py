@@ -14,10 +14,17 @@ matches with the exact sequential semantics in one call.
 Frames are ``uint8`` on the ROS path (``ros_simulate.py:100-101``): the library
 then lives on the GPU and a score wraps mod 256 like numpy's uint8 subtraction.
 float32 / float64 frames follow the reference's float semantics instead (a true
-sum of |T - Q| in numpy's summation order, ``rs_sad_scores`` on the GPU): once a
-float frame is matched the library is scored pair-wise per match (a fidelity
-path for float callers, not the throughput path).  The subsampling mask is the
-reference's, with Python-2 integer division (:44-54).
+sum of |T - Q| in numpy's summation order, bit for bit).  When the first frame an
+empty ``ViewTemplates`` sees is a float frame, a float library of that dtype is
+created on the GPU (``rs_vtf_*``, ``csrc/view_templates_float.hip``): templates are
+uploaded once, ``match`` uploads one query and ``match_batch`` one batch, and
+``add`` / ``scores`` / ``match_templates`` take arrays of that dtype
+(``scan_form() == 'sad-resident'``).  Anything that mixes dtypes -- a float frame
+at a library that holds uint8 templates, a float32 frame at a float64 library or
+the reverse, a uint8 frame at a float library -- leaves the device library behind
+and scores the Python template list pair-wise per match (``rs_sad_scores``): that
+mixed state is a fidelity path, not a throughput path.  The subsampling mask is
+the reference's, with Python-2 integer division (:44-54).
 """
 import ctypes
 import threading
@@ -139,7 +146,11 @@ class ViewTemplates:
         self.templates = []
         self.device = int(device)
         self.rank, self.nranks = 0, 1
-        self._float = False      # float frames seen: pair-wise float scoring (module doc)
+        self._float = False      # mixed dtypes seen: pair-wise float scoring (module doc)
+        self._vtf = None         # float-resident library (rs_vtf), its dtype in _fdtype
+        self._fdtype = None
+        self._capacity = int(capacity)
+        self._timing = False
         self._mutex = threading.Lock()
         self._h = None
         self._lib = _lib.require_device()
@@ -157,7 +168,8 @@ class ViewTemplates:
         if getattr(self, '_h', None) is not None and self._h.value:
             st = self._lib.rs_vt_destroy(self._h)   # (reports an error of queued work)
         self._h = None
-        _lib.check(st)
+        sf = self._drop_resident()
+        _lib.check(st or sf)
 
     def __del__(self):
         try:
@@ -199,18 +211,121 @@ class ViewTemplates:
 
     def count(self):
         c = ctypes.c_int64()
-        _lib.check(self._lib.rs_vt_count(self._h, ctypes.byref(c)))
+        if self._vtf is not None:
+            _lib.check(self._lib.rs_vtf_count(self._vtf, ctypes.byref(c)))
+        else:
+            _lib.check(self._lib.rs_vt_count(self._h, ctypes.byref(c)))
         return c.value
 
     def _refuse_float(self, what):
-        # after a float frame the Python template list holds templates the device
-        # library does not (the float path scores pair-wise on the host's list)
-        if self._float:
+        # after a float frame the Python template list holds templates the uint8 device
+        # library does not (they live in the float library, or -- mixed dtypes -- only
+        # in the host's list, scored pair-wise)
+        if self._float or self._vtf is not None:
             raise TypeError('this library has matched float frames: %s works on uint8 '
                             'device libraries only; use match() / match_batch()' % what)
 
+    # -- float-resident library ----------------------------------------------------
+    _resident_ok = True      # (a sharded library keeps the pair-wise float path)
+
+    def _resident_for(self, dtype):
+        """True if arrays of ``dtype`` go through the float-resident library, creating
+        it when this is the first frame of an empty, unsharded ViewTemplates."""
+        if self._float or dtype not in _FLOAT_CODES:
+            return False
+        if self._vtf is not None:
+            return dtype == self._fdtype
+        with self._mutex:
+            if self._vtf is not None:            # another thread's first frame got here first
+                return dtype == self._fdtype
+            if not self._resident_ok or self.nranks != 1 or self.templates:
+                return False
+            h = ctypes.c_void_p()
+            _lib.check(self._lib.rs_vtf_create(self.shape[0], self.shape[1], MAX_OFFSET,
+                                               _FLOAT_CODES[dtype], int(self._capacity), self.device,
+                                               ctypes.byref(h)))
+            if self._timing:
+                _lib.check(self._lib.rs_vtf_set_timing(h, 1))
+            self._vtf, self._fdtype = h, dtype
+        return True
+
+    def _use_resident(self, arrays):
+        # add() / scores() / match_templates(): on a float-resident library always (a wrong
+        # dtype is then a TypeError), and float arrays create one on an empty library
+        return self._vtf is not None or self._resident_for(np.asarray(arrays).dtype)
+
+    def _drop_resident(self):
+        st = 0
+        if getattr(self, '_vtf', None) is not None and self._vtf.value:
+            st = self._lib.rs_vtf_destroy(self._vtf)
+        self._vtf = None
+        return st
+
+    def _check_float(self, t, what):
+        t = np.asarray(t)
+        if t.dtype != self._fdtype:
+            raise TypeError('this library has matched float frames and holds %s templates: '
+                            '%s takes %s arrays, got %s' % (self._fdtype, what, self._fdtype, t.dtype))
+        if t.shape[-2:] != self.shape:
+            raise ValueError('template shape %r != %r' % (t.shape[-2:], self.shape))
+        return np.ascontiguousarray(t.reshape((-1,) + self.shape))
+
+    def _resident_match(self, q, pcs):
+        """``[match(x, *pc) for x, pc in zip(q, pcs)]`` (view_templates.py:63-75) on the
+        float-resident library: one frozen scan of the batch (with the in-batch scores
+        when it holds more than one query), the reference's rule per query on the host
+        -- ``min(match_val) > match_threshold`` on a numpy scalar of the scores' dtype,
+        first argmin -- and one append of the queries that became templates.
+        Returns (index, score, is_new); call with the mutex held."""
+        n = q.shape[0]
+        best = np.empty(n, dtype=self._fdtype)
+        bidx = np.empty(n, dtype=np.int64)
+        inb = np.empty((n, n), dtype=self._fdtype) if n > 1 else None
+        _lib.check(self._lib.rs_vtf_scan(
+            self._vtf, n, ctypes.c_void_p(q.ctypes.data), int(n > 1), ctypes.c_void_p(best.ctypes.data),
+            _lib.ptr(bidx, ctypes.c_int64), None if inb is None else ctypes.c_void_p(inb.ctypes.data)))
+        base = len(self.templates)
+        idx = np.empty(n, dtype=np.int64)
+        score = np.empty(n, dtype=self._fdtype)
+        new = np.zeros(n, dtype=bool)
+        added = []                      # staged queries appended so far, in order
+        for i in range(n):
+            m, arg = best[i], int(bidx[i])      # min / first argmin over the library as scanned
+            if added:
+                s = inb[i, added]               # ... then over the templates this batch appended
+                k = int(np.argmin(s))
+                if arg < 0 or s[k] < m:         # (a tie keeps the earlier, library, index)
+                    m, arg = s[k], base + k
+            score[i] = m
+            if arg < 0 or m > self.match_threshold:
+                idx[i], new[i] = base + len(added), True
+                added.append(i)
+            else:
+                idx[i] = arg
+        if added:
+            first = ctypes.c_int64()
+            which = np.asarray(added, dtype=np.int32)
+            _lib.check(self._lib.rs_vtf_append_staged(self._vtf, len(added), _lib.ptr(which, ctypes.c_int32),
+                                                      ctypes.byref(first)))
+            assert first.value == base, (first.value, base)
+            for k, i in enumerate(added):
+                p = pcs[i]
+                self.templates.append(ViewTemplate(p[0], p[1], p[2], base + k, q[i].copy(), _owner=self))
+        return idx, score, new
+
     def add(self, templates, locations=None):
         """Append templates unconditionally (indices len .. len+n-1)."""
+        if self._use_resident(templates):
+            t = self._check_float(templates, 'add()')
+            first = ctypes.c_int64()
+            with self._mutex:
+                _lib.check(self._lib.rs_vtf_add(self._vtf, t.shape[0], ctypes.c_void_p(t.ctypes.data),
+                                                ctypes.byref(first)))
+                for i in range(t.shape[0]):
+                    loc = locations[i] if locations is not None else (0, 0, 0)
+                    self.templates.append(ViewTemplate(loc[0], loc[1], loc[2], first.value + i, t[i],
+                                                       _owner=self))
+            return first.value
         self._refuse_float('add()')
         t = self._check_templates(templates)
         first = ctypes.c_int64()
@@ -224,7 +339,16 @@ class ViewTemplates:
         return first.value
 
     def scores(self, queries, t0=0, nt=None):
-        """uint64 (nq, nt) scores of queries vs templates [t0, t0+nt) -- ViewTemplate.match."""
+        """(nq, nt) scores of queries vs templates [t0, t0+nt) -- ViewTemplate.match:
+        uint64 on a uint8 library, the library's dtype on a float-resident one."""
+        if self._use_resident(queries):
+            q = self._check_float(queries, 'scores()')
+            nt = self.count() - t0 if nt is None else nt
+            out = np.empty((q.shape[0], nt), dtype=self._fdtype)
+            with self._mutex:
+                _lib.check(self._lib.rs_vtf_scores(self._vtf, q.shape[0], ctypes.c_void_p(q.ctypes.data),
+                                                   int(t0), int(nt), ctypes.c_void_p(out.ctypes.data)))
+            return out
         self._refuse_float('scores()')
         q = self._check_templates(queries)
         nt = self.count() - t0 if nt is None else nt
@@ -245,7 +369,21 @@ class ViewTemplates:
         return [self.templates[int(j)] for j in idx]
 
     def match_templates(self, queries, pcs=None, mode=_lib.RS_VT_SEQUENTIAL):
-        """Match already-subsampled (nq, H, W) queries; returns (index, score, is_new)."""
+        """Match already-subsampled (nq, H, W) queries; returns (index, score, is_new).
+        On a float-resident library the queries and scores have the library's dtype
+        (+inf where the library was empty)."""
+        if self._use_resident(queries):
+            q = self._check_float(queries, 'match_templates()')
+            n = q.shape[0]
+            with self._mutex:
+                if mode == _lib.RS_VT_SEQUENTIAL:
+                    return self._resident_match(q, pcs if pcs is not None else [(0, 0, 0)] * n)
+                score = np.empty(n, dtype=self._fdtype)
+                idx = np.empty(n, dtype=np.int64)
+                _lib.check(self._lib.rs_vtf_scan(self._vtf, n, ctypes.c_void_p(q.ctypes.data), 0,
+                                                 ctypes.c_void_p(score.ctypes.data),
+                                                 _lib.ptr(idx, ctypes.c_int64), None))
+            return idx, score, np.zeros(n, dtype=bool)
         self._refuse_float('match_templates()')
         q = self._check_templates(queries)
         n = q.shape[0]
@@ -292,7 +430,11 @@ class ViewTemplates:
     def match(self, input, pc_x, pc_y, pc_th):
         """Best template for a frame, or a new one (view_templates.py:63-75)."""
         t = self.subsample(input)
-        if t.dtype != np.uint8 or self._float:
+        if self._resident_for(t.dtype):
+            with self._mutex:
+                idx, _, _ = self._resident_match(np.ascontiguousarray(t)[None], [(pc_x, pc_y, pc_th)])
+            return self.templates[int(idx[0])]
+        if t.dtype != np.uint8 or self._float or self._vtf is not None:
             return self._match_float(t, (pc_x, pc_y, pc_th))
         idx, _, _ = self.match_templates(t[None], [(pc_x, pc_y, pc_th)])
         return self.templates[int(idx[0])]
@@ -302,7 +444,11 @@ class ViewTemplates:
         q = [self.subsample(im) for im in images]
         if not q:
             return []
-        if self._float or any(x.dtype != np.uint8 for x in q):
+        if all(x.dtype == q[0].dtype for x in q) and self._resident_for(q[0].dtype):
+            with self._mutex:
+                idx, _, _ = self._resident_match(np.stack(q), pcs)
+            return [self.templates[int(i)] for i in idx]
+        if self._float or self._vtf is not None or any(x.dtype != np.uint8 for x in q):
             return [self._match_float(x, pc) for x, pc in zip(q, pcs)]
         idx, _, _ = self.match_templates(np.stack(q), pcs)
         return [self.templates[int(i)] for i in idx]
@@ -316,6 +462,7 @@ class ViewTemplates:
             raise TypeError('float frames are not supported by a sharded library')
         with self._mutex:
             self._float = True
+            _lib.check(self._drop_resident())   # mixed dtypes: the host's list is the library
             match_val = [None] * len(self.templates)
             groups = {}
             for i, tm in enumerate(self.templates):
@@ -404,16 +551,25 @@ class ViewTemplates:
     def device_ms(self):
         """Scan kernel time (HIP events) of the last match, ms; -1 if it ran untimed."""
         ms = ctypes.c_double()
-        _lib.check(self._lib.rs_vt_last_ms(self._h, ctypes.byref(ms)))
+        if self._vtf is not None:
+            _lib.check(self._lib.rs_vtf_last_ms(self._vtf, ctypes.byref(ms)))
+        else:
+            _lib.check(self._lib.rs_vt_last_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
     def set_timing(self, enable=True):
         """HIP events around every scan (default off; rs_vt_set_timing).  While on, a
         call waits for its keys with a stream synchronisation instead of polling them."""
         _lib.check(self._lib.rs_vt_set_timing(self._h, int(bool(enable))))
+        self._timing = bool(enable)
+        if self._vtf is not None:
+            _lib.check(self._lib.rs_vtf_set_timing(self._vtf, int(self._timing)))
 
     def scan_form(self):
-        """Scan kernel family used for this shape ('plane', 'carry', 'sad', ...)."""
+        """Scan kernel family used for this shape ('plane', 'carry', 'sad', ...);
+        'sad-resident' for a float-resident library."""
+        if self._vtf is not None:
+            return 'sad-resident'
         return self._lib.rs_vt_scan_form(self._h).decode()
 
 
@@ -429,6 +585,7 @@ class ShardedViewTemplates(ViewTemplates):
     Every rank sees all queries and keeps the full ``.templates`` metadata; the
     template bytes of g live only on rank g % n.
     """
+    _resident_ok = False
 
     def __init__(self, x_range, y_range, x_step, y_step, im_x, im_y, match_threshold,
                  rank, nranks, reducer='rccl', unique_id=None, device=0, capacity=1024):
