@@ -295,7 +295,10 @@ int rs_vt_set_timing(rs_vt* h, int enable);
 /* which scan kernel family the handle uses for its shape: "plane" (bit-plane
  * borrow count, W == 32, H in {32, 64}, max_offset 8), "carry" (byte-SWAR carry
  * count, max_offset 8, H in {32, 64}; RS_VT_SCAN=carry forces it) or "generic";
- * NULL for a null handle */
+ * NULL for a null handle.  "carry" names the family, not the launch: a key scan of
+ * little work (fewer than 2,048 template blocks x queries, at most 8 dword columns)
+ * runs its column form, vt_scan_carry_col_kernel; score matrices and every other
+ * key scan run vt_scan_carry_kernel */
 const char* rs_vt_scan_form(const rs_vt* h);
 
 /* ViewTemplates.match's strict threshold (view_templates.py:67) as a double: a
