@@ -51,6 +51,11 @@
  *   rs_vt_set_subsample / rs_vt_match_frames
  *                   input[self.mask].reshape(...) view_templates.py:48-57,64 (on device)
  *   rs_comm_*, rs_vt_attach_comm  (new) RCCL sharding of the library over GPUs
+ *   rs_vo_create    SimpleVisualOdometer()        ros_simulate.py:5, 90 (the imported module
+ *                   is absent from the reference; the arithmetic is defined below)
+ *   rs_vo_run       vis_odom.update(im) per frame ros_simulate.py:119-122, the (vtrans, vrot)
+ *                   deltas the main loop feeds to update_posecells, :163-165
+ *   rs_vo_select    the shift choice inside update(), on the host alone
  */
 #ifndef RATSLAM_ABI_H
 #define RATSLAM_ABI_H
@@ -371,6 +376,58 @@ int rs_vtf_last_ms(rs_vtf* h, double* ms);
  * kernel executes for a window of n elements, lane for lane, in that precision.
  * Equal to numpy's np.sum bit for bit; checks the summation order without a GPU. */
 int rs_sad_plan_sum(int dtype, int64_t n, const void* values, void* out);
+
+/* ------------------------------------------------------------------------ */
+/* Scanline visual odometer                                                  */
+/* ------------------------------------------------------------------------ */
+/* The odometer of the node's camera-only mode (USE_VISUAL_ODOMETRY, ros_simulate.py:81:
+ * no odometry subscription, every frame through vis_odom.update(im), :119-122).  The
+ * reference fixes the interface only; the arithmetic, in exact integers:
+ *   region   rows [y0, y1) x columns [x0, x1) of a mono8 frame, one for `trans`, one for
+ *            `rot`;  R = y1 - y0, Wd = x1 - x0
+ *   profile  prof[c] = sum over the region's rows of frame[y][x0 + c]          (uint32)
+ *   table    against the previous frame's profile of the same region, for signed shifts
+ *            s in [-(S-1), S-1]:  tab[s] = sum |cur[k] - prev[k + s]| over the Wd - |s|
+ *            values of k with both indices valid (uint32, stored at index s + S - 1)
+ *   select   best = +inf, shift = 0; for o = 0 .. S-1, candidates s = -o then s = +o:
+ *            v = (double)tab[s] / (double)((Wd - o) * R * 255), taken if v < best
+ *   deltas   vrot = shift_rot * rad_per_column;
+ *            vtrans = min(best_trans * vtrans_scale, vtrans_max)
+ * S = max_shift in [1, 64], Wd >= S and R * 255 * Wd < 2^32 per region, else RS_ERR_ARG
+ * (checked before any device call).  A positive shift: new[k] == old[k + s].  The first
+ * frame after rs_vo_create / rs_vo_reset returns (0, 0), has an all-zero table and only
+ * stores its profiles; the state carries across calls. */
+typedef struct rs_vo rs_vo;
+
+typedef struct rs_vo_params {
+    int trans_y0, trans_y1, trans_x0, trans_x1;
+    int rot_y0, rot_y1, rot_x0, rot_x1;
+    int max_shift;
+    double rad_per_column;      /* radians(fov_deg) / im_w, computed by the caller */
+    double vtrans_scale;
+    double vtrans_max;
+} rs_vo_params;
+
+int rs_vo_create(int im_h, int im_w, const rs_vo_params* params, int device, rs_vo** out);
+/* synchronises and reports an error of queued work, like rs_vt_destroy */
+int rs_vo_destroy(rs_vo* h);
+/* forget the previous frame: the next one returns (0, 0) */
+int rs_vo_reset(rs_vo* h);
+/* nf frames (im_h * im_w bytes each, back to back; host memory, staged 256 frames at a
+ * time through pinned memory, or device memory read in place) -> deltas[nf*2] =
+ * (vtrans, vrot) per frame.  Optional exports, both regions per frame, trans first:
+ * tables[nf * 2 * (2*max_shift - 1)], profiles[nf * (Wd_trans + Wd_rot)] (NULL: none). */
+int rs_vo_run(rs_vo* h, int nf, const uint8_t* frames, double* deltas, uint32_t* tables,
+              uint32_t* profiles);
+/* the selection rule on the host alone (no handle, no device): table[2*max_shift - 1] of
+ * a region `width` columns by `rows` rows -> the shift and its normalised difference */
+int rs_vo_select(int max_shift, int width, int rows, const uint32_t* table, int* shift,
+                 double* mindiff);
+/* HIP events around the profile and the shift launches (default off); rs_vo_last_ms:
+ * ms[0] = profile kernel, ms[1] = shift kernel of the last rs_vo_run, -1 when it ran
+ * untimed or in several chunks */
+int rs_vo_set_timing(rs_vo* h, int enable);
+int rs_vo_last_ms(rs_vo* h, double ms[2]);
 
 /* Multi-GPU: one process per GPU, library sharded round-robin (template g lives
  * on rank g % nranks at slot g / nranks); per query the local first-argmin keys

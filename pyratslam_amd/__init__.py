@@ -8,5 +8,6 @@ with the reference's API (``/root/reference/ratslam/posecell_network.py``,
 """
 from .posecell_network import PoseCellNetwork  # noqa: F401
 from .view_templates import ShardedViewTemplates, ViewTemplate, ViewTemplates  # noqa: F401
+from .visual_odometer import NumpyVisualOdometer, SimpleVisualOdometer  # noqa: F401
 
 __version__ = '0.1.0'

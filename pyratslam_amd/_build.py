@@ -12,7 +12,8 @@ CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(ROOT, 'include')
 LIB = os.path.join(HERE, 'libratslam_hip.so')
 OBJDIR = os.path.join(HERE, 'build')
-SOURCES = ['rs_common.cpp', 'posecell.hip', 'view_templates.hip', 'view_templates_float.hip']
+SOURCES = ['rs_common.cpp', 'posecell.hip', 'view_templates.hip', 'view_templates_float.hip',
+           'visual_odometer.hip']
 # per-source flags: the plane scan's batch takes are single-lane atomics; the
 # wave-aggregating atomic optimizer only adds a readfirstlane round trip to them.
 # The pose-cell stencils keep scalar FMAs: SLP packing into v_pk_fma_f32 pairs the

@@ -39,6 +39,7 @@ _c_int_p = ctypes.POINTER(ctypes.c_int)
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _i64p = ctypes.POINTER(ctypes.c_int64)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
+_u32p = ctypes.POINTER(ctypes.c_uint32)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _f64p = ctypes.POINTER(ctypes.c_double)
 _vp = ctypes.c_void_p
@@ -54,6 +55,16 @@ class PcParams(ctypes.Structure):
         ('k_scale', ctypes.c_double),
         ('nfilters', ctypes.c_int),
         ('xy_filters', _f64p),
+    ]
+
+
+class VoParams(ctypes.Structure):
+    """``rs_vo_params`` (ratslam_abi.h)."""
+    _fields_ = [(r + '_' + b, ctypes.c_int) for r in ('trans', 'rot') for b in ('y0', 'y1', 'x0', 'x1')] + [
+        ('max_shift', ctypes.c_int),
+        ('rad_per_column', ctypes.c_double),
+        ('vtrans_scale', ctypes.c_double),
+        ('vtrans_max', ctypes.c_double),
     ]
 
 
@@ -128,6 +139,14 @@ SIGNATURES = {
     'rs_vtf_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
     'rs_vtf_last_ms': (ctypes.c_int, [_vp, _f64p]),
     'rs_sad_plan_sum': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, _vp]),
+    'rs_vo_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(VoParams), ctypes.c_int,
+                                    ctypes.POINTER(_vp)]),
+    'rs_vo_destroy': (ctypes.c_int, [_vp]),
+    'rs_vo_reset': (ctypes.c_int, [_vp]),
+    'rs_vo_run': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _f64p, _u32p, _u32p]),
+    'rs_vo_select': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _u32p, _c_int_p, _f64p]),
+    'rs_vo_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'rs_vo_last_ms': (ctypes.c_int, [_vp, _f64p]),
     'rs_comm_unique_id': (ctypes.c_int, [_u8p]),
     'rs_vt_attach_comm': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _u8p]),
     'rs_vt_set_shard': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),

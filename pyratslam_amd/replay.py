@@ -26,8 +26,15 @@ Outputs (the node's published topics): ``pc_max`` per update, ``em_points``
 (``navbot/experiencemap``, :142-146) and ``template_index`` per frame
 (``navbot/templatematches``, :110-113).
 
+``use_visual_odometry=True`` is the node's ``USE_VISUAL_ODOMETRY`` mode (:81, :90,
+:119-122, :163-165): odometry messages are ignored, ``vis_callback`` matches the
+frame at the current peak and then queues ``vo.update(im)``, and that delta is
+applied, undivided and unfiltered, right after its frame.  ``replay_frames`` is the
+same pipeline over an array of frames, batched on the GPU.
+
 ``python -m pyratslam_amd.replay --bag FILE`` replays a bag;
-``--synthetic N`` writes and replays a synthetic one (``synthetic.ros_stream``).
+``--synthetic N`` writes and replays a synthetic one (``synthetic.ros_stream``);
+``--visual-odometry`` replays either from the camera alone.
 """
 import argparse
 import json
@@ -65,7 +72,8 @@ class RatslamReplay:
     def __init__(self, pose_size=POSE_SIZE, im_size=IM_SIZE, x_range=X_RANGE, y_range=Y_RANGE,
                  x_step=X_STEP, y_step=Y_STEP, match_threshold=MATCH_THRESHOLD,
                  odom_freq=ODOM_FREQ, feedback_energy=None, pcn=None, vts=None, em=None,
-                 device=0, precision='float32', batch=True, publish=False):
+                 device=0, precision='float32', batch=True, publish=False,
+                 use_visual_odometry=False, vo=None):
         # publish: the node's per-step work in full -- every update reads the whole
         # .posecells volume, as ros_simulate.py:140-145 does to publish it -- so steps
         # go one by one (no batched run()) and the network exports eagerly
@@ -86,13 +94,24 @@ class RatslamReplay:
         self.batch = batch and hasattr(pcn, 'run') and not publish
         self.published = 0   # .posecells volumes read (publish=True)
         self.twist_data = deque()
+        # USE_VISUAL_ODOMETRY (ros_simulate.py:81, 90): no odometry subscription, every
+        # frame through vo.update(im); vo = any object with update() (NumpyVisualOdometer)
+        self.use_visual_odometry = bool(use_visual_odometry)
+        if self.use_visual_odometry and vo is None:
+            from .visual_odometer import SimpleVisualOdometer
+            vo = SimpleVisualOdometer(device=device)
+        self.vo = vo
+        self.vis_odom_data = deque()
+        self.deltas = []     # the visual deltas, one (vtrans, vrot) per frame
         # ros_simulate.py:56-57 (Python-2 int / 2, then math.floor)
         self.pcn.inject(1, tuple(int(math.floor(s // 2)) for s in pose_size))
         self.pc_max, self.em_points, self.template_index = [], [], []
 
     # -- callbacks ---------------------------------------------------------------
     def odom_callback(self, twist):
-        """ros_simulate.py:125-129."""
+        """ros_simulate.py:125-129 (not subscribed under visual odometry, :81)."""
+        if self.use_visual_odometry:
+            return
         if abs(twist.linear[0]) > 0.001 or abs(twist.angular[2]) > 0.001:
             self.twist_data.append(twist)
 
@@ -103,6 +122,10 @@ class RatslamReplay:
         self.template_index.append(int(template_match.get_index()))
         if self.feedback_energy:
             self.pcn.inject(self.feedback_energy, tuple(template_match.location()))
+        if self.use_visual_odometry:   # ros_simulate.py:119-122
+            delta = self.vo.update(im)
+            self.deltas.append((float(delta[0]), float(delta[1])))
+            self.vis_odom_data.append(delta)
 
     def update_posecells(self, vtrans, vrot):
         """ros_simulate.py:134-146 (publishing reduced to recording; with publish=True
@@ -120,13 +143,17 @@ class RatslamReplay:
         self.em_points.append(tuple(float(v) for v in self.em.get_current_point()))
 
     def drain(self):
-        """The main loop's queue drain (ros_simulate.py:156-162)."""
-        if not self.twist_data:
-            return
+        """The main loop's queue drain (ros_simulate.py:156-166): twists divided by
+        ODOM_FREQ, visual deltas as they are (no 0.001 filter, no division)."""
         steps = []
         while self.twist_data:
             twist = self.twist_data.popleft()
             steps.append((twist.linear[0] / self.odom_freq, twist.angular[2] / self.odom_freq))
+        while self.vis_odom_data:
+            vtrans, vrot = self.vis_odom_data.popleft()
+            steps.append((float(vtrans), float(vrot)))
+        if not steps:
+            return
         if self.batch:
             maxes = self.pcn.run(np.array(steps, dtype=np.float64))
             for (vt, vr), m in zip(steps, maxes):
@@ -144,6 +171,8 @@ class RatslamReplay:
             else:
                 self.drain()
                 self.vis_callback(ev[2])
+                if self.use_visual_odometry:   # a visual delta is applied right after its frame
+                    self.drain()
         self.drain()
         return self
 
@@ -159,7 +188,64 @@ class RatslamReplay:
             else:
                 self.drain()
                 self.vis_callback(rosbag.image_to_mono8(rosbag.decode_image(m.data)))
+                if self.use_visual_odometry:
+                    self.drain()
         self.drain()
+        return self
+
+    def replay_frames(self, frames, batch=64):
+        """The camera-only pipeline (``use_visual_odometry=True``) over a uint8
+        ``(n, im_h, im_w)`` array, batched: each batch is uploaded once into a
+        ``DeviceBuffer``; ``vo.run`` on the buffer gives its deltas, ``pcn.run(deltas)``
+        its peaks, and ``vts.match_frames`` matches frame i at the peak after deltas
+        0..i-1 (the last peak carries over from the batch before).  Without feedback
+        that is exactly the per-frame order -- match at the current peak, then the
+        frame's delta, then the step.  With ``feedback_energy`` (the match changes the
+        state the next step starts from), or with a drop-in ``vo`` / ``vts`` / ``pcn``
+        that has no batched form, the frames go one by one through ``vis_callback``."""
+        if not self.use_visual_odometry:
+            raise ValueError('replay_frames is the camera-only pipeline: construct with '
+                             'use_visual_odometry=True')
+        f = np.asarray(frames)
+        if f.dtype != np.uint8:
+            raise TypeError('replay_frames takes uint8 frames (mono8); got %s' % f.dtype)
+        if f.ndim != 3:
+            raise ValueError('frames must be (n, im_h, im_w), got shape %r' % (f.shape,))
+        from .visual_odometer import SimpleVisualOdometer
+        batched = (not self.feedback_energy and self.batch and batch > 1
+                   and isinstance(self.vo, SimpleVisualOdometer)
+                   and hasattr(self.vts, 'match_frames') and getattr(self.vts, 'nranks', 1) == 1)
+        if not batched:
+            for im in f:
+                self.vis_callback(im)
+                self.drain()
+            return self
+        if f.shape[0] == 0:
+            return self
+        mask = getattr(self.vts, 'mask', None)
+        if mask is not None and f.shape[1:] != mask.shape:
+            raise ValueError('frame shape %r does not match the mask %r' % (f.shape[1:], mask.shape))
+        from . import _lib
+        f = np.ascontiguousarray(f)
+        self.drain()
+        self.vo.setup(f.shape[1:])
+        buf = _lib.DeviceBuffer(int(batch) * f[0].size, device=self.vo.device)
+        try:
+            for i0 in range(0, f.shape[0], int(batch)):
+                chunk = f[i0:i0 + int(batch)]
+                n = chunk.shape[0]
+                buf.upload(chunk)
+                deltas = self.vo.run((n, buf))
+                peak = tuple(int(v) for v in self.pcn.get_pc_max())
+                maxes = self.pcn.run(deltas)
+                pcs = [peak] + [tuple(int(v) for v in m) for m in maxes[:-1]]
+                idx, _, _ = self.vts.match_frames((n, buf), pcs)
+                self.template_index.extend(int(j) for j in idx)
+                for (vt, vr), m in zip(deltas, maxes):
+                    self.deltas.append((float(vt), float(vr)))
+                    self._record(float(vt), float(vr), m)
+        finally:
+            buf.close()
         return self
 
     def results(self):
@@ -197,6 +283,10 @@ def main(argv=None):
     ap.add_argument('--gpus', type=int, default=1,
                     help='ranks (launched here, or by torch.distributed.run): the template '
                          'library is sharded over them, the pose cells are replicated')
+    ap.add_argument('--visual-odometry', action='store_true',
+                    help='camera-only replay (USE_VISUAL_ODOMETRY, ros_simulate.py:81): odometry '
+                         'messages are ignored, every frame goes through SimpleVisualOdometer; '
+                         'each rank runs its own odometer replica')
     ap.add_argument('--host-reduce', action='store_true',
                     help='combine the ranks\' keys on the host (several ranks on one GPU)')
     args = ap.parse_args(argv)
@@ -208,7 +298,8 @@ def main(argv=None):
     d = Dist(args.gpus)
     dev = d.local if args.device is None else args.device
     vts = sharded_templates(d, dev, args.host_reduce) if d.world > 1 else None
-    r = RatslamReplay(device=dev, precision=args.precision, feedback_energy=args.feedback, vts=vts)
+    r = RatslamReplay(device=dev, precision=args.precision, feedback_energy=args.feedback, vts=vts,
+                      use_visual_odometry=args.visual_odometry)
     d.barrier()
     t0 = time.perf_counter()
     if args.bag:
