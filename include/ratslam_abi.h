@@ -305,6 +305,18 @@ int rs_vt_set_timing(rs_vt* h, int enable);
  * runs its column form, vt_scan_carry_col_kernel; score matrices and every other
  * key scan run vt_scan_carry_kernel */
 const char* rs_vt_scan_form(const rs_vt* h);
+/* "plane-pruned": a plane handle (H == 64) whose large frozen key scans prune template
+ * blocks by an exact partial-score bound: a prefilter bounds every
+ * (64-template block, query) pair from below, pass B1 scans each query against its
+ * most promising block, pass B2 against every other block whose bound does not exceed
+ * the score B1 found.  Exact for every input.  RS_VT_PRUNE (read at create): "0"
+ * dense launch everywhere ("plane"), "1" (default) prune scans of at least 512 queries
+ * over at least two template blocks, "force" prune at any size.
+ * rs_vt_prune_stats: of the last pruned scan launch, out[0] = (block, query) pairs of
+ * pass B1 (= queries), out[1] = pairs of pass B2, out[2] = template blocks x queries,
+ * out[3] = scan passes launched; all 0 before the first pruned scan.  Reads the device
+ * counters on demand (synchronises the handle's stream); the match calls do not. */
+int rs_vt_prune_stats(rs_vt* h, int64_t out[4]);
 
 /* ViewTemplates.match's strict threshold (view_templates.py:67) as a double: a
  * score makes a new template when (double)score > threshold -- numpy's own

@@ -124,6 +124,7 @@ SIGNATURES = {
     'rs_vt_last_ms': (ctypes.c_int, [_vp, _f64p]),
     'rs_vt_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
     'rs_vt_scan_form': (ctypes.c_char_p, [_vp]),
+    'rs_vt_prune_stats': (ctypes.c_int, [_vp, _i64p]),
     'rs_vt_set_threshold': (ctypes.c_int, [_vp, ctypes.c_double]),
     'rs_sad_scores': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp]),
@@ -153,6 +154,10 @@ SIGNATURES = {
     'rs_vt_rank': (ctypes.c_int, [_vp, _c_int_p, _c_int_p]),
 }
 
+# statistics calls an older build of the library lacks: tools/stream_ab.py loads such
+# builds by path for an A/B; calling one of these on them raises AttributeError
+NEWER_SYMBOLS = {'rs_vt_prune_stats'}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -173,6 +178,8 @@ def load(path=LIB_PATH):
                 '(there is no CPU fallback)')
         lib = ctypes.CDLL(path)
         for name, (res, args) in SIGNATURES.items():
+            if name in NEWER_SYMBOLS and not hasattr(lib, name):
+                continue
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

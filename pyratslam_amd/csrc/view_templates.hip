@@ -377,6 +377,19 @@ constexpr int PL_CG = 4;       // column groups of 8 bytes: W = 32
 #endif
 constexpr int PL_NB = 4;  // queries per LDS batch (staged planes; one reducing wave each)
 
+// Pruned plane scan (H = 64): the prefilter bounds every score from below by its
+// exact partial sum over PF_NU template units (4 rows x 32 columns each).  A unit J
+// with 4J-(M-1) >= M and 4J+M+2 <= H-M-1 (J in [4, 11]) meets only query rows inside
+// the window at every offset.  One unit (J = 7) or two (J = 5 and 10).
+#ifndef VT_PF_UNITS
+#define VT_PF_UNITS 1
+#endif
+constexpr int PF_NU = VT_PF_UNITS;
+static_assert(PF_NU == 1 || PF_NU == 2, "one or two prefilter units");
+__host__ __device__ constexpr int pf_unit(int u) { return PF_NU == 1 ? 7 : (u == 0 ? 5 : 10); }
+static_assert(4 * pf_unit(0) - (FAST_M - 1) >= FAST_M && 4 * pf_unit(PF_NU - 1) + FAST_M + 2 <= 64 - FAST_M - 1,
+              "the units' query rows lie inside the window at every offset");
+
 // One block per stored template: planes + TS of raw template src[t] into slot dst[t].
 __global__ __launch_bounds__(256) void vt_plane_store_kernel(const uint8_t* __restrict__ raw,
                                                              const int32_t* __restrict__ src,
@@ -450,13 +463,22 @@ __device__ inline void transpose4x4_bytes(uint32_t a, uint32_t b, uint32_t c, ui
 // the segment to QS.  Phase 2: each thread assembles one unit (4 rows from start
 // row S0 + si, column group cg): plane k = byte k of its 4 segments, two 16-byte
 // stores.  Bit b of plane k = bit k of pixel (row + b/8, col 8cg + b%8).
+// With a prune buffer (qsj, H = 64): also QS_J(S), the byte sum of rows S..S+3, for
+// the start rows S = 4J+7-x, x = 0..2M-2, that prefilter unit J meets
+// (qsj[(query * PF_NU + u) * 16 + x]).
 __global__ __launch_bounds__(256) void vt_qplane_kernel(const uint8_t* __restrict__ raw, int H,
                                                         int M, uint32_t* __restrict__ qp,
                                                         uint32_t* __restrict__ qsum,
-                                                        uint8_t* __restrict__ raw_copy) {
+                                                        uint8_t* __restrict__ raw_copy,
+                                                        uint32_t* __restrict__ qsj) {
     constexpr int W = 8 * PL_CG;
     __shared__ uint32_t s_red[4];
     __shared__ uint2 s_t[64 * W / 8];   // transposed segments (H <= 64)
+    __shared__ uint32_t s_rs[64];       // byte sums of the rows (prune buffer only)
+    if (qsj) {   // (kernel argument: uniform)
+        if (threadIdx.x < 64) s_rs[threadIdx.x] = 0u;
+        __syncthreads();
+    }
     const int NS = H - 2 * M + 3, S0 = M - 3;
     const uint8_t* Q = raw + (size_t)blockIdx.x * H * W;
     uint32_t* out = qp + (size_t)blockIdx.x * PL_CG * NS * 8;
@@ -469,6 +491,7 @@ __global__ __launch_bounds__(256) void vt_qplane_kernel(const uint8_t* __restric
         const int r = d / (W / 8);
         const bool live = r >= M && r < H - M;
         if (live) part = __builtin_amdgcn_sad_u8(v.y, 0u, __builtin_amdgcn_sad_u8(v.x, 0u, part));
+        if (qsj) atomicAdd(&s_rs[r], __builtin_amdgcn_sad_u8(v.y, 0u, __builtin_amdgcn_sad_u8(v.x, 0u, 0u)));
         transpose8x8(v.x, v.y);
         s_t[d] = live ? v : make_uint2(0u, 0u);
     }
@@ -484,6 +507,11 @@ __global__ __launch_bounds__(256) void vt_qplane_kernel(const uint8_t* __restric
         uint4* o = reinterpret_cast<uint4*>(out + (size_t)u * 8);
         o[0] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
         o[1] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+    }
+    if (qsj && threadIdx.x < PF_NU * 16) {
+        const int u = threadIdx.x >> 4, x = threadIdx.x & 15;
+        const int S = 4 * pf_unit(u) + M - 1 - min(x, 2 * M - 2);
+        qsj[((size_t)blockIdx.x * PF_NU + u) * 16 + x] = s_rs[S] + s_rs[S + 1] + s_rs[S + 2] + s_rs[S + 3];
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
@@ -693,13 +721,22 @@ __device__ __forceinline__ void plane_load_units(const uint4* __restrict__ plane
 // variable and each DMA the other, and hipcc leaves the DMA in flight through the
 // compute (a runtime choice of buffer made it wait vmcnt(0) before the first read).
 // Returns false once the block has no batch left.
-template <int H, int HALF, bool MATRIX, int CUR>
+// LIST (pruned scan): the block's queries are the nq entries of its list ids[]: a
+// batch is PL_NB consecutive entries, each DMA lane takes its source from its
+// entry's query id, and the finish uses the id.  The ids of the batch being
+// computed (qc) and of the one staged next (qnv, entry lane & 3) are carried from
+// batch to batch: the ids of the batch after next are read right after the barrier.
+struct PlaneIds {
+    int qc[PL_NB];  // query ids of the batch being computed (wave-uniform)
+    int qnv;        // lane: query id of entry (lane & 3) of the batch staged next
+};
+template <int H, int HALF, bool MATRIX, int CUR, bool LIST>
 __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HALF>::NUH][8], int it,
                                             int& bi, int nbatch, int64_t slot, int64_t count,
                                             const uint4* __restrict__ qp4, const uint32_t* __restrict__ qsum,
                                             int nq, unsigned* __restrict__ ctr, int G, int g, ScanOut out,
                                             int rank, int nranks, int wave, int cg, int lane,
-                                            unsigned& failed) {
+                                            unsigned& failed, const int* __restrict__ ids, PlaneIds& pid) {
     using R = PlaneRange<H, HALF>;
     using LD = PlaneLds<H>;
     constexpr int NO = LD::NO, NK = LD::NK, NS = LD::NS, NT = 64 * LD::NW;
@@ -722,17 +759,31 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
     }
     // the next batch's planes go global -> LDS directly (global_load_lds, 1 KiB per
     // wave-instruction, lane-linear), in flight through this batch's compute
+    int qnx[PL_NB] = {0, 0, 0, 0};  // LIST: the next batch's query ids
     if (bn < nbatch) {
         const int qn = (bn * G + g) * PL_NB, nbn = min(PL_NB, nq - qn);
         const int lim = nbn * LD::QW / 4;
         const uint4* src = qp4 + (size_t)qn * (LD::QW / 4);
+        if constexpr (LIST) {
+            static_assert(PL_NB == 4, "four ids per batch");
+#pragma unroll
+            for (int e = 0; e < PL_NB; ++e) qnx[e] = __builtin_amdgcn_readlane(pid.qnv, e);
+        }
 #pragma unroll
         for (int k = 0; k < (LD::QP + NT - 1) / NT; ++k) {
             const int i0 = wave * 64 + k * NT;  // wave-uniform
-            if (i0 < lim)
-                __builtin_amdgcn_global_load_lds(
-                    (__attribute__((address_space(1))) const void*)(src + min(i0 + lane, lim - 1)),
-                    (__attribute__((address_space(3))) void*)(qnxt + i0), 16, 0, 0);
+            if (i0 < lim) {
+                const uint4* from;
+                if constexpr (LIST) {   // a 1 KiB piece may straddle two entries: per-lane source
+                    const int i = min(i0 + lane, lim - 1), e = i / (LD::QW / 4);
+                    const int id = e == 0 ? qnx[0] : e == 1 ? qnx[1] : e == 2 ? qnx[2] : qnx[3];
+                    from = qp4 + (size_t)id * (LD::QW / 4) + (i - e * (LD::QW / 4));
+                } else {
+                    from = src + min(i0 + lane, lim - 1);
+                }
+                __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)from,
+                                                 (__attribute__((address_space(3))) void*)(qnxt + i0), 16, 0, 0);
+            }
         }
     }
     const uint32_t* sq0 = reinterpret_cast<const uint32_t*>(qcur) + cg * NS * 8;
@@ -751,7 +802,8 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     __syncthreads();
     if (wave < nb) {  // wave w finishes query qb + w of the batch
-        const int qi = qb + wave;
+        const int qi = !LIST ? qb + wave
+                             : wave == 0 ? pid.qc[0] : wave == 1 ? pid.qc[1] : wave == 2 ? pid.qc[2] : pid.qc[3];
         uint32_t best = 0xFFFFFFFFu, t[NK];
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
@@ -761,19 +813,25 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
 #pragma unroll
         for (int x = 0; x < NO; ++x)   // each count with its own TS(o)
             best = min(best, vt_pl_ts[x][lane] + 256u * (pl_half(x) ? t[pl_slot(x)] >> 16 : t[pl_slot(x)] & 0xFFFFu));
-        emit_score<MATRIX>(out, slot, count, qi, nq, best - qsum[qi], rank, nranks, lane == 0);
+        emit_score<MATRIX>(out, slot, count, qi, LIST ? qi + 1 : nq, best - qsum[qi], rank, nranks, lane == 0);
+    }
+    if constexpr (LIST) {
+#pragma unroll
+        for (int e = 0; e < PL_NB; ++e) pid.qc[e] = qnx[e];
+        const int b2 = vt_pl_bidx[r2];   // thread 0 wrote it before the barrier
+        pid.qnv = b2 < nbatch ? ids[min((b2 * G + g) * PL_NB + (lane & 3), nq - 1)] : 0;
     }
     bi = bn;
     return true;
 }
 
-template <int H, int HALF, bool MATRIX>
+template <int H, int HALF, bool MATRIX, bool LIST>
 __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes,
                                            int tb, int64_t count, const uint4* __restrict__ qp4,
                                            const uint32_t* __restrict__ qsum, int nq,
                                            unsigned* __restrict__ ctr, int G, int g, ScanOut out,
                                            int rank, int nranks, int wave, int cg, int lane,
-                                           unsigned& failed) {
+                                           unsigned& failed, const int* __restrict__ ids) {
     using R = PlaneRange<H, HALF>;
     uint32_t P[R::NUH][8];
     plane_load_units<H, HALF>(planes, tb, cg, lane, P);
@@ -781,21 +839,29 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes,
     const int nbatch = ((nq + PL_NB - 1) / PL_NB - g + G - 1) / G;
     const int64_t slot = (int64_t)tb * 64 + lane;
     int bi = vt_pl_bidx[0];
+    PlaneIds pid{{0, 0, 0, 0}, 0};
+    if constexpr (LIST) {   // the ids of the first batch (staged by the prologue) and of the second
+        const int b1 = vt_pl_bidx[1];
+        const int v0 = ids[min((bi * G + g) * PL_NB + (lane & 3), nq - 1)];
+        pid.qnv = b1 < nbatch ? ids[min((b1 * G + g) * PL_NB + (lane & 3), nq - 1)] : 0;
+#pragma unroll
+        for (int e = 0; e < PL_NB; ++e) pid.qc[e] = __builtin_amdgcn_readlane(v0, e);
+    }
     // unrolled by two: even iterations compute from qa and stage into qb, odd ones
     // the other way round (the prologue staged the first batch into qa)
     // The first batch is peeled off the loop: hipcc's wait analysis is exact for the
     // LDS accesses after a DMA issued in the same loop iteration but not across the
     // loop header's merge, so the loop body starts with an odd batch, whose compute
     // follows its own DMA issue, not the header.
-    if (!plane_batch<H, HALF, MATRIX, 0>(P, 0, bi, nbatch, slot, count, qp4, qsum, nq, ctr, G, g, out, rank,
-                                         nranks, wave, cg, lane, failed))
+    if (!plane_batch<H, HALF, MATRIX, 0, LIST>(P, 0, bi, nbatch, slot, count, qp4, qsum, nq, ctr, G, g, out, rank,
+                                               nranks, wave, cg, lane, failed, ids, pid))
         return;
     for (int it = 1;; it += 2) {
-        if (!plane_batch<H, HALF, MATRIX, 1>(P, it, bi, nbatch, slot, count, qp4, qsum, nq, ctr, G, g, out,
-                                             rank, nranks, wave, cg, lane, failed))
+        if (!plane_batch<H, HALF, MATRIX, 1, LIST>(P, it, bi, nbatch, slot, count, qp4, qsum, nq, ctr, G, g, out,
+                                                   rank, nranks, wave, cg, lane, failed, ids, pid))
             break;
-        if (!plane_batch<H, HALF, MATRIX, 0>(P, it + 1, bi, nbatch, slot, count, qp4, qsum, nq, ctr, G, g,
-                                             out, rank, nranks, wave, cg, lane, failed))
+        if (!plane_batch<H, HALF, MATRIX, 0, LIST>(P, it + 1, bi, nbatch, slot, count, qp4, qsum, nq, ctr, G, g,
+                                                   out, rank, nranks, wave, cg, lane, failed, ids, pid))
             break;
     }
 }
@@ -803,13 +869,29 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes,
 // nqc blocks serve each template block; they take query batches of PL_NB from
 // the template block's counter, so blocks that the SIMDs' oldest-first issue
 // favours take more batches and no SIMD is left running a lone straggler.
-template <int H, bool MATRIX>
+// LIST (pruned scan, passes B1 and B2): template block tb scans only the queries of
+// its list, pl.ids[tb * pl.ld ..] (pl.cnt[tb] entries, any order); nq is then the
+// list's length.  A block whose list is empty leaves at once, one whose group has
+// no batch after its one failed take (before it loads its template planes).
+// Batches per block of a list-driven pass (headline step, ms: 2 -> 0.525, 3 -> 0.515,
+// 4 -> 0.527, 6 -> 0.567).
+#ifndef VT_LIST_PER
+#define VT_LIST_PER 3
+#endif
+struct PlaneList {
+    const int* ids = nullptr;
+    const unsigned* cnt = nullptr;
+    int ld = 0;
+};
+template <int H, bool MATRIX, bool LIST = false>
 __global__ __launch_bounds__(64 * PL_CG * PL_SPLIT) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __restrict__ tsum,
                           int ntb, int64_t count, const uint32_t* __restrict__ qp,
                           const uint32_t* __restrict__ qsum, int nq, int nqc,
-                          unsigned* __restrict__ next_batch, ScanOut out, int rank, int nranks) {
+                          unsigned* __restrict__ next_batch, ScanOut out, int rank, int nranks,
+                          PlaneList pl) {
     static_assert(PL_SPLIT == 2, "two row ranges");
+    static_assert(!(LIST && MATRIX), "lists feed the key scan only");
     // The nqc blocks of a template block are adjacent block ids, so they are dispatched
     // together and split its query batches dynamically even when the grid runs in
     // several rounds.  XCD-aware: blocks b and b+8 share an XCD (and its L2); with
@@ -818,6 +900,20 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
     const int tb = (int)(blockIdx.x / (unsigned)nqc);
     const int G = nqc >= 8 ? 8 : 1, g = nqc >= 8 ? (int)(blockIdx.x & 7) : 0;
     unsigned* ctr = next_batch + (size_t)tb * 8 + g;
+    const int* ids = nullptr;
+    if constexpr (LIST) {
+        nq = (int)pl.cnt[tb];   // block-uniform
+        if (nq == 0) return;
+        ids = pl.ids + (size_t)tb * pl.ld;
+        // The grid is sized for a list of every query; a shorter list is served by
+        // the first `use` of the template block's nqc blocks, about VT_LIST_PER batches
+        // each, so a block's fixed cost (its template planes, 128 KiB) is not paid per
+        // batch.  The others leave before they touch the batch counter.
+        int use = ((nq + PL_NB - 1) / PL_NB + VT_LIST_PER - 1) / VT_LIST_PER;
+        use = nqc >= 8 ? min(nqc, max(8, (use + 7) & ~7)) : min(nqc, max(1, use));
+        if ((int)(blockIdx.x - (unsigned)tb * (unsigned)nqc) >= use) return;
+        nqc = use;
+    }
     VT_STAMP(0);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63, cg = wave % PL_CG, half = wave / PL_CG;
@@ -845,16 +941,24 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
         constexpr int QW4 = PlaneLds<H>::QW / 4;
         const int qb = (vt_pl_bidx[0] * G + g) * PL_NB, nb = min(PL_NB, nq - qb);
         const uint4* qp4 = reinterpret_cast<const uint4*>(qp);
-        for (int i = threadIdx.x; i < nb * QW4; i += blockDim.x) vt_pl_qa<H>[i] = qp4[(size_t)qb * QW4 + i];
+        for (int i = threadIdx.x; i < nb * QW4; i += blockDim.x) {
+            if constexpr (LIST) {
+                const int e = i / QW4;
+                vt_pl_qa<H>[i] = qp4[(size_t)ids[qb + e] * QW4 + (i - e * QW4)];
+            } else {
+                vt_pl_qa<H>[i] = qp4[(size_t)qb * QW4 + i];
+            }
+        }
     }
     __syncthreads();
     const uint4* qp4 = reinterpret_cast<const uint4*>(qp);
-    if (half == 0)
-        plane_wave<H, 0, MATRIX>(planes, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
-                                 wave, cg, lane, failed);
+    if (LIST && vt_pl_bidx[0] >= nbatch) {   // (block-uniform) no batch for this block
+    } else if (half == 0)
+        plane_wave<H, 0, MATRIX, LIST>(planes, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
+                                       wave, cg, lane, failed, ids);
     else
-        plane_wave<H, 1, MATRIX>(planes, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
-                                 wave, cg, lane, failed);
+        plane_wave<H, 1, MATRIX, LIST>(planes, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
+                                       wave, cg, lane, failed, ids);
     // Each of the nqc / G blocks sharing a counter ends on exactly one failed take, so
     // the block whose failed take returned (group batches) + nqc / G - 1 is the
     // counter's last user in this launch: it rewinds the counter for the next launch
@@ -893,6 +997,225 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
         }
     }
     VT_STAMP(1);
+}
+
+// --- Pruned plane scan (H = 64, keys): partial-distortion elimination.  Every term
+// of a score is >= 0, so the sum over the byte pairs of PF_NU template units,
+//   LB(t, q, o) = sum_J  TS_J(t) - QS_J(q, 4J - o) + 256 * B_J(t, q, o)
+// (TS_J the unit's byte sum, QS_J the byte sum of the four query rows it meets at
+// offset o, B_J their borrow count), is an exact lower bound of score(t, q, o), and
+// minLB[tb][q] = min over the block's templates and the offsets bounds every score of
+// template block tb against q.  Pass B1 scans each query against its candidate block
+// tb* = argmin_tb minLB (lowest on ties) only, which leaves an upper bound U(q) in
+// best[]; pass B2 scans it against every other block with minLB <= U(q) -- "<=": a
+// block that may hold an equal score at a lower index is scanned too.  A block left
+// out has minLB > U(q) >= the minimum, so none of its scores is the minimum.
+constexpr int PF_WAVES = 4;   // waves per thread block
+// Template blocks per wave: every staged query plane is read once (an LDS broadcast)
+// for both, which halves the LDS reads per VALU instruction: at one block per wave,
+// 120 ds_read_b128 against 600 VALU per query, the reads set the pace (167 us against
+// 135 us at the dense scan's VALU rate, headline shape).  Two units of two blocks
+// would not fit the VGPRs.
+#ifndef VT_PF_TPW
+#define VT_PF_TPW (VT_PF_UNITS == 1 ? 2 : 1)
+#endif
+constexpr int PF_TPW = VT_PF_TPW;
+constexpr int PF_NB = 4;      // queries staged per step
+constexpr int PF_QW4 = PF_NU * PL_CG * PL_NO * 2;   // staged uint4 per query
+
+// minlb[tb * nq + q].  Lane = template; the wave keeps the PF_NU units of its PF_TPW
+// template blocks in VGPRs and reads the staged query planes as wave-uniform LDS
+// broadcasts, two column groups at a time (2 * PF_TPW independent borrow chains).
+__global__ __launch_bounds__(64 * PF_WAVES) __attribute__((amdgpu_waves_per_eu(4)))
+void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
+                                                                    int64_t count,
+                                                                    const uint4* __restrict__ qp4,
+                                                                    const uint32_t* __restrict__ qsj, int nq,
+                                                                    uint32_t* __restrict__ minlb) {
+    constexpr int M = FAST_M, NU = 64 / 4, NS = PlaneLds<64>::NS, S0 = M - 3;
+    static_assert(PL_CG % 2 == 0, "column groups in pairs");
+    __shared__ uint4 s_q[PF_NB][PF_NU][PL_CG][PL_NO][2];
+    __shared__ uint32_t s_qs[PF_NB][PF_NU][16];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int tb0 = (blockIdx.x * PF_WAVES + wave) * PF_TPW;
+    const bool live = tb0 < ntb;   // wave-uniform; a wave past the library still stages
+    uint32_t P[PF_TPW][PF_NU][PL_CG][8], ts[PF_TPW][PF_NU];
+    bool valid[PF_TPW];
+#pragma unroll
+    for (int t = 0; t < PF_TPW; ++t) {
+        const int tbc = min(tb0 + t, ntb - 1);
+        valid[t] = tb0 + t < ntb && (int64_t)(tb0 + t) * 64 + lane < count;
+#pragma unroll
+        for (int u = 0; u < PF_NU; ++u) {
+            ts[t][u] = 0u;
+#pragma unroll
+            for (int cg = 0; cg < PL_CG; ++cg) {
+                const uint4* src = planes + ((size_t)(tbc * PL_CG + cg) * NU + pf_unit(u)) * 128 + lane;
+                const uint4 a = src[0], b = src[64];
+                uint32_t(&p)[8] = P[t][u][cg];
+                p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w;
+                p[4] = b.x; p[5] = b.y; p[6] = b.z; p[7] = b.w;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) ts[t][u] += (uint32_t)__builtin_popcount(p[k]) << k;
+            }
+        }
+    }
+    for (int q0 = blockIdx.y * PF_NB; q0 < nq; q0 += gridDim.y * PF_NB) {   // block-uniform
+        const int nb = min(PF_NB, nq - q0);
+        __syncthreads();   // the batch before has been read
+        for (int i = threadIdx.x; i < nb * PF_QW4; i += blockDim.x) {
+            const int qq = i / PF_QW4, r = i - qq * PF_QW4;
+            const int u = r / (PL_CG * PL_NO * 2), r2 = r - u * (PL_CG * PL_NO * 2);
+            const int cg = r2 / (PL_NO * 2), w = r2 - cg * (PL_NO * 2);
+            // start rows 4J-(M-1) .. 4J+(M-1) of column group cg, two uint4 each
+            (&s_q[0][0][0][0][0])[i] =
+                qp4[((size_t)(q0 + qq) * PL_CG + cg) * (NS * 2) + (4 * pf_unit(u) - (M - 1) - S0) * 2 + w];
+        }
+        if ((int)threadIdx.x < nb * PF_NU * 16)
+            (&s_qs[0][0][0])[threadIdx.x] = qsj[(size_t)q0 * PF_NU * 16 + threadIdx.x];
+        __syncthreads();
+        if (!live) continue;
+#pragma unroll 1
+        for (int qq = 0; qq < nb; ++qq) {
+            uint32_t m[PF_TPW];
+#pragma unroll
+            for (int t = 0; t < PF_TPW; ++t) m[t] = 0xFFFFFFFFu;
+#pragma unroll
+            for (int x = 0; x < PL_NO; ++x) {   // offset o = x - (M-1): start row 4J - o
+                uint32_t lb[PF_TPW];
+#pragma unroll
+                for (int t = 0; t < PF_TPW; ++t) lb[t] = 0u;
+#pragma unroll
+                for (int u = 0; u < PF_NU; ++u) {
+                    uint32_t c[PF_TPW];
+#pragma unroll
+                    for (int t = 0; t < PF_TPW; ++t) c[t] = 0u;
+#pragma unroll
+                    for (int cp = 0; cp < PL_CG; cp += 2) {
+                        uint32_t q[2][8], b[PF_TPW][2];
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) {
+                            const uint4 lo = s_q[qq][u][cp + i][PL_NO - 1 - x][0];
+                            const uint4 hi = s_q[qq][u][cp + i][PL_NO - 1 - x][1];
+                            q[i][0] = lo.x; q[i][1] = lo.y; q[i][2] = lo.z; q[i][3] = lo.w;
+                            q[i][4] = hi.x; q[i][5] = hi.y; q[i][6] = hi.z; q[i][7] = hi.w;
+                        }
+#pragma unroll
+                        for (int k = 0; k < 8; ++k)
+#pragma unroll
+                            for (int t = 0; t < PF_TPW; ++t)
+#pragma unroll
+                                for (int i = 0; i < 2; ++i)
+                                    b[t][i] = __builtin_amdgcn_bitop3_b32(P[t][u][cp + i][k], q[i][k],
+                                                                          k ? b[t][i] : 0u, 0x8E);
+#pragma unroll
+                        for (int t = 0; t < PF_TPW; ++t)
+#pragma unroll
+                            for (int i = 0; i < 2; ++i)
+                                asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(c[t]) : "v"(b[t][i]), "v"(c[t]));
+                        // (the max-ILP scheduler would pull the reads of many offsets ahead and
+                        // spill; the SIMD's other waves cover this wave's read latency)
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    const uint32_t qs = s_qs[qq][u][x];
+#pragma unroll
+                    for (int t = 0; t < PF_TPW; ++t)
+                        lb[t] += (c[t] << 8) + (ts[t][u] - qs);   // >= 0 in all; the parts wrap mod 2^32
+                }
+#pragma unroll
+                for (int t = 0; t < PF_TPW; ++t) m[t] = min(m[t], lb[t]);
+            }
+#pragma unroll
+            for (int t = 0; t < PF_TPW; ++t) {
+                uint32_t v = valid[t] ? m[t] : 0xFFFFFFFFu;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor(v, off));
+                if (lane == 0 && tb0 + t < ntb) minlb[(size_t)(tb0 + t) * nq + q0 + qq] = v;
+            }
+        }
+    }
+}
+
+// Append q to a template block's list where `in`.  Atomics of the whole device on one
+// counter run one after the other at memory (about 0.2 us each, measured: 160 waves'
+// adds on each of 16 counters took 32 us), so a thread block of 1,024 queries adds
+// once: ballots, a scan of the waves' counts in LDS, one atomic.  The order within a
+// list does not matter, keys meet by atomicMin.
+constexpr int VT_LIST_T = 1024;
+__device__ __forceinline__ void list_append(bool in, int q, unsigned* __restrict__ cnt, int* __restrict__ list) {
+    __shared__ unsigned s_w[VT_LIST_T / 64];
+    __shared__ unsigned s_base;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long mask = __ballot(in);
+    if (lane == 0) s_w[wave] = (unsigned)__popcll(mask);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0u;
+        for (int w = 0; w < VT_LIST_T / 64; ++w) {
+            const unsigned c = s_w[w];
+            s_w[w] = t;
+            t += c;
+        }
+        s_base = t ? atomicAdd(cnt, t) : 0u;
+    }
+    __syncthreads();
+    if (in) list[s_base + s_w[wave] + (unsigned)__popcll(mask & ((1ull << lane) - 1ull))] = q;
+}
+
+// List (a): the candidate block of every query, tb* = argmin_tb minLB[tb][q] ...
+__global__ __launch_bounds__(256) void vt_prune_pick_kernel(const uint32_t* __restrict__ minlb, int ntb, int nq,
+                                                            int* __restrict__ tbstar) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq) return;
+    uint32_t best = minlb[q];
+    int bt = 0;
+    for (int tb = 1; tb < ntb; ++tb) {
+        const uint32_t v = minlb[(size_t)tb * nq + q];
+        if (v < best) {   // strict: the lowest block on ties
+            best = v;
+            bt = tb;
+        }
+    }
+    tbstar[q] = bt;
+}
+
+// ... and list1[tb] = the queries whose candidate block is tb (blockIdx.y = tb).
+__global__ __launch_bounds__(VT_LIST_T) void vt_prune_first_kernel(int nq, const int* __restrict__ tbstar,
+                                                                   unsigned* __restrict__ cnt,
+                                                                   int* __restrict__ list) {
+    const int q = blockIdx.x * VT_LIST_T + threadIdx.x, tb = blockIdx.y;
+    list_append(q < nq && tbstar[q] == tb, q, cnt + tb, list + (size_t)tb * nq);
+}
+
+// List (b), after pass B1: q joins the list of every other block whose bound does not
+// exceed U(q) = the score B1 left in best[q].
+__global__ __launch_bounds__(VT_LIST_T) void vt_prune_rest_kernel(const uint32_t* __restrict__ minlb, int nq,
+                                                                  const int* __restrict__ tbstar,
+                                                                  const unsigned long long* __restrict__ best,
+                                                                  unsigned* __restrict__ cnt,
+                                                                  int* __restrict__ list) {
+    const int q = blockIdx.x * VT_LIST_T + threadIdx.x, tb = blockIdx.y;
+    const bool in = q < nq && tb != tbstar[q] && minlb[(size_t)tb * nq + q] <= (uint32_t)(best[q] >> 32);
+    list_append(in, q, cnt + tb, list + (size_t)tb * nq);
+}
+
+// The lists' totals for rs_vt_prune_stats, and both sets of counters back to zero.
+__global__ __launch_bounds__(256) void vt_prune_finish_kernel(unsigned* __restrict__ cnt1, unsigned* __restrict__ cnt2,
+                                                              int ntb, unsigned long long* __restrict__ stat) {
+    __shared__ unsigned long long s_sum[2];
+    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0ull;
+    __syncthreads();
+    unsigned long long a = 0ull, b = 0ull;
+    for (int tb = threadIdx.x; tb < ntb; tb += blockDim.x) {
+        a += cnt1[tb];
+        b += cnt2[tb];
+        cnt1[tb] = 0u;
+        cnt2[tb] = 0u;
+    }
+    atomicAdd(&s_sum[0], a);
+    atomicAdd(&s_sum[1], b);
+    __syncthreads();
+    if (threadIdx.x < 2) stat[threadIdx.x] = s_sum[threadIdx.x];
 }
 
 // ===========================================================================
@@ -1065,6 +1388,21 @@ struct rs_vt {
     unsigned* dDone = nullptr; // plane scan blocks finished (the folded key export; reset by the last)
     bool keysFolded = false;   // the running scan exports its own keys (vt_fetch_keys: no export launch)
     int ctrCap = 0;
+    // pruned plane scan (H = 64 frozen key scans; RS_VT_PRUNE): 0 dense everywhere, 1 above
+    // VT_PRUNE_MIN_Q queries and one template block, 2 ("force") at any size
+    int prune = 0;
+    uint32_t* dQsj = nullptr;        // QS_J of the queries in dQp (with dQp's capacity)
+    uint32_t* dQsjStream = nullptr;  // ... of dQpStream
+    uint32_t* dMinLB = nullptr;      // [ntb][nq]
+    int* dList = nullptr;            // list1 [ntb][nq], then list2 [ntb][nq]
+    size_t pruneCap = 0;             // ntb * nq the two are sized for
+    int* dTbStar = nullptr;          // [nq] candidate block
+    int tbStarCap = 0;
+    unsigned* dListCnt = nullptr;    // [2][listCntCap] entries per list; zero between calls
+    int listCntCap = 0;
+    unsigned long long* dPruneStat = nullptr;  // list totals of the last pruned launch
+    int64_t prunePairs = 0;          // its ntb * nq
+    int prunePasses = 0;             // its scan passes (0: no pruned launch yet)
     // on-device subsampling of camera frames (rs_vt_set_subsample / rs_vt_match_frames)
     int32_t* dPix = nullptr;   // H*W byte offsets of the kept pixels in a frame
     int64_t frameBytes = 0;
@@ -1163,11 +1501,13 @@ int vt_grow_queries(rs_vt* h, int nq) {
     if (h->hBest) RS_HIP(hipHostFree(h->hBest));
     if (h->dQp) RS_HIP(hipFree(h->dQp));
     if (h->dQsumRaw) RS_HIP(hipFree(h->dQsumRaw));
-    h->dQp = h->dQsumRaw = nullptr;
+    if (h->dQsj) RS_HIP(hipFree(h->dQsj));
+    h->dQp = h->dQsumRaw = h->dQsj = nullptr;
     const size_t qb = (size_t)h->H * h->W;
     if (h->planar) {
         RS_HIP(hipMalloc(&h->dQp, sizeof(uint32_t) * PL_CG * plane_ns(h) * 8 * (size_t)cap));
         RS_HIP(hipMalloc(&h->dQsumRaw, sizeof(uint32_t) * cap));
+        if (h->prune) RS_HIP(hipMalloc(&h->dQsj, sizeof(uint32_t) * PF_NU * 16 * (size_t)cap));
     }
     RS_HIP(hipMalloc(&h->dQraw, qb * cap));
     RS_HIP(hipHostMalloc(&h->hQraw, qb * cap, hipHostMallocMapped | hipHostMallocCoherent));
@@ -1254,7 +1594,7 @@ int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
         std::memcpy(h->hQraw, queries, qb);
         h->qrawBusy = true;
         hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(256), 0, h->stream, h->hQrawDev, h->H, h->M, h->dQp,
-                           h->dQsumRaw, h->dQraw);
+                           h->dQsumRaw, h->dQraw, h->dQsj);
         RS_HIP(hipGetLastError());
         return RS_OK;
     }
@@ -1270,7 +1610,7 @@ int vt_build_forms(rs_vt* h, int nq, const uint8_t* src) {
                            h->WD, h->M, h->dQf, h->dQsum);
     else
         hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(256), 0, h->stream, src, h->H,
-                           h->M, h->dQp, h->dQsumRaw, nullptr);
+                           h->M, h->dQp, h->dQsumRaw, nullptr, h->dQsj);
     RS_HIP(hipGetLastError());
     return RS_OK;
 }
@@ -1353,6 +1693,9 @@ int plane_split(int ntb, int nbatch, int slots) {
     return nqc;
 }
 
+// Frozen key scans of at least this many queries prune (RS_VT_PRUNE=1, the default).
+constexpr int VT_PRUNE_MIN_Q = 512;
+
 // Launch a scan of queries [0, nq) (forms in dQf) against `count` slots of lib.
 template <bool MATRIX>
 int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int rank,
@@ -1373,14 +1716,90 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
     const uint4* planes = reinterpret_cast<const uint4*>(
         reinterpret_cast<const uint8_t*>(cand ? h->dCandP : h->dLibP) + (size_t)tb0 * pblock_bytes(h));
     const uint32_t* ts = (cand ? h->dCandTs : h->dLibTs) + (size_t)tb0 * (TS_BLOCK_BYTES / 4);
+    if constexpr (!MATRIX) {
+        // Pruned scan of the frozen library.  Below VT_PRUNE_MIN_Q queries the call is one
+        // latency-bound launch and the prefilter, the list kernels and two scan passes
+        // cost more than they save; one template block has nothing to prune.
+        const bool pruned = h->H == 64 && !cand && tb0 == 0 && h->dQsj && ntb <= 65535 &&
+                            (h->prune == 2 || (h->prune == 1 && nq >= VT_PRUNE_MIN_Q && ntb >= 2));
+        if (pruned) {
+            const size_t pairs = (size_t)ntb * nq;
+            if (pairs > h->pruneCap) {
+                const size_t cap = std::max(pairs, 2 * h->pruneCap);
+                if (h->dMinLB) RS_HIP(hipFree(h->dMinLB));
+                if (h->dList) RS_HIP(hipFree(h->dList));
+                h->dMinLB = nullptr;
+                h->dList = nullptr;
+                h->pruneCap = 0;
+                RS_HIP(hipMalloc(&h->dMinLB, sizeof(uint32_t) * cap));
+                RS_HIP(hipMalloc(&h->dList, sizeof(int) * 2 * cap));
+                h->pruneCap = cap;
+            }
+            if (nq > h->tbStarCap) {
+                if (h->dTbStar) RS_HIP(hipFree(h->dTbStar));
+                h->dTbStar = nullptr;
+                h->tbStarCap = 0;
+                RS_HIP(hipMalloc(&h->dTbStar, sizeof(int) * (size_t)nq));
+                h->tbStarCap = nq;
+            }
+            if (ntb > h->listCntCap) {  // like dCtr: zero at first, and every call leaves them at zero
+                const int cap = std::max(ntb, 2 * h->listCntCap);
+                if (h->dListCnt) RS_HIP(hipFree(h->dListCnt));
+                h->dListCnt = nullptr;
+                h->listCntCap = 0;
+                RS_HIP(hipMalloc(&h->dListCnt, sizeof(unsigned) * 2 * (size_t)cap));
+                RS_HIP(hipMemsetAsync(h->dListCnt, 0, sizeof(unsigned) * 2 * (size_t)cap, h->stream));
+                h->listCntCap = cap;
+            }
+            if (!h->dPruneStat) {
+                RS_HIP(hipMalloc(&h->dPruneStat, 2 * sizeof(unsigned long long)));
+                RS_HIP(hipMemsetAsync(h->dPruneStat, 0, 2 * sizeof(unsigned long long), h->stream));
+            }
+            unsigned* cnt1 = h->dListCnt;
+            unsigned* cnt2 = h->dListCnt + h->listCntCap;
+            int* list1 = h->dList;
+            int* list2 = h->dList + pairs;
+            const int nqb = (nq + PF_NB - 1) / PF_NB, pfx = (ntb + PF_WAVES * PF_TPW - 1) / (PF_WAVES * PF_TPW);
+            const dim3 pgrid((unsigned)pfx, (unsigned)std::min(nqb, std::max(1, 4096 / pfx)));
+            hipLaunchKernelGGL(vt_prefilter_kernel, pgrid, dim3(64 * PF_WAVES), 0, h->stream, planes, ntb, count,
+                               reinterpret_cast<const uint4*>(h->dQp), h->dQsj, nq, h->dMinLB);
+            hipLaunchKernelGGL(vt_prune_pick_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, h->stream,
+                               h->dMinLB, ntb, nq, h->dTbStar);
+            const dim3 lgrid((unsigned)((nq + VT_LIST_T - 1) / VT_LIST_T), (unsigned)ntb);
+            hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar, cnt1,
+                               list1);
+            // the passes min into the same keys; the folded export (out.host) needs one
+            // launch to be the last, so a pruned call exports with vt_keys_export
+            ScanOut po = out;
+            po.host = nullptr;
+            po.done = nullptr;
+            hipLaunchKernelGGL((vt_scan_plane_kernel<64, false, true>), grid, dim3(64 * PL_CG * PL_SPLIT), 0,
+                               h->stream, planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, po, rank,
+                               nranks, PlaneList{list1, cnt1, nq});
+            hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB, nq,
+                               h->dTbStar, out.best, cnt2, list2);
+            hipLaunchKernelGGL((vt_scan_plane_kernel<64, false, true>), grid, dim3(64 * PL_CG * PL_SPLIT), 0,
+                               h->stream, planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, po, rank,
+                               nranks, PlaneList{list2, cnt2, nq});
+            hipLaunchKernelGGL(vt_prune_finish_kernel, dim3(1), dim3(256), 0, h->stream, cnt1, cnt2, ntb,
+                               h->dPruneStat);
+            if (out.host)
+                hipLaunchKernelGGL(vt_keys_export, dim3((nq + 255) / 256 < 64 ? (nq + 255) / 256 : 64), dim3(256), 0,
+                                   h->stream, out.best, nq, out.host);
+            RS_HIP(hipGetLastError());
+            h->prunePairs = (int64_t)pairs;
+            h->prunePasses = 2;
+            return RS_OK;
+        }
+    }
     if (h->H == 64)
         hipLaunchKernelGGL((vt_scan_plane_kernel<64, MATRIX>), grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream,
                            planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, out, rank,
-                           nranks);
+                           nranks, PlaneList{});
     else
         hipLaunchKernelGGL((vt_scan_plane_kernel<32, MATRIX>), grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream,
                            planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, out, rank,
-                           nranks);
+                           nranks, PlaneList{});
     RS_HIP(hipGetLastError());
     return RS_OK;
 }
@@ -1695,21 +2114,25 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
         rs_vt* h;
         uint32_t* p;
         uint32_t* q;
-        ~PlaneBufRestore() { h->dQp = p; h->dQsumRaw = q; }
-    } restore{h, h->dQp, h->dQsumRaw};
+        uint32_t* j;
+        ~PlaneBufRestore() { h->dQp = p; h->dQsumRaw = q; h->dQsj = j; }
+    } restore{h, h->dQp, h->dQsumRaw, h->dQsj};
     if (allplanes) {
         if (total > h->qpStreamCap) {
             if (h->dQpStream) RS_HIP(hipFree(h->dQpStream));
             if (h->dQsumStream) RS_HIP(hipFree(h->dQsumStream));
-            h->dQpStream = h->dQsumStream = nullptr;
+            if (h->dQsjStream) RS_HIP(hipFree(h->dQsjStream));
+            h->dQpStream = h->dQsumStream = h->dQsjStream = nullptr;
             h->qpStreamCap = 0;
             RS_HIP(hipMalloc(&h->dQpStream, sizeof(uint32_t) * qpq * total));
             RS_HIP(hipMalloc(&h->dQsumStream, sizeof(uint32_t) * total));
+            if (h->prune) RS_HIP(hipMalloc(&h->dQsjStream, sizeof(uint32_t) * PF_NU * 16 * total));
             h->qpStreamCap = total;
         }
         RS_CHECK(total <= INT32_MAX, RS_ERR_ARG, "too many queries in one stream");
         h->dQp = h->dQpStream;
         h->dQsumRaw = h->dQsumStream;
+        h->dQsj = h->dQsjStream;
         if (!hostgroups) {
             RS_TRY(vt_build_forms(h, (int)total, queries));
             const ScanOut out{h->dStream, nullptr, 0};
@@ -1755,6 +2178,7 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
                 RS_HIP(hipStreamWaitEvent(h->stream, h->evUp[bi], 0));
                 h->dQp = h->dQpStream + qpq * (size_t)b0 * nq;
                 h->dQsumRaw = h->dQsumStream + (size_t)b0 * nq;
+                if (h->dQsjStream) h->dQsj = h->dQsjStream + (size_t)PF_NU * 16 * b0 * nq;
                 RS_TRY(vt_build_forms(h, n * nq, h->dUp[bi]));
                 RS_HIP(hipEventRecord(h->evUsed[bi], h->stream));
                 const ScanOut out{h->dStream + (size_t)b0 * nq, nullptr, 0};
@@ -1853,6 +2277,18 @@ int rs_vt_create(int H, int W, int max_offset, uint64_t thr, int64_t capacity, i
             return RS_ERR_ARG;
         }
     }
+    if (h->planar && h->H == 64) {
+        // A/B switch: "0" keeps the dense launch everywhere, "force" prunes at any size
+        // (tests), "1" (or unset) prunes the large frozen scans
+        const char* e = std::getenv("RS_VT_PRUNE");
+        if (!e || e[0] == 0 || std::strcmp(e, "1") == 0) h->prune = 1;
+        else if (std::strcmp(e, "force") == 0) h->prune = 2;
+        else if (std::strcmp(e, "0") != 0) {
+            rs::set_error("RS_VT_PRUNE='%s': expected 0, 1 or force", e);
+            delete h;
+            return RS_ERR_ARG;
+        }
+    }
     if (h->planar) {
         // resident blocks per CU: the occupancy API, capped by the kernel's own VGPR and
         // LDS arithmetic (the API has read one block high on gfx950 for some SGPR counts)
@@ -1909,7 +2345,9 @@ int rs_vt_destroy(rs_vt* h) {
     for (void* p : {(void*)h->dLib, (void*)h->dQraw, (void*)h->dQf, (void*)h->dQsum, (void*)h->dBest,
                     (void*)h->dSrc, (void*)h->dDst, (void*)h->dCand, (void*)h->dMat, (void*)h->dLibP,
                     (void*)h->dLibTs, (void*)h->dCandP, (void*)h->dCandTs, (void*)h->dQp,
-                    (void*)h->dQsumRaw, (void*)h->dCtr, (void*)h->dDone, (void*)h->dPix, (void*)h->dFrames})
+                    (void*)h->dQsumRaw, (void*)h->dCtr, (void*)h->dDone, (void*)h->dPix, (void*)h->dFrames,
+                    (void*)h->dQsj, (void*)h->dQsjStream, (void*)h->dMinLB, (void*)h->dList, (void*)h->dTbStar,
+                    (void*)h->dListCnt, (void*)h->dPruneStat})
         if (p) (void)hipFree(p);
     if (h->hStream) (void)hipHostFree(h->hStream);
     if (h->dStream) (void)hipFree(h->dStream);
@@ -2125,9 +2563,25 @@ int rs_vt_set_threshold(rs_vt* h, double threshold) {
 
 const char* rs_vt_scan_form(const rs_vt* h) {
     if (!h) return nullptr;
-    if (h->planar) return "plane";
+    if (h->planar) return h->prune ? "plane-pruned" : "plane";
     if (h->M != FAST_M || (h->H != 64 && h->H != 32)) return "generic";
     return "carry";
+}
+
+int rs_vt_prune_stats(rs_vt* h, int64_t out[4]) {
+    rs::clear_error();
+    RS_CHECK(h && out, RS_ERR_ARG, "null argument");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (h->prunePasses == 0) return RS_OK;
+    RS_HIP(hipSetDevice(h->device));
+    unsigned long long s[2] = {0ull, 0ull};
+    RS_HIP(hipMemcpyAsync(s, h->dPruneStat, sizeof(s), hipMemcpyDeviceToHost, h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream));
+    out[0] = (int64_t)s[0];
+    out[1] = (int64_t)s[1];
+    out[2] = h->prunePairs;
+    out[3] = h->prunePasses;
+    return RS_OK;
 }
 
 int rs_vt_last_ms(rs_vt* h, double* ms) {

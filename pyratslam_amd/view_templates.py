@@ -572,6 +572,14 @@ class ViewTemplates:
             return 'sad-resident'
         return self._lib.rs_vt_scan_form(self._h).decode()
 
+    def prune_stats(self):
+        """Of the last pruned scan launch ('plane-pruned' handles): (block, query) pairs
+        scanned by pass B1, by pass B2, template blocks x queries, passes launched;
+        zeros before the first pruned scan (rs_vt_prune_stats)."""
+        out = (ctypes.c_int64 * 4)()
+        _lib.check(self._lib.rs_vt_prune_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
 
 class ShardedViewTemplates(ViewTemplates):
     """Template library sharded round-robin over ranks (template g on rank g % n).
