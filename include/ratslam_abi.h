@@ -309,14 +309,22 @@ const char* rs_vt_scan_form(const rs_vt* h);
  * blocks by an exact partial-score bound: a prefilter bounds every
  * (64-template block, query) pair from below, pass B1 scans each query against its
  * most promising block, pass B2 against every other block whose bound does not exceed
- * the score B1 found.  Exact for every input.  RS_VT_PRUNE (read at create): "0"
+ * the score B1 found.  Before B1 the one template that holds the block's minimum bound
+ * is scored exactly; where every other template's bound in the block exceeds that score
+ * the query is settled without a block scan.  Exact for every
+ * input.  RS_VT_PRUNE (read at create): "0"
  * dense launch everywhere ("plane"), "1" (default) prune scans of at least 512 queries
  * over at least two template blocks, "force" prune at any size.
- * rs_vt_prune_stats: of the last pruned scan launch, out[0] = (block, query) pairs of
- * pass B1 (= queries), out[1] = pairs of pass B2, out[2] = template blocks x queries,
- * out[3] = scan passes launched; all 0 before the first pruned scan.  Reads the device
- * counters on demand (synchronises the handle's stream); the match calls do not. */
+ * rs_vt_prune_stats: of the last pruned scan launch, out[0] = the queries pass B1
+ * settled in their candidate block, by verifying one template or by scanning the block
+ * (= queries), out[1] = (block, query) pairs of pass B2, out[2] = template blocks x
+ * queries, out[3] = scan passes launched; all 0 before the first pruned scan.  Reads the
+ * device counters on demand (synchronises the handle's stream); the match calls do not. */
 int rs_vt_prune_stats(rs_vt* h, int64_t out[4]);
+/* *out = the queries the last pruned scan launch settled by verification alone (they
+ * took no block scan in pass B1); 0 before the first pruned scan.  Reads on demand like
+ * rs_vt_prune_stats. */
+int rs_vt_prune_verified(rs_vt* h, int64_t* out);
 
 /* ViewTemplates.match's strict threshold (view_templates.py:67) as a double: a
  * score makes a new template when (double)score > threshold -- numpy's own

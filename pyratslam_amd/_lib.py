@@ -125,6 +125,7 @@ SIGNATURES = {
     'rs_vt_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
     'rs_vt_scan_form': (ctypes.c_char_p, [_vp]),
     'rs_vt_prune_stats': (ctypes.c_int, [_vp, _i64p]),
+    'rs_vt_prune_verified': (ctypes.c_int, [_vp, _i64p]),
     'rs_vt_set_threshold': (ctypes.c_int, [_vp, ctypes.c_double]),
     'rs_sad_scores': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp]),
@@ -156,7 +157,7 @@ SIGNATURES = {
 
 # statistics calls an older build of the library lacks: tools/stream_ab.py loads such
 # builds by path for an A/B; calling one of these on them raises AttributeError
-NEWER_SYMBOLS = {'rs_vt_prune_stats'}
+NEWER_SYMBOLS = {'rs_vt_prune_stats', 'rs_vt_prune_verified'}
 
 _lib = None
 _lock = threading.Lock()

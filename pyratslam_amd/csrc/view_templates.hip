@@ -875,13 +875,21 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes,
 // no batch after its one failed take (before it loads its template planes).
 // Batches per block of a list-driven pass (headline step, ms: 2 -> 0.525, 3 -> 0.515,
 // 4 -> 0.527, 6 -> 0.567).
+// Per launch (PlaneList::per): pass B1's lists hold only the queries the verification
+// left unsettled, about 64 per template block at the headline shape: one batch per
+// block there (VT_LIST_PER_B1; headline step, ms: 1 -> 0.467, 2 -> 0.473, 3 -> 0.493;
+// DESIGN section 19).
 #ifndef VT_LIST_PER
 #define VT_LIST_PER 3
+#endif
+#ifndef VT_LIST_PER_B1
+#define VT_LIST_PER_B1 1
 #endif
 struct PlaneList {
     const int* ids = nullptr;
     const unsigned* cnt = nullptr;
     int ld = 0;
+    int per = VT_LIST_PER;
 };
 template <int H, bool MATRIX, bool LIST = false>
 __global__ __launch_bounds__(64 * PL_CG * PL_SPLIT) __attribute__((amdgpu_waves_per_eu(4, 4)))
@@ -906,10 +914,10 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
         if (nq == 0) return;
         ids = pl.ids + (size_t)tb * pl.ld;
         // The grid is sized for a list of every query; a shorter list is served by
-        // the first `use` of the template block's nqc blocks, about VT_LIST_PER batches
+        // the first `use` of the template block's nqc blocks, about pl.per batches
         // each, so a block's fixed cost (its template planes, 128 KiB) is not paid per
         // batch.  The others leave before they touch the batch counter.
-        int use = ((nq + PL_NB - 1) / PL_NB + VT_LIST_PER - 1) / VT_LIST_PER;
+        int use = ((nq + PL_NB - 1) / PL_NB + pl.per - 1) / pl.per;
         use = nqc >= 8 ? min(nqc, max(8, (use + 7) & ~7)) : min(nqc, max(1, use));
         if ((int)(blockIdx.x - (unsigned)tb * (unsigned)nqc) >= use) return;
         nqc = use;
@@ -1022,8 +1030,25 @@ constexpr int PF_WAVES = 4;   // waves per thread block
 constexpr int PF_TPW = VT_PF_TPW;
 constexpr int PF_NB = 4;      // queries staged per step
 constexpr int PF_QW4 = PF_NU * PL_CG * PL_NO * 2;   // staged uint4 per query
+constexpr uint32_t PF_NONE = (1u << 26) - 1u;       // "no other template": above every score
 
-// minlb[tb * nq + q].  Lane = template; the wave keeps the PF_NU units of its PF_TPW
+// Wave-wide minimum as a wave-uniform value, without the LDS pipe (the prefilter's pace
+// is set by its LDS reads, and a shuffle is a ds_bpermute): four DPP steps leave each
+// row of 16 lanes its minimum (lanes ^1, ^2, then the row's other half-row and the
+// other half mirrored), and the four rows meet through scalar registers.
+__device__ __forceinline__ uint32_t wave_min_u32_dpp(uint32_t v) {
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false));    // quad_perm [1,0,3,2]
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false));    // quad_perm [2,3,0,1]
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false));   // row_half_mirror
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false));   // row_mirror
+    return min(min((uint32_t)__builtin_amdgcn_readlane((int)v, 0), (uint32_t)__builtin_amdgcn_readlane((int)v, 16)),
+               min((uint32_t)__builtin_amdgcn_readlane((int)v, 32), (uint32_t)__builtin_amdgcn_readlane((int)v, 48)));
+}
+
+// minlb[tb * nq + q], and second[tb * nq + q] = (min2 << 6) | lane: the lane that holds
+// the block's minimum (the lowest on ties) and min2, the minimum over the block's other
+// valid templates (PF_NONE when it has no other).  The pick verifies that one template
+// (vt_prune_verify_kernel).  Lane = template; the wave keeps the PF_NU units of its PF_TPW
 // template blocks in VGPRs and reads the staged query planes as wave-uniform LDS
 // broadcasts, two column groups at a time (2 * PF_TPW independent borrow chains).
 __global__ __launch_bounds__(64 * PF_WAVES) __attribute__((amdgpu_waves_per_eu(4)))
@@ -1031,9 +1056,11 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
                                                                     int64_t count,
                                                                     const uint4* __restrict__ qp4,
                                                                     const uint32_t* __restrict__ qsj, int nq,
-                                                                    uint32_t* __restrict__ minlb) {
+                                                                    uint32_t* __restrict__ minlb,
+                                                                    uint32_t* __restrict__ second) {
     constexpr int M = FAST_M, NU = 64 / 4, NS = PlaneLds<64>::NS, S0 = M - 3;
     static_assert(PL_CG % 2 == 0, "column groups in pairs");
+    static_assert(PF_NU * 128 * 255 < (int)PF_NONE, "a bound and a lane fit one word");
     __shared__ uint4 s_q[PF_NB][PF_NU][PL_CG][PL_NO][2];
     __shared__ uint32_t s_qs[PF_NB][PF_NU][16];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1127,10 +1154,15 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
             }
 #pragma unroll
             for (int t = 0; t < PF_TPW; ++t) {
-                uint32_t v = valid[t] ? m[t] : 0xFFFFFFFFu;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor(v, off));
-                if (lane == 0 && tb0 + t < ntb) minlb[(size_t)(tb0 + t) * nq + q0 + qq] = v;
+                // value and lane in one reduction (a bound is below 2^26; the lowest lane on
+                // ties), then the minimum over the valid templates other than that lane
+                const uint32_t v = wave_min_u32_dpp(valid[t] ? (m[t] << 6) | (uint32_t)lane : 0xFFFFFFFFu);
+                const uint32_t w = wave_min_u32_dpp(valid[t] && lane != (int)(v & 63u) ? m[t] : PF_NONE);
+                if (lane == 0 && tb0 + t < ntb) {
+                    // (a block of the library holds a valid template: v is a packed bound)
+                    minlb[(size_t)(tb0 + t) * nq + q0 + qq] = v >> 6;
+                    second[(size_t)(tb0 + t) * nq + q0 + qq] = (w << 6) | (v & 63u);
+                }
             }
         }
     }
@@ -1163,28 +1195,117 @@ __device__ __forceinline__ void list_append(bool in, int q, unsigned* __restrict
 }
 
 // List (a): the candidate block of every query, tb* = argmin_tb minLB[tb][q] ...
-__global__ __launch_bounds__(256) void vt_prune_pick_kernel(const uint32_t* __restrict__ minlb, int ntb, int nq,
-                                                            int* __restrict__ tbstar) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= nq) return;
-    uint32_t best = minlb[q];
-    int bt = 0;
-    for (int tb = 1; tb < ntb; ++tb) {
-        const uint32_t v = minlb[(size_t)tb * nq + q];
-        if (v < best) {   // strict: the lowest block on ties
-            best = v;
-            bt = tb;
+// (strict <: the lowest block on ties), and the verification of the one template the
+// prefilter singled out in it, t^ = the lane of the block's minimum bound.  One wave per
+// query.  U0 = the exact score of (t^, q), from the resident planes the scan reads:
+// lane (x, cg) counts the borrows of offset x - (M-1) in column group cg over the
+// template units j whose query start row 4j - o lies in [M-3, H-M-1] (the others meet
+// zeroed rows only), the four column groups meet by shuffles, and
+//   U0 = min_x TS(x) + 256 * B(x) - QS,
+// the scan's own expression.  If min2 > U0, every other template of the block has
+// score >= bound >= min2 > U0: the block's first argmin is t^ with score U0, the key
+// the block scan would leave, and the query is settled: its key goes into best[] here
+// and tbstar[q] = ~tb* keeps it off list1.  ">": a template whose bound equals U0 may
+// hold an equal score at a lower index, so that query is block-scanned.
+constexpr int VT_VQ4 = PlaneLds<64>::QW / 4;   // uint4 of a query's planes
+__global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __restrict__ minlb,
+                                                             const uint32_t* __restrict__ second, int ntb, int nq,
+                                                             const uint4* __restrict__ planes,
+                                                             const uint32_t* __restrict__ tsum,
+                                                             const uint4* __restrict__ qp4,
+                                                             const uint32_t* __restrict__ qsum,
+                                                             unsigned long long* __restrict__ best, int rank,
+                                                             int nranks, int* __restrict__ tbstar) {
+    constexpr int M = FAST_M, NU = 64 / 4, NS = PlaneLds<64>::NS, S0 = M - 3, S1 = 64 - M - 1;
+    static_assert(PL_NO * PL_CG <= 64, "one lane per (offset, column group)");
+    constexpr int QK = (VT_VQ4 + 63) / 64;
+    __shared__ uint4 s_q[QK * 64];           // [cg][start row - S0][2], padded to whole wave stores
+    __shared__ uint4 s_t[PL_CG * NU * 2];    // [cg][unit][2]
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const int x = lane >> 2, cg = lane & 3, o = x - (M - 1);
+    // what does not wait for the pick, in flight through it: the query's planes and QS
+    uint4 qv[QK];
+#pragma unroll
+    for (int k = 0; k < QK; ++k) qv[k] = qp4[(size_t)q * VT_VQ4 + min(lane + 64 * k, VT_VQ4 - 1)];
+    const uint32_t qs = qsum[q];
+    // the pick: each lane's blocks with their `second`, so the winner's is at hand
+    unsigned long long pk = ~0ull;
+    uint32_t sec = 0u;
+    for (int tb = lane; tb < ntb; tb += 64) {
+        const unsigned long long k = ((unsigned long long)minlb[(size_t)tb * nq + q] << 32) | (unsigned)tb;
+        const uint32_t s2 = second[(size_t)tb * nq + q];
+        const bool lt = k < pk;   // (selects: a branch would put the second read behind the first)
+        pk = lt ? k : pk;
+        sec = lt ? s2 : sec;
+    }
+    // (keeps the plane reads above in front of the reduction: left alone they sink to
+    // their LDS stores, one memory round trip each)
+#pragma unroll
+    for (int k = 0; k < QK; ++k) asm volatile("" : "+v"(qv[k].x), "+v"(qv[k].y), "+v"(qv[k].z), "+v"(qv[k].w));
+    const unsigned long long mk = wave_min_u64(pk);
+    const int tbs = (int)(unsigned)mk;
+    sec = (uint32_t)__shfl((int)sec, __ffsll((unsigned long long)__ballot(pk == mk)) - 1);   // (one lane holds block tbs)
+    const int tl = (int)(sec & 63u);
+    const uint32_t ts = x < PL_NO ? tsum[((size_t)tbs * 16 + x) * 64 + tl] : 0u;
+    static_assert(PL_CG * NU * 2 == 128, "two template chunks per lane");
+    const uint4 t0 = planes[((size_t)tbs * 128 + lane) * 64 + tl];
+    const uint4 t1 = planes[((size_t)tbs * 128 + 64 + lane) * 64 + tl];
+    s_t[lane] = t0;
+    s_t[64 + lane] = t1;
+#pragma unroll
+    for (int k = 0; k < QK; ++k) s_q[lane + 64 * k] = qv[k];   // (past VT_VQ4: copies of the last chunk, never read)
+    __syncthreads();
+    uint32_t cnt = 0u;
+    if (x < PL_NO) {
+        // (four units' reads in flight: unrolled fully, the max-ILP scheduler reads all
+        // sixteen ahead into 176 VGPRs, two waves per SIMD.  Branch-free: a unit whose
+        // start row lies outside the window reads a clamped row and counts nothing)
+#pragma unroll 4
+        for (int j = 0; j < NU; ++j) {
+            const bool in = 4 * j - o >= S0 && 4 * j - o <= S1;
+            const int s = min(max(4 * j - o, S0), S1);
+            const uint4 ta = s_t[(cg * NU + j) * 2], tc = s_t[(cg * NU + j) * 2 + 1];
+            const uint4 qa = s_q[(cg * NS + s - S0) * 2], qc = s_q[(cg * NS + s - S0) * 2 + 1];
+            uint32_t b = __builtin_amdgcn_bitop3_b32(ta.x, qa.x, 0u, 0x8E);
+            b = __builtin_amdgcn_bitop3_b32(ta.y, qa.y, b, 0x8E);
+            b = __builtin_amdgcn_bitop3_b32(ta.z, qa.z, b, 0x8E);
+            b = __builtin_amdgcn_bitop3_b32(ta.w, qa.w, b, 0x8E);
+            b = __builtin_amdgcn_bitop3_b32(tc.x, qc.x, b, 0x8E);
+            b = __builtin_amdgcn_bitop3_b32(tc.y, qc.y, b, 0x8E);
+            b = __builtin_amdgcn_bitop3_b32(tc.z, qc.z, b, 0x8E);
+            b = __builtin_amdgcn_bitop3_b32(tc.w, qc.w, b, 0x8E);
+            cnt += in ? (uint32_t)__builtin_popcount(b) : 0u;
         }
     }
-    tbstar[q] = bt;
+    cnt += __shfl_xor(cnt, 1);
+    cnt += __shfl_xor(cnt, 2);
+    uint32_t u0 = x < PL_NO ? ts + 256u * cnt : 0xFFFFFFFFu;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) u0 = min(u0, (uint32_t)__shfl_xor(u0, off));
+    u0 -= qs;
+    if (lane == 0) {
+        const bool settled = (sec >> 6) > u0;
+        if (settled) {
+            const unsigned long long g = ((unsigned long long)tbs * 64 + tl) * nranks + rank;
+            atomicMin(best + q, ((unsigned long long)u0 << 32) | g);
+        }
+        tbstar[q] = settled ? ~tbs : tbs;
+    }
 }
 
-// ... and list1[tb] = the queries whose candidate block is tb (blockIdx.y = tb).
+// ... and list1[tb] = the unsettled queries whose candidate block is tb (blockIdx.y =
+// tb).  The thread blocks of tb = 0 also count the settled queries (one add each).
 __global__ __launch_bounds__(VT_LIST_T) void vt_prune_first_kernel(int nq, const int* __restrict__ tbstar,
                                                                    unsigned* __restrict__ cnt,
-                                                                   int* __restrict__ list) {
+                                                                   int* __restrict__ list,
+                                                                   unsigned* __restrict__ verified) {
     const int q = blockIdx.x * VT_LIST_T + threadIdx.x, tb = blockIdx.y;
-    list_append(q < nq && tbstar[q] == tb, q, cnt + tb, list + (size_t)tb * nq);
+    const int ts = q < nq ? tbstar[q] : INT_MAX;
+    if (tb == 0) {   // (block-uniform)
+        const int n = __syncthreads_count(ts < 0);
+        if (threadIdx.x == 0 && n) atomicAdd(verified, (unsigned)n);
+    }
+    list_append(ts == tb, q, cnt + tb, list + (size_t)tb * nq);
 }
 
 // List (b), after pass B1: q joins the list of every other block whose bound does not
@@ -1195,13 +1316,17 @@ __global__ __launch_bounds__(VT_LIST_T) void vt_prune_rest_kernel(const uint32_t
                                                                   unsigned* __restrict__ cnt,
                                                                   int* __restrict__ list) {
     const int q = blockIdx.x * VT_LIST_T + threadIdx.x, tb = blockIdx.y;
-    const bool in = q < nq && tb != tbstar[q] && minlb[(size_t)tb * nq + q] <= (uint32_t)(best[q] >> 32);
+    const int ts = q < nq ? tbstar[q] : 0;   // ~tb* where the verification settled the query
+    const bool in = q < nq && tb != (ts < 0 ? ~ts : ts) && minlb[(size_t)tb * nq + q] <= (uint32_t)(best[q] >> 32);
     list_append(in, q, cnt + tb, list + (size_t)tb * nq);
 }
 
-// The lists' totals for rs_vt_prune_stats, and both sets of counters back to zero.
+// The lists' totals for rs_vt_prune_stats (stat[0] = the queries pass B1 settled, by
+// verification or by block scan; stat[1] = the pairs of B2; stat[2] = the verified
+// ones alone), and all the counters back to zero.
 __global__ __launch_bounds__(256) void vt_prune_finish_kernel(unsigned* __restrict__ cnt1, unsigned* __restrict__ cnt2,
-                                                              int ntb, unsigned long long* __restrict__ stat) {
+                                                              unsigned* __restrict__ verified, int ntb,
+                                                              unsigned long long* __restrict__ stat) {
     __shared__ unsigned long long s_sum[2];
     if (threadIdx.x < 2) s_sum[threadIdx.x] = 0ull;
     __syncthreads();
@@ -1215,7 +1340,13 @@ __global__ __launch_bounds__(256) void vt_prune_finish_kernel(unsigned* __restri
     atomicAdd(&s_sum[0], a);
     atomicAdd(&s_sum[1], b);
     __syncthreads();
-    if (threadIdx.x < 2) stat[threadIdx.x] = s_sum[threadIdx.x];
+    if (threadIdx.x == 0) {
+        const unsigned v = *verified;
+        *verified = 0u;
+        stat[0] = s_sum[0] + v;
+        stat[1] = s_sum[1];
+        stat[2] = v;
+    }
 }
 
 // ===========================================================================
@@ -1394,13 +1525,14 @@ struct rs_vt {
     uint32_t* dQsj = nullptr;        // QS_J of the queries in dQp (with dQp's capacity)
     uint32_t* dQsjStream = nullptr;  // ... of dQpStream
     uint32_t* dMinLB = nullptr;      // [ntb][nq]
+    uint32_t* dSecond = nullptr;     // [ntb][nq] (min2 << 6) | lane of the minimum
     int* dList = nullptr;            // list1 [ntb][nq], then list2 [ntb][nq]
-    size_t pruneCap = 0;             // ntb * nq the two are sized for
-    int* dTbStar = nullptr;          // [nq] candidate block
+    size_t pruneCap = 0;             // ntb * nq the three are sized for
+    int* dTbStar = nullptr;          // [nq] candidate block (~block: settled by verification)
     int tbStarCap = 0;
-    unsigned* dListCnt = nullptr;    // [2][listCntCap] entries per list; zero between calls
+    unsigned* dListCnt = nullptr;    // [2][listCntCap] entries per list, then the verified count; zero between calls
     int listCntCap = 0;
-    unsigned long long* dPruneStat = nullptr;  // list totals of the last pruned launch
+    unsigned long long* dPruneStat = nullptr;  // list totals and verified count of the last pruned launch
     int64_t prunePairs = 0;          // its ntb * nq
     int prunePasses = 0;             // its scan passes (0: no pruned launch yet)
     // on-device subsampling of camera frames (rs_vt_set_subsample / rs_vt_match_frames)
@@ -1727,11 +1859,14 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
             if (pairs > h->pruneCap) {
                 const size_t cap = std::max(pairs, 2 * h->pruneCap);
                 if (h->dMinLB) RS_HIP(hipFree(h->dMinLB));
+                if (h->dSecond) RS_HIP(hipFree(h->dSecond));
                 if (h->dList) RS_HIP(hipFree(h->dList));
                 h->dMinLB = nullptr;
+                h->dSecond = nullptr;
                 h->dList = nullptr;
                 h->pruneCap = 0;
                 RS_HIP(hipMalloc(&h->dMinLB, sizeof(uint32_t) * cap));
+                RS_HIP(hipMalloc(&h->dSecond, sizeof(uint32_t) * cap));
                 RS_HIP(hipMalloc(&h->dList, sizeof(int) * 2 * cap));
                 h->pruneCap = cap;
             }
@@ -1747,27 +1882,30 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
                 if (h->dListCnt) RS_HIP(hipFree(h->dListCnt));
                 h->dListCnt = nullptr;
                 h->listCntCap = 0;
-                RS_HIP(hipMalloc(&h->dListCnt, sizeof(unsigned) * 2 * (size_t)cap));
-                RS_HIP(hipMemsetAsync(h->dListCnt, 0, sizeof(unsigned) * 2 * (size_t)cap, h->stream));
+                RS_HIP(hipMalloc(&h->dListCnt, sizeof(unsigned) * (2 * (size_t)cap + 1)));
+                RS_HIP(hipMemsetAsync(h->dListCnt, 0, sizeof(unsigned) * (2 * (size_t)cap + 1), h->stream));
                 h->listCntCap = cap;
             }
             if (!h->dPruneStat) {
-                RS_HIP(hipMalloc(&h->dPruneStat, 2 * sizeof(unsigned long long)));
-                RS_HIP(hipMemsetAsync(h->dPruneStat, 0, 2 * sizeof(unsigned long long), h->stream));
+                RS_HIP(hipMalloc(&h->dPruneStat, 3 * sizeof(unsigned long long)));
+                RS_HIP(hipMemsetAsync(h->dPruneStat, 0, 3 * sizeof(unsigned long long), h->stream));
             }
             unsigned* cnt1 = h->dListCnt;
             unsigned* cnt2 = h->dListCnt + h->listCntCap;
+            unsigned* verified = h->dListCnt + 2 * (size_t)h->listCntCap;
             int* list1 = h->dList;
             int* list2 = h->dList + pairs;
             const int nqb = (nq + PF_NB - 1) / PF_NB, pfx = (ntb + PF_WAVES * PF_TPW - 1) / (PF_WAVES * PF_TPW);
             const dim3 pgrid((unsigned)pfx, (unsigned)std::min(nqb, std::max(1, 4096 / pfx)));
             hipLaunchKernelGGL(vt_prefilter_kernel, pgrid, dim3(64 * PF_WAVES), 0, h->stream, planes, ntb, count,
-                               reinterpret_cast<const uint4*>(h->dQp), h->dQsj, nq, h->dMinLB);
-            hipLaunchKernelGGL(vt_prune_pick_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, h->stream,
-                               h->dMinLB, ntb, nq, h->dTbStar);
+                               reinterpret_cast<const uint4*>(h->dQp), h->dQsj, nq, h->dMinLB,
+                               h->dSecond);
+            hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, h->dMinLB,
+                               h->dSecond, ntb, nq, planes, ts, reinterpret_cast<const uint4*>(h->dQp), h->dQsumRaw,
+                               out.best, rank, nranks, h->dTbStar);
             const dim3 lgrid((unsigned)((nq + VT_LIST_T - 1) / VT_LIST_T), (unsigned)ntb);
             hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar, cnt1,
-                               list1);
+                               list1, verified);
             // the passes min into the same keys; the folded export (out.host) needs one
             // launch to be the last, so a pruned call exports with vt_keys_export
             ScanOut po = out;
@@ -1775,14 +1913,14 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
             po.done = nullptr;
             hipLaunchKernelGGL((vt_scan_plane_kernel<64, false, true>), grid, dim3(64 * PL_CG * PL_SPLIT), 0,
                                h->stream, planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, po, rank,
-                               nranks, PlaneList{list1, cnt1, nq});
+                               nranks, PlaneList{list1, cnt1, nq, VT_LIST_PER_B1});
             hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB, nq,
                                h->dTbStar, out.best, cnt2, list2);
             hipLaunchKernelGGL((vt_scan_plane_kernel<64, false, true>), grid, dim3(64 * PL_CG * PL_SPLIT), 0,
                                h->stream, planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, po, rank,
-                               nranks, PlaneList{list2, cnt2, nq});
-            hipLaunchKernelGGL(vt_prune_finish_kernel, dim3(1), dim3(256), 0, h->stream, cnt1, cnt2, ntb,
-                               h->dPruneStat);
+                               nranks, PlaneList{list2, cnt2, nq, VT_LIST_PER});
+            hipLaunchKernelGGL(vt_prune_finish_kernel, dim3(1), dim3(256), 0, h->stream, cnt1, cnt2, verified,
+                               ntb, h->dPruneStat);
             if (out.host)
                 hipLaunchKernelGGL(vt_keys_export, dim3((nq + 255) / 256 < 64 ? (nq + 255) / 256 : 64), dim3(256), 0,
                                    h->stream, out.best, nq, out.host);
@@ -2346,7 +2484,7 @@ int rs_vt_destroy(rs_vt* h) {
                     (void*)h->dSrc, (void*)h->dDst, (void*)h->dCand, (void*)h->dMat, (void*)h->dLibP,
                     (void*)h->dLibTs, (void*)h->dCandP, (void*)h->dCandTs, (void*)h->dQp,
                     (void*)h->dQsumRaw, (void*)h->dCtr, (void*)h->dDone, (void*)h->dPix, (void*)h->dFrames,
-                    (void*)h->dQsj, (void*)h->dQsjStream, (void*)h->dMinLB, (void*)h->dList, (void*)h->dTbStar,
+                    (void*)h->dQsj, (void*)h->dQsjStream, (void*)h->dMinLB, (void*)h->dSecond, (void*)h->dList, (void*)h->dTbStar,
                     (void*)h->dListCnt, (void*)h->dPruneStat})
         if (p) (void)hipFree(p);
     if (h->hStream) (void)hipHostFree(h->hStream);
@@ -2581,6 +2719,19 @@ int rs_vt_prune_stats(rs_vt* h, int64_t out[4]) {
     out[1] = (int64_t)s[1];
     out[2] = h->prunePairs;
     out[3] = h->prunePasses;
+    return RS_OK;
+}
+
+int rs_vt_prune_verified(rs_vt* h, int64_t* out) {
+    rs::clear_error();
+    RS_CHECK(h && out, RS_ERR_ARG, "null argument");
+    *out = 0;
+    if (h->prunePasses == 0) return RS_OK;
+    RS_HIP(hipSetDevice(h->device));
+    unsigned long long v = 0ull;
+    RS_HIP(hipMemcpyAsync(&v, h->dPruneStat + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream));
+    *out = (int64_t)v;
     return RS_OK;
 }
 

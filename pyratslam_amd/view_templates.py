@@ -580,6 +580,14 @@ class ViewTemplates:
         _lib.check(self._lib.rs_vt_prune_stats(self._h, out))
         return tuple(int(v) for v in out)
 
+    def prune_verified(self):
+        """Of the last pruned scan launch: the queries settled by verifying the one
+        template the prefilter singled out, without a block scan in pass B1; 0 before
+        the first pruned scan (rs_vt_prune_verified)."""
+        out = ctypes.c_int64(0)
+        _lib.check(self._lib.rs_vt_prune_verified(self._h, ctypes.byref(out)))
+        return int(out.value)
+
 
 class ShardedViewTemplates(ViewTemplates):
     """Template library sharded round-robin over ranks (template g on rank g % n).

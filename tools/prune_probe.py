@@ -5,10 +5,11 @@
            1,000 templates at several query counts, RS_VT_PRUNE=0 against force: the
            query count from which pruning is faster (VT_PRUNE_MIN_Q)
   allmiss  the headline shape (10 x 1,024 HBM-resident queries, 1,000 templates) with
-           hit_frac = 0 and 0.9, RS_VT_PRUNE=0 against 1, with prune_stats; under
+           hit_frac = 0, 0.5 and 0.9, RS_VT_PRUNE=0 against 1, with prune_stats; under
            ``rocprofv3 --kernel-trace`` the trace holds the passes' own times
 
-usage: python tools/prune_probe.py [sweep] [allmiss] [--reps 20]"""
+usage: python tools/prune_probe.py [sweep] [allmiss] [--reps 20] [--lib OTHER.so]
+(--lib: another build of the library, e.g. the parent commit's, for a before/after)"""
 import argparse
 import json
 import os
@@ -42,8 +43,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('what', nargs='*', default=['sweep', 'allmiss'])
     ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--lib', default=None)
     a = ap.parse_args()
     from pyratslam_amd import _lib, synthetic
+    if a.lib:
+        _lib.load(a.lib)
+
+    def stats(h):   # with the verified count where the build has it
+        return list(h.prune_stats()) + ([h.prune_verified()] if hasattr(_lib.load(), 'rs_vt_prune_verified') else [])
     lib = synthetic.library(1000, seed=1)
     hs = {p: handle(p) for p in ('0', '1', 'force')}
     for h in hs.values():
@@ -57,7 +64,7 @@ def main():
         for nq in (64, 96, 128, 192, 256, 384, 512, 1024, 2048, 4096):
             q = synthetic.queries_fast(lib, nq, seed=7 + nq)[0]
             buf = _lib.DeviceBuffer(q.nbytes).upload(q)
-            rec = {'probe': 'sweep', 'templates': 1000, 'queries': nq}
+            rec = {'probe': 'sweep', 'lib': a.lib or 'tree', 'templates': 1000, 'queries': nq}
             outs = {}
             for p in ('0', 'force'):
                 med, mn, outs[p] = timed(hs[p], (2, nq // 2, buf), a.reps)   # two batches: one timed scan launch
@@ -65,14 +72,14 @@ def main():
                 rec['ms_min_prune_' + p] = round(mn, 5)
             rec['same_keys'] = bool(np.array_equal(outs['0'][0], outs['force'][0]) and
                                     np.array_equal(outs['0'][1], outs['force'][1]))
-            rec['prune_stats'] = hs['force'].prune_stats()
+            rec['prune_stats'] = stats(hs['force'])
             print(json.dumps(rec), flush=True)
             buf.close()
     if 'allmiss' in a.what:
-        for hit in (0.0, 0.9):
+        for hit in (0.0, 0.5, 0.9):
             qs = np.stack([synthetic.queries_fast(lib, 1024, seed=2 + 1000 * b, hit_frac=hit)[0] for b in range(10)])
             buf = _lib.DeviceBuffer(qs.nbytes).upload(qs)
-            rec = {'probe': 'allmiss', 'hit_frac': hit, 'templates': 1000, 'queries': 10240}
+            rec = {'probe': 'allmiss', 'lib': a.lib or 'tree', 'hit_frac': hit, 'templates': 1000, 'queries': 10240}
             outs = {}
             for p in ('0', '1'):
                 med, mn, outs[p] = timed(hs[p], (10, 1024, buf), a.reps)
@@ -80,7 +87,7 @@ def main():
                 rec['ms_min_prune_' + p] = round(mn, 5)
             rec['same_keys'] = bool(np.array_equal(outs['0'][0], outs['1'][0]) and
                                     np.array_equal(outs['0'][1], outs['1'][1]))
-            rec['prune_stats'] = hs['1'].prune_stats()
+            rec['prune_stats'] = stats(hs['1'])
             print(json.dumps(rec), flush=True)
             buf.close()
     for h in hs.values():
