@@ -389,6 +389,14 @@ static_assert(PF_NU == 1 || PF_NU == 2, "one or two prefilter units");
 __host__ __device__ constexpr int pf_unit(int u) { return PF_NU == 1 ? 7 : (u == 0 ? 5 : 10); }
 static_assert(4 * pf_unit(0) - (FAST_M - 1) >= FAST_M && 4 * pf_unit(PF_NU - 1) + FAST_M + 2 <= 64 - FAST_M - 1,
               "the units' query rows lie inside the window at every offset");
+// The bound is taken over column groups 0 .. PF_CGS-1 of a unit only (columns 0 .. 8*PF_CGS-1
+// of its 4 rows): any subset of a score's byte pairs sums to a lower bound of it, and half
+// a unit (64 pairs) still separates a hit's bound from every other template's by a wide
+// margin.  4 = the whole unit.
+#ifndef VT_PF_CGS
+#define VT_PF_CGS 2
+#endif
+constexpr int PF_CGS = VT_PF_CGS;
 
 // One block per stored template: planes + TS of raw template src[t] into slot dst[t].
 __global__ __launch_bounds__(256) void vt_plane_store_kernel(const uint8_t* __restrict__ raw,
@@ -463,7 +471,8 @@ __device__ inline void transpose4x4_bytes(uint32_t a, uint32_t b, uint32_t c, ui
 // the segment to QS.  Phase 2: each thread assembles one unit (4 rows from start
 // row S0 + si, column group cg): plane k = byte k of its 4 segments, two 16-byte
 // stores.  Bit b of plane k = bit k of pixel (row + b/8, col 8cg + b%8).
-// With a prune buffer (qsj, H = 64): also QS_J(S), the byte sum of rows S..S+3, for
+// With a prune buffer (qsj, H = 64): also QS_J(S), the byte sum of columns
+// 0 .. 8*PF_CGS-1 of rows S..S+3 (the pairs the prefilter's bound covers), for
 // the start rows S = 4J+7-x, x = 0..2M-2, that prefilter unit J meets
 // (qsj[(query * PF_NU + u) * 16 + x]).
 __global__ __launch_bounds__(256) void vt_qplane_kernel(const uint8_t* __restrict__ raw, int H,
@@ -474,7 +483,7 @@ __global__ __launch_bounds__(256) void vt_qplane_kernel(const uint8_t* __restric
     constexpr int W = 8 * PL_CG;
     __shared__ uint32_t s_red[4];
     __shared__ uint2 s_t[64 * W / 8];   // transposed segments (H <= 64)
-    __shared__ uint32_t s_rs[64];       // byte sums of the rows (prune buffer only)
+    __shared__ uint32_t s_rs[64];       // byte sums of the rows' first PF_CGS column groups (prune buffer only)
     if (qsj) {   // (kernel argument: uniform)
         if (threadIdx.x < 64) s_rs[threadIdx.x] = 0u;
         __syncthreads();
@@ -491,7 +500,9 @@ __global__ __launch_bounds__(256) void vt_qplane_kernel(const uint8_t* __restric
         const int r = d / (W / 8);
         const bool live = r >= M && r < H - M;
         if (live) part = __builtin_amdgcn_sad_u8(v.y, 0u, __builtin_amdgcn_sad_u8(v.x, 0u, part));
-        if (qsj) atomicAdd(&s_rs[r], __builtin_amdgcn_sad_u8(v.y, 0u, __builtin_amdgcn_sad_u8(v.x, 0u, 0u)));
+        // (d = row * PL_CG + column group: only the groups the prefilter's bound covers)
+        if (qsj && d % PL_CG < PF_CGS)
+            atomicAdd(&s_rs[r], __builtin_amdgcn_sad_u8(v.y, 0u, __builtin_amdgcn_sad_u8(v.x, 0u, 0u)));
         transpose8x8(v.x, v.y);
         s_t[d] = live ? v : make_uint2(0u, 0u);
     }
@@ -1011,7 +1022,8 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
 // of a score is >= 0, so the sum over the byte pairs of PF_NU template units,
 //   LB(t, q, o) = sum_J  TS_J(t) - QS_J(q, 4J - o) + 256 * B_J(t, q, o)
 // (TS_J the unit's byte sum, QS_J the byte sum of the four query rows it meets at
-// offset o, B_J their borrow count), is an exact lower bound of score(t, q, o), and
+// offset o, B_J their borrow count, all three over the unit's first PF_CGS column groups
+// only), is an exact lower bound of score(t, q, o), and
 // minLB[tb][q] = min over the block's templates and the offsets bounds every score of
 // template block tb against q.  Pass B1 scans each query against its candidate block
 // tb* = argmin_tb minLB (lowest on ties) only, which leaves an upper bound U(q) in
@@ -1020,16 +1032,37 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
 // out has minLB > U(q) >= the minimum, so none of its scores is the minimum.
 constexpr int PF_WAVES = 4;   // waves per thread block
 // Template blocks per wave: every staged query plane is read once (an LDS broadcast)
-// for both, which halves the LDS reads per VALU instruction: at one block per wave,
-// 120 ds_read_b128 against 600 VALU per query, the reads set the pace (167 us against
-// 135 us at the dense scan's VALU rate, headline shape).  Two units of two blocks
+// for all of them, which divides the LDS reads per VALU instruction: at one block per
+// wave and a whole unit, 120 ds_read_b128 against 600 VALU per query, the reads set the
+// pace (167 us against 135 us at the dense scan's VALU rate, headline shape).  A wave
+// holds 64 plane VGPRs: two blocks of a whole unit, or four of half a unit (one
+// ds_read_b128 per 18 VALU, the dense walk's ratio).  Two whole units of two blocks
 // would not fit the VGPRs.
 #ifndef VT_PF_TPW
-#define VT_PF_TPW (VT_PF_UNITS == 1 ? 2 : 1)
+#define VT_PF_TPW (VT_PF_UNITS == 1 ? 8 / (VT_PF_CGS) : 1)
 #endif
 constexpr int PF_TPW = VT_PF_TPW;
+// 1: the staged planes of the next step are read while this step's chains run.  Kept for
+// A/B builds: measured no faster at two or at four blocks per wave.
+#ifndef VT_PF_AHEAD
+#define VT_PF_AHEAD 0
+#endif
+constexpr bool PF_AHEAD = VT_PF_AHEAD != 0;
+// Column groups per step of the walk: PF_TPW * PF_CPS independent borrow chains, four as
+// the whole unit's two blocks had (two groups of four blocks at once: 117 VGPRs, and
+// measured slower).
+#ifndef VT_PF_CPS
+#define VT_PF_CPS (VT_PF_TPW >= 4 ? 1 : 2)
+#endif
+constexpr int PF_CPS = VT_PF_CPS;
+// Upper limit of the prefilter's thread blocks: beyond it a thread block takes several
+// batches of PF_NB queries and loads its template planes once for them (2048 and 1024
+// measured slower than 4096 at the headline shape).
+#ifndef VT_PF_GRID_CAP
+#define VT_PF_GRID_CAP 4096
+#endif
 constexpr int PF_NB = 4;      // queries staged per step
-constexpr int PF_QW4 = PF_NU * PL_CG * PL_NO * 2;   // staged uint4 per query
+constexpr int PF_QW4 = PF_NU * PF_CGS * PL_NO * 2;   // staged uint4 per query
 constexpr uint32_t PF_NONE = (1u << 26) - 1u;       // "no other template": above every score
 
 // Wave-wide minimum as a wave-uniform value, without the LDS pipe (the prefilter's pace
@@ -1048,9 +1081,10 @@ __device__ __forceinline__ uint32_t wave_min_u32_dpp(uint32_t v) {
 // minlb[tb * nq + q], and second[tb * nq + q] = (min2 << 6) | lane: the lane that holds
 // the block's minimum (the lowest on ties) and min2, the minimum over the block's other
 // valid templates (PF_NONE when it has no other).  The pick verifies that one template
-// (vt_prune_verify_kernel).  Lane = template; the wave keeps the PF_NU units of its PF_TPW
-// template blocks in VGPRs and reads the staged query planes as wave-uniform LDS
-// broadcasts, two column groups at a time (2 * PF_TPW independent borrow chains).
+// (vt_prune_verify_kernel).  Lane = template; the wave keeps the first PF_CGS column groups
+// of the PF_NU units of its PF_TPW template blocks in VGPRs and reads the staged query
+// planes as wave-uniform LDS broadcasts, PF_CPS column groups at a time (PF_CPS * PF_TPW
+// independent borrow chains).
 __global__ __launch_bounds__(64 * PF_WAVES) __attribute__((amdgpu_waves_per_eu(4)))
 void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
                                                                     int64_t count,
@@ -1059,14 +1093,14 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
                                                                     uint32_t* __restrict__ minlb,
                                                                     uint32_t* __restrict__ second) {
     constexpr int M = FAST_M, NU = 64 / 4, NS = PlaneLds<64>::NS, S0 = M - 3;
-    static_assert(PL_CG % 2 == 0, "column groups in pairs");
-    static_assert(PF_NU * 128 * 255 < (int)PF_NONE, "a bound and a lane fit one word");
-    __shared__ uint4 s_q[PF_NB][PF_NU][PL_CG][PL_NO][2];
+    static_assert(PF_CGS % PF_CPS == 0 && PF_CGS >= 1 && PF_CGS <= PL_CG, "whole steps of column groups, of the unit");
+    static_assert(PF_NU * PF_CGS * 32 * 255 < (int)PF_NONE, "a bound and a lane fit one word");
+    __shared__ uint4 s_q[PF_NB][PF_NU][PF_CGS][PL_NO][2];
     __shared__ uint32_t s_qs[PF_NB][PF_NU][16];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int tb0 = (blockIdx.x * PF_WAVES + wave) * PF_TPW;
     const bool live = tb0 < ntb;   // wave-uniform; a wave past the library still stages
-    uint32_t P[PF_TPW][PF_NU][PL_CG][8], ts[PF_TPW][PF_NU];
+    uint32_t P[PF_TPW][PF_NU][PF_CGS][8], ts[PF_TPW][PF_NU];
     bool valid[PF_TPW];
 #pragma unroll
     for (int t = 0; t < PF_TPW; ++t) {
@@ -1076,7 +1110,7 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
         for (int u = 0; u < PF_NU; ++u) {
             ts[t][u] = 0u;
 #pragma unroll
-            for (int cg = 0; cg < PL_CG; ++cg) {
+            for (int cg = 0; cg < PF_CGS; ++cg) {
                 const uint4* src = planes + ((size_t)(tbc * PL_CG + cg) * NU + pf_unit(u)) * 128 + lane;
                 const uint4 a = src[0], b = src[64];
                 uint32_t(&p)[8] = P[t][u][cg];
@@ -1092,9 +1126,9 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
         __syncthreads();   // the batch before has been read
         for (int i = threadIdx.x; i < nb * PF_QW4; i += blockDim.x) {
             const int qq = i / PF_QW4, r = i - qq * PF_QW4;
-            const int u = r / (PL_CG * PL_NO * 2), r2 = r - u * (PL_CG * PL_NO * 2);
+            const int u = r / (PF_CGS * PL_NO * 2), r2 = r - u * (PF_CGS * PL_NO * 2);
             const int cg = r2 / (PL_NO * 2), w = r2 - cg * (PL_NO * 2);
-            // start rows 4J-(M-1) .. 4J+(M-1) of column group cg, two uint4 each
+            // start rows 4J-(M-1) .. 4J+(M-1) of column group cg < PF_CGS, two uint4 each
             (&s_q[0][0][0][0][0])[i] =
                 qp4[((size_t)(q0 + qq) * PL_CG + cg) * (NS * 2) + (4 * pf_unit(u) - (M - 1) - S0) * 2 + w];
         }
@@ -1107,6 +1141,18 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
             uint32_t m[PF_TPW];
 #pragma unroll
             for (int t = 0; t < PF_TPW; ++t) m[t] = 0xFFFFFFFFu;
+            // the planes of offset x, unit u, column groups cp .. cp + PF_CPS - 1
+            auto read_q = [&](int x, int u, int cp, uint32_t(&q)[PF_CPS][8]) {
+#pragma unroll
+                for (int i = 0; i < PF_CPS; ++i) {
+                    const uint4 lo = s_q[qq][u][cp + i][PL_NO - 1 - x][0];
+                    const uint4 hi = s_q[qq][u][cp + i][PL_NO - 1 - x][1];
+                    q[i][0] = lo.x; q[i][1] = lo.y; q[i][2] = lo.z; q[i][3] = lo.w;
+                    q[i][4] = hi.x; q[i][5] = hi.y; q[i][6] = hi.z; q[i][7] = hi.w;
+                }
+            };
+            uint32_t qn[PF_CPS][8];   // (PF_AHEAD) the step after this one's
+            if (PF_AHEAD) read_q(0, 0, 0, qn);
 #pragma unroll
             for (int x = 0; x < PL_NO; ++x) {   // offset o = x - (M-1): start row 4J - o
                 uint32_t lb[PF_TPW];
@@ -1118,27 +1164,30 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
 #pragma unroll
                     for (int t = 0; t < PF_TPW; ++t) c[t] = 0u;
 #pragma unroll
-                    for (int cp = 0; cp < PL_CG; cp += 2) {
-                        uint32_t q[2][8], b[PF_TPW][2];
+                    for (int cp = 0; cp < PF_CGS; cp += PF_CPS) {
+                        uint32_t q[PF_CPS][8], b[PF_TPW][PF_CPS];
+                        if (!PF_AHEAD) {
+                            read_q(x, u, cp, q);
+                        } else {
 #pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            const uint4 lo = s_q[qq][u][cp + i][PL_NO - 1 - x][0];
-                            const uint4 hi = s_q[qq][u][cp + i][PL_NO - 1 - x][1];
-                            q[i][0] = lo.x; q[i][1] = lo.y; q[i][2] = lo.z; q[i][3] = lo.w;
-                            q[i][4] = hi.x; q[i][5] = hi.y; q[i][6] = hi.z; q[i][7] = hi.w;
+                            for (int i = 0; i < PF_CPS; ++i)
+#pragma unroll
+                                for (int k = 0; k < 8; ++k) q[i][k] = qn[i][k];
+                            const bool cw = cp + PF_CPS >= PF_CGS, uw = cw && u + 1 >= PF_NU;
+                            if (!uw || x + 1 < PL_NO) read_q(uw ? x + 1 : x, uw ? 0 : (cw ? u + 1 : u), cw ? 0 : cp + PF_CPS, qn);
                         }
 #pragma unroll
                         for (int k = 0; k < 8; ++k)
 #pragma unroll
                             for (int t = 0; t < PF_TPW; ++t)
 #pragma unroll
-                                for (int i = 0; i < 2; ++i)
+                                for (int i = 0; i < PF_CPS; ++i)
                                     b[t][i] = __builtin_amdgcn_bitop3_b32(P[t][u][cp + i][k], q[i][k],
                                                                           k ? b[t][i] : 0u, 0x8E);
 #pragma unroll
                         for (int t = 0; t < PF_TPW; ++t)
 #pragma unroll
-                            for (int i = 0; i < 2; ++i)
+                            for (int i = 0; i < PF_CPS; ++i)
                                 asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(c[t]) : "v"(b[t][i]), "v"(c[t]));
                         // (the max-ILP scheduler would pull the reads of many offsets ahead and
                         // spill; the SIMD's other waves cover this wave's read latency)
@@ -1152,17 +1201,25 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
 #pragma unroll
                 for (int t = 0; t < PF_TPW; ++t) m[t] = min(m[t], lb[t]);
             }
+            // All the reductions before the first store: behind a store's branch, a block's
+            // running minimum is used in a later basic block only, its updates sink there,
+            // and the 15 counts per block they wait for stay live (spills at four blocks).
+            uint32_t v[PF_TPW], w[PF_TPW];
 #pragma unroll
             for (int t = 0; t < PF_TPW; ++t) {
                 // value and lane in one reduction (a bound is below 2^26; the lowest lane on
                 // ties), then the minimum over the valid templates other than that lane
-                const uint32_t v = wave_min_u32_dpp(valid[t] ? (m[t] << 6) | (uint32_t)lane : 0xFFFFFFFFu);
-                const uint32_t w = wave_min_u32_dpp(valid[t] && lane != (int)(v & 63u) ? m[t] : PF_NONE);
-                if (lane == 0 && tb0 + t < ntb) {
-                    // (a block of the library holds a valid template: v is a packed bound)
-                    minlb[(size_t)(tb0 + t) * nq + q0 + qq] = v >> 6;
-                    second[(size_t)(tb0 + t) * nq + q0 + qq] = (w << 6) | (v & 63u);
-                }
+                v[t] = wave_min_u32_dpp(valid[t] ? (m[t] << 6) | (uint32_t)lane : 0xFFFFFFFFu);
+                w[t] = wave_min_u32_dpp(valid[t] && lane != (int)(v[t] & 63u) ? m[t] : PF_NONE);
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int t = 0; t < PF_TPW; ++t)
+                    if (tb0 + t < ntb) {
+                        // (a block of the library holds a valid template: v is a packed bound)
+                        minlb[(size_t)(tb0 + t) * nq + q0 + qq] = v[t] >> 6;
+                        second[(size_t)(tb0 + t) * nq + q0 + qq] = (w[t] << 6) | (v[t] & 63u);
+                    }
             }
         }
     }
@@ -1896,7 +1953,7 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
             int* list1 = h->dList;
             int* list2 = h->dList + pairs;
             const int nqb = (nq + PF_NB - 1) / PF_NB, pfx = (ntb + PF_WAVES * PF_TPW - 1) / (PF_WAVES * PF_TPW);
-            const dim3 pgrid((unsigned)pfx, (unsigned)std::min(nqb, std::max(1, 4096 / pfx)));
+            const dim3 pgrid((unsigned)pfx, (unsigned)std::min(nqb, std::max(1, VT_PF_GRID_CAP / pfx)));
             hipLaunchKernelGGL(vt_prefilter_kernel, pgrid, dim3(64 * PF_WAVES), 0, h->stream, planes, ntb, count,
                                reinterpret_cast<const uint4*>(h->dQp), h->dQsj, nq, h->dMinLB,
                                h->dSecond);

@@ -8,8 +8,10 @@
            hit_frac = 0, 0.5 and 0.9, RS_VT_PRUNE=0 against 1, with prune_stats; under
            ``rocprofv3 --kernel-trace`` the trace holds the passes' own times
 
-usage: python tools/prune_probe.py [sweep] [allmiss] [--reps 20] [--lib OTHER.so]
-(--lib: another build of the library, e.g. the parent commit's, for a before/after)"""
+usage: python tools/prune_probe.py [sweep] [allmiss] [--reps 20] [--lib OTHER.so] [--noise N]
+(--lib: another build of the library, e.g. the parent commit's, for a before/after;
+--noise: a hit is its template lowered by 0..N per pixel, 3 as the bench's: the larger, the
+closer a hit's score comes to the other blocks' bounds and the less the prefilter prunes)"""
 import argparse
 import json
 import os
@@ -44,6 +46,7 @@ def main():
     ap.add_argument('what', nargs='*', default=['sweep', 'allmiss'])
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--lib', default=None)
+    ap.add_argument('--noise', type=int, default=3)
     a = ap.parse_args()
     from pyratslam_amd import _lib, synthetic
     if a.lib:
@@ -62,9 +65,9 @@ def main():
         hs['0'].match_stream((2, 512, wbuf))
     if 'sweep' in a.what:
         for nq in (64, 96, 128, 192, 256, 384, 512, 1024, 2048, 4096):
-            q = synthetic.queries_fast(lib, nq, seed=7 + nq)[0]
+            q = synthetic.queries_fast(lib, nq, seed=7 + nq, noise=a.noise)[0]
             buf = _lib.DeviceBuffer(q.nbytes).upload(q)
-            rec = {'probe': 'sweep', 'lib': a.lib or 'tree', 'templates': 1000, 'queries': nq}
+            rec = {'probe': 'sweep', 'lib': a.lib or 'tree', 'noise': a.noise, 'templates': 1000, 'queries': nq}
             outs = {}
             for p in ('0', 'force'):
                 med, mn, outs[p] = timed(hs[p], (2, nq // 2, buf), a.reps)   # two batches: one timed scan launch
@@ -77,9 +80,9 @@ def main():
             buf.close()
     if 'allmiss' in a.what:
         for hit in (0.0, 0.5, 0.9):
-            qs = np.stack([synthetic.queries_fast(lib, 1024, seed=2 + 1000 * b, hit_frac=hit)[0] for b in range(10)])
+            qs = np.stack([synthetic.queries_fast(lib, 1024, seed=2 + 1000 * b, hit_frac=hit, noise=a.noise)[0] for b in range(10)])
             buf = _lib.DeviceBuffer(qs.nbytes).upload(qs)
-            rec = {'probe': 'allmiss', 'lib': a.lib or 'tree', 'hit_frac': hit, 'templates': 1000, 'queries': 10240}
+            rec = {'probe': 'allmiss', 'lib': a.lib or 'tree', 'noise': a.noise, 'hit_frac': hit, 'templates': 1000, 'queries': 10240}
             outs = {}
             for p in ('0', '1'):
                 med, mn, outs[p] = timed(hs[p], (10, 1024, buf), a.reps)
