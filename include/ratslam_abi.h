@@ -114,7 +114,10 @@ typedef struct rs_pc_params {
     double gi[RS_FILTER_LEN];
     double k_scale;             /* 1 / |sum(ge^3 - gi^3)|                         */
     /* table of 7x7 path-integration filters (posecell_network.py:47,50-59),
-     * row-major [nfilters][7][7], F[x][y] with x along the first grid axis */
+     * row-major [nfilters][7][7], F[x][y] with x along the first grid axis.
+     * A table of more than 8 filters needs Y <= 128 (only the "rows" step kernels read
+     * a table that is not staged in LDS); on a wider grid rs_pc_create returns
+     * RS_ERR_ARG */
     int nfilters;
     const double* xy_filters;
 } rs_pc_params;
@@ -200,8 +203,8 @@ int rs_pc_set_profiling(rs_pc* h, int enable);
 int rs_pc_kernel_ms(rs_pc* h, double ms[2]);
 /* step kernels in use: "rows" (row-tiled excite + path launches, Y <= 128),
  * "cols" (column tiles through all layers, large grids), "halo" (one launch per
- * step, the excitation recomputed on each tile's halo; float32, TH = 36, 18 or 10), "stream"
- * (layer streaming, large grids outside the column form's limits) or "tiles" (3-D tiles) */
+ * step, the excitation recomputed on each tile's halo; float32, TH = 36, 18 or 10) or
+ * "stream" (layer streaming, large grids outside the column form's limits) */
 const char* rs_pc_step_form(const rs_pc* h);
 /* Test hooks (no reference counterpart):
  *   RS_PC_DBG_POISON       fill every buffer a step writes before it reads (the

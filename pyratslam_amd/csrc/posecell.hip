@@ -1,26 +1,31 @@
 // Pose-cell network step on MI355X (gfx950).
 //
-// Replaces PoseCellNetwork.update (/root/reference/ratslam/posecell_network.py:326-353)
+// Replaces PoseCellNetwork.update (the reference's ratslam/posecell_network.py:326-353)
 // and the three OpenCL kernels it drives through Convolution.conv_im
 // (convolution.py:228-246 `conv`, :320-340 `conv_xy_origin_filters`,
 // :344-359 `conv_z`) plus the host-side numpy passes between them.
 //
-// Device layout: the volume is stored layer-major, P[th][x][y] (y fastest), so
-// each theta layer -- the unit the path-integration shift acts on -- is one
-// contiguous periodic 2-D image.  The reference's C-order (x, y, th) appears
-// only at the boundary (rs_pc_read/write) and in the argmax tie-break index.
+// A step: the 3-D DoG excitation as the exact rank-2 separable form (ge^3 - gi^3)*scale,
+// three 7-tap passes per Gaussian, the global inhibition relu(v - 0.2) and per-block
+// float64 partial sums of the total; then the per-layer shifted 7x7 filter (path
+// integration), clamp, 7-tap theta filter, clamp, the division by the total and the
+// argmax (first max in the reference's C order).  max(conv(Q/t), 0) == max(conv(Q), 0)/t
+// for t > 0, so the normalisation is applied once, at the end of the step.
 //
-// One update() = two kernels on one stream:
-//   pc_excite : 3-D DoG excitation as the exact rank-2 separable form
-//               (ge^3 - gi^3)*scale, three 7-tap passes per Gaussian staged in
-//               LDS, fused with the global inhibition relu(v - 0.2) and a
-//               per-block float64 partial sum (normalisation total).
-//   pc_path   : sums the partials (-> total), per-layer shifted 7x7 filter
-//               (path integration), clamp, 7-tap theta filter, clamp, divide by
-//               total, write the new state, fused argmax (first max in the
-//               reference's C order) via a packed 64-bit atomicMax.
-// max(conv(Q/t), 0) == max(conv(Q), 0)/t for t > 0, so the normalisation is
-// applied once, at the end of the step.
+// Four kernel families ("forms"), one per handle (rs_pc::form, chosen by pc_choose_form):
+//   rows   : pc_excite_rows + pc_path_rows, a block owns a few layers and rows over the
+//            whole Y extent (Y <= 128); small grids, and any filter table too large for LDS
+//   stream : pc_excite_stream + pc_path_stream, a block walks a chunk of layers behind a
+//            prefetch ring; large grids outside the column form's limits
+//   cols   : pc_excite_cols + pc_path_cols, a block owns an 8 x 8 tile through all layers
+//            (or a theta chunk); large grids
+//   halo   : pc_step_halo, one launch per step: a block owns a 4 x 4 tile through all
+//            layers and recomputes the excitation on its halo (float32, small grids)
+// rows and stream keep the volume layer-major, P[th][x][y] (y fastest): each theta layer,
+// the unit the path-integration shift acts on, is one contiguous periodic 2-D image.
+// cols and halo keep it theta-fastest, P[x][y][th], the reference's C order (pc_thfast):
+// their blocks hold whole theta columns.  Q has P's layout.  Elsewhere the reference's
+// order appears only in rs_pc_read/write and in the argmax tie-break index.
 #include <type_traits>
 #include <utility>
 #include <hip/hip_runtime.h>
@@ -187,10 +192,6 @@ __device__ inline void st_wt(V* p, V v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Tile shapes (output cells per block = BK layers x BX rows x BY cols).
-constexpr int EX_BX = 8, EX_BY = 16, EX_BK = 4;
-constexpr int PI_BX = 8, PI_BY = 16, PI_BK = 4;
-
 // Deterministic block sum of one double per thread (same value returned to all).
 __device__ inline double block_sum(double v, double* s_red) {
 #pragma unroll
@@ -203,221 +204,6 @@ __device__ inline double block_sum(double v, double* s_red) {
     for (int i = 0; i < NT / 64; ++i) t += s_red[i];
     __syncthreads();
     return t;
-}
-
-// ---------------------------------------------------------------------------
-// Kernel 1: excitation (3-D DoG, separable) + global inhibition + partial sums
-// posecell_network.py:336-343 (conv -> inhibit -> sum)
-// ---------------------------------------------------------------------------
-template <typename T, int BX, int BY, int BK>
-__global__ __launch_bounds__(NT) void pc_excite_kernel(const T* __restrict__ P, T* __restrict__ Q,
-                                                        double* __restrict__ part,
-                                                        unsigned long long* __restrict__ res_slot,
-                                                        int X, int Y, int TH, SepKernel<T> k) {
-    constexpr int HX = BX + 2 * HALF, HY = BY + 2 * HALF, HK = BK + 2 * HALF;
-    __shared__ T s_in[HK * HX * HY];
-    __shared__ T s_ey[HK * HX * BY];
-    __shared__ T s_iy[HK * HX * BY];
-    __shared__ T s_exy[HK * BX * BY];
-    __shared__ T s_ixy[HK * BX * BY];
-    __shared__ double s_red[NT / 64];
-
-    const int tid = threadIdx.x;
-    const int j0 = blockIdx.x * BY, i0 = blockIdx.y * BX, k0 = blockIdx.z * BK;
-    if (res_slot != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
-        for (int i = tid; i < RES_SLOTS; i += NT) st_wt(&res_slot[i], 0ull);  // this step's path kernel max-reduces into them
-
-    for (int idx = tid; idx < HK * HX * HY; idx += NT) {
-        const int kk = idx / (HX * HY);
-        const int rem = idx - kk * (HX * HY);
-        const int a = rem / HY, b = rem - a * HY;
-        const int L = rs::wrapi(k0 - HALF + kk, TH);
-        const int r = rs::wrapi(i0 - HALF + a, X);
-        const int c = rs::wrapi(j0 - HALF + b, Y);
-        s_in[idx] = P[((size_t)L * X + r) * Y + c];
-    }
-    __syncthreads();
-
-    // pass along y (contiguous axis)
-    for (int idx = tid; idx < HK * HX * BY; idx += NT) {
-        const int row = idx / BY, j = idx - row * BY;
-        const T* src = s_in + row * HY + j;
-        T e = 0, g = 0;
-#pragma unroll
-        for (int t = 0; t < FL; ++t) {
-            const T v = src[t];
-            e += k.ge[t] * v;
-            g += k.gi[t] * v;
-        }
-        s_ey[idx] = e;
-        s_iy[idx] = g;
-    }
-    __syncthreads();
-
-    // pass along x
-    for (int idx = tid; idx < HK * BX * BY; idx += NT) {
-        const int kk = idx / (BX * BY);
-        const int rem = idx - kk * (BX * BY);
-        const int i = rem / BY, j = rem - i * BY;
-        const int base = (kk * HX + i) * BY + j;
-        T e = 0, g = 0;
-#pragma unroll
-        for (int t = 0; t < FL; ++t) {
-            e += k.ge[t] * s_ey[base + t * BY];
-            g += k.gi[t] * s_iy[base + t * BY];
-        }
-        s_exy[idx] = e;
-        s_ixy[idx] = g;
-    }
-    __syncthreads();
-
-    // pass along theta, then relu(v - inhib) (posecell_network.py:339-340)
-    double sum = 0.0;
-    for (int idx = tid; idx < BK * BX * BY; idx += NT) {
-        const int kq = idx / (BX * BY);
-        const int rem = idx - kq * (BX * BY);
-        const int i = rem / BY, j = rem - i * BY;
-        const int gk = k0 + kq, gi = i0 + i, gj = j0 + j;
-        if (gk < TH && gi < X && gj < Y) {
-            T e = 0, g = 0;
-#pragma unroll
-            for (int t = 0; t < FL; ++t) {
-                e += k.ge[t] * s_exy[idx + t * BX * BY];
-                g += k.gi[t] * s_ixy[idx + t * BX * BY];
-            }
-            const T v = (e - g) * k.scale;
-            const T q = (v < k.inhib) ? T(0) : v - k.inhib;
-            Q[((size_t)gk * X + gi) * Y + gj] = q;
-            sum += (double)q;
-        }
-    }
-    sum = block_sum(sum, s_red);
-    if (tid == 0) st_wt(&part[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x], sum);
-}
-
-// ---------------------------------------------------------------------------
-// Kernel 2: path integration (posecell_network.py:252-314) + normalisation
-// (:343-345, applied at the end) + argmax (:317-319)
-// ---------------------------------------------------------------------------
-template <typename T, int BX, int BY, int BK, typename CTL>
-__global__ __launch_bounds__(NT) void pc_path_kernel(
-    const T* __restrict__ Q, T* __restrict__ P, const double* __restrict__ part, int npart,
-    const T* __restrict__ filt, CTL ctl, unsigned long long* __restrict__ res_slot,
-    T* __restrict__ bmax, unsigned* __restrict__ bidx, int X, int Y, int TH) {
-    constexpr int HX = BX + 2 * HALF, HY = BY + 2 * HALF, HK = BK + 2 * HALF;
-    __shared__ T s_win[HK * HX * HY];
-    __shared__ T s_r[HK * BX * BY];
-    __shared__ T s_f[HK * FT];
-    __shared__ int s_ox[HK], s_oy[HK];
-    __shared__ T s_zf[FL];
-    __shared__ double s_red[NT / 64];
-    __shared__ T s_bv[NT / 64];
-    __shared__ unsigned s_bl[NT / 64];
-
-    const int tid = threadIdx.x;
-    const int j0 = blockIdx.x * BY, i0 = blockIdx.y * BX, k0 = blockIdx.z * BK;
-
-    // normalisation total = sum of the excitation kernel's partials (fixed order)
-    double tot = 0.0;
-    for (int i = tid; i < npart; i += NT) tot += part[i];
-    tot = block_sum(tot, s_red);
-
-    if (tid < HK) {
-        const int L = rs::wrapi(k0 - HALF + tid, TH);
-        s_ox[tid] = ctl_ox(ctl, L);
-        s_oy[tid] = ctl_oy(ctl, L);
-    }
-    if (tid < FL) s_zf[tid] = (T)ctl_zf(ctl, tid);
-    for (int idx = tid; idx < HK * FT; idx += NT) {
-        const int kk = idx / FT, tap = idx - kk * FT;
-        const int L = rs::wrapi(k0 - HALF + kk, TH);
-        s_f[idx] = filt[ctl_fi(ctl, L) * FT + tap];
-    }
-    __syncthreads();
-
-    // shifted window of every layer this tile (plus theta halo) needs
-    for (int idx = tid; idx < HK * HX * HY; idx += NT) {
-        const int kk = idx / (HX * HY);
-        const int rem = idx - kk * (HX * HY);
-        const int a = rem / HY, b = rem - a * HY;
-        const int L = rs::wrapi(k0 - HALF + kk, TH);
-        const int r = rs::wrapi(i0 - HALF + s_ox[kk] + a, X);
-        const int c = rs::wrapi(j0 - HALF + s_oy[kk] + b, Y);
-        s_win[idx] = Q[((size_t)L * X + r) * Y + c];
-    }
-    __syncthreads();
-
-    // per-layer 7x7 correlation with the layer's filter, clamp (:300)
-    for (int idx = tid; idx < HK * BX * BY; idx += NT) {
-        const int kk = idx / (BX * BY);
-        const int rem = idx - kk * (BX * BY);
-        const int i = rem / BY, j = rem - i * BY;
-        const T* w = s_win + (kk * HX + i) * HY + j;
-        const T* f = s_f + kk * FT;
-        T acc = 0;
-#pragma unroll
-        for (int x = 0; x < FL; ++x)
-#pragma unroll
-            for (int y = 0; y < FL; ++y) acc += w[x * HY + y] * f[x * FL + y];
-        s_r[idx] = pc_clamp(acc);
-    }
-    __syncthreads();
-
-    // theta filter, clamp (:310-314), normalise, store, argmax
-    T bv = -std::numeric_limits<T>::infinity();
-    unsigned bl = 0xFFFFFFFFu;
-    const PcNorm<T> nrm(tot);
-    for (int idx = tid; idx < BK * BX * BY; idx += NT) {
-        const int kq = idx / (BX * BY);
-        const int rem = idx - kq * (BX * BY);
-        const int i = rem / BY, j = rem - i * BY;
-        const int gk = k0 + kq, gi = i0 + i, gj = j0 + j;
-        if (gk < TH && gi < X && gj < Y) {
-            T acc = 0;
-#pragma unroll
-            for (int z = 0; z < FL; ++z) acc += s_r[idx + z * BX * BY] * s_zf[z];
-            T v = pc_clamp(acc);
-            v = nrm(v);
-            P[((size_t)gk * X + gi) * Y + gj] = v;
-            const unsigned lin = ((unsigned)gi * Y + gj) * TH + gk;
-            if (pc_better(v, lin, bv, bl)) {
-                bv = v;
-                bl = lin;
-            }
-        }
-    }
-    {
-        // wave argmax, then block argmax: one (value, index) partial per block,
-        // reduced per step by pc_argmax_steps (no same-address atomics)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const T ov = __shfl_xor(bv, off);
-            const unsigned ol = __shfl_xor(bl, off);
-            if (pc_better(ov, ol, bv, bl)) {
-                bv = ov;
-                bl = ol;
-            }
-        }
-        if ((tid & 63) == 0) {
-            s_bv[tid >> 6] = bv;
-            s_bl[tid >> 6] = bl;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < NT / 64; ++w)
-                if (pc_better(s_bv[w], s_bl[w], bv, bl)) {
-                    bv = s_bv[w];
-                    bl = s_bl[w];
-                }
-            const int b = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-            if constexpr (sizeof(T) == 4) {
-                atomicMax(res_slot + (b & (RES_SLOTS - 1)), argmax_key((float)bv, bl));
-            } else {
-                bmax[b] = bv;
-                bidx[b] = bl;
-            }
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -3181,6 +2967,9 @@ struct OdoTables {
     std::vector<int32_t> ownRows;
 };
 
+// The step-kernel family of a handle (the file's header comment; rs_pc_step_form names it).
+enum class PcForm { Rows, Stream, Cols, Halo };
+
 struct rs_pc {
     int X = 0, Y = 0, TH = 0, prec = RS_PREC_F32, device = 0;
     size_t n = 0, esz = 4;
@@ -3190,14 +2979,13 @@ struct rs_pc {
     void* dFilt = nullptr;
     int nf = 0;
     double* dPart = nullptr;
-    int nPart = 0;               // blocks of the excitation kernel
-    int nPathBlocks = 0;         // blocks of the path kernel
-    void* dBmax = nullptr;       // f64 argmax partials (max(nPathBlocks, argmax grid))
+    int nPart = 0;               // blocks of a step kernel (excitation and path alike; set by the form)
+    void* dBmax = nullptr;       // f64 argmax partials (max(nPart, argmax grid))
     unsigned* dBidx = nullptr;
     int nBmaxCap = 0;
     unsigned long long* dRes = nullptr;
     int resCap = 0;
-    void* dArgV = nullptr;        // per-step per-block argmax partials [resCap][nPathBlocks]
+    void* dArgV = nullptr;        // per-step per-block argmax partials [resCap][nPart]
     unsigned* dArgI = nullptr;
     unsigned long long* hRes = nullptr;  // pinned
     unsigned long long* hResDev = nullptr;  // hRes in the device's address space (pc_res_export)
@@ -3215,12 +3003,8 @@ struct rs_pc {
     bool profKernels = false;  // ... and around every launch (kernel_ms; the events add gaps)
     std::vector<hipEvent_t> evPool;
     double kernelMs[2] = {0.0, 0.0};
-    int tiling = 0;  // 64 / 128: row-tiled kernels for Y <= 64 / 128; 0: generic 3-D tiles
-    bool streamed = false;  // layer-streaming kernels (default; RS_PC_FORM=rows|tiles|stream:BX,WR,KC)
-    bool cols = false;      // column kernels (RS_PC_FORM=cols[:KC]): TX x TY tiles through KC layers;
-                            // P and Q are then theta-fastest (C order (x, y, th))
-    bool halo = false;      // one launch per step (RS_PC_FORM=halo): HF_T x HF_T tiles through all
-                            // layers, the excitation recomputed on each tile's halo; P theta-fastest
+    PcForm form = PcForm::Rows;  // the step-kernel family (pc_choose_form); its geometry below
+    int rowsYP = 0;         // rows: the kernels' YP instance, 64 (Y <= 64) or 128 (Y <= 128)
     unsigned long long* dRec = nullptr;  // halo: the last launch's per-block (key of max U, near count)
     unsigned long long* hRec = nullptr;  // ... for a one-step call: pinned host records (hRecDev on the device)
     unsigned long long* hRecDev = nullptr;
@@ -3233,9 +3017,9 @@ struct rs_pc {
     int haloCur = 0, haloPart = 0;  // its partial sums in half haloPart of dPart (pc_halo_settle)
     long haloAmbig = 0;     // calls whose last step was keyed by the finishing pass (RES_AMBIG)
     bool haloSettleAlways = false;  // rs_pc_debug(RS_PC_DBG_HALO_SETTLE)
-    int cgx = 0, cgy = 0;   // column (or halo) tiles along x and y
-    int coKC = 0, coNch = 1;  // layers per theta chunk (KC == TH: whole extent, no halo), chunks
-    int sbx = 1, swr = 8, swc = 1;  // streaming tile: BX rows per wave, WR row groups, WC column tiles
+    int cgx = 0, cgy = 0;   // cols, halo: tiles along x and y (CO_TX x CO_TY, HF_T x HF_T)
+    int coKC = 0, coNch = 1;  // cols: layers per theta chunk (KC == TH: whole extent, no halo), chunks
+    int sbx = 1, swr = 8, swc = 1;  // stream: BX rows per wave, WR row groups, WC column tiles
     StreamGrid sg{};
     // odometry -> control tables (rs_pc_set_odometry_tables) and per-call scratch
     bool odoReady = false;
@@ -3252,7 +3036,7 @@ namespace {
 
 // P (and Q) theta-fastest, the reference's C order (x, y, th): the column and halo
 // forms; the others keep P layer-major
-inline bool pc_thfast(const rs_pc* h) { return h->cols || h->halo; }
+inline bool pc_thfast(const rs_pc* h) { return h->form == PcForm::Cols || h->form == PcForm::Halo; }
 
 // Per-step buffers of a call of n steps, grown in powers of two: the result slots and
 // words always; the control ring (pinned staging + device copy, ctlStride bytes a step)
@@ -3282,8 +3066,8 @@ int pc_grow_steps(rs_pc* h, int n, bool ctl = true) {
         for (int s = 0; s < cap; ++s) h->hRes[s] = RES_NONE;
         RS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hResDev), h->hRes, 0));
         if (h->prec == RS_PREC_F64) {  // float64 argmax: per-block partials + pc_argmax_steps
-            RS_HIP(hipMalloc(&h->dArgV, h->esz * (size_t)cap * h->nPathBlocks));
-            RS_HIP(hipMalloc(&h->dArgI, sizeof(unsigned) * (size_t)cap * h->nPathBlocks));
+            RS_HIP(hipMalloc(&h->dArgV, h->esz * (size_t)cap * h->nPart));
+            RS_HIP(hipMalloc(&h->dArgI, sizeof(unsigned) * (size_t)cap * h->nPart));
         }
         h->resCap = cap;
     }
@@ -3430,13 +3214,10 @@ struct StepOut {
     void* bmax;
     unsigned* bidx;
 };
-inline StepOut step_out(unsigned long long* res, void* argv, unsigned* argi, size_t esz, int nblocks, int s) {
-    return StepOut{res + (size_t)s * RES_SLOTS,
-                   argv ? static_cast<char*>(argv) + esz * (size_t)s * nblocks : nullptr,
-                   argi ? argi + (size_t)s * nblocks : nullptr};
-}
 inline StepOut step_out(const rs_pc* h, int s) {
-    return step_out(h->dRes, h->dArgV, h->dArgI, h->esz, h->nPathBlocks, s);
+    return StepOut{h->dRes + (size_t)s * RES_SLOTS,
+                   h->dArgV ? static_cast<char*>(h->dArgV) + h->esz * (size_t)s * h->nPart : nullptr,
+                   h->dArgI ? h->dArgI + (size_t)s * h->nPart : nullptr};
 }
 
 // Wait for a call's result words (pinned host memory, each one 8-byte system-scope store
@@ -3579,7 +3360,8 @@ int pc_halo_settle_read(rs_pc* h, double* xp_dev, bool* done) {
 // eager readback (the float64 volume into the caller's pinned array), or when the
 // records cannot settle the last step's first maximum (RES_AMBIG: a cell within
 // HF_NEAR of the peak), pc_halo_finish normalises the state into dP, keys it and
-// exports.  One host sync (two for RES_AMBIG).  RS_PC_HALO_SETTLE=1 always finishes.
+// exports.  One host sync (two for RES_AMBIG).  rs_pc_debug(RS_PC_DBG_HALO_SETTLE) makes
+// every later call finish.
 int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
                 const double* zf, int32_t* out_xyz) {
     RS_TRY(pc_grow_steps(h, n, false));   // (the control travels as kernel arguments)
@@ -3782,7 +3564,8 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
     unsigned* bidx = so.bidx;
     const T* filt = static_cast<const T*>(h->dFilt);
     if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base], h->stream));
-    if (h->cols) {
+    switch (h->form) {
+    case PcForm::Cols: {
         const dim3 g(h->cgx * h->cgy * h->coNch);
         const bool whole = h->coKC >= h->TH;
         constexpr int THF = co_thmax<T>(), THC = co_thmax_chunk<T>();
@@ -3829,11 +3612,14 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
                                dim3(64 * CO_NW_CHUNK), 0, h->stream, Q, h->X, h->Y, h->TH, h->cgx, h->cgy,
                                (int)g.x, static_cast<T*>(h->dP), h->dPart, h->nPart, filt, h->nf, *ctl, slot,
                                bmax, bidx, h->coKC);
-    } else if (h->streamed) {
+        break;
+    }
+    case PcForm::Stream:
         RS_TRY((pc_launch_stream<T, CTL>(h, P, Q, slot, bmax, bidx, ctl, prof_base)));
-    } else if (h->tiling == 64 || h->tiling == 128) {
+        break;
+    case PcForm::Rows: {
         const dim3 g((h->X + RT_BX - 1) / RT_BX, (h->TH + RT_BK - 1) / RT_BK);
-        if (h->tiling == 64)
+        if (h->rowsYP == 64)
             hipLaunchKernelGGL((pc_excite_rows<T, 64>), g, dim3(RT_NT), 0, h->stream, P, Q,
                                h->dPart, slot, h->X, h->Y, h->TH, k);
         else
@@ -3843,7 +3629,7 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
         if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 1], h->stream));
         if (!ctl) return RS_OK;  // rs_pc_excite() normalises with pc_scale_kernel
         if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 2], h->stream));
-        if (h->tiling == 64)
+        if (h->rowsYP == 64)
             hipLaunchKernelGGL((pc_path_rows<T, 64, CTL>), g, dim3(RT_NT), 0, h->stream, Q,
                                static_cast<T*>(h->dP), h->dPart, h->nPart, filt, h->nf, *ctl, slot,
                                bmax, bidx, h->X, h->Y, h->TH);
@@ -3851,20 +3637,10 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
             hipLaunchKernelGGL((pc_path_rows<T, 128, CTL>), g, dim3(RT_NT), 0, h->stream, Q,
                                static_cast<T*>(h->dP), h->dPart, h->nPart, filt, h->nf, *ctl, slot,
                                bmax, bidx, h->X, h->Y, h->TH);
-    } else {
-        const dim3 gA((h->Y + EX_BY - 1) / EX_BY, (h->X + EX_BX - 1) / EX_BX,
-                      (h->TH + EX_BK - 1) / EX_BK);
-        hipLaunchKernelGGL((pc_excite_kernel<T, EX_BX, EX_BY, EX_BK>), gA, dim3(NT), 0, h->stream,
-                           P, Q, h->dPart, slot, h->X, h->Y, h->TH, k);
-        RS_HIP(hipGetLastError());
-        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 1], h->stream));
-        if (!ctl) return RS_OK;
-        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 2], h->stream));
-        const dim3 gB((h->Y + PI_BY - 1) / PI_BY, (h->X + PI_BX - 1) / PI_BX,
-                      (h->TH + PI_BK - 1) / PI_BK);
-        hipLaunchKernelGGL((pc_path_kernel<T, PI_BX, PI_BY, PI_BK, CTL>), gB, dim3(NT), 0, h->stream, Q,
-                           static_cast<T*>(h->dP), h->dPart, h->nPart, filt, *ctl, slot, bmax,
-                           bidx, h->X, h->Y, h->TH);
+        break;
+    }
+    case PcForm::Halo:  // one launch per step: pc_run_halo, rs_pc_excite
+        RS_CHECK(false, RS_ERR_STATE, "the halo form has no two-launch step");
     }
     RS_HIP(hipGetLastError());
     if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 3], h->stream));
@@ -3883,12 +3659,12 @@ void decode_xyz(const rs_pc* h, unsigned long long key, int32_t* out) {
 int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
                   const double* zf, int32_t* out_xyz) {
     if (n == 0) return RS_OK;
-    if (h->halo) return pc_run_halo(h, n, ox, oy, fidx, zf, out_xyz);
+    if (h->form == PcForm::Halo) return pc_run_halo(h, n, ox, oy, fidx, zf, out_xyz);
     // Batches: the column form takes each step's control as kernel arguments too (its
     // path kernel then starts its window loads without a global round trip for the
     // shifts: 128x128x72 27.5 -> 27.1 us per step with the filter table staged behind
     // the window); the other forms read the device ring
-    const bool inline_ctl = (n == 1 || h->cols) && h->TH <= CTL_INLINE_MAX;
+    const bool inline_ctl = (n == 1 || h->form == PcForm::Cols) && h->TH <= CTL_INLINE_MAX;
     RS_TRY(pc_grow_steps(h, n, !inline_ctl));
     if (!inline_ctl) {
         RS_TRY(pc_pack_ctl(h, n, ox, oy, fidx, zf));
@@ -3917,7 +3693,7 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     }
     if (h->prec == RS_PREC_F64) {
         hipLaunchKernelGGL((pc_argmax_steps<double>), dim3(n), dim3(NT), 0, h->stream,
-                           static_cast<const double*>(h->dArgV), h->dArgI, h->nPathBlocks, h->dRes);
+                           static_cast<const double*>(h->dArgV), h->dArgI, h->nPart, h->dRes);
         RS_HIP(hipGetLastError());
     }
     for (int s = 0; s < n; ++s) h->hRes[s] = RES_NONE;
@@ -4089,13 +3865,21 @@ __global__ void pc_scale_kernel(T* __restrict__ P, size_t n, const double* __res
         P[e] = nrm(P[e]);
 }
 
-// Step-kernel form.  Default: rows below ST_MIN_CELLS; above it the column form
-// where it fits (pc_cols_fit), else layer streaming with one wave per 64 columns
-// and 8 row groups of BX rows, KC (layers per block) the smallest chunk that keeps
-// the grid within ~2 blocks per CU (fewer, longer blocks re-evaluate fewer halo
-// layers).  RS_PC_FORM=rows|tiles|cols|stream:BX,WR[,KC] overrides (A/B, tests).
+// Step-kernel form.  Each form has a fit predicate (its kernels' limits on this grid,
+// precision and filter table) and a set function (the form, its geometry and nPart);
+// pc_choose_form, below them, takes RS_PC_FORM's request or walks the default order.
+// rows: a grid row within the YP = 128 instance; a filter table of any size (read in place).
+bool pc_rows_fit(const rs_pc* h) { return h->Y <= 128; }
+
+int pc_rows_set(rs_pc* h) {
+    h->form = PcForm::Rows;
+    h->rowsYP = h->Y <= 64 ? 64 : 128;
+    h->nPart = ((h->X + RT_BX - 1) / RT_BX) * ((h->TH + RT_BK - 1) / RT_BK);
+    return RS_OK;
+}
+
 // Scratch traffic in the layer loop defeats the streaming kernels' prefetch
-// pipeline: refuse a variant that spills.
+// pipeline: pc_stream_set refuses a variant that spills.
 template <typename T>
 int pc_stream_scratch(int bx, int wr, int wc, size_t* bytes) {
     hipFuncAttributes a{};
@@ -4143,12 +3927,12 @@ int pc_cols_set(rs_pc* h, int kc) {
     RS_CHECK(kc < h->TH ? kc + 2 * HALF <= thc : h->TH <= thf, RS_ERR_ARG,
              "cols KC=%d: %d window layers exceed the LDS window (%d whole, %d per chunk)", kc,
              kc < h->TH ? kc + 2 * HALF : kc, thf, thc);
-    h->streamed = false;
-    h->cols = true;
+    h->form = PcForm::Cols;
     h->cgx = (h->X + CO_TX - 1) / CO_TX;
     h->cgy = (h->Y + CO_TY - 1) / CO_TY;
     h->coKC = kc;
     h->coNch = (h->TH + kc - 1) / kc;
+    h->nPart = h->cgx * h->cgy * h->coNch;
     return RS_OK;
 }
 
@@ -4164,11 +3948,10 @@ bool pc_halo_fit(const rs_pc* h) {
 }
 
 int pc_halo_set(rs_pc* h) {
-    h->streamed = false;
-    h->cols = false;
-    h->halo = true;
+    h->form = PcForm::Halo;
     h->cgx = (h->X + HF_T - 1) / HF_T;
     h->cgy = (h->Y + HF_T - 1) / HF_T;
+    h->nPart = h->cgx * h->cgy;
     return RS_OK;
 }
 
@@ -4181,63 +3964,13 @@ bool pc_halo_default(const rs_pc* h) {
                                  (size_t)HF_DEFAULT_MAX_TILES;
 }
 
-int pc_choose_form(rs_pc* h) {
-    int bx = 1, wr = 8, wc = 1, kc = 0;
-    const char* env = std::getenv("RS_PC_FORM");
-    if ((env == nullptr || env[0] == 0) && pc_halo_default(h)) return pc_halo_set(h);
-    if (env && std::strcmp(env, "halo") == 0) {
-        RS_CHECK(pc_halo_fit(h), RS_ERR_ARG,
-                 "RS_PC_FORM=halo needs float32, TH 10, 18 or %d, %d <= X, Y <= 32767 and at most %d path filters", HF_TH,
-                 HF_W, RT_NFMAX);
-        return pc_halo_set(h);
-    }
-    if (env && std::strcmp(env, "rows") == 0) {
-        RS_CHECK(h->tiling != 0, RS_ERR_ARG, "RS_PC_FORM=rows needs Y <= 128");
-        h->streamed = false;
-        return RS_OK;
-    }
-    if (env && std::strcmp(env, "tiles") == 0) {
-        h->streamed = false;
-        h->tiling = 0;
-        return RS_OK;
-    }
-    if (env && (std::strcmp(env, "cols") == 0 || std::strncmp(env, "cols:", 5) == 0)) {
-        RS_CHECK(pc_cols_fit(h), RS_ERR_ARG,
-                 "RS_PC_FORM=cols needs X >= %d, Y >= %d and a multiple of %d, TH >= %d and at most %d "
-                 "path filters",
-                 CO_TX + 2 * HALF, CO_TY + 2 * HALF + 4, h->esz == 4 ? co_vec<float>() : co_vec<double>(),
-                 CO_CH + 2, RT_NFMAX);
-        return pc_cols_set(h, env[4] == ':' ? std::atoi(env + 5) : 0);
-    }
-    const bool explicit_stream = env && std::strncmp(env, "stream:", 7) == 0;
-    if (explicit_stream) {
-        const int n = std::sscanf(env + 7, "%d,%d,%d,%d", &bx, &wr, &wc, &kc);
-        RS_CHECK(n >= 3, RS_ERR_ARG, "RS_PC_FORM=stream:BX,WR,WC[,KC], got '%s'", env);
-    } else {
-        RS_CHECK(env == nullptr || env[0] == 0 || std::strcmp(env, "stream") == 0, RS_ERR_ARG,
-                 "unknown RS_PC_FORM '%s' (rows | tiles | cols | halo | stream[:BX,WR,WC[,KC]])", env);
-        // default: one pass per kernel (rows) while the whole grid fits in one wave of
-        // blocks -- the step is latency-bound there (64x64x36: 17 us rows vs 23 us
-        // streamed); streamed once the rows form's 4x theta-halo recompute dominates
-        // (128x128x72: 57 us rows vs 41 us streamed)
-        const bool big = (size_t)h->X * h->Y * h->TH >= ST_MIN_CELLS;
-        if ((env == nullptr || env[0] == 0) && h->tiling != 0 && !big) {
-            h->streamed = false;
-            return RS_OK;
-        }
-        // large grids: the column form where it fits (128x128x72: 29.3 us per step
-        // vs 38.8 us streamed, tools/pc_sweep.py), else the streamed form
-        if ((env == nullptr || env[0] == 0) && big && pc_cols_fit(h)) return pc_cols_set(h, 0);
-        bx = h->esz == 4 ? ST_DEF_BX : 1;
-        wr = ST_DEF_WR;
-        wc = ST_DEF_WC;
-    }
-    if (h->nf > RT_NFMAX) {  // filter table too large to stage in LDS: rows / tiles forms
-        RS_CHECK(env == nullptr || std::strncmp(env, "stream", 6) != 0, RS_ERR_ARG,
-                 "stream form stages at most %d path filters, table has %d", RT_NFMAX, h->nf);
-        h->streamed = false;
-        return RS_OK;
-    }
+// The streaming kernels' limit: the filter table staged in LDS.
+bool pc_stream_fit(const rs_pc* h) { return h->nf <= RT_NFMAX; }
+
+// The streaming form with tile (bx, wr, wc): one wave per 64 columns, wr row groups of
+// bx rows.  kc (layers per block) = 0 picks the smallest chunk that keeps the grid
+// within one block per CU.
+int pc_stream_set(rs_pc* h, int bx, int wr, int wc, int kc) {
     bool known = false;
 #define PC_KNOWN(bx_, wr_, wc_) known = known || (bx == bx_ && wr == wr_ && wc == wc_);
     PC_STREAM_VARIANTS(PC_KNOWN)
@@ -4257,9 +3990,8 @@ int pc_choose_form(rs_pc* h) {
     g.gy = (h->Y + yt - 1) / yt;
     const int maxkc = st_maxkc((int)h->esz, bxb, yt);
     if (kc <= 0) {
-        // smallest chunk that keeps the grid within one block per CU: a second block
-        // on some CUs doubles their share (fewer, longer blocks also re-evaluate
-        // fewer halo layers)
+        // a second block on some CUs doubles their share (fewer, longer blocks also
+        // re-evaluate fewer halo layers)
         const int target = 256;
         kc = 2;
         while (kc < maxkc && kc < h->TH && (long)g.gx * g.gy * ((h->TH + kc - 1) / kc) > target) ++kc;
@@ -4270,12 +4002,69 @@ int pc_choose_form(rs_pc* h) {
     g.gz = (h->TH + g.KC - 1) / g.KC;
     RS_CHECK((long)g.gx * g.gy * g.gz <= NPP_MAX_BLOCKS, RS_ERR_ARG,
              "streaming grid of %ld blocks exceeds %d", (long)g.gx * g.gy * g.gz, NPP_MAX_BLOCKS);
-    h->streamed = true;
+    h->form = PcForm::Stream;
     h->sbx = bx;
     h->swr = wr;
     h->swc = wc;
     h->sg = g;
+    h->nPart = g.gx * g.gy * g.gz;
     return RS_OK;
+}
+
+int pc_choose_form(rs_pc* h) {
+    const int def_bx = h->esz == 4 ? ST_DEF_BX : 1;
+    // 1. RS_PC_FORM=rows|cols[:KC]|halo|stream[:BX,WR,WC[,KC]] (A/B runs, tests): that form,
+    // or RS_ERR_ARG where it does not fit
+    const char* env = std::getenv("RS_PC_FORM");
+    if (env && std::strcmp(env, "halo") == 0) {
+        RS_CHECK(pc_halo_fit(h), RS_ERR_ARG,
+                 "RS_PC_FORM=halo needs float32, TH 10, 18 or %d, %d <= X, Y <= 32767 and at most %d path filters", HF_TH,
+                 HF_W, RT_NFMAX);
+        return pc_halo_set(h);
+    }
+    if (env && std::strcmp(env, "rows") == 0) {
+        RS_CHECK(pc_rows_fit(h), RS_ERR_ARG, "RS_PC_FORM=rows needs Y <= 128");
+        return pc_rows_set(h);
+    }
+    if (env && (std::strcmp(env, "cols") == 0 || std::strncmp(env, "cols:", 5) == 0)) {
+        RS_CHECK(pc_cols_fit(h), RS_ERR_ARG,
+                 "RS_PC_FORM=cols needs X >= %d, Y >= %d and a multiple of %d, TH >= %d and at most %d "
+                 "path filters",
+                 CO_TX + 2 * HALF, CO_TY + 2 * HALF + 4, h->esz == 4 ? co_vec<float>() : co_vec<double>(),
+                 CO_CH + 2, RT_NFMAX);
+        return pc_cols_set(h, env[4] == ':' ? std::atoi(env + 5) : 0);
+    }
+    if (env && env[0]) {
+        int bx = def_bx, wr = ST_DEF_WR, wc = ST_DEF_WC, kc = 0;
+        if (std::strncmp(env, "stream:", 7) == 0) {
+            const int n = std::sscanf(env + 7, "%d,%d,%d,%d", &bx, &wr, &wc, &kc);
+            RS_CHECK(n >= 3, RS_ERR_ARG, "RS_PC_FORM=stream:BX,WR,WC[,KC], got '%s'", env);
+        } else {
+            RS_CHECK(std::strcmp(env, "stream") == 0, RS_ERR_ARG,
+                     "unknown RS_PC_FORM '%s' (rows | cols | halo | stream[:BX,WR,WC[,KC]])", env);
+        }
+        RS_CHECK(pc_stream_fit(h), RS_ERR_ARG, "stream form stages at most %d path filters, table has %d", RT_NFMAX,
+                 h->nf);
+        return pc_stream_set(h, bx, wr, wc, kc);
+    }
+    // 2. the default order
+    if (pc_halo_default(h)) return pc_halo_set(h);
+    // one pass per kernel (rows) while the whole grid fits in one wave of blocks -- the
+    // step is latency-bound there (64x64x36: 17 us rows vs 23 us streamed); streamed once
+    // the rows form's 4x theta-halo recompute dominates (128x128x72: 57 us rows vs 41 us
+    // streamed)
+    const bool big = (size_t)h->X * h->Y * h->TH >= ST_MIN_CELLS;
+    if (pc_rows_fit(h) && !big) return pc_rows_set(h);
+    // large grids: the column form where it fits (128x128x72: 29.3 us per step vs 38.8 us
+    // streamed, tools/pc_sweep.py), else the streamed form
+    if (big && pc_cols_fit(h)) return pc_cols_set(h, 0);
+    if (pc_stream_fit(h)) return pc_stream_set(h, def_bx, ST_DEF_WR, ST_DEF_WC, 0);
+    // a filter table too large to stage in LDS: only the rows kernels read it in place
+    RS_CHECK(pc_rows_fit(h), RS_ERR_ARG,
+             "a table of %d path filters needs Y <= 128 (grid has Y = %d): the other step kernels stage at "
+             "most %d filters",
+             h->nf, h->Y, RT_NFMAX);
+    return pc_rows_set(h);
 }
 
 }  // namespace
@@ -4310,29 +4099,11 @@ int rs_pc_create(int X, int Y, int TH, const rs_pc_params* p, int device, rs_pc*
     fill_sep(h->kf, p);
     fill_sep(h->kd, p);
     h->ctlStride = rs::round_up(ctl_off_zf(h) + sizeof(double) * 8, 16);
-    h->tiling = Y <= 64 ? 64 : (Y <= 128 ? 128 : 0);
     if (int st = pc_choose_form(h); st != RS_OK) {
         delete h;
         return st;
     }
-    if (h->halo) {
-        h->nPart = h->cgx * h->cgy;
-        h->nPathBlocks = h->nPart;
-    } else if (h->cols) {
-        h->nPart = h->cgx * h->cgy * h->coNch;
-        h->nPathBlocks = h->nPart;
-    } else if (h->streamed) {
-        h->nPart = h->sg.gx * h->sg.gy * h->sg.gz;
-        h->nPathBlocks = h->nPart;
-    } else if (h->tiling) {
-        h->nPart = ((X + RT_BX - 1) / RT_BX) * ((TH + RT_BK - 1) / RT_BK);
-        h->nPathBlocks = h->nPart;
-    } else {
-        h->nPart = ((Y + EX_BY - 1) / EX_BY) * ((X + EX_BX - 1) / EX_BX) * ((TH + EX_BK - 1) / EX_BK);
-        h->nPathBlocks =
-            ((Y + PI_BY - 1) / PI_BY) * ((X + PI_BX - 1) / PI_BX) * ((TH + PI_BK - 1) / PI_BK);
-    }
-    h->nBmaxCap = h->nPathBlocks > 1024 ? h->nPathBlocks : 1024;
+    h->nBmaxCap = h->nPart > 1024 ? h->nPart : 1024;
 
     auto fail = [&](int code) { rs_pc_destroy(h); return code; };
     hipError_t e = hipSuccess;
@@ -4356,16 +4127,14 @@ int rs_pc_create(int X, int Y, int TH, const rs_pc_params* p, int device, rs_pc*
     PC_ALLOC(hipMalloc(&h->dPart, sizeof(double) * h->nPart * 2));
     PC_ALLOC(hipMemsetAsync(h->dPart, 0, sizeof(double) * h->nPart * 2, h->stream));
     PC_ALLOC(hipMalloc(&h->dRec, sizeof(unsigned long long) * 2 * h->nPart));
-    if (h->halo) {
-        PC_ALLOC(hipHostMalloc(&h->hRec, sizeof(unsigned long long) * 2 * h->nPart,
-                               hipHostMallocMapped | hipHostMallocCoherent));
-        PC_ALLOC(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hRecDev), h->hRec, 0));
-    }
     // the volume-writing kernels' per-block flags (pc_halo_finish, pc_export2_kernel)
     PC_ALLOC(hipHostMalloc(&h->hFlag, sizeof(unsigned) * HF_FLAGS, hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(h->hFlag, 0, sizeof(unsigned) * HF_FLAGS);
     PC_ALLOC(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hFlagDev), h->hFlag, 0));
-    if (h->halo) {
+    if (h->form == PcForm::Halo) {
+        PC_ALLOC(hipHostMalloc(&h->hRec, sizeof(unsigned long long) * 2 * h->nPart,
+                               hipHostMallocMapped | hipHostMallocCoherent));
+        PC_ALLOC(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hRecDev), h->hRec, 0));
         PC_ALLOC(hipHostMalloc(&h->hKey, sizeof(unsigned long long) * HF_FLAGS,
                                hipHostMallocMapped | hipHostMallocCoherent));
         PC_ALLOC(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hKeyDev), h->hKey, 0));
@@ -4448,7 +4217,7 @@ int rs_pc_excite(rs_pc* h) {
     RS_CHECK(h, RS_ERR_STATE, "null pose-cell handle");
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(pc_halo_settle(h));  // (halo: a state a call left unnormalised)
-    if (h->halo) {
+    if (h->form == PcForm::Halo) {
         // the halo kernel's excitation-only instance: no shifts, Q of the own cells
         PcCtlHalo c{};
         c.uw = (short)HF_W;
@@ -4459,17 +4228,17 @@ int rs_pc_excite(rs_pc* h) {
                            static_cast<float*>(h->dQ), h->dPart, nullptr, nullptr, static_cast<const float*>(h->dFilt), h->nf, c, h->kf,
                            nullptr);
         RS_HIP(hipGetLastError());
-        hipLaunchKernelGGL((pc_scale_kernel<float>), dim3(64), dim3(NT), 0, h->stream,
-                           static_cast<float*>(h->dQ), h->n, h->dPart, h->nPart);
     } else if (h->prec == RS_PREC_F32) {
         RS_TRY((pc_launch_step<float, PcCtlRing>(h, step_out(h, 0), nullptr, -1)));
-        hipLaunchKernelGGL((pc_scale_kernel<float>), dim3(64), dim3(NT), 0, h->stream,
-                           static_cast<float*>(h->dQ), h->n, h->dPart, h->nPart);
     } else {
         RS_TRY((pc_launch_step<double, PcCtlRing>(h, step_out(h, 0), nullptr, -1)));
+    }
+    if (h->prec == RS_PREC_F32)
+        hipLaunchKernelGGL((pc_scale_kernel<float>), dim3(64), dim3(NT), 0, h->stream,
+                           static_cast<float*>(h->dQ), h->n, h->dPart, h->nPart);
+    else
         hipLaunchKernelGGL((pc_scale_kernel<double>), dim3(64), dim3(NT), 0, h->stream,
                            static_cast<double*>(h->dQ), h->n, h->dPart, h->nPart);
-    }
     RS_HIP(hipGetLastError());
     // Q has P's layout in every form (the column form: both theta-fastest)
     RS_HIP(hipMemcpyAsync(h->dP, h->dQ, h->n * h->esz, hipMemcpyDeviceToDevice, h->stream));
@@ -4771,10 +4540,13 @@ int rs_pc_kernel_ms(rs_pc* h, double ms[2]) {
 
 const char* rs_pc_step_form(const rs_pc* h) {
     if (!h) return nullptr;
-    if (h->streamed) return "stream";
-    if (h->halo) return "halo";
-    if (h->cols) return "cols";
-    return h->tiling ? "rows" : "tiles";
+    switch (h->form) {
+    case PcForm::Rows: return "rows";
+    case PcForm::Stream: return "stream";
+    case PcForm::Cols: return "cols";
+    case PcForm::Halo: return "halo";
+    }
+    return nullptr;
 }
 
 int rs_pc_debug(rs_pc* h, int op) {
@@ -4790,9 +4562,9 @@ int rs_pc_debug(rs_pc* h, int op) {
         RS_HIP(hipMemsetAsync(h->dRes, 0xFF, sizeof(unsigned long long) * RES_SLOTS * h->resCap, h->stream));
         RS_HIP(hipMemsetAsync(h->dBmax, 0xFF, h->esz * h->nBmaxCap, h->stream));
         RS_HIP(hipMemsetAsync(h->dBidx, 0xFF, sizeof(unsigned) * h->nBmaxCap, h->stream));
-        if (h->dArgV) RS_HIP(hipMemsetAsync(h->dArgV, 0xFF, h->esz * (size_t)h->resCap * h->nPathBlocks, h->stream));
+        if (h->dArgV) RS_HIP(hipMemsetAsync(h->dArgV, 0xFF, h->esz * (size_t)h->resCap * h->nPart, h->stream));
         if (h->dArgI)
-            RS_HIP(hipMemsetAsync(h->dArgI, 0xFF, sizeof(unsigned) * (size_t)h->resCap * h->nPathBlocks, h->stream));
+            RS_HIP(hipMemsetAsync(h->dArgI, 0xFF, sizeof(unsigned) * (size_t)h->resCap * h->nPart, h->stream));
         for (int s = 0; s < h->resCap; ++s) h->hRes[s] = ~0ull;
         RS_HIP(hipStreamSynchronize(h->stream));
         return RS_OK;

@@ -376,7 +376,7 @@ class PoseCellNetwork:
         return ms.value
 
     def step_form(self):
-        """Step kernels in use: 'rows', 'tiles', 'cols', 'halo' or 'stream' (rs_pc_step_form)."""
+        """Step kernels in use: 'rows', 'cols', 'halo' or 'stream' (rs_pc_step_form)."""
         return self._lib.rs_pc_step_form(self._h).decode()
 
     def set_profiling(self, enable=True, per_kernel=True):
@@ -387,7 +387,7 @@ class PoseCellNetwork:
     def kernel_ms(self):
         """Kernel times of the last run (profiling on, per_kernel=True), as
         rs_pc_kernel_ms returns them: (excite_ms, path_ms) summed over the steps for
-        the two-launch forms (rows, tiles, cols, tc, stream); for the halo form
+        the two-launch forms (rows, cols, stream); for the halo form
         (step_ms, finish_ms): the step kernels summed, then the one pc_halo_finish."""
         ms = np.zeros(2)
         _lib.check(self._lib.rs_pc_kernel_ms(self._h, _lib.ptr(ms, ctypes.c_double)))

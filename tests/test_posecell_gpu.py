@@ -45,7 +45,7 @@ def test_golden_trajectory(pcn, name, precision, tol):
 
 
 @pytest.mark.parametrize('precision,tol', [('float32', F32_TOL), ('float64', F64_TOL)])
-@pytest.mark.parametrize('form', ['rows', 'cols', 'stream', 'tiles'])
+@pytest.mark.parametrize('form', ['rows', 'cols', 'stream'])
 @pytest.mark.parametrize('name', ['pc_death64', 'pc_death32'])
 def test_network_death_vs_reference(pcn, monkeypatch, name, form, precision, tol):
     """Golden fixture made by the reference (gen_golden.py --only death): a
@@ -195,7 +195,7 @@ def test_large_grid_full_rollout_vs_c_oracle(pcn):
 # step that read an excited cell, a partial sum or an argmax slot it had not
 # written in that step would give NaN state or a wrong peak, every time
 POISON_CASES = [((128, 128, 72), 'cols'), ((128, 128, 100), 'cols'), ((64, 64, 36), 'rows'),
-                ((40, 44, 20), 'tiles'), ((128, 130, 72), 'stream')]
+                ((40, 44, 20), 'rows'), ((128, 130, 72), 'stream')]
 
 
 @pytest.mark.parametrize('precision,tol', [('float32', F32_TOL), ('float64', F64_TOL)])
@@ -349,13 +349,13 @@ def test_simulate_driver(pcn):
         assert sim.current_pose_cell == tuple(case['max_pc'][s])
 
 
-# every step-kernel form (RS_PC_FORM) against the oracle: the row-tiled and 3-D
-# tiled single-pass forms, the column form and the layer-streaming form at several tile shapes
-# (rows per wave, row groups, layers per block), incl. ragged tiles and grids
-# whose theta extent is not a multiple of the chunk
-FORMS = {'float32': ['rows', 'tiles', 'cols', 'cols:5', 'cols:12', 'stream:1,8,1,2', 'stream:1,8,1,5',
+# every two-launch step-kernel form (RS_PC_FORM) against the oracle: the row-tiled form,
+# the column form (whole theta extent and chunked) and the layer-streaming form at several
+# tile shapes (rows per wave, row groups, layers per block), incl. ragged tiles and grids
+# whose theta extent is not a multiple of the chunk (the halo form: tests/test_halo_gpu.py)
+FORMS = {'float32': ['rows', 'cols', 'cols:5', 'cols:12', 'stream:1,8,1,2', 'stream:1,8,1,5',
                      'stream:2,8,1,3', 'stream:2,8,1,6'],
-         'float64': ['rows', 'tiles', 'cols', 'cols:7', 'stream:1,8,1,2', 'stream:1,8,1,5']}
+         'float64': ['rows', 'cols', 'cols:7', 'stream:1,8,1,2', 'stream:1,8,1,5']}
 
 
 def cols_fit(shape, precision, form='cols'):
@@ -416,6 +416,85 @@ def test_default_form_by_grid_size(pcn, monkeypatch):
     monkeypatch.setenv('RS_PC_FORM', 'stream:2,8,1,3')   # spills at float64: refused
     with pytest.raises(ValueError):
         pcn((64, 64, 36), precision='float64')
+    monkeypatch.setenv('RS_PC_FORM', 'tiles')            # the removed 3-D tiles form: unknown
+    with pytest.raises(ValueError):
+        pcn((64, 64, 36))
+
+
+def _create_with_table(lib, shape, precision, table):
+    """rs_pc_create with an explicit path-filter table; returns the handle."""
+    from pyratslam_amd import _lib
+    from pyratslam_amd import filters as F
+    ge, gi, scale = F.separable_factors()
+    params = _lib.PcParams()
+    params.precision = _lib.RS_PREC_F32 if precision == 'float32' else _lib.RS_PREC_F64
+    params.global_inhibition = 0.2
+    params.ge[:] = list(ge)
+    params.gi[:] = list(gi)
+    params.k_scale = scale
+    params.nfilters = table.shape[0]
+    params.xy_filters = _lib.ptr(table, ctypes.c_double)
+    h = ctypes.c_void_p()
+    _lib.check(lib.rs_pc_create(*shape, ctypes.byref(params), 0, ctypes.byref(h)))
+    return h
+
+
+@pytest.fixture(scope='module')
+def nine_filter_table(pcn):
+    """The product's 4 path filters followed by 5 copies of row 0: more than the 8 rows
+    the cols, stream and halo kernels stage in LDS."""
+    from pyratslam_amd import filters as F
+    t = np.ascontiguousarray(F.FilterTable().filters, dtype=np.float64)
+    assert t.shape[0] == 4
+    return np.ascontiguousarray(np.concatenate([t, np.repeat(t[:1], 5, axis=0)]))
+
+
+def test_large_filter_table_refused_beyond_rows(pcn, monkeypatch, nine_filter_table):
+    """9 filters on a grid with Y > 128: no step kernel takes it (the rows kernels read
+    the table in place but need Y <= 128, the others stage at most 8 filters)."""
+    from pyratslam_amd import _lib
+    monkeypatch.delenv('RS_PC_FORM', raising=False)
+    lib = _lib.require_device()
+    with pytest.raises(ValueError, match='9 path filters.*at most 8 filters'):
+        _create_with_table(lib, (16, 130, 10), 'float32', nine_filter_table)
+
+
+@pytest.mark.parametrize('precision', ['float32', 'float64'])
+def test_large_filter_table_rows_reads_unstaged_row(pcn, monkeypatch, nine_filter_table, precision):
+    """9 filters with Y <= 128 go to the rows form, whose path kernel reads an unstaged
+    table from global memory: three updates that take every layer's filter from row 8
+    (a copy of row 0) leave a state and peaks bit-identical to those of row 0."""
+    from pyratslam_amd import _lib
+    monkeypatch.delenv('RS_PC_FORM', raising=False)
+    lib = _lib.require_device()
+    shape = (16, 40, 10)
+    k = np.arange(shape[2])
+    zf = np.ascontiguousarray(P.dog_offset_1d(0), dtype=np.float64)
+    states, peaks = [], []
+    for row in (8, 0):
+        h = _create_with_table(lib, shape, precision, nine_filter_table)
+        try:
+            assert lib.rs_pc_step_form(h) == b'rows'
+            _lib.check(lib.rs_pc_inject(h, 1.0, 8, 20, 5))
+            fidx = np.full(shape[2], row, dtype=np.int32)
+            out = np.empty(3, dtype=np.int32)
+            got = []
+            for s in range(3):
+                ox = np.ascontiguousarray((k + s) % 5 - 2, dtype=np.int32)   # per-layer shifts
+                oy = np.ascontiguousarray((3 * k + s) % 7 - 3, dtype=np.int32)
+                _lib.check(lib.rs_pc_update(h, _lib.ptr(ox, ctypes.c_int32), _lib.ptr(oy, ctypes.c_int32),
+                                            _lib.ptr(fidx, ctypes.c_int32), _lib.ptr(zf, ctypes.c_double),
+                                            _lib.ptr(out, ctypes.c_int32)))
+                got.append(tuple(int(v) for v in out))
+            vol = np.empty(shape, dtype=np.float64)
+            _lib.check(lib.rs_pc_read(h, _lib.ptr(vol, ctypes.c_double)))
+        finally:
+            _lib.check(lib.rs_pc_destroy(h))
+        states.append(vol)
+        peaks.append(got)
+    assert peaks[0] == peaks[1]
+    assert states[0].tobytes() == states[1].tobytes()
+    assert states[0].any() and np.isfinite(states[0]).all()   # a live state, not two dead ones
 
 
 @pytest.mark.parametrize('shape', [(32, 32, 18), (64, 64, 36)])

@@ -3,7 +3,7 @@
 
 usage: python tools/pc_ab.py LIB.so[@ENV=V,...] [LIB2.so ...] [--shape 128,128,72] [--steps 2000] [--rounds 3]
        [--mode run|update|node]
-(``@RS_PC_CTL=inline`` runs that library with the variable set; ``;`` separates several)
+(``@RS_PC_FORM=rows`` runs that library with the variable set; ``;`` separates several)
 Each library runs in its own process (ctypes loads one copy), interleaved over
 rounds so clock drift hits every build alike: batched run() steps/s after a clock
 warm-up, and the state after the same odometry, compared across builds.  A build

@@ -123,10 +123,12 @@ int main(int argc, char** argv) {
                                       "excite_cols", "path_cols", "halo"};
     static const int kns[NKID] = {4, 6, 5, 5, 0, 5, 5, 7};
     std::vector<int> kids;
-    if (h->halo) kids = {7};
-    else if (h->cols) kids = {5, 6};
-    else if (h->streamed) kids = {2, 3};
-    else if (h->tiling) kids = {0, 1};
+    switch (h->form) {
+    case PcForm::Halo: kids = {7}; break;
+    case PcForm::Cols: kids = {5, 6}; break;
+    case PcForm::Stream: kids = {2, 3}; break;
+    case PcForm::Rows: kids = {0, 1}; break;
+    }
     auto stamped = [&](int kid, int i) {
         for (int b = 0; b < nb; ++b)
             if (slot(kid, b, i) == 0) return false;
@@ -172,7 +174,7 @@ int main(int argc, char** argv) {
         printf("boundary %s -> %s: %.2f us (excite first start -> path last end %.2f us)\n", kname[ek],
                kname[pk], ((double)p0 - (double)e1) * 1e-2, ((double)p1 - (double)e0) * 1e-2);
     }
-    if (h->halo && stamped(11, 0) && stamped(11, 1) && stamped(10, 0) && stamped(10, 1) && stamped(7, 1)) {
+    if (h->form == PcForm::Halo && stamped(11, 0) && stamped(11, 1) && stamped(10, 0) && stamped(10, 1) && stamped(7, 1)) {
         // the halo kernel's phase-1 DMA (stamps 10, 0..1) and theta pass (11, 0..1)
         std::vector<double> a, b;
         for (int bb = 0; bb < h->nPart; ++bb) {
@@ -226,7 +228,7 @@ int main(int argc, char** argv) {
         }
         printf("\n");
     }
-    if (h->halo) {  // back-to-back launch cost of the halo kernel alone, and of an empty one
+    if (h->form == PcForm::Halo) {  // back-to-back launch cost of the halo kernel alone, and of an empty one
         hipEvent_t c0, c1;
         CK(hipEventCreate(&c0));
         CK(hipEventCreate(&c1));
@@ -254,13 +256,13 @@ int main(int argc, char** argv) {
         rs_pc_destroy(h);
         return 0;
     }
-    if (h->streamed) {
+    if (h->form == PcForm::Stream) {
         printf("stream tile BX=%d WR=%d KC=%d grid %d blocks\n", h->sbx, h->swr, h->sg.KC,
                h->sg.gx * h->sg.gy * h->sg.gz);
         rs_pc_destroy(h);
         return 0;
     }
-    if (h->cols && h->coKC >= TH) {  // back-to-back launch costs of the column kernels
+    if (h->form == PcForm::Cols && h->coKC >= TH) {  // back-to-back launch costs of the column kernels
         hipEvent_t c0, c1;
         CK(hipEventCreate(&c0));
         CK(hipEventCreate(&c1));
@@ -297,11 +299,11 @@ int main(int argc, char** argv) {
         rs_pc_destroy(h);
         return 0;
     }
-    if (h->cols) {
+    if (h->form == PcForm::Cols) {
         rs_pc_destroy(h);
         return 0;
     }
-    if (Y > 64) {
+    if (h->rowsYP != 64) {
         rs_pc_destroy(h);
         return 0;
     }
