@@ -314,7 +314,9 @@ const char* rs_vt_scan_form(const rs_vt* h);
  * most promising block, pass B2 against every other block whose bound does not exceed
  * the score B1 found.  Before B1 the one template that holds the block's minimum bound
  * is scored exactly; where every other template's bound in the block exceeds that score
- * the query is settled without a block scan.  Exact for every
+ * the query is settled without a block scan.  Ahead of such a scan
+ * only the query planes of the aligned start rows are built; the verification expands
+ * the rest for the queries a scan pass reads.  Exact for every
  * input.  RS_VT_PRUNE (read at create): "0"
  * dense launch everywhere ("plane"), "1" (default) prune scans of at least 512 queries
  * over at least two template blocks, "force" prune at any size.

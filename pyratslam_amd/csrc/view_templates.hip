@@ -465,6 +465,46 @@ __device__ inline void transpose4x4_bytes(uint32_t a, uint32_t b, uint32_t c, ui
     o[3] = __builtin_amdgcn_perm(cd_hi, ab_hi, 0x07060302u);
 }
 
+// Compact query planes (H = 64): the units of the aligned start rows S0 + 4i, i < QC_NA
+// (rows 5, 9, .., 53).  Bit b of a plane is pixel (S + b/8, b%8), so the unit of start
+// row S + r, r in 0..3, is the low word of (unit(S + 4) : unit(S)) >> 8r, plane by plane;
+// the unit past the last (start row 57: rows 57..60, all zeroed) is zero.
+constexpr int QC_NA = (64 - 2 * FAST_M + 3 + 3) / 4;   // 13
+constexpr int QC_Q4 = PL_CG * QC_NA * 2;                // uint4 per query
+static_assert((FAST_M - 3) + 4 * QC_NA >= 64 - FAST_M, "the unit past the last aligned one is all zero");
+__device__ __forceinline__ uint4 qc_shift(uint4 lo, uint4 hi, uint32_t sh) {
+    return make_uint4(__builtin_amdgcn_alignbit(hi.x, lo.x, sh), __builtin_amdgcn_alignbit(hi.y, lo.y, sh),
+                      __builtin_amdgcn_alignbit(hi.z, lo.z, sh), __builtin_amdgcn_alignbit(hi.w, lo.w, sh));
+}
+// chunk c (of two) of the unit of start row S0 + si, column group cg, from a query's
+// compact planes in global memory
+__device__ __forceinline__ uint4 qc_unit(const uint4* __restrict__ qcq, int cg, int si, int c) {
+    const int ia = si >> 2;
+    const uint4 lo = qcq[(cg * QC_NA + ia) * 2 + c];
+    const uint4 hi = ia + 1 < QC_NA ? qcq[(cg * QC_NA + ia + 1) * 2 + c] : make_uint4(0u, 0u, 0u, 0u);
+    return qc_shift(lo, hi, 8u * (uint32_t)(si & 3));
+}
+
+// Every start row of queries [0, nq) from their compact planes: for the consumers that
+// read all queries' planes after a compact build (a matrix or dense scan).
+__global__ __launch_bounds__(256) void vt_qexpand_kernel(const uint4* __restrict__ qc4, uint4* __restrict__ qp4) {
+    constexpr int NS = 64 - 2 * FAST_M + 3;
+    const uint4* qcq = qc4 + (size_t)blockIdx.x * QC_Q4;
+    for (int i = threadIdx.x; i < PL_CG * NS * 2; i += blockDim.x) {
+        const int cg = i / (NS * 2), r = i - cg * (NS * 2);
+        qp4[(size_t)blockIdx.x * (PL_CG * NS * 2) + i] = qc_unit(qcq, cg, r >> 1, r & 1);
+    }
+}
+// ... and the compact planes from the full ones (a pruned scan after a full build).
+__global__ __launch_bounds__(128) void vt_qcompact_kernel(const uint4* __restrict__ qp4, uint4* __restrict__ qc4) {
+    constexpr int NS = 64 - 2 * FAST_M + 3;
+    const int i = threadIdx.x;
+    if (i < QC_Q4) {
+        const int cg = i / (QC_NA * 2), r = i - cg * (QC_NA * 2);
+        qc4[(size_t)blockIdx.x * QC_Q4 + i] = qp4[(size_t)blockIdx.x * (PL_CG * NS * 2) + (cg * NS + 4 * (r >> 1)) * 2 + (r & 1)];
+    }
+}
+
 // One block per query: query planes for every start row, and QS.  Phase 1: each
 // thread bit-transposes one 8-byte row segment (row r, column group cg) so byte
 // k holds bit k of its 8 pixels (rows outside [M, H-M) become zero), and adds
@@ -475,22 +515,29 @@ __device__ inline void transpose4x4_bytes(uint32_t a, uint32_t b, uint32_t c, ui
 // 0 .. 8*PF_CGS-1 of rows S..S+3 (the pairs the prefilter's bound covers), for
 // the start rows S = 4J+7-x, x = 0..2M-2, that prefilter unit J meets
 // (qsj[(query * PF_NU + u) * 16 + x]).
+// Compact mode (qc, H = 64, ahead of a pruned scan): phase 2 assembles only the QC_NA
+// aligned start rows S0 + 4i into qc[((q*CG + cg)*QC_NA + i)*8 + k] and leaves qp alone.
+// Every other start row is a funnel shift of two aligned units (qc_shift); the pruned
+// scan's kernels read these, and expand into qp the queries a scan pass will stage.
 __global__ __launch_bounds__(256) void vt_qplane_kernel(const uint8_t* __restrict__ raw, int H,
                                                         int M, uint32_t* __restrict__ qp,
                                                         uint32_t* __restrict__ qsum,
                                                         uint8_t* __restrict__ raw_copy,
-                                                        uint32_t* __restrict__ qsj) {
+                                                        uint32_t* __restrict__ qsj,
+                                                        uint32_t* __restrict__ qc) {
     constexpr int W = 8 * PL_CG;
     __shared__ uint32_t s_red[4];
     __shared__ uint2 s_t[64 * W / 8];   // transposed segments (H <= 64)
     __shared__ uint32_t s_rs[64];       // byte sums of the rows' first PF_CGS column groups (prune buffer only)
+    if (threadIdx.x < 4) s_red[threadIdx.x] = 0u;   // (a block may be fewer than four waves)
     if (qsj) {   // (kernel argument: uniform)
         if (threadIdx.x < 64) s_rs[threadIdx.x] = 0u;
         __syncthreads();
     }
-    const int NS = H - 2 * M + 3, S0 = M - 3;
+    // (compact: the aligned start rows only, NS of them at stride 4)
+    const int NS = qc ? QC_NA : H - 2 * M + 3, S0 = M - 3, SS = qc ? 4 : 1;
     const uint8_t* Q = raw + (size_t)blockIdx.x * H * W;
-    uint32_t* out = qp + (size_t)blockIdx.x * PL_CG * NS * 8;
+    uint32_t* out = (qc ? qc : qp) + (size_t)blockIdx.x * PL_CG * NS * 8;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     uint32_t part = 0;
     for (int d = threadIdx.x; d < H * W / 8; d += blockDim.x) {
@@ -509,7 +556,7 @@ __global__ __launch_bounds__(256) void vt_qplane_kernel(const uint8_t* __restric
     __syncthreads();
     const int NU = PL_CG * NS;
     for (int u = threadIdx.x; u < NU; u += blockDim.x) {
-        const int cg = u / NS, r0 = S0 + (u - cg * NS);
+        const int cg = u / NS, r0 = S0 + SS * (u - cg * NS);
         const uint2 q0 = s_t[(r0 + 0) * PL_CG + cg], q1 = s_t[(r0 + 1) * PL_CG + cg];
         const uint2 q2 = s_t[(r0 + 2) * PL_CG + cg], q3 = s_t[(r0 + 3) * PL_CG + cg];
         uint32_t lo[4], hi[4];
@@ -1088,11 +1135,11 @@ __device__ __forceinline__ uint32_t wave_min_u32_dpp(uint32_t v) {
 __global__ __launch_bounds__(64 * PF_WAVES) __attribute__((amdgpu_waves_per_eu(4)))
 void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
                                                                     int64_t count,
-                                                                    const uint4* __restrict__ qp4,
+                                                                    const uint4* __restrict__ qc4,
                                                                     const uint32_t* __restrict__ qsj, int nq,
                                                                     uint32_t* __restrict__ minlb,
                                                                     uint32_t* __restrict__ second) {
-    constexpr int M = FAST_M, NU = 64 / 4, NS = PlaneLds<64>::NS, S0 = M - 3;
+    constexpr int M = FAST_M, NU = 64 / 4, S0 = M - 3;
     static_assert(PF_CGS % PF_CPS == 0 && PF_CGS >= 1 && PF_CGS <= PL_CG, "whole steps of column groups, of the unit");
     static_assert(PF_NU * PF_CGS * 32 * 255 < (int)PF_NONE, "a bound and a lane fit one word");
     __shared__ uint4 s_q[PF_NB][PF_NU][PF_CGS][PL_NO][2];
@@ -1128,9 +1175,10 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
             const int qq = i / PF_QW4, r = i - qq * PF_QW4;
             const int u = r / (PF_CGS * PL_NO * 2), r2 = r - u * (PF_CGS * PL_NO * 2);
             const int cg = r2 / (PL_NO * 2), w = r2 - cg * (PL_NO * 2);
-            // start rows 4J-(M-1) .. 4J+(M-1) of column group cg < PF_CGS, two uint4 each
-            (&s_q[0][0][0][0][0])[i] =
-                qp4[((size_t)(q0 + qq) * PL_CG + cg) * (NS * 2) + (4 * pf_unit(u) - (M - 1) - S0) * 2 + w];
+            // start rows 4J-(M-1) .. 4J+(M-1) of column group cg < PF_CGS, two uint4 each,
+            // shifted out of the two aligned units around each
+            (&s_q[0][0][0][0][0])[i] = qc_unit(qc4 + (size_t)(q0 + qq) * QC_Q4, cg,
+                                               4 * pf_unit(u) - (M - 1) - S0 + (w >> 1), w & 1);
         }
         if ((int)threadIdx.x < nb * PF_NU * 16)
             (&s_qs[0][0][0])[threadIdx.x] = qsj[(size_t)q0 * PF_NU * 16 + threadIdx.x];
@@ -1264,34 +1312,45 @@ __device__ __forceinline__ void list_append(bool in, int q, unsigned* __restrict
 // the block scan would leave, and the query is settled: its key goes into best[] here
 // and tbstar[q] = ~tb* keeps it off list1.  ">": a template whose bound equals U0 may
 // hold an equal score at a lower index, so that query is block-scanned.
+// The query's planes come from its compact units (vt_qplane_kernel): lane (x, cg) walks
+// the aligned units upwards and shifts each pair by its own constant 8 * ((-o - 5) & 3).
+// Once U0 is known the wave writes every start row of the query into qp4 if a scan pass
+// will stage it: it is unsettled (list1), or another block's bound does not exceed U0
+// (the rule of vt_prune_rest_kernel: list2).  Nothing else reads a query's full planes.
 constexpr int VT_VQ4 = PlaneLds<64>::QW / 4;   // uint4 of a query's planes
+constexpr int VT_VR = QC_NA + 7;               // staged unit rows: 3 never-counted, the units, the zero unit, 3 more
 __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __restrict__ minlb,
                                                              const uint32_t* __restrict__ second, int ntb, int nq,
                                                              const uint4* __restrict__ planes,
                                                              const uint32_t* __restrict__ tsum,
-                                                             const uint4* __restrict__ qp4,
+                                                             const uint4* __restrict__ qc4,
+                                                             uint4* __restrict__ qp4,
                                                              const uint32_t* __restrict__ qsum,
                                                              unsigned long long* __restrict__ best, int rank,
                                                              int nranks, int* __restrict__ tbstar) {
     constexpr int M = FAST_M, NU = 64 / 4, NS = PlaneLds<64>::NS, S0 = M - 3, S1 = 64 - M - 1;
     static_assert(PL_NO * PL_CG <= 64, "one lane per (offset, column group)");
-    constexpr int QK = (VT_VQ4 + 63) / 64;
-    __shared__ uint4 s_q[QK * 64];           // [cg][start row - S0][2], padded to whole wave stores
+    constexpr int QK = (QC_Q4 + 63) / 64;
+    // [cg][3 + aligned unit][2]: unit QC_NA is the zero unit; the rows before and after are
+    // read (never counted) where a template unit meets no start row of the window
+    __shared__ uint4 s_q[PL_CG * VT_VR * 2];
     __shared__ uint4 s_t[PL_CG * NU * 2];    // [cg][unit][2]
     const int q = blockIdx.x, lane = threadIdx.x;
     const int x = lane >> 2, cg = lane & 3, o = x - (M - 1);
     // what does not wait for the pick, in flight through it: the query's planes and QS
     uint4 qv[QK];
 #pragma unroll
-    for (int k = 0; k < QK; ++k) qv[k] = qp4[(size_t)q * VT_VQ4 + min(lane + 64 * k, VT_VQ4 - 1)];
+    for (int k = 0; k < QK; ++k) qv[k] = qc4[(size_t)q * QC_Q4 + min(lane + 64 * k, QC_Q4 - 1)];
     const uint32_t qs = qsum[q];
-    // the pick: each lane's blocks with their `second`, so the winner's is at hand
+    // the pick: each lane's blocks with their `second`, so the winner's is at hand, and
+    // the lane's lowest bound but one (for the lowest bound of the blocks other than tb*)
     unsigned long long pk = ~0ull;
-    uint32_t sec = 0u;
+    uint32_t sec = 0u, m2 = 0xFFFFFFFFu;
     for (int tb = lane; tb < ntb; tb += 64) {
         const unsigned long long k = ((unsigned long long)minlb[(size_t)tb * nq + q] << 32) | (unsigned)tb;
         const uint32_t s2 = second[(size_t)tb * nq + q];
         const bool lt = k < pk;   // (selects: a branch would put the second read behind the first)
+        m2 = min(m2, (uint32_t)((lt ? pk : k) >> 32));
         pk = lt ? k : pk;
         sec = lt ? s2 : sec;
     }
@@ -1301,6 +1360,9 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
     for (int k = 0; k < QK; ++k) asm volatile("" : "+v"(qv[k].x), "+v"(qv[k].y), "+v"(qv[k].z), "+v"(qv[k].w));
     const unsigned long long mk = wave_min_u64(pk);
     const int tbs = (int)(unsigned)mk;
+    uint32_t other = pk == mk ? m2 : (uint32_t)(pk >> 32);   // min over tb != tb* of minLB[tb][q]
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) other = min(other, (uint32_t)__shfl_xor((int)other, off));
     sec = (uint32_t)__shfl((int)sec, __ffsll((unsigned long long)__ballot(pk == mk)) - 1);   // (one lane holds block tbs)
     const int tl = (int)(sec & 63u);
     const uint32_t ts = x < PL_NO ? tsum[((size_t)tbs * 16 + x) * 64 + tl] : 0u;
@@ -1310,19 +1372,30 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
     s_t[lane] = t0;
     s_t[64 + lane] = t1;
 #pragma unroll
-    for (int k = 0; k < QK; ++k) s_q[lane + 64 * k] = qv[k];   // (past VT_VQ4: copies of the last chunk, never read)
+    for (int k = 0; k < QK; ++k) {
+        const int c = lane + 64 * k, g = c / (QC_NA * 2);
+        if (c < QC_Q4) s_q[(g * VT_VR + 3) * 2 + (c - g * (QC_NA * 2))] = qv[k];
+    }
+    if (lane < 2 * PL_CG) s_q[((lane >> 1) * VT_VR + 3 + QC_NA) * 2 + (lane & 1)] = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
     uint32_t cnt = 0u;
     if (x < PL_NO) {
+        // start row 4j - o = S0 + 4 (j + a) + r: the units a + j and a + j + 1, shifted by 8r
+        const int a = (-o - S0) >> 2;   // (arithmetic: -3 .. 0)
+        const uint32_t sh = 8u * (uint32_t)((-o - S0) & 3);
+        const uint4* sq = s_q + (cg * VT_VR + 3 + a) * 2;
+        uint4 la = sq[0], lc = sq[1];
         // (four units' reads in flight: unrolled fully, the max-ILP scheduler reads all
         // sixteen ahead into 176 VGPRs, two waves per SIMD.  Branch-free: a unit whose
-        // start row lies outside the window reads a clamped row and counts nothing)
+        // start row lies outside the window reads rows nobody staged and counts nothing)
 #pragma unroll 4
         for (int j = 0; j < NU; ++j) {
             const bool in = 4 * j - o >= S0 && 4 * j - o <= S1;
-            const int s = min(max(4 * j - o, S0), S1);
             const uint4 ta = s_t[(cg * NU + j) * 2], tc = s_t[(cg * NU + j) * 2 + 1];
-            const uint4 qa = s_q[(cg * NS + s - S0) * 2], qc = s_q[(cg * NS + s - S0) * 2 + 1];
+            const uint4 ha = sq[(j + 1) * 2], hc = sq[(j + 1) * 2 + 1];
+            const uint4 qa = qc_shift(la, ha, sh), qc = qc_shift(lc, hc, sh);
+            la = ha;
+            lc = hc;
             uint32_t b = __builtin_amdgcn_bitop3_b32(ta.x, qa.x, 0u, 0x8E);
             b = __builtin_amdgcn_bitop3_b32(ta.y, qa.y, b, 0x8E);
             b = __builtin_amdgcn_bitop3_b32(ta.z, qa.z, b, 0x8E);
@@ -1340,8 +1413,18 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) u0 = min(u0, (uint32_t)__shfl_xor(u0, off));
     u0 -= qs;
+    const bool settled = (sec >> 6) > u0;
+    if (!settled || other <= u0) {   // (wave-uniform) a scan pass stages this query
+#pragma unroll
+        for (int k = 0; k < (VT_VQ4 + 63) / 64; ++k) {
+            const int i = lane + 64 * k, g = i / (NS * 2), r = i - g * (NS * 2), si = r >> 1;
+            if (i < VT_VQ4) {
+                const uint4* su = s_q + (g * VT_VR + 3 + (si >> 2)) * 2 + (r & 1);
+                qp4[(size_t)q * VT_VQ4 + i] = qc_shift(su[0], su[2], 8u * (uint32_t)(si & 3));
+            }
+        }
+    }
     if (lane == 0) {
-        const bool settled = (sec >> 6) > u0;
         if (settled) {
             const unsigned long long g = ((unsigned long long)tbs * 64 + tl) * nranks + rank;
             atomicMin(best + q, ((unsigned long long)u0 << 32) | g);
@@ -1352,12 +1435,17 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
 
 // ... and list1[tb] = the unsettled queries whose candidate block is tb (blockIdx.y =
 // tb).  The thread blocks of tb = 0 also count the settled queries (one add each).
+// The first thread block zeroes cnt2[]: the B2 pass of the call before has read it, this
+// call's vt_prune_rest_kernel fills it, and rs_vt_prune_stats totals it in between.
 __global__ __launch_bounds__(VT_LIST_T) void vt_prune_first_kernel(int nq, const int* __restrict__ tbstar,
                                                                    unsigned* __restrict__ cnt,
                                                                    int* __restrict__ list,
-                                                                   unsigned* __restrict__ verified) {
+                                                                   unsigned* __restrict__ verified,
+                                                                   unsigned* __restrict__ cnt2, int ntb) {
     const int q = blockIdx.x * VT_LIST_T + threadIdx.x, tb = blockIdx.y;
     const int ts = q < nq ? tbstar[q] : INT_MAX;
+    if (blockIdx.x == 0 && tb == 0)
+        for (int b = threadIdx.x; b < ntb; b += VT_LIST_T) cnt2[b] = 0u;
     if (tb == 0) {   // (block-uniform)
         const int n = __syncthreads_count(ts < 0);
         if (threadIdx.x == 0 && n) atomicAdd(verified, (unsigned)n);
@@ -1367,42 +1455,39 @@ __global__ __launch_bounds__(VT_LIST_T) void vt_prune_first_kernel(int nq, const
 
 // List (b), after pass B1: q joins the list of every other block whose bound does not
 // exceed U(q) = the score B1 left in best[q].
+// The first thread block also closes list (a), which pass B1 has read: stat[0] = the
+// queries pass B1 settled, by verification or by block scan, stat[2] = the verified ones
+// alone (rs_vt_prune_stats; the pairs of B2 are the sum of cnt[], taken on the host), and
+// cnt1[] and the verified count back to zero for the next call.
 __global__ __launch_bounds__(VT_LIST_T) void vt_prune_rest_kernel(const uint32_t* __restrict__ minlb, int nq,
                                                                   const int* __restrict__ tbstar,
                                                                   const unsigned long long* __restrict__ best,
                                                                   unsigned* __restrict__ cnt,
-                                                                  int* __restrict__ list) {
+                                                                  int* __restrict__ list,
+                                                                  unsigned* __restrict__ cnt1,
+                                                                  unsigned* __restrict__ verified, int ntb,
+                                                                  unsigned long long* __restrict__ stat) {
     const int q = blockIdx.x * VT_LIST_T + threadIdx.x, tb = blockIdx.y;
     const int ts = q < nq ? tbstar[q] : 0;   // ~tb* where the verification settled the query
     const bool in = q < nq && tb != (ts < 0 ? ~ts : ts) && minlb[(size_t)tb * nq + q] <= (uint32_t)(best[q] >> 32);
     list_append(in, q, cnt + tb, list + (size_t)tb * nq);
-}
-
-// The lists' totals for rs_vt_prune_stats (stat[0] = the queries pass B1 settled, by
-// verification or by block scan; stat[1] = the pairs of B2; stat[2] = the verified
-// ones alone), and all the counters back to zero.
-__global__ __launch_bounds__(256) void vt_prune_finish_kernel(unsigned* __restrict__ cnt1, unsigned* __restrict__ cnt2,
-                                                              unsigned* __restrict__ verified, int ntb,
-                                                              unsigned long long* __restrict__ stat) {
-    __shared__ unsigned long long s_sum[2];
-    if (threadIdx.x < 2) s_sum[threadIdx.x] = 0ull;
-    __syncthreads();
-    unsigned long long a = 0ull, b = 0ull;
-    for (int tb = threadIdx.x; tb < ntb; tb += blockDim.x) {
-        a += cnt1[tb];
-        b += cnt2[tb];
-        cnt1[tb] = 0u;
-        cnt2[tb] = 0u;
-    }
-    atomicAdd(&s_sum[0], a);
-    atomicAdd(&s_sum[1], b);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned v = *verified;
-        *verified = 0u;
-        stat[0] = s_sum[0] + v;
-        stat[1] = s_sum[1];
-        stat[2] = v;
+    if (blockIdx.x == 0 && tb == 0) {   // (block-uniform)
+        __shared__ unsigned long long s_sum;
+        if (threadIdx.x == 0) s_sum = 0ull;
+        __syncthreads();
+        unsigned long long a = 0ull;
+        for (int b = threadIdx.x; b < ntb; b += VT_LIST_T) {
+            a += cnt1[b];
+            cnt1[b] = 0u;
+        }
+        if (a) atomicAdd(&s_sum, a);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned v = *verified;
+            *verified = 0u;
+            stat[0] = s_sum + v;
+            stat[2] = v;
+        }
     }
 }
 
@@ -1581,17 +1666,28 @@ struct rs_vt {
     int prune = 0;
     uint32_t* dQsj = nullptr;        // QS_J of the queries in dQp (with dQp's capacity)
     uint32_t* dQsjStream = nullptr;  // ... of dQpStream
+    // compact query planes (the aligned start rows; with dQp's / dQpStream's capacity).  A
+    // build ahead of a pruned scan fills dQc only and the verification expands into dQp
+    // the queries a scan pass reads; every other reader of dQp expands the rest first.
+    uint32_t* dQc = nullptr;
+    uint32_t* dQcStream = nullptr;
+    bool qpFull = true;              // dQp holds every start row of all the queries last built
+    bool qcValid = false;            // dQc holds their compact planes
     uint32_t* dMinLB = nullptr;      // [ntb][nq]
     uint32_t* dSecond = nullptr;     // [ntb][nq] (min2 << 6) | lane of the minimum
     int* dList = nullptr;            // list1 [ntb][nq], then list2 [ntb][nq]
     size_t pruneCap = 0;             // ntb * nq the three are sized for
     int* dTbStar = nullptr;          // [nq] candidate block (~block: settled by verification)
     int tbStarCap = 0;
-    unsigned* dListCnt = nullptr;    // [2][listCntCap] entries per list, then the verified count; zero between calls
+    // [2][listCntCap] entries per list, then the verified count.  List 1's and the verified
+    // count are zero between calls (vt_prune_rest_kernel); list 2's stay for
+    // rs_vt_prune_stats until the next pruned launch's vt_prune_first_kernel zeroes them
+    unsigned* dListCnt = nullptr;
     int listCntCap = 0;
-    unsigned long long* dPruneStat = nullptr;  // list totals and verified count of the last pruned launch
+    unsigned long long* dPruneStat = nullptr;  // list 1's total ([0]) and the verified count ([2]) of the last pruned launch
     int64_t prunePairs = 0;          // its ntb * nq
     int prunePasses = 0;             // its scan passes (0: no pruned launch yet)
+    int pruneNtb = 0;                // its template blocks (the entries of list2's counters)
     // on-device subsampling of camera frames (rs_vt_set_subsample / rs_vt_match_frames)
     int32_t* dPix = nullptr;   // H*W byte offsets of the kept pixels in a frame
     int64_t frameBytes = 0;
@@ -1691,12 +1787,14 @@ int vt_grow_queries(rs_vt* h, int nq) {
     if (h->dQp) RS_HIP(hipFree(h->dQp));
     if (h->dQsumRaw) RS_HIP(hipFree(h->dQsumRaw));
     if (h->dQsj) RS_HIP(hipFree(h->dQsj));
-    h->dQp = h->dQsumRaw = h->dQsj = nullptr;
+    if (h->dQc) RS_HIP(hipFree(h->dQc));
+    h->dQp = h->dQsumRaw = h->dQsj = h->dQc = nullptr;
     const size_t qb = (size_t)h->H * h->W;
     if (h->planar) {
         RS_HIP(hipMalloc(&h->dQp, sizeof(uint32_t) * PL_CG * plane_ns(h) * 8 * (size_t)cap));
         RS_HIP(hipMalloc(&h->dQsumRaw, sizeof(uint32_t) * cap));
         if (h->prune) RS_HIP(hipMalloc(&h->dQsj, sizeof(uint32_t) * PF_NU * 16 * (size_t)cap));
+        if (h->prune) RS_HIP(hipMalloc(&h->dQc, sizeof(uint4) * QC_Q4 * (size_t)cap));
     }
     RS_HIP(hipMalloc(&h->dQraw, qb * cap));
     RS_HIP(hipHostMalloc(&h->hQraw, qb * cap, hipHostMallocMapped | hipHostMallocCoherent));
@@ -1756,6 +1854,32 @@ int vt_grow_cand(rs_vt* h, int64_t slots) {
 
 int vt_build_forms(rs_vt* h, int nq);
 
+// Frozen key scans of at least this many queries prune (RS_VT_PRUNE=1, the default).
+constexpr int VT_PRUNE_MIN_Q = 512;
+
+// Whether a scan of nq queries against `count` slots from block tb0 takes the pruned path.
+// Below VT_PRUNE_MIN_Q queries the call is one latency-bound launch and the prefilter, the
+// list kernels and two scan passes cost more than they save; one template block has
+// nothing to prune.
+bool vt_prunes(const rs_vt* h, bool cand, int64_t tb0, int64_t count, int nq) {
+    const int64_t ntb = (count + 63) / 64;
+    return h->H == 64 && !cand && tb0 == 0 && h->dQsj && h->dQc && ntb <= 65535 &&
+           (h->prune == 2 || (h->prune == 1 && nq >= VT_PRUNE_MIN_Q && ntb >= 2));
+}
+// The plane build ahead of a key scan of the library: compact where that scan will prune.
+// A wrong guess costs a conversion launch (vt_launch_plane), never a result.
+// Threads of a compact build's block: phase 2 has 52 units to assemble, and two waves per
+// query measured faster than four and level with one (15.8, 12.9 and 13.7 us at the
+// headline shape).
+constexpr int VT_QC_THREADS = 128;
+uint32_t* vt_compact_for(rs_vt* h, int nq) {
+    const int64_t lc = local_count_of(h, h->count);
+    const bool compact = h->planar && lc > 0 && vt_prunes(h, false, 0, lc, nq);
+    h->qpFull = !compact;
+    h->qcValid = compact;
+    return compact ? h->dQc : nullptr;
+}
+
 // Batches of at most this many queries are read by the plane kernel straight from the
 // pinned staging array (one launch in place of a host-to-device copy and the launch;
 // the kernel leaves the raw bytes in dQraw for the template stores); RS_VT_ZC=0: always
@@ -1782,8 +1906,9 @@ int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
     if (h->planar && nq <= VT_ZC_MAX && vt_zc_env()) {
         std::memcpy(h->hQraw, queries, qb);
         h->qrawBusy = true;
-        hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(256), 0, h->stream, h->hQrawDev, h->H, h->M, h->dQp,
-                           h->dQsumRaw, h->dQraw, h->dQsj);
+        uint32_t* const qc = vt_compact_for(h, nq);
+        hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(qc ? VT_QC_THREADS : 256), 0, h->stream, h->hQrawDev, h->H,
+                           h->M, h->dQp, h->dQsumRaw, h->dQraw, h->dQsj, qc);
         RS_HIP(hipGetLastError());
         return RS_OK;
     }
@@ -1797,9 +1922,11 @@ int vt_build_forms(rs_vt* h, int nq, const uint8_t* src) {
     if (!h->planar)
         hipLaunchKernelGGL(vt_qform_kernel, dim3(nq), dim3(256), 0, h->stream, src, h->H, h->W,
                            h->WD, h->M, h->dQf, h->dQsum);
-    else
-        hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(256), 0, h->stream, src, h->H,
-                           h->M, h->dQp, h->dQsumRaw, nullptr, h->dQsj);
+    else {
+        uint32_t* const qc = vt_compact_for(h, nq);
+        hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(qc ? VT_QC_THREADS : 256), 0, h->stream, src, h->H,
+                           h->M, h->dQp, h->dQsumRaw, nullptr, h->dQsj, qc);
+    }
     RS_HIP(hipGetLastError());
     return RS_OK;
 }
@@ -1882,9 +2009,6 @@ int plane_split(int ntb, int nbatch, int slots) {
     return nqc;
 }
 
-// Frozen key scans of at least this many queries prune (RS_VT_PRUNE=1, the default).
-constexpr int VT_PRUNE_MIN_Q = 512;
-
 // Launch a scan of queries [0, nq) (forms in dQf) against `count` slots of lib.
 template <bool MATRIX>
 int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int rank,
@@ -1906,12 +2030,13 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
         reinterpret_cast<const uint8_t*>(cand ? h->dCandP : h->dLibP) + (size_t)tb0 * pblock_bytes(h));
     const uint32_t* ts = (cand ? h->dCandTs : h->dLibTs) + (size_t)tb0 * (TS_BLOCK_BYTES / 4);
     if constexpr (!MATRIX) {
-        // Pruned scan of the frozen library.  Below VT_PRUNE_MIN_Q queries the call is one
-        // latency-bound launch and the prefilter, the list kernels and two scan passes
-        // cost more than they save; one template block has nothing to prune.
-        const bool pruned = h->H == 64 && !cand && tb0 == 0 && h->dQsj && ntb <= 65535 &&
-                            (h->prune == 2 || (h->prune == 1 && nq >= VT_PRUNE_MIN_Q && ntb >= 2));
-        if (pruned) {
+        // Pruned scan of the frozen library (vt_prunes).
+        if (vt_prunes(h, cand, tb0, count, nq)) {
+            if (!h->qcValid) {   // the build before did not expect this scan to prune
+                hipLaunchKernelGGL(vt_qcompact_kernel, dim3((unsigned)nq), dim3(128), 0, h->stream,
+                                   reinterpret_cast<const uint4*>(h->dQp), reinterpret_cast<uint4*>(h->dQc));
+                h->qcValid = true;
+            }
             const size_t pairs = (size_t)ntb * nq;
             if (pairs > h->pruneCap) {
                 const size_t cap = std::max(pairs, 2 * h->pruneCap);
@@ -1934,7 +2059,7 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
                 RS_HIP(hipMalloc(&h->dTbStar, sizeof(int) * (size_t)nq));
                 h->tbStarCap = nq;
             }
-            if (ntb > h->listCntCap) {  // like dCtr: zero at first, and every call leaves them at zero
+            if (ntb > h->listCntCap) {  // zero at first; the list kernels zero what they are about to fill
                 const int cap = std::max(ntb, 2 * h->listCntCap);
                 if (h->dListCnt) RS_HIP(hipFree(h->dListCnt));
                 h->dListCnt = nullptr;
@@ -1955,14 +2080,15 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
             const int nqb = (nq + PF_NB - 1) / PF_NB, pfx = (ntb + PF_WAVES * PF_TPW - 1) / (PF_WAVES * PF_TPW);
             const dim3 pgrid((unsigned)pfx, (unsigned)std::min(nqb, std::max(1, VT_PF_GRID_CAP / pfx)));
             hipLaunchKernelGGL(vt_prefilter_kernel, pgrid, dim3(64 * PF_WAVES), 0, h->stream, planes, ntb, count,
-                               reinterpret_cast<const uint4*>(h->dQp), h->dQsj, nq, h->dMinLB,
+                               reinterpret_cast<const uint4*>(h->dQc), h->dQsj, nq, h->dMinLB,
                                h->dSecond);
             hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, h->dMinLB,
-                               h->dSecond, ntb, nq, planes, ts, reinterpret_cast<const uint4*>(h->dQp), h->dQsumRaw,
+                               h->dSecond, ntb, nq, planes, ts, reinterpret_cast<const uint4*>(h->dQc),
+                               reinterpret_cast<uint4*>(h->dQp), h->dQsumRaw,
                                out.best, rank, nranks, h->dTbStar);
             const dim3 lgrid((unsigned)((nq + VT_LIST_T - 1) / VT_LIST_T), (unsigned)ntb);
             hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar, cnt1,
-                               list1, verified);
+                               list1, verified, cnt2, ntb);
             // the passes min into the same keys; the folded export (out.host) needs one
             // launch to be the last, so a pruned call exports with vt_keys_export
             ScanOut po = out;
@@ -1972,20 +2098,24 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
                                h->stream, planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, po, rank,
                                nranks, PlaneList{list1, cnt1, nq, VT_LIST_PER_B1});
             hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB, nq,
-                               h->dTbStar, out.best, cnt2, list2);
+                               h->dTbStar, out.best, cnt2, list2, cnt1, verified, ntb, h->dPruneStat);
             hipLaunchKernelGGL((vt_scan_plane_kernel<64, false, true>), grid, dim3(64 * PL_CG * PL_SPLIT), 0,
                                h->stream, planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, po, rank,
                                nranks, PlaneList{list2, cnt2, nq, VT_LIST_PER});
-            hipLaunchKernelGGL(vt_prune_finish_kernel, dim3(1), dim3(256), 0, h->stream, cnt1, cnt2, verified,
-                               ntb, h->dPruneStat);
             if (out.host)
                 hipLaunchKernelGGL(vt_keys_export, dim3((nq + 255) / 256 < 64 ? (nq + 255) / 256 : 64), dim3(256), 0,
                                    h->stream, out.best, nq, out.host);
             RS_HIP(hipGetLastError());
             h->prunePairs = (int64_t)pairs;
             h->prunePasses = 2;
+            h->pruneNtb = ntb;
             return RS_OK;
         }
+    }
+    if (!h->qpFull) {   // a compact build, and a scan that reads every query's planes
+        hipLaunchKernelGGL(vt_qexpand_kernel, dim3((unsigned)nq), dim3(256), 0, h->stream,
+                           reinterpret_cast<const uint4*>(h->dQc), reinterpret_cast<uint4*>(h->dQp));
+        h->qpFull = true;
     }
     if (h->H == 64)
         hipLaunchKernelGGL((vt_scan_plane_kernel<64, MATRIX>), grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream,
@@ -2310,24 +2440,28 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
         uint32_t* p;
         uint32_t* q;
         uint32_t* j;
-        ~PlaneBufRestore() { h->dQp = p; h->dQsumRaw = q; h->dQsj = j; }
-    } restore{h, h->dQp, h->dQsumRaw, h->dQsj};
+        uint32_t* c;
+        ~PlaneBufRestore() { h->dQp = p; h->dQsumRaw = q; h->dQsj = j; h->dQc = c; }
+    } restore{h, h->dQp, h->dQsumRaw, h->dQsj, h->dQc};
     if (allplanes) {
         if (total > h->qpStreamCap) {
             if (h->dQpStream) RS_HIP(hipFree(h->dQpStream));
             if (h->dQsumStream) RS_HIP(hipFree(h->dQsumStream));
             if (h->dQsjStream) RS_HIP(hipFree(h->dQsjStream));
-            h->dQpStream = h->dQsumStream = h->dQsjStream = nullptr;
+            if (h->dQcStream) RS_HIP(hipFree(h->dQcStream));
+            h->dQpStream = h->dQsumStream = h->dQsjStream = h->dQcStream = nullptr;
             h->qpStreamCap = 0;
             RS_HIP(hipMalloc(&h->dQpStream, sizeof(uint32_t) * qpq * total));
             RS_HIP(hipMalloc(&h->dQsumStream, sizeof(uint32_t) * total));
             if (h->prune) RS_HIP(hipMalloc(&h->dQsjStream, sizeof(uint32_t) * PF_NU * 16 * total));
+            if (h->prune) RS_HIP(hipMalloc(&h->dQcStream, sizeof(uint4) * QC_Q4 * total));
             h->qpStreamCap = total;
         }
         RS_CHECK(total <= INT32_MAX, RS_ERR_ARG, "too many queries in one stream");
         h->dQp = h->dQpStream;
         h->dQsumRaw = h->dQsumStream;
         h->dQsj = h->dQsjStream;
+        h->dQc = h->dQcStream;
         if (!hostgroups) {
             RS_TRY(vt_build_forms(h, (int)total, queries));
             const ScanOut out{h->dStream, nullptr, 0};
@@ -2374,6 +2508,7 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
                 h->dQp = h->dQpStream + qpq * (size_t)b0 * nq;
                 h->dQsumRaw = h->dQsumStream + (size_t)b0 * nq;
                 if (h->dQsjStream) h->dQsj = h->dQsjStream + (size_t)PF_NU * 16 * b0 * nq;
+                if (h->dQcStream) h->dQc = h->dQcStream + (size_t)QC_Q4 * 4 * b0 * nq;
                 RS_TRY(vt_build_forms(h, n * nq, h->dUp[bi]));
                 RS_HIP(hipEventRecord(h->evUsed[bi], h->stream));
                 const ScanOut out{h->dStream + (size_t)b0 * nq, nullptr, 0};
@@ -2541,7 +2676,7 @@ int rs_vt_destroy(rs_vt* h) {
                     (void*)h->dSrc, (void*)h->dDst, (void*)h->dCand, (void*)h->dMat, (void*)h->dLibP,
                     (void*)h->dLibTs, (void*)h->dCandP, (void*)h->dCandTs, (void*)h->dQp,
                     (void*)h->dQsumRaw, (void*)h->dCtr, (void*)h->dDone, (void*)h->dPix, (void*)h->dFrames,
-                    (void*)h->dQsj, (void*)h->dQsjStream, (void*)h->dMinLB, (void*)h->dSecond, (void*)h->dList, (void*)h->dTbStar,
+                    (void*)h->dQsj, (void*)h->dQsjStream, (void*)h->dQc, (void*)h->dQcStream, (void*)h->dMinLB, (void*)h->dSecond, (void*)h->dList, (void*)h->dTbStar,
                     (void*)h->dListCnt, (void*)h->dPruneStat})
         if (p) (void)hipFree(p);
     if (h->hStream) (void)hipHostFree(h->hStream);
@@ -2769,11 +2904,15 @@ int rs_vt_prune_stats(rs_vt* h, int64_t out[4]) {
     out[0] = out[1] = out[2] = out[3] = 0;
     if (h->prunePasses == 0) return RS_OK;
     RS_HIP(hipSetDevice(h->device));
-    unsigned long long s[2] = {0ull, 0ull};
-    RS_HIP(hipMemcpyAsync(s, h->dPruneStat, sizeof(s), hipMemcpyDeviceToHost, h->stream));
+    // the pairs of B2: list2's counters, which stay until the next pruned launch's lists
+    unsigned long long s0 = 0ull;
+    std::vector<unsigned> c2((size_t)h->pruneNtb);
+    RS_HIP(hipMemcpyAsync(&s0, h->dPruneStat, sizeof(s0), hipMemcpyDeviceToHost, h->stream));
+    RS_HIP(hipMemcpyAsync(c2.data(), h->dListCnt + h->listCntCap, sizeof(unsigned) * c2.size(), hipMemcpyDeviceToHost,
+                          h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
-    out[0] = (int64_t)s[0];
-    out[1] = (int64_t)s[1];
+    out[0] = (int64_t)s0;
+    for (const unsigned c : c2) out[1] += (int64_t)c;
     out[2] = h->prunePairs;
     out[3] = h->prunePasses;
     return RS_OK;
