@@ -2970,31 +2970,32 @@ struct OdoTables {
 // The step-kernel family of a handle (the file's header comment; rs_pc_step_form names it).
 enum class PcForm { Rows, Stream, Cols, Halo };
 
+// The buffers are rs::DevBuf / rs::PinnedBuf members (rs_common.h; untyped ones count bytes,
+// the element being esz wide).  Group capacities: resCap (dRes, hRes, dArgV, dArgI), ctlCap.
 struct rs_pc {
     int X = 0, Y = 0, TH = 0, prec = RS_PREC_F32, device = 0;
     size_t n = 0, esz = 4;
     hipStream_t stream = nullptr;
-    void* dP = nullptr;
-    void* dQ = nullptr;
-    void* dFilt = nullptr;
+    rs::DevBuf<void> dP;
+    rs::DevBuf<void> dQ;
+    rs::DevBuf<void> dFilt;
     int nf = 0;
-    double* dPart = nullptr;
+    rs::DevBuf<double> dPart;
     int nPart = 0;               // blocks of a step kernel (excitation and path alike; set by the form)
-    void* dBmax = nullptr;       // f64 argmax partials (max(nPart, argmax grid))
-    unsigned* dBidx = nullptr;
+    rs::DevBuf<void> dBmax;      // f64 argmax partials (max(nPart, argmax grid))
+    rs::DevBuf<unsigned> dBidx;
     int nBmaxCap = 0;
-    unsigned long long* dRes = nullptr;
+    rs::DevBuf<unsigned long long> dRes;
     int resCap = 0;
-    void* dArgV = nullptr;        // per-step per-block argmax partials [resCap][nPart]
-    unsigned* dArgI = nullptr;
-    unsigned long long* hRes = nullptr;  // pinned
-    unsigned long long* hResDev = nullptr;  // hRes in the device's address space (pc_res_export)
-    unsigned char* dCtl = nullptr;
-    unsigned char* hCtl = nullptr;       // pinned
+    rs::DevBuf<void> dArgV;       // per-step per-block argmax partials [resCap][nPart]
+    rs::DevBuf<unsigned> dArgI;
+    rs::PinnedBuf<unsigned long long> hRes;  // fine-grained; dev(): where pc_res_export stores
+    rs::DevBuf<unsigned char> dCtl;
+    rs::PinnedBuf<unsigned char> hCtl;
     size_t ctlStride = 0;
     int ctlCap = 0;
-    double* dTmp = nullptr;              // export/import staging (n doubles)
-    double* dScalar = nullptr;
+    rs::DevBuf<double> dTmp;             // export/import staging (n doubles)
+    rs::DevBuf<double> dScalar;
     SepKernel<float> kf{};
     SepKernel<double> kd{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -3005,13 +3006,10 @@ struct rs_pc {
     double kernelMs[2] = {0.0, 0.0};
     PcForm form = PcForm::Rows;  // the step-kernel family (pc_choose_form); its geometry below
     int rowsYP = 0;         // rows: the kernels' YP instance, 64 (Y <= 64) or 128 (Y <= 128)
-    unsigned long long* dRec = nullptr;  // halo: the last launch's per-block (key of max U, near count)
-    unsigned long long* hRec = nullptr;  // ... for a one-step call: pinned host records (hRecDev on the device)
-    unsigned long long* hRecDev = nullptr;
-    unsigned* hFlag = nullptr;      // halo: pc_halo_finish's per-block flags (pinned; eager readback polls)
-    unsigned* hFlagDev = nullptr;
-    unsigned long long* hKey = nullptr;     // halo: pc_halo_finish's per-block keys of a call's last step (pinned)
-    unsigned long long* hKeyDev = nullptr;
+    rs::DevBuf<unsigned long long> dRec;     // halo: the last launch's per-block (key of max U, near count)
+    rs::PinnedBuf<unsigned long long> hRec;  // ... for a one-step call: pinned host records
+    rs::PinnedBuf<unsigned> hFlag;           // halo: pc_halo_finish's per-block flags (pinned; eager readback polls)
+    rs::PinnedBuf<unsigned long long> hKey;  // halo: pc_halo_finish's per-block keys of a call's last step (pinned)
     unsigned flagSeq = 0u;
     bool haloPend = false;  // halo: the state is U, unnormalised, in buffer haloCur (0 dP, 1 dQ) with
     int haloCur = 0, haloPart = 0;  // its partial sums in half haloPart of dPart (pc_halo_settle)
@@ -3028,8 +3026,7 @@ struct rs_pc {
     std::vector<double> cZf;
     bool dbgSkipExport = false;  // rs_pc_debug(RS_PC_DBG_SKIP_EXPORT): the next run leaves hRes unwritten
     double* exportDev = nullptr;  // rs_pc_update_odom_read: the state export queued behind the step
-    double* hRead = nullptr;     // rs_pc_read: pinned float64 volume the export kernel writes in place
-    double* hReadDev = nullptr;
+    rs::PinnedBuf<double> hRead; // rs_pc_read: pinned float64 volume the export kernel writes in place
 };
 
 namespace {
@@ -3043,43 +3040,34 @@ inline bool pc_thfast(const rs_pc* h) { return h->form == PcForm::Cols || h->for
 // only for the forms that read it (ctl): the halo and column forms take each step's
 // control as kernel arguments, and a 10,000-step batch's 16 MiB of pinned ring was a
 // few milliseconds of page-locking inside its first call.
+constexpr unsigned PC_FINE = hipHostMallocMapped | hipHostMallocCoherent;
+
 int pc_grow_steps(rs_pc* h, int n, bool ctl = true) {
     if (n > h->resCap) {
         int cap = h->resCap > 0 ? h->resCap : 16;
         while (cap < n) cap *= 2;
-        if (h->dRes) RS_HIP(hipFree(h->dRes));
-        if (h->hRes) RS_HIP(hipHostFree(h->hRes));
-        if (h->dArgV) RS_HIP(hipFree(h->dArgV));
-        if (h->dArgI) RS_HIP(hipFree(h->dArgI));
-        h->dRes = nullptr; h->hRes = nullptr; h->hResDev = nullptr;
-        h->dArgV = nullptr; h->dArgI = nullptr;
         h->resCap = 0;
-        RS_HIP(hipMalloc(&h->dRes, sizeof(unsigned long long) * RES_SLOTS * cap));
+        RS_TRY(h->dRes.reserve((size_t)RES_SLOTS * cap));
         // every slot starts zeroed (the excitation's block 0 zeroes a step's slots again
         // before its path kernel max-reduces into them; no step ever reads freed data)
-        RS_HIP(hipMemsetAsync(h->dRes, 0, sizeof(unsigned long long) * RES_SLOTS * cap, h->stream));
+        RS_HIP(hipMemsetAsync(h->dRes.get(), 0, sizeof(unsigned long long) * RES_SLOTS * cap, h->stream));
         // the export kernel stores each step's key here with a system-scope store:
         // fine-grained (coherent) host memory, so the store is visible once the stream
         // has synchronised; pc_run_impl also checks a sentinel per step (RES_NONE)
-        RS_HIP(hipHostMalloc(&h->hRes, sizeof(unsigned long long) * cap,
-                             hipHostMallocMapped | hipHostMallocCoherent));
-        for (int s = 0; s < cap; ++s) h->hRes[s] = RES_NONE;
-        RS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hResDev), h->hRes, 0));
+        RS_TRY(h->hRes.reserve((size_t)cap, PC_FINE));
+        for (int s = 0; s < cap; ++s) h->hRes.get()[s] = RES_NONE;
         if (h->prec == RS_PREC_F64) {  // float64 argmax: per-block partials + pc_argmax_steps
-            RS_HIP(hipMalloc(&h->dArgV, h->esz * (size_t)cap * h->nPart));
-            RS_HIP(hipMalloc(&h->dArgI, sizeof(unsigned) * (size_t)cap * h->nPart));
+            RS_TRY(h->dArgV.reserve(h->esz * (size_t)cap * h->nPart));
+            RS_TRY(h->dArgI.reserve((size_t)cap * h->nPart));
         }
         h->resCap = cap;
     }
     if (ctl && n > h->ctlCap) {
         int cap = h->ctlCap > 0 ? h->ctlCap : 16;
         while (cap < n) cap *= 2;
-        if (h->dCtl) RS_HIP(hipFree(h->dCtl));
-        if (h->hCtl) RS_HIP(hipHostFree(h->hCtl));
-        h->dCtl = nullptr; h->hCtl = nullptr;
         h->ctlCap = 0;
-        RS_HIP(hipMalloc(&h->dCtl, h->ctlStride * cap));
-        RS_HIP(hipHostMalloc(&h->hCtl, h->ctlStride * cap, hipHostMallocDefault));
+        RS_TRY(h->dCtl.reserve(h->ctlStride * cap));
+        RS_TRY(h->hCtl.reserve(h->ctlStride * cap, hipHostMallocDefault));
         h->ctlCap = cap;
     }
     return RS_OK;
@@ -3118,7 +3106,7 @@ int pc_pack_ctl(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
                 const double* zf, unsigned char* dst = nullptr) {
     const int TH = h->TH;
     for (int s = 0; s < n; ++s) {
-        unsigned char* rec = (dst ? dst : h->hCtl) + (size_t)s * h->ctlStride;
+        unsigned char* rec = (dst ? dst : h->hCtl.get()) + (size_t)s * h->ctlStride;
         std::memcpy(rec, ox + (size_t)s * TH, sizeof(int32_t) * TH);
         std::memcpy(rec + ctl_off_oy(h), oy + (size_t)s * TH, sizeof(int32_t) * TH);
         std::memcpy(rec + ctl_off_f(h), fidx + (size_t)s * TH, sizeof(int32_t) * TH);
@@ -3158,7 +3146,7 @@ void make_ctl_inline(const rs_pc* h, int s, const int32_t* ox, const int32_t* oy
 
 // ... or as pointers into the device ring record of step s.
 PcCtlRing make_ctl_ring(const rs_pc* h, int s, const unsigned char* ring = nullptr) {
-    const unsigned char* rec = (ring ? ring : h->dCtl) + (size_t)s * h->ctlStride;
+    const unsigned char* rec = (ring ? ring : h->dCtl.get()) + (size_t)s * h->ctlStride;
     return PcCtlRing{reinterpret_cast<const int*>(rec),
                      reinterpret_cast<const int*>(rec + ctl_off_oy(h)),
                      reinterpret_cast<const int*>(rec + ctl_off_f(h)),
@@ -3215,9 +3203,9 @@ struct StepOut {
     unsigned* bidx;
 };
 inline StepOut step_out(const rs_pc* h, int s) {
-    return StepOut{h->dRes + (size_t)s * RES_SLOTS,
-                   h->dArgV ? static_cast<char*>(h->dArgV) + h->esz * (size_t)s * h->nPart : nullptr,
-                   h->dArgI ? h->dArgI + (size_t)s * h->nPart : nullptr};
+    return StepOut{h->dRes.get() + (size_t)s * RES_SLOTS,
+                   h->dArgV.get() ? static_cast<char*>(h->dArgV.get()) + h->esz * (size_t)s * h->nPart : nullptr,
+                   h->dArgI.get() ? h->dArgI.get() + (size_t)s * h->nPart : nullptr};
 }
 
 // Wait for a call's result words (pinned host memory, each one 8-byte system-scope store
@@ -3227,7 +3215,7 @@ inline StepOut step_out(const rs_pc* h, int s) {
 // same reason as the halo form's record polling (pc_run_halo): the host reads nothing
 // else the call wrote, and every later device access is ordered on the stream.
 bool pc_poll_words(const rs_pc* h, int s0, int s1) {
-    const volatile unsigned long long* w = h->hRes;
+    const volatile unsigned long long* w = h->hRes.get();
     int s = s0;
     for (long spin = 0; spin < 4000000 && s < s1; ++spin)
         while (s < s1 && w[s] != RES_NONE) ++s;
@@ -3252,14 +3240,14 @@ bool halo_flags_env() {
     return on;
 }
 bool xp_poll_ok(const rs_pc* h, int n, bool poll_env) {
-    return poll_env && halo_flags_env() && h->exportDev && h->hFlag && !h->profiling && !h->dbgSkipExport &&
+    return poll_env && halo_flags_env() && h->exportDev && h->hFlag.get() && !h->profiling && !h->dbgSkipExport &&
            n <= HF_POLL_MAX && (int)std::min<size_t>(1024, (h->n / 4 + 255) / 256) <= HF_FLAGS;
 }
 
 // Spin until pc_halo_finish's nb blocks have each stored flag value seq (bounded; false
 // when the spin runs out and the caller must synchronise the stream instead).
 bool pc_poll_flags(const rs_pc* h, int nb, unsigned seq) {
-    const volatile unsigned* f = h->hFlag;
+    const volatile unsigned* f = h->hFlag.get();
     int b = 0;
     for (long spin = 0; spin < 4000000 && b < nb; ++spin)
         while (b < nb && f[b] == seq) ++b;
@@ -3274,7 +3262,7 @@ unsigned pc_next_seq(rs_pc* h) {
     return seq;
 }
 bool pc_flags_ok(const rs_pc* h, int nb) {
-    return halo_poll_env() && halo_flags_env() && h->hFlag && !h->profiling && nb <= HF_FLAGS;
+    return halo_poll_env() && halo_flags_env() && h->hFlag.get() && !h->profiling && nb <= HF_FLAGS;
 }
 // The export kernel's grid when its flags are polled: at most 128 blocks, each thread
 // storing a few 16-byte pieces (fewer blocks, fewer flags; 64x64x36 rows-form read 32-36
@@ -3312,10 +3300,10 @@ unsigned long long halo_key_from_records(const unsigned long long* rec, int nrec
 // it first.  (The next call's first launch consumes it as it is: it scales on load.)
 int pc_halo_settle(rs_pc* h) {
     if (!h->haloPend) return RS_OK;
-    float* buf[2] = {static_cast<float*>(h->dP), static_cast<float*>(h->dQ)};
+    float* buf[2] = {static_cast<float*>(h->dP.get()), static_cast<float*>(h->dQ.get())};
     const int n4 = (int)(h->n / 4), nb = std::min(1024, (n4 + 255) / 256);
     hipLaunchKernelGGL(pc_halo_finish, dim3(nb), dim3(256), 0, h->stream, buf[h->haloCur], buf[0], n4,
-                       h->dPart + (size_t)h->haloPart * h->nPart, h->nPart, nullptr, nullptr, 0, nullptr,
+                       h->dPart.get() + (size_t)h->haloPart * h->nPart, h->nPart, nullptr, nullptr, 0, nullptr,
                        nullptr, nullptr, (int)(h->n * sizeof(float)), nullptr, 0u);
     RS_HIP(hipGetLastError());
     h->haloPend = false;
@@ -3335,13 +3323,13 @@ int pc_halo_settle(rs_pc* h) {
 int pc_halo_settle_read(rs_pc* h, double* xp_dev, bool* done) {
     *done = false;
     if (!h->haloPend) return RS_OK;
-    float* buf[2] = {static_cast<float*>(h->dP), static_cast<float*>(h->dQ)};
+    float* buf[2] = {static_cast<float*>(h->dP.get()), static_cast<float*>(h->dQ.get())};
     const int n4 = (int)(h->n / 4), nb = std::min(1024, (n4 + 255) / 256);
     const bool fl = pc_flags_ok(h, nb);
     const unsigned seq = fl ? pc_next_seq(h) : 0u;
     hipLaunchKernelGGL(pc_halo_finish, dim3(nb), dim3(256), 0, h->stream, buf[h->haloCur], buf[0], n4,
-                       h->dPart + (size_t)h->haloPart * h->nPart, h->nPart, nullptr, nullptr, 0, nullptr,
-                       nullptr, xp_dev, (int)(h->n * sizeof(float)), fl ? h->hFlagDev : nullptr, seq);
+                       h->dPart.get() + (size_t)h->haloPart * h->nPart, h->nPart, nullptr, nullptr, 0, nullptr,
+                       nullptr, xp_dev, (int)(h->n * sizeof(float)), fl ? h->hFlag.dev() : nullptr, seq);
     RS_HIP(hipGetLastError());
     h->haloPend = false;
     h->haloCur = 0;
@@ -3367,17 +3355,17 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     RS_TRY(pc_grow_steps(h, n, false));   // (the control travels as kernel arguments)
     const bool pk = h->profiling && h->profKernels;
     if (pk) RS_TRY(pc_ensure_events(h, (size_t)2 * n + 2));
-    for (int s = 0; s < n; ++s) h->hRes[s] = RES_NONE;
+    for (int s = 0; s < n; ++s) h->hRes.get()[s] = RES_NONE;
     // RS_PC_HALO_POLL=0: a one-step call waits for the kernel's completion signal instead
     // of returning once every block's record has reached host memory (below)
     const bool poll_env = halo_poll_env();
     const bool lazy = h->exportDev == nullptr && !h->haloSettleAlways;
     // a one-step call: the blocks' records go straight to pinned host memory and the host
     // reduces them after its wait (no export launch)
-    const bool host_rec = lazy && n == 1 && h->hRec;
-    if (host_rec) std::memset(h->hRec, 0, sizeof(unsigned long long) * 2 * h->nPart);
+    const bool host_rec = lazy && n == 1 && h->hRec.get();
+    if (host_rec) std::memset(h->hRec.get(), 0, sizeof(unsigned long long) * 2 * h->nPart);
     if (h->profiling) RS_HIP(hipEventRecord(h->ev0, h->stream));
-    float* buf[2] = {static_cast<float*>(h->dP), static_cast<float*>(h->dQ)};
+    float* buf[2] = {static_cast<float*>(h->dP.get()), static_cast<float*>(h->dQ.get())};
     const dim3 grid(h->cgx * h->cgy);
     const bool pend = h->haloPend;
     const int c0 = pend ? h->haloCur : 0;          // the buffer step 0 reads
@@ -3385,17 +3373,17 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     for (int s = 0; s < n; ++s) {
         PcCtlHalo c;
         make_ctl_halo(h, s, ox, oy, fidx, zf, &c);
-        const double* part_in = s > 0 ? h->dPart + (size_t)((p0 + s - 1) & 1) * h->nPart
-                                      : h->dPart + (size_t)(pend ? h->haloPart : 0) * h->nPart;
+        const double* part_in = s > 0 ? h->dPart.get() + (size_t)((p0 + s - 1) & 1) * h->nPart
+                                      : h->dPart.get() + (size_t)(pend ? h->haloPart : 0) * h->nPart;
         const int npart_in = s > 0 || pend ? h->nPart : 0;
         if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s], h->stream));
         hf_launch<false>(h->TH, grid, h->stream, static_cast<const float*>(buf[(c0 + s) & 1]),
                            hf_pack(h->X, h->Y), hf_pack(h->cgx, grid.x), hf_pack(c.ux, c.uy), hf_pack(c.uw, c.uh),
                            hf_magic(h->cgx), hf_magic(c.uh), part_in, npart_in, buf[(c0 + s + 1) & 1],
-                           h->dPart + (size_t)((p0 + s) & 1) * h->nPart,
-                           s == 0 ? nullptr : h->dRes + (size_t)(s - 1) * RES_SLOTS,
-                           h->dRes + (size_t)s * RES_SLOTS, static_cast<const float*>(h->dFilt), h->nf, c, h->kf,
-                           lazy && s == n - 1 ? (host_rec ? h->hRecDev : h->dRec) : nullptr);
+                           h->dPart.get() + (size_t)((p0 + s) & 1) * h->nPart,
+                           s == 0 ? nullptr : h->dRes.get() + (size_t)(s - 1) * RES_SLOTS,
+                           h->dRes.get() + (size_t)s * RES_SLOTS, static_cast<const float*>(h->dFilt.get()), h->nf, c, h->kf,
+                           lazy && s == n - 1 ? (host_rec ? h->hRec.dev() : h->dRec.get()) : nullptr);
         RS_HIP(hipGetLastError());
         if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s + 1], h->stream));
     }
@@ -3408,11 +3396,11 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     // n-1 into hKey, reduced here once the launch has been waited for
     auto finish = [&](int nexp_own, double* xp) -> int {
         const bool fl = flag_poll && xp != nullptr;
-        if (nexp_own > 0) std::memset(h->hKey, 0, sizeof(unsigned long long) * nb);
+        if (nexp_own > 0) std::memset(h->hKey.get(), 0, sizeof(unsigned long long) * nb);
         hipLaunchKernelGGL(pc_halo_finish, dim3(nb), dim3(256), 0, h->stream, buf[cl], buf[0], n4,
-                           h->dPart + (size_t)pl * h->nPart, h->nPart, h->dRes + (size_t)(n - 1) * RES_SLOTS,
-                           h->dRes, nexp_own, h->hResDev, nexp_own > 0 ? h->hKeyDev : nullptr, xp,
-                           (int)(h->n * sizeof(float)), fl ? h->hFlagDev : nullptr, seq);
+                           h->dPart.get() + (size_t)pl * h->nPart, h->nPart, h->dRes.get() + (size_t)(n - 1) * RES_SLOTS,
+                           h->dRes.get(), nexp_own, h->hRes.dev(), nexp_own > 0 ? h->hKey.dev() : nullptr, xp,
+                           (int)(h->n * sizeof(float)), fl ? h->hFlag.dev() : nullptr, seq);
         RS_HIP(hipGetLastError());
         h->haloPend = false;
         h->haloCur = 0;
@@ -3422,8 +3410,8 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     bool own_export = false;
     if (lazy) {
         if (!h->dbgSkipExport && !host_rec) {
-            hipLaunchKernelGGL(pc_halo_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes, n,
-                               h->dRec, (int)grid.x, h->hResDev);
+            hipLaunchKernelGGL(pc_halo_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes.get(), n,
+                               h->dRec.get(), (int)grid.x, h->hRes.dev());
             RS_HIP(hipGetLastError());
         }
         h->haloPend = true;
@@ -3433,8 +3421,8 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         own_export = !h->dbgSkipExport && n <= HF_EXP_MAX;
         RS_TRY(finish(own_export ? n : 0, h->exportDev));
         if (!h->dbgSkipExport && !own_export) {
-            hipLaunchKernelGGL(pc_res_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes, n,
-                               h->hResDev);
+            hipLaunchKernelGGL(pc_res_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes.get(), n,
+                               h->hRes.dev());
             RS_HIP(hipGetLastError());
         }
     }
@@ -3461,7 +3449,7 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     }
     if (lazy && !skipped && poll_env && !h->profiling && n <= HF_POLL_MAX) {
         if (host_rec) {
-            const volatile unsigned long long* r = h->hRec;
+            const volatile unsigned long long* r = h->hRec.get();
             const int nr = (int)grid.x;
             int b = 0;
             for (long spin = 0; spin < 4000000 && b < nr; ++spin)
@@ -3472,29 +3460,29 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         }
     }
     if (!polled) RS_HIP(hipStreamSynchronize(h->stream));
-    if (host_rec && !skipped) h->hRes[n - 1] = halo_key_from_records(h->hRec, (int)grid.x);
+    if (host_rec && !skipped) h->hRes.get()[n - 1] = halo_key_from_records(h->hRec.get(), (int)grid.x);
     if (own_export) {   // the finishing blocks' keys of the last step (a key is never 0)
         unsigned long long m = 0ull;
         bool all = true;
         for (int b = 0; b < nb; ++b) {
-            all &= h->hKey[b] != 0ull;
-            m = std::max(m, h->hKey[b]);
+            all &= h->hKey.get()[b] != 0ull;
+            m = std::max(m, h->hKey.get()[b]);
         }
-        h->hRes[n - 1] = all ? m : RES_NONE;
+        h->hRes.get()[n - 1] = all ? m : RES_NONE;
     }
-    if (lazy && !skipped && h->hRes[n - 1] == RES_AMBIG) {
+    if (lazy && !skipped && h->hRes.get()[n - 1] == RES_AMBIG) {
         // a cell within HF_NEAR of the last step's peak: key the normalised state itself
         // (its slots were zeroed by the last launch and nothing has reduced into them)
-        h->hRes[n - 1] = RES_NONE;
+        h->hRes.get()[n - 1] = RES_NONE;
         RS_TRY(finish(0, nullptr));
-        hipLaunchKernelGGL(pc_res_export, dim3(1), dim3(64), 0, h->stream, h->dRes + (size_t)(n - 1) * RES_SLOTS, 1,
-                           h->hResDev + (n - 1));
+        hipLaunchKernelGGL(pc_res_export, dim3(1), dim3(64), 0, h->stream, h->dRes.get() + (size_t)(n - 1) * RES_SLOTS, 1,
+                           h->hRes.dev() + (n - 1));
         RS_HIP(hipGetLastError());
         if (!(poll_env && pc_poll_words(h, n - 1, n))) RS_HIP(hipStreamSynchronize(h->stream));
         ++h->haloAmbig;
     }
     for (int s = 0; s < n; ++s)
-        RS_CHECK(h->hRes[s] != RES_NONE, RS_ERR_HIP,
+        RS_CHECK(h->hRes.get()[s] != RES_NONE, RS_ERR_HIP,
                  "step %d of %d: its argmax key did not reach the host result buffer after the "
                  "stream synchronised", s, n);
     if (h->profiling) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
@@ -3511,7 +3499,7 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         h->kernelMs[1] = b;
     }
     if (out_xyz)
-        for (int s = 0; s < n; ++s) decode_xyz(h, h->hRes[s], out_xyz + 3 * (size_t)s);
+        for (int s = 0; s < n; ++s) decode_xyz(h, h->hRes.get()[s], out_xyz + 3 * (size_t)s);
     return RS_OK;
 }
 
@@ -3524,13 +3512,13 @@ int pc_launch_stream(rs_pc* h, const T* P, T* Q, unsigned long long* slot, T* bm
     const StreamGrid G = h->sg;
     const dim3 grid(G.gx * G.gy * G.gz), block(64 * h->swr * h->swc);
     const SepKernel<T>& k = sep_of<T>(h);
-    const T* filt = static_cast<const T*>(h->dFilt);
+    const T* filt = static_cast<const T*>(h->dFilt.get());
     bool done = false;
 #define PC_EXCITE_CASE(bx_, wr_, wc_)                                                         \
     if (!done && h->sbx == bx_ && h->swr == wr_ && h->swc == wc_) {                           \
         hipLaunchKernelGGL((pc_excite_stream<T, bx_, wr_, wc_>), grid, block, 0, h->stream, P, \
                            Q,                                                                 \
-                           h->dPart, slot, h->X, h->Y, h->TH, G, k);                          \
+                           h->dPart.get(), slot, h->X, h->Y, h->TH, G, k);                          \
         done = true;                                                                          \
     }
     PC_STREAM_VARIANTS(PC_EXCITE_CASE)
@@ -3544,7 +3532,7 @@ int pc_launch_stream(rs_pc* h, const T* P, T* Q, unsigned long long* slot, T* bm
 #define PC_PATH_CASE(bx_, wr_, wc_)                                                              \
     if (!done && h->sbx == bx_ && h->swr == wr_ && h->swc == wc_) {                              \
         hipLaunchKernelGGL((pc_path_stream<T, bx_, wr_, wc_, CTL>), grid, block, 0, h->stream, Q, \
-                           static_cast<T*>(h->dP), h->dPart, h->nPart, filt, h->nf, *ctl, slot,  \
+                           static_cast<T*>(h->dP.get()), h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot,  \
                            bmax, bidx, h->X, h->Y, h->TH, G);                                    \
         done = true;                                                                             \
     }
@@ -3556,13 +3544,13 @@ int pc_launch_stream(rs_pc* h, const T* P, T* Q, unsigned long long* slot, T* bm
 
 template <typename T, typename CTL>
 int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
-    const T* P = static_cast<const T*>(h->dP);
-    T* Q = static_cast<T*>(h->dQ);
+    const T* P = static_cast<const T*>(h->dP.get());
+    T* Q = static_cast<T*>(h->dQ.get());
     const SepKernel<T>& k = sep_of<T>(h);
     unsigned long long* slot = so.slot;
     T* bmax = static_cast<T*>(so.bmax);
     unsigned* bidx = so.bidx;
-    const T* filt = static_cast<const T*>(h->dFilt);
+    const T* filt = static_cast<const T*>(h->dFilt.get());
     if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base], h->stream));
     switch (h->form) {
     case PcForm::Cols: {
@@ -3574,19 +3562,19 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
             if (whole && h->TH == CO_DMA_TH) {  // configs[3]'s theta extent
                 hipLaunchKernelGGL((pc_excite_cols<float, CO_TX, CO_TY, CO_NW, CO_DMA_TH, false, CO_DMA_TH>), g,
                                    dim3(64 * CO_NW), 0, h->stream, P, h->X, h->Y, h->TH, h->cgx, h->cgy,
-                                   (int)g.x, Q, h->dPart, slot, h->coKC, k);
+                                   (int)g.x, Q, h->dPart.get(), slot, h->coKC, k);
                 fixed = true;
             }
         }
         if (fixed) {
         } else if (whole)
             hipLaunchKernelGGL((pc_excite_cols<T, CO_TX, CO_TY, co_nw<T>(), THF, false>), g, dim3(64 * co_nw<T>()), 0,
-                               h->stream, P, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x, Q, h->dPart, slot,
+                               h->stream, P, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x, Q, h->dPart.get(), slot,
                                h->coKC, k);
         else
             hipLaunchKernelGGL((pc_excite_cols<T, CO_TX, CO_TY, CO_NW_CHUNK, THC, true>), g,
                                dim3(64 * CO_NW_CHUNK), 0, h->stream, P, h->X, h->Y, h->TH, h->cgx, h->cgy,
-                               (int)g.x, Q, h->dPart, slot, h->coKC, k);
+                               (int)g.x, Q, h->dPart.get(), slot, h->coKC, k);
         RS_HIP(hipGetLastError());
         if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 1], h->stream));
         if (!ctl) return RS_OK;
@@ -3597,7 +3585,7 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
             if (whole && h->TH == CO_DMA_TH) {
                 hipLaunchKernelGGL((pc_path_cols<float, CO_TX, CO_TY, CO_NW, CO_DMA_TH, false, PcCtlInline, CO_DMA_TH>),
                                    g, dim3(64 * CO_NW), 0, h->stream, Q, h->X, h->Y, h->TH, h->cgx, h->cgy,
-                                   (int)g.x, static_cast<T*>(h->dP), h->dPart, h->nPart, filt, h->nf, *ctl, slot,
+                                   (int)g.x, static_cast<T*>(h->dP.get()), h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot,
                                    bmax, bidx, h->coKC);
                 launched = true;
             }
@@ -3605,12 +3593,12 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
         if (launched) {
         } else if (whole)
             hipLaunchKernelGGL((pc_path_cols<T, CO_TX, CO_TY, co_nw<T>(), THF, false, CTL>), g, dim3(64 * co_nw<T>()), 0,
-                               h->stream, Q, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x, static_cast<T*>(h->dP),
-                               h->dPart, h->nPart, filt, h->nf, *ctl, slot, bmax, bidx, h->coKC);
+                               h->stream, Q, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x, static_cast<T*>(h->dP.get()),
+                               h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot, bmax, bidx, h->coKC);
         else
             hipLaunchKernelGGL((pc_path_cols<T, CO_TX, CO_TY, CO_NW_CHUNK, THC, true, CTL>), g,
                                dim3(64 * CO_NW_CHUNK), 0, h->stream, Q, h->X, h->Y, h->TH, h->cgx, h->cgy,
-                               (int)g.x, static_cast<T*>(h->dP), h->dPart, h->nPart, filt, h->nf, *ctl, slot,
+                               (int)g.x, static_cast<T*>(h->dP.get()), h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot,
                                bmax, bidx, h->coKC);
         break;
     }
@@ -3621,21 +3609,21 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
         const dim3 g((h->X + RT_BX - 1) / RT_BX, (h->TH + RT_BK - 1) / RT_BK);
         if (h->rowsYP == 64)
             hipLaunchKernelGGL((pc_excite_rows<T, 64>), g, dim3(RT_NT), 0, h->stream, P, Q,
-                               h->dPart, slot, h->X, h->Y, h->TH, k);
+                               h->dPart.get(), slot, h->X, h->Y, h->TH, k);
         else
             hipLaunchKernelGGL((pc_excite_rows<T, 128>), g, dim3(RT_NT), 0, h->stream, P, Q,
-                               h->dPart, slot, h->X, h->Y, h->TH, k);
+                               h->dPart.get(), slot, h->X, h->Y, h->TH, k);
         RS_HIP(hipGetLastError());
         if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 1], h->stream));
         if (!ctl) return RS_OK;  // rs_pc_excite() normalises with pc_scale_kernel
         if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 2], h->stream));
         if (h->rowsYP == 64)
             hipLaunchKernelGGL((pc_path_rows<T, 64, CTL>), g, dim3(RT_NT), 0, h->stream, Q,
-                               static_cast<T*>(h->dP), h->dPart, h->nPart, filt, h->nf, *ctl, slot,
+                               static_cast<T*>(h->dP.get()), h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot,
                                bmax, bidx, h->X, h->Y, h->TH);
         else
             hipLaunchKernelGGL((pc_path_rows<T, 128, CTL>), g, dim3(RT_NT), 0, h->stream, Q,
-                               static_cast<T*>(h->dP), h->dPart, h->nPart, filt, h->nf, *ctl, slot,
+                               static_cast<T*>(h->dP.get()), h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot,
                                bmax, bidx, h->X, h->Y, h->TH);
         break;
     }
@@ -3668,7 +3656,7 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     RS_TRY(pc_grow_steps(h, n, !inline_ctl));
     if (!inline_ctl) {
         RS_TRY(pc_pack_ctl(h, n, ox, oy, fidx, zf));
-        RS_HIP(hipMemcpyAsync(h->dCtl, h->hCtl, h->ctlStride * n, hipMemcpyHostToDevice,
+        RS_HIP(hipMemcpyAsync(h->dCtl.get(), h->hCtl.get(), h->ctlStride * n, hipMemcpyHostToDevice,
                               h->stream));
     }
     const bool pk = h->profiling && h->profKernels;
@@ -3693,14 +3681,14 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     }
     if (h->prec == RS_PREC_F64) {
         hipLaunchKernelGGL((pc_argmax_steps<double>), dim3(n), dim3(NT), 0, h->stream,
-                           static_cast<const double*>(h->dArgV), h->dArgI, h->nPart, h->dRes);
+                           static_cast<const double*>(h->dArgV.get()), h->dArgI.get(), h->nPart, h->dRes.get());
         RS_HIP(hipGetLastError());
     }
-    for (int s = 0; s < n; ++s) h->hRes[s] = RES_NONE;
+    for (int s = 0; s < n; ++s) h->hRes.get()[s] = RES_NONE;
     const bool skipped = h->dbgSkipExport;
     if (!h->dbgSkipExport) {
         hipLaunchKernelGGL(pc_res_export, dim3(n < 1024 ? n : 1024), dim3(64), 0,
-                           h->stream, h->dRes, n, h->hResDev);
+                           h->stream, h->dRes.get(), n, h->hRes.dev());
         RS_HIP(hipGetLastError());
     }
     h->dbgSkipExport = false;
@@ -3714,14 +3702,14 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
         const bool fl = may_poll && pc_flags_ok(h, xnb);
         if (fl) xnb = pc_xflag_nb(xnb);
         seq = fl ? pc_next_seq(h) : 0u;
-        unsigned* flag = fl ? h->hFlagDev : nullptr;
+        unsigned* flag = fl ? h->hFlag.dev() : nullptr;
         if (h->prec == RS_PREC_F32)
             hipLaunchKernelGGL((pc_export2_kernel<float>), dim3(xnb), dim3(NT), 0, h->stream,
-                               static_cast<const float*>(h->dP), h->exportDev, h->X, h->Y, h->TH, (int)pc_thfast(h),
+                               static_cast<const float*>(h->dP.get()), h->exportDev, h->X, h->Y, h->TH, (int)pc_thfast(h),
                                flag, seq);
         else
             hipLaunchKernelGGL((pc_export2_kernel<double>), dim3(xnb), dim3(NT), 0, h->stream,
-                               static_cast<const double*>(h->dP), h->exportDev, h->X, h->Y, h->TH, (int)pc_thfast(h),
+                               static_cast<const double*>(h->dP.get()), h->exportDev, h->X, h->Y, h->TH, (int)pc_thfast(h),
                                flag, seq);
         RS_HIP(hipGetLastError());
     }
@@ -3734,7 +3722,7 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
                         pc_poll_words(h, 0, n);
     if (!polled) RS_HIP(hipStreamSynchronize(h->stream));
     for (int s = 0; s < n; ++s)
-        RS_CHECK(h->hRes[s] != RES_NONE, RS_ERR_HIP,
+        RS_CHECK(h->hRes.get()[s] != RES_NONE, RS_ERR_HIP,
                  "step %d of %d: its argmax key did not reach the host result buffer after the "
                  "stream synchronised", s, n);
     if (h->profiling) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
@@ -3751,7 +3739,7 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     }
     if (out_xyz)
         for (int s = 0; s < n; ++s)
-            decode_xyz(h, h->hRes[s], out_xyz + 3 * (size_t)s);
+            decode_xyz(h, h->hRes.get()[s], out_xyz + 3 * (size_t)s);
     return RS_OK;
 }
 
@@ -3828,16 +3816,16 @@ template <typename T>
 int pc_argmax_impl(rs_pc* h, int32_t* out) {
     const int nb = h->nBmaxCap < 1024 ? h->nBmaxCap : 1024;
     hipLaunchKernelGGL((pc_argmax_blocks<T>), dim3(nb), dim3(NT), 0, h->stream,
-                       static_cast<const T*>(h->dP), h->X, h->Y, h->TH, static_cast<T*>(h->dBmax),
-                       h->dBidx, (int)pc_thfast(h));
+                       static_cast<const T*>(h->dP.get()), h->X, h->Y, h->TH, static_cast<T*>(h->dBmax.get()),
+                       h->dBidx.get(), (int)pc_thfast(h));
     RS_HIP(hipGetLastError());
     hipLaunchKernelGGL((pc_argmax_finalize<T>), dim3(1), dim3(NT), 0, h->stream,
-                       static_cast<const T*>(h->dBmax), h->dBidx, nb, h->dRes);
+                       static_cast<const T*>(h->dBmax.get()), h->dBidx.get(), nb, h->dRes.get());
     RS_HIP(hipGetLastError());
-    RS_HIP(hipMemcpyAsync(h->hRes, h->dRes, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+    RS_HIP(hipMemcpyAsync(h->hRes.get(), h->dRes.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost,
                           h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
-    decode_xyz(h, h->hRes[0], out);
+    decode_xyz(h, h->hRes.get()[0], out);
     return RS_OK;
 }
 
@@ -4105,62 +4093,49 @@ int rs_pc_create(int X, int Y, int TH, const rs_pc_params* p, int device, rs_pc*
     }
     h->nBmaxCap = h->nPart > 1024 ? h->nPart : 1024;
 
-    auto fail = [&](int code) { rs_pc_destroy(h); return code; };
-    hipError_t e = hipSuccess;
-#define PC_ALLOC(call)                                                         \
-    do {                                                                       \
-        e = (call);                                                            \
-        if (e != hipSuccess) {                                                 \
-            rs::set_error("%s failed: %s", #call, hipGetErrorString(e));       \
-            return fail(e == hipErrorOutOfMemory ? RS_ERR_NOMEM : RS_ERR_HIP); \
-        }                                                                      \
-    } while (0)
-    PC_ALLOC(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    PC_ALLOC(hipMalloc(&h->dP, h->n * h->esz));
-    PC_ALLOC(hipMalloc(&h->dQ, h->n * h->esz));
-    PC_ALLOC(hipMemsetAsync(h->dP, 0, h->n * h->esz, h->stream));  // zeros(shape), :27
-    // Q and the partials are rewritten in full by every excitation before a path
-    // kernel reads them; zeroed anyway so that no launch can see a freed handle's data
-    // (rs_pc_debug(RS_PC_DBG_POISON) + tests/test_posecell_gpu.py check the former)
-    PC_ALLOC(hipMemsetAsync(h->dQ, 0, h->n * h->esz, h->stream));
-    // (the halo form keeps two steps' partial sums: the one it reads, the one it writes)
-    PC_ALLOC(hipMalloc(&h->dPart, sizeof(double) * h->nPart * 2));
-    PC_ALLOC(hipMemsetAsync(h->dPart, 0, sizeof(double) * h->nPart * 2, h->stream));
-    PC_ALLOC(hipMalloc(&h->dRec, sizeof(unsigned long long) * 2 * h->nPart));
-    // the volume-writing kernels' per-block flags (pc_halo_finish, pc_export2_kernel)
-    PC_ALLOC(hipHostMalloc(&h->hFlag, sizeof(unsigned) * HF_FLAGS, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(h->hFlag, 0, sizeof(unsigned) * HF_FLAGS);
-    PC_ALLOC(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hFlagDev), h->hFlag, 0));
-    if (h->form == PcForm::Halo) {
-        PC_ALLOC(hipHostMalloc(&h->hRec, sizeof(unsigned long long) * 2 * h->nPart,
-                               hipHostMallocMapped | hipHostMallocCoherent));
-        PC_ALLOC(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hRecDev), h->hRec, 0));
-        PC_ALLOC(hipHostMalloc(&h->hKey, sizeof(unsigned long long) * HF_FLAGS,
-                               hipHostMallocMapped | hipHostMallocCoherent));
-        PC_ALLOC(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hKeyDev), h->hKey, 0));
-    }
-    PC_ALLOC(hipMalloc(&h->dBmax, h->esz * h->nBmaxCap));
-    PC_ALLOC(hipMalloc(&h->dBidx, sizeof(unsigned) * h->nBmaxCap));
-    PC_ALLOC(hipMalloc(&h->dTmp, sizeof(double) * h->n));
-    PC_ALLOC(hipMalloc(&h->dScalar, sizeof(double)));
-    PC_ALLOC(hipMalloc(&h->dFilt, h->esz * FT * h->nf));
-    if (h->prec == RS_PREC_F32) {
-        std::vector<float> f(FT * (size_t)h->nf);
-        for (size_t i = 0; i < f.size(); ++i) f[i] = (float)p->xy_filters[i];
-        PC_ALLOC(hipMemcpy(h->dFilt, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
-    } else {
-        PC_ALLOC(hipMemcpy(h->dFilt, p->xy_filters, FT * (size_t)h->nf * sizeof(double),
-                           hipMemcpyHostToDevice));
-    }
-    PC_ALLOC(hipEventCreate(&h->ev0));
-    PC_ALLOC(hipEventCreate(&h->ev1));
-#undef PC_ALLOC
-    int s = pc_grow_steps(h, 16);
-    if (s != RS_OK) return fail(s);
-    e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        rs::set_error("hipStreamSynchronize failed: %s", hipGetErrorString(e));
-        return fail(RS_ERR_HIP);
+    // everything the handle allocates; what a failure leaves behind goes with rs_pc_destroy
+    auto init = [&]() -> int {
+        RS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        RS_TRY(h->dP.reserve(h->n * h->esz));
+        RS_TRY(h->dQ.reserve(h->n * h->esz));
+        RS_HIP(hipMemsetAsync(h->dP.get(), 0, h->n * h->esz, h->stream));  // zeros(shape), :27
+        // Q and the partials are rewritten in full by every excitation before a path
+        // kernel reads them; zeroed anyway so that no launch can see a freed handle's data
+        // (rs_pc_debug(RS_PC_DBG_POISON) + tests/test_posecell_gpu.py check the former)
+        RS_HIP(hipMemsetAsync(h->dQ.get(), 0, h->n * h->esz, h->stream));
+        // (the halo form keeps two steps' partial sums: the one it reads, the one it writes)
+        RS_TRY(h->dPart.reserve((size_t)h->nPart * 2));
+        RS_HIP(hipMemsetAsync(h->dPart.get(), 0, sizeof(double) * h->nPart * 2, h->stream));
+        RS_TRY(h->dRec.reserve(2 * (size_t)h->nPart));
+        // the volume-writing kernels' per-block flags (pc_halo_finish, pc_export2_kernel)
+        RS_TRY(h->hFlag.reserve(HF_FLAGS, PC_FINE));
+        std::memset(h->hFlag.get(), 0, sizeof(unsigned) * HF_FLAGS);
+        if (h->form == PcForm::Halo) {
+            RS_TRY(h->hRec.reserve(2 * (size_t)h->nPart, PC_FINE));
+            RS_TRY(h->hKey.reserve(HF_FLAGS, PC_FINE));
+        }
+        RS_TRY(h->dBmax.reserve(h->esz * h->nBmaxCap));
+        RS_TRY(h->dBidx.reserve((size_t)h->nBmaxCap));
+        RS_TRY(h->dTmp.reserve(h->n));
+        RS_TRY(h->dScalar.reserve(1));
+        RS_TRY(h->dFilt.reserve(h->esz * FT * h->nf));
+        if (h->prec == RS_PREC_F32) {
+            std::vector<float> f(FT * (size_t)h->nf);
+            for (size_t i = 0; i < f.size(); ++i) f[i] = (float)p->xy_filters[i];
+            RS_HIP(hipMemcpy(h->dFilt.get(), f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+        } else {
+            RS_HIP(hipMemcpy(h->dFilt.get(), p->xy_filters, FT * (size_t)h->nf * sizeof(double),
+                             hipMemcpyHostToDevice));
+        }
+        RS_HIP(hipEventCreate(&h->ev0));
+        RS_HIP(hipEventCreate(&h->ev1));
+        RS_TRY(pc_grow_steps(h, 16));
+        RS_HIP(hipStreamSynchronize(h->stream));
+        return RS_OK;
+    };
+    if (const int st = init(); st != RS_OK) {
+        rs_pc_destroy(h);
+        return st;
     }
     *out = h;
     return RS_OK;
@@ -4172,22 +4147,11 @@ int rs_pc_destroy(rs_pc* h) {
     // the handle's last queued work: a fault or launch error the early-returning calls
     // left on the stream is reported here instead of being dropped
     const hipError_t se = h->stream ? hipStreamSynchronize(h->stream) : hipSuccess;
-    if (h->hRead) (void)hipHostFree(h->hRead);
-    for (void* p : {h->dP, h->dQ, h->dFilt, (void*)h->dPart, (void*)h->dRec, h->dBmax,
-                    (void*)h->dBidx, h->dArgV,
-                    (void*)h->dArgI,
-                    (void*)h->dRes, (void*)h->dCtl, (void*)h->dTmp, (void*)h->dScalar})
-        if (p) (void)hipFree(p);
-    if (h->hRes) (void)hipHostFree(h->hRes);
-    if (h->hRec) (void)hipHostFree(h->hRec);
-    if (h->hFlag) (void)hipHostFree(h->hFlag);
-    if (h->hKey) (void)hipHostFree(h->hKey);
-    if (h->hCtl) (void)hipHostFree(h->hCtl);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     for (hipEvent_t e : h->evPool) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;  // (the buffers go with their members)
     RS_CHECK(se == hipSuccess, RS_ERR_HIP, "work queued before rs_pc_destroy failed: %s", hipGetErrorString(se));
     return RS_OK;
 }
@@ -4223,9 +4187,9 @@ int rs_pc_excite(rs_pc* h) {
         c.uw = (short)HF_W;
         c.uh = (short)HF_W;
         hf_launch<true>(h->TH, dim3(h->cgx * h->cgy), h->stream,
-                           static_cast<const float*>(h->dP), hf_pack(h->X, h->Y), hf_pack(h->cgx, h->cgx * h->cgy),
-                           hf_pack(c.ux, c.uy), hf_pack(c.uw, c.uh), hf_magic(h->cgx), hf_magic(c.uh), h->dPart, 0,
-                           static_cast<float*>(h->dQ), h->dPart, nullptr, nullptr, static_cast<const float*>(h->dFilt), h->nf, c, h->kf,
+                           static_cast<const float*>(h->dP.get()), hf_pack(h->X, h->Y), hf_pack(h->cgx, h->cgx * h->cgy),
+                           hf_pack(c.ux, c.uy), hf_pack(c.uw, c.uh), hf_magic(h->cgx), hf_magic(c.uh), h->dPart.get(), 0,
+                           static_cast<float*>(h->dQ.get()), h->dPart.get(), nullptr, nullptr, static_cast<const float*>(h->dFilt.get()), h->nf, c, h->kf,
                            nullptr);
         RS_HIP(hipGetLastError());
     } else if (h->prec == RS_PREC_F32) {
@@ -4235,13 +4199,13 @@ int rs_pc_excite(rs_pc* h) {
     }
     if (h->prec == RS_PREC_F32)
         hipLaunchKernelGGL((pc_scale_kernel<float>), dim3(64), dim3(NT), 0, h->stream,
-                           static_cast<float*>(h->dQ), h->n, h->dPart, h->nPart);
+                           static_cast<float*>(h->dQ.get()), h->n, h->dPart.get(), h->nPart);
     else
         hipLaunchKernelGGL((pc_scale_kernel<double>), dim3(64), dim3(NT), 0, h->stream,
-                           static_cast<double*>(h->dQ), h->n, h->dPart, h->nPart);
+                           static_cast<double*>(h->dQ.get()), h->n, h->dPart.get(), h->nPart);
     RS_HIP(hipGetLastError());
     // Q has P's layout in every form (the column form: both theta-fastest)
-    RS_HIP(hipMemcpyAsync(h->dP, h->dQ, h->n * h->esz, hipMemcpyDeviceToDevice, h->stream));
+    RS_HIP(hipMemcpyAsync(h->dP.get(), h->dQ.get(), h->n * h->esz, hipMemcpyDeviceToDevice, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     return RS_OK;
 }
@@ -4413,10 +4377,10 @@ int rs_pc_inject(rs_pc* h, double energy, int x, int y, int th) {
     const size_t idx = pc_thfast(h) ? ((size_t)x * h->Y + y) * h->TH + th : ((size_t)th * h->X + x) * h->Y + y;
     if (h->prec == RS_PREC_F32)
         hipLaunchKernelGGL((pc_inject_kernel<float>), dim3(1), dim3(64), 0, h->stream,
-                           static_cast<float*>(h->dP), idx, energy);
+                           static_cast<float*>(h->dP.get()), idx, energy);
     else
         hipLaunchKernelGGL((pc_inject_kernel<double>), dim3(1), dim3(64), 0, h->stream,
-                           static_cast<double*>(h->dP), idx, energy);
+                           static_cast<double*>(h->dP.get()), idx, energy);
     RS_HIP(hipGetLastError());
     // no host sync: the add is ordered on the handle's stream before the next step,
     // read or argmax (template -> pose-cell feedback costs one queued launch)
@@ -4444,13 +4408,13 @@ int pc_read_volume(rs_pc* h, double* dst) {
     const bool fl = pc_flags_ok(h, nb);
     if (fl) nb = pc_xflag_nb(nb);
     const unsigned seq = fl ? pc_next_seq(h) : 0u;
-    unsigned* flag = fl ? h->hFlagDev : nullptr;
+    unsigned* flag = fl ? h->hFlag.dev() : nullptr;
     if (h->prec == RS_PREC_F32)
         hipLaunchKernelGGL((pc_export2_kernel<float>), dim3(nb), dim3(NT), 0, h->stream,
-                           static_cast<const float*>(h->dP), dst, h->X, h->Y, h->TH, (int)pc_thfast(h), flag, seq);
+                           static_cast<const float*>(h->dP.get()), dst, h->X, h->Y, h->TH, (int)pc_thfast(h), flag, seq);
     else
         hipLaunchKernelGGL((pc_export2_kernel<double>), dim3(nb), dim3(NT), 0, h->stream,
-                           static_cast<const double*>(h->dP), dst, h->X, h->Y, h->TH, (int)pc_thfast(h), flag, seq);
+                           static_cast<const double*>(h->dP.get()), dst, h->X, h->Y, h->TH, (int)pc_thfast(h), flag, seq);
     RS_HIP(hipGetLastError());
     if (!(fl && pc_poll_flags(h, nb, seq))) RS_HIP(hipStreamSynchronize(h->stream));
     return RS_OK;
@@ -4463,12 +4427,9 @@ int rs_pc_read(rs_pc* h, double* host) {
     // The export kernel writes the float64 C-order volume straight into pinned host
     // memory (one launch, no copy engine), then the host copies it into the caller's
     // array.
-    if (!h->hRead) {
-        RS_HIP(hipHostMalloc(&h->hRead, sizeof(double) * h->n, hipHostMallocMapped | hipHostMallocCoherent));
-        RS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hReadDev), h->hRead, 0));
-    }
-    RS_TRY(pc_read_volume(h, h->hReadDev));
-    std::memcpy(host, h->hRead, sizeof(double) * h->n);
+    RS_TRY(h->hRead.reserve(h->n, PC_FINE));
+    RS_TRY(pc_read_volume(h, h->hRead.dev()));
+    std::memcpy(host, h->hRead.get(), sizeof(double) * h->n);
     return RS_OK;
 }
 
@@ -4488,13 +4449,13 @@ int rs_pc_write(rs_pc* h, const double* host) {
     RS_HIP(hipSetDevice(h->device));
     h->haloPend = false;  // (halo: the whole state is replaced)
     h->haloCur = 0;
-    RS_HIP(hipMemcpyAsync(h->dTmp, host, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
+    RS_HIP(hipMemcpyAsync(h->dTmp.get(), host, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
     if (h->prec == RS_PREC_F32)
-        hipLaunchKernelGGL((pc_import_kernel<float>), dim3(256), dim3(NT), 0, h->stream, h->dTmp,
-                           static_cast<float*>(h->dP), h->X, h->Y, h->TH, (int)pc_thfast(h));
+        hipLaunchKernelGGL((pc_import_kernel<float>), dim3(256), dim3(NT), 0, h->stream, h->dTmp.get(),
+                           static_cast<float*>(h->dP.get()), h->X, h->Y, h->TH, (int)pc_thfast(h));
     else
-        hipLaunchKernelGGL((pc_import_kernel<double>), dim3(256), dim3(NT), 0, h->stream, h->dTmp,
-                           static_cast<double*>(h->dP), h->X, h->Y, h->TH, (int)pc_thfast(h));
+        hipLaunchKernelGGL((pc_import_kernel<double>), dim3(256), dim3(NT), 0, h->stream, h->dTmp.get(),
+                           static_cast<double*>(h->dP.get()), h->X, h->Y, h->TH, (int)pc_thfast(h));
     RS_HIP(hipGetLastError());
     RS_HIP(hipStreamSynchronize(h->stream));
     return RS_OK;
@@ -4507,12 +4468,12 @@ int rs_pc_total(rs_pc* h, double* total) {
     RS_TRY(pc_halo_settle(h));  // (halo: a state a call left unnormalised)
     if (h->prec == RS_PREC_F32)
         hipLaunchKernelGGL((pc_total_kernel<float>), dim3(1), dim3(NT), 0, h->stream,
-                           static_cast<const float*>(h->dP), h->n, h->dScalar);
+                           static_cast<const float*>(h->dP.get()), h->n, h->dScalar.get());
     else
         hipLaunchKernelGGL((pc_total_kernel<double>), dim3(1), dim3(NT), 0, h->stream,
-                           static_cast<const double*>(h->dP), h->n, h->dScalar);
+                           static_cast<const double*>(h->dP.get()), h->n, h->dScalar.get());
     RS_HIP(hipGetLastError());
-    RS_HIP(hipMemcpyAsync(total, h->dScalar, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    RS_HIP(hipMemcpyAsync(total, h->dScalar.get(), sizeof(double), hipMemcpyDeviceToHost, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     return RS_OK;
 }
@@ -4557,15 +4518,15 @@ int rs_pc_debug(rs_pc* h, int op) {
     if (op == RS_PC_DBG_POISON) {
         // every buffer a step writes before it reads: all bits set (NaN volumes, the
         // largest possible argmax key in every slot of every step)
-        RS_HIP(hipMemsetAsync(h->dQ, 0xFF, h->n * h->esz, h->stream));
-        RS_HIP(hipMemsetAsync(h->dPart, 0xFF, sizeof(double) * h->nPart * 2, h->stream));
-        RS_HIP(hipMemsetAsync(h->dRes, 0xFF, sizeof(unsigned long long) * RES_SLOTS * h->resCap, h->stream));
-        RS_HIP(hipMemsetAsync(h->dBmax, 0xFF, h->esz * h->nBmaxCap, h->stream));
-        RS_HIP(hipMemsetAsync(h->dBidx, 0xFF, sizeof(unsigned) * h->nBmaxCap, h->stream));
-        if (h->dArgV) RS_HIP(hipMemsetAsync(h->dArgV, 0xFF, h->esz * (size_t)h->resCap * h->nPart, h->stream));
-        if (h->dArgI)
-            RS_HIP(hipMemsetAsync(h->dArgI, 0xFF, sizeof(unsigned) * (size_t)h->resCap * h->nPart, h->stream));
-        for (int s = 0; s < h->resCap; ++s) h->hRes[s] = ~0ull;
+        RS_HIP(hipMemsetAsync(h->dQ.get(), 0xFF, h->n * h->esz, h->stream));
+        RS_HIP(hipMemsetAsync(h->dPart.get(), 0xFF, sizeof(double) * h->nPart * 2, h->stream));
+        RS_HIP(hipMemsetAsync(h->dRes.get(), 0xFF, sizeof(unsigned long long) * RES_SLOTS * h->resCap, h->stream));
+        RS_HIP(hipMemsetAsync(h->dBmax.get(), 0xFF, h->esz * h->nBmaxCap, h->stream));
+        RS_HIP(hipMemsetAsync(h->dBidx.get(), 0xFF, sizeof(unsigned) * h->nBmaxCap, h->stream));
+        if (h->dArgV.get()) RS_HIP(hipMemsetAsync(h->dArgV.get(), 0xFF, h->esz * (size_t)h->resCap * h->nPart, h->stream));
+        if (h->dArgI.get())
+            RS_HIP(hipMemsetAsync(h->dArgI.get(), 0xFF, sizeof(unsigned) * (size_t)h->resCap * h->nPart, h->stream));
+        for (int s = 0; s < h->resCap; ++s) h->hRes.get()[s] = ~0ull;
         RS_HIP(hipStreamSynchronize(h->stream));
         return RS_OK;
     }

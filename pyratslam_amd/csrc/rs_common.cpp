@@ -16,6 +16,27 @@ void set_error(const char* fmt, ...) {
 
 void clear_error() { g_err[0] = 0; }
 
+// (a refused allocation is the caller's error code, not a pending error for the next launch check)
+static hipError_t forget(hipError_t e) {
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e;
+}
+
+hipError_t dev_alloc(void** ptr, size_t bytes) { return forget(hipMalloc(ptr, bytes)); }
+
+hipError_t dev_free(void* ptr) { return forget(hipFree(ptr)); }
+
+hipError_t pinned_alloc(void** ptr, void** dev, size_t bytes, unsigned flags) {
+    hipError_t e = hipHostMalloc(ptr, bytes, flags);
+    if (e == hipSuccess && (e = hipHostGetDevicePointer(dev, *ptr, 0)) != hipSuccess) {
+        (void)hipHostFree(*ptr);
+        *ptr = nullptr;
+    }
+    return forget(e);
+}
+
+hipError_t pinned_free(void* ptr) { return forget(hipHostFree(ptr)); }
+
 }  // namespace rs
 
 extern "C" {
@@ -35,13 +56,13 @@ int rs_dev_malloc(int device, size_t bytes, void** ptr) {
     RS_CHECK(ptr, RS_ERR_ARG, "null output pointer");
     *ptr = nullptr;
     RS_HIP(hipSetDevice(device));
-    RS_HIP(hipMalloc(ptr, bytes));
+    RS_HIP(rs::dev_alloc(ptr, bytes));
     return RS_OK;
 }
 
 int rs_dev_free(void* ptr) {
     rs::clear_error();
-    if (ptr) RS_HIP(hipFree(ptr));
+    if (ptr) RS_HIP(rs::dev_free(ptr));
     return RS_OK;
 }
 
@@ -56,13 +77,14 @@ int rs_host_alloc(size_t bytes, void** ptr) {
     rs::clear_error();
     RS_CHECK(ptr, RS_ERR_ARG, "null output pointer");
     *ptr = nullptr;
-    RS_HIP(hipHostMalloc(ptr, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    void* dev = nullptr;
+    RS_HIP(rs::pinned_alloc(ptr, &dev, bytes, hipHostMallocMapped | hipHostMallocCoherent));
     return RS_OK;
 }
 
 int rs_host_free(void* ptr) {
     rs::clear_error();
-    if (ptr) RS_HIP(hipHostFree(ptr));
+    if (ptr) RS_HIP(rs::pinned_free(ptr));
     return RS_OK;
 }
 

@@ -1,11 +1,14 @@
-// Shared helpers of libratslam_hip: error state and HIP call checking.
+// Shared helpers of libratslam_hip: error state, HIP call checking and the two owning
+// buffer types (rs::DevBuf, rs::PinnedBuf) that hold every handle's device and pinned memory.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <string>
+#include <utility>
 
 #include "ratslam_abi.h"
 
@@ -46,5 +49,116 @@ __host__ __device__ inline int wrapi(int v, int n) {
 }
 
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
+
+// The library's only allocation and release calls (rs_common.cpp): hipMalloc, hipFree,
+// hipHostMalloc (with the block's device address, hipHostGetDevicePointer) and hipHostFree.
+// A refused call leaves no error behind for a later hipGetLastError.
+hipError_t dev_alloc(void** ptr, size_t bytes);
+hipError_t dev_free(void* ptr);
+hipError_t pinned_alloc(void** ptr, void** dev, size_t bytes, unsigned flags);
+hipError_t pinned_free(void* ptr);
+
+inline int alloc_failed(hipError_t e, const char* what, size_t bytes) {
+    set_error("%s: allocating %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? RS_ERR_NOMEM : RS_ERR_HIP;
+}
+
+template <class T> constexpr size_t elem_bytes = sizeof(T);
+template <> inline constexpr size_t elem_bytes<void> = 1;  // untyped buffers count bytes
+
+// Owning, move-only device buffer of capacity() elements.  reserve() within the capacity
+// does nothing; beyond it, it releases the old block first (a growth never holds both, and
+// never copies) and allocates exactly n.  If that fails the buffer is empty: get() ==
+// nullptr, capacity() == 0.  So after a failed growth no member of a handle points at freed
+// memory; and a handle that guards several buffers by one capacity zeroes it before the
+// first reserve of the group and sets it after the last, so that a non-zero group capacity
+// means every buffer of the group holds at least that much.  How far to grow, the fill of a
+// fresh block and the synchronise its old readers need stay with the caller; a buffer that
+// keeps its contents reserves a fresh DevBuf, copies, and move-assigns it.
+template <class T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = std::exchange(o.p_, nullptr);
+            n_ = std::exchange(o.n_, 0);
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+
+    T* get() const { return p_; }
+    size_t capacity() const { return n_; }
+    void reset() { (void)release(); }
+    int reserve(size_t n, const char* what = "device buffer") {
+        if (n <= n_) return RS_OK;
+        void* p = nullptr;
+        hipError_t e = release();
+        if (e == hipSuccess) e = dev_alloc(&p, elem_bytes<T> * n);
+        if (e != hipSuccess) return alloc_failed(e, what, elem_bytes<T> * n);
+        p_ = static_cast<T*>(p);
+        n_ = n;
+        return RS_OK;
+    }
+
+private:
+    hipError_t release() {
+        const hipError_t e = p_ ? dev_free(p_) : hipSuccess;
+        p_ = nullptr;
+        n_ = 0;
+        return e;
+    }
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// The same for page-locked host memory; dev() is the block in the device's address space.
+// The hipHostMalloc flags are the caller's, buffer by buffer: Mapped | Coherent for words
+// the host polls while a kernel stores them, Default for staging a copy engine reads.
+template <class T>
+class PinnedBuf {
+public:
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept { *this = std::move(o); }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = std::exchange(o.p_, nullptr);
+            d_ = std::exchange(o.d_, nullptr);
+            n_ = std::exchange(o.n_, 0);
+        }
+        return *this;
+    }
+    ~PinnedBuf() { reset(); }
+
+    T* get() const { return p_; }
+    T* dev() const { return d_; }
+    size_t capacity() const { return n_; }
+    void reset() { (void)release(); }
+    int reserve(size_t n, unsigned flags, const char* what = "pinned buffer") {
+        if (n <= n_) return RS_OK;
+        void *p = nullptr, *d = nullptr;
+        hipError_t e = release();
+        if (e == hipSuccess) e = pinned_alloc(&p, &d, elem_bytes<T> * n, flags);
+        if (e != hipSuccess) return alloc_failed(e, what, elem_bytes<T> * n);
+        p_ = static_cast<T*>(p);
+        d_ = static_cast<T*>(d);
+        n_ = n;
+        return RS_OK;
+    }
+
+private:
+    hipError_t release() {
+        const hipError_t e = p_ ? pinned_free(p_) : hipSuccess;
+        p_ = d_ = nullptr;
+        n_ = 0;
+        return e;
+    }
+    T *p_ = nullptr, *d_ = nullptr;
+    size_t n_ = 0;
+};
 
 }  // namespace rs

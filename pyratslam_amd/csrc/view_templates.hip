@@ -1589,6 +1589,18 @@ __global__ __launch_bounds__(256) void vt_keys_export(unsigned long long* __rest
 // ===========================================================================
 // Host side
 // ===========================================================================
+// The query forms a scan reads (planes, raw sums, QS_J, compact planes): a non-owning view
+// of the handle's per-batch buffers (vt_batch_view) or, for rs_vt_match_stream, into its
+// stream buffers (vt_stream_view), passed to the build and to the scan that reads it.
+struct QueryForms {
+    uint32_t *qp = nullptr, *qsum = nullptr, *qsj = nullptr, *qc = nullptr;
+};
+
+// The buffers are rs::DevBuf / rs::PinnedBuf members (rs_common.h, with the invariant the
+// group capacities qCap, idxCap, matCap, candCap, frameCap, pruneCap, listCntCap,
+// qpStreamCap, streamCap and upCap keep).  The library (localCap: dLib, dLibP, dLibTs) is
+// copied when it grows, each buffer into a new block before its old one goes, so localCap
+// simply stays until all three have grown.
 struct rs_vt {
     int H = 0, W = 0, M = 0, WD = 0, HQ = 0;
     // ViewTemplates.match's threshold (view_templates.py:67): a score (< 2^32, exact in
@@ -1599,49 +1611,46 @@ struct rs_vt {
     int rank = 0, nranks = 1;
     ncclComm_t comm = nullptr;
     int64_t count = 0;     // global number of templates
-    int64_t localCap = 0;  // local slots allocated (multiple of 64)
-    uint4* dLib = nullptr;
+    int64_t localCap = 0;  // local slots allocated (multiple of 64): dLib, dLibP, dLibTs
+    rs::DevBuf<uint4> dLib;
     hipStream_t stream = nullptr;
     // query staging
     int qCap = 0;
-    uint8_t* dQraw = nullptr;
-    uint8_t* hQraw = nullptr;  // pinned, fine-grained (a small batch's plane kernel reads it in place)
-    uint8_t* hQrawDev = nullptr;  // hQraw in the device's address space
+    rs::DevBuf<uint8_t> dQraw;
+    rs::PinnedBuf<uint8_t> hQraw;  // fine-grained (a small batch's plane kernel reads it in place)
     bool qrawBusy = false;     // hQraw read by queued work not yet known to have run
-    uint2* dQf = nullptr;
-    uint32_t* dQsum = nullptr;
-    unsigned long long* dBest = nullptr;
-    unsigned long long* hBest = nullptr;  // pinned
-    unsigned long long* hBestDev = nullptr;  // hBest in the device's address space
+    rs::DevBuf<uint2> dQf;
+    rs::DevBuf<uint32_t> dQsum;
+    rs::DevBuf<unsigned long long> dBest;
+    rs::PinnedBuf<unsigned long long> hBest;  // fine-grained: vt_fetch_keys polls the words the export kernel stores
     bool stagingBusy = false;  // copies from hSrc / hDst queued and not yet known to have run
     hipStream_t cstream = nullptr;           // rs_vt_match_stream's collective stream
     hipEvent_t evScan = nullptr, evComm = nullptr;
     hipStream_t ustream = nullptr;           // rs_vt_match_stream: host batches' upload stream
     hipEvent_t evUp[2] = {nullptr, nullptr}, evUsed[2] = {nullptr, nullptr};
-    uint8_t* dUp[2] = {nullptr, nullptr};    // ... and its two raw-query group buffers
+    rs::DevBuf<uint8_t> dUp[2];              // ... and its two raw-query group buffers
     size_t upCap = 0;                        // bytes per group buffer
-    uint32_t* dQpStream = nullptr;           // rs_vt_match_stream: every batch's query planes
-    uint32_t* dQsumStream = nullptr;
-    size_t qpStreamCap = 0;                  // queries
-    unsigned long long* dStream = nullptr;   // keys of rs_vt_match_stream, one row per batch
-    unsigned long long* hStream = nullptr;   // pinned copy (nb * nq)
-    unsigned long long* hStreamDev = nullptr;  // hStream in the device's address space
+    rs::DevBuf<uint32_t> dQpStream;          // rs_vt_match_stream: every batch's query planes
+    rs::DevBuf<uint32_t> dQsumStream;
+    size_t qpStreamCap = 0;                  // queries (dQpStream, dQsumStream, dQsjStream, dQcStream)
+    rs::DevBuf<unsigned long long> dStream;  // keys of rs_vt_match_stream, one row per batch
+    rs::PinnedBuf<unsigned long long> hStream;  // pinned copy (nb * nq)
     size_t streamCap = 0;
     bool streamClean = false;                // dStream holds UINT64_MAX (vt_keys_export resets it)
     int bestClean = 0;     // leading dBest entries known to hold UINT64_MAX
     int bestPending = 0;   // bestClean once the keys of the running scan are exported
     // index lists for stores
     int idxCap = 0;
-    int32_t* dSrc = nullptr;
-    int64_t* dDst = nullptr;
-    int32_t* hSrc = nullptr;  // pinned
-    int64_t* hDst = nullptr;  // pinned
+    rs::DevBuf<int32_t> dSrc;
+    rs::DevBuf<int64_t> dDst;
+    rs::PinnedBuf<int32_t> hSrc;   // (staging a copy engine reads: not fine-grained)
+    rs::PinnedBuf<int64_t> hDst;
     // candidate library and score matrix for in-batch resolution
-    int64_t candCap = 0;
-    uint4* dCand = nullptr;
+    int64_t candCap = 0;   // slots: dCand, dCandP, dCandTs
+    rs::DevBuf<uint4> dCand;
     size_t matCap = 0;
-    uint32_t* dMat = nullptr;
-    uint32_t* hMat = nullptr;  // pinned
+    rs::DevBuf<uint32_t> dMat;
+    rs::PinnedBuf<uint32_t> hMat;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timing = false;  // HIP events around every scan (rs_vt_set_timing; off: the keys are polled)
     bool timedScan = false;  // the last scan recorded ev0/ev1
@@ -1650,49 +1659,44 @@ struct rs_vt {
     // bit-plane scan (default when W == 32, H in {32, 64}, max_offset 8; RS_VT_SCAN=plane):
     // planes + TS of the library and candidate slots, query planes + raw sums
     bool planar = false;
-    uint32_t* dLibP = nullptr;
-    uint32_t* dLibTs = nullptr;
-    uint32_t* dCandP = nullptr;
-    uint32_t* dCandTs = nullptr;
-    uint32_t* dQp = nullptr;
-    uint32_t* dQsumRaw = nullptr;
+    rs::DevBuf<uint32_t> dLibP, dLibTs, dCandP, dCandTs;
+    rs::DevBuf<uint32_t> dQp, dQsumRaw;   // (with qCap, like dQsj and dQc)
     int planeSlots = 0;  // resident plane-scan blocks on the device (occupancy x CUs)
-    unsigned* dCtr = nullptr;  // per template block x query group: next batch (plane scan)
-    unsigned* dDone = nullptr; // plane scan blocks finished (the folded key export; reset by the last)
+    rs::DevBuf<unsigned> dCtr;   // per template block x query group: next batch (plane scan)
+    rs::DevBuf<unsigned> dDone;  // plane scan blocks finished (the folded key export; reset by the last)
     bool keysFolded = false;   // the running scan exports its own keys (vt_fetch_keys: no export launch)
-    int ctrCap = 0;
     // pruned plane scan (H = 64 frozen key scans; RS_VT_PRUNE): 0 dense everywhere, 1 above
     // VT_PRUNE_MIN_Q queries and one template block, 2 ("force") at any size
     int prune = 0;
-    uint32_t* dQsj = nullptr;        // QS_J of the queries in dQp (with dQp's capacity)
-    uint32_t* dQsjStream = nullptr;  // ... of dQpStream
-    // compact query planes (the aligned start rows; with dQp's / dQpStream's capacity).  A
-    // build ahead of a pruned scan fills dQc only and the verification expands into dQp
-    // the queries a scan pass reads; every other reader of dQp expands the rest first.
-    uint32_t* dQc = nullptr;
-    uint32_t* dQcStream = nullptr;
-    bool qpFull = true;              // dQp holds every start row of all the queries last built
-    bool qcValid = false;            // dQc holds their compact planes
-    uint32_t* dMinLB = nullptr;      // [ntb][nq]
-    uint32_t* dSecond = nullptr;     // [ntb][nq] (min2 << 6) | lane of the minimum
-    int* dList = nullptr;            // list1 [ntb][nq], then list2 [ntb][nq]
+    rs::DevBuf<uint32_t> dQsj;        // QS_J of the queries in dQp
+    rs::DevBuf<uint32_t> dQsjStream;  // ... of dQpStream
+    // compact query planes (the aligned start rows).  A build ahead of a pruned scan fills
+    // the view's qc only and the verification expands into its qp the queries a scan pass
+    // reads; every other reader of qp expands the rest first.
+    rs::DevBuf<uint32_t> dQc;
+    rs::DevBuf<uint32_t> dQcStream;
+    // the queries last built, in the view (QueryForms) they were built into:
+    bool qpFull = true;              // qp holds every start row of all of them
+    bool qcValid = false;            // qc holds their compact planes
+    rs::DevBuf<uint32_t> dMinLB;     // [ntb][nq]
+    rs::DevBuf<uint32_t> dSecond;    // [ntb][nq] (min2 << 6) | lane of the minimum
+    rs::DevBuf<int> dList;           // list1 [ntb][nq], then list2 [ntb][nq]
     size_t pruneCap = 0;             // ntb * nq the three are sized for
-    int* dTbStar = nullptr;          // [nq] candidate block (~block: settled by verification)
-    int tbStarCap = 0;
+    rs::DevBuf<int> dTbStar;         // [nq] candidate block (~block: settled by verification)
     // [2][listCntCap] entries per list, then the verified count.  List 1's and the verified
     // count are zero between calls (vt_prune_rest_kernel); list 2's stay for
     // rs_vt_prune_stats until the next pruned launch's vt_prune_first_kernel zeroes them
-    unsigned* dListCnt = nullptr;
-    int listCntCap = 0;
-    unsigned long long* dPruneStat = nullptr;  // list 1's total ([0]) and the verified count ([2]) of the last pruned launch
+    rs::DevBuf<unsigned> dListCnt;
+    int listCntCap = 0;              // (dListCnt holds 2 * listCntCap + 1 words)
+    rs::DevBuf<unsigned long long> dPruneStat;  // list 1's total ([0]) and the verified count ([2]) of the last pruned launch
     int64_t prunePairs = 0;          // its ntb * nq
     int prunePasses = 0;             // its scan passes (0: no pruned launch yet)
     int pruneNtb = 0;                // its template blocks (the entries of list2's counters)
     // on-device subsampling of camera frames (rs_vt_set_subsample / rs_vt_match_frames)
-    int32_t* dPix = nullptr;   // H*W byte offsets of the kept pixels in a frame
+    rs::DevBuf<int32_t> dPix;  // H*W byte offsets of the kept pixels in a frame
     int64_t frameBytes = 0;
-    uint8_t* dFrames = nullptr;
-    uint8_t* hFrames = nullptr;  // pinned staging for host frames
+    rs::DevBuf<uint8_t> dFrames;
+    rs::PinnedBuf<uint8_t> hFrames;  // staging for host frames
     int frameCap = 0;
 };
 
@@ -1703,25 +1707,22 @@ size_t pblock_bytes(const rs_vt* h) { return (size_t)PL_CG * (h->H / 4) * 128 * 
 constexpr size_t TS_BLOCK_BYTES = 16 * 64 * sizeof(uint32_t);
 int plane_ns(const rs_vt* h) { return h->H - 2 * h->M + 3; }
 
-// (Re)allocate a slot buffer of `blocks` 64-slot blocks of `bb` bytes, keeping
-// the first `keep` blocks.
-int vt_realloc_blocks(rs_vt* h, void** buf, int64_t keep, int64_t blocks, size_t bb) {
-    void* nb = nullptr;
+// Grow a slot buffer to `blocks` zeroed 64-slot blocks of `bb` bytes, keeping the first
+// `keep` blocks: the new block is allocated and filled before the old one goes (the one
+// growth that copies), so a failure leaves the old block and its capacity in place.
+template <class T>
+int vt_realloc_blocks(rs_vt* h, rs::DevBuf<T>& buf, int64_t keep, int64_t blocks, size_t bb,
+                      const char* what = "template buffer growth") {
+    rs::DevBuf<T> nb;
     const size_t bytes = (size_t)blocks * bb;
-    hipError_t e = hipMalloc(&nb, bytes);
-    if (e != hipSuccess) {
-        rs::set_error("template buffer growth to %lld slots (%zu bytes) failed: %s",
-                      (long long)blocks * 64, bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? RS_ERR_NOMEM : RS_ERR_HIP;
-    }
-    RS_HIP(hipMemsetAsync(nb, 0, bytes, h->stream));
-    if (*buf) {
+    RS_TRY(nb.reserve(bytes / sizeof(T), what));
+    RS_HIP(hipMemsetAsync(nb.get(), 0, bytes, h->stream));
+    if (buf.get()) {
         if (keep > 0)
-            RS_HIP(hipMemcpyAsync(nb, *buf, (size_t)keep * bb, hipMemcpyDeviceToDevice, h->stream));
+            RS_HIP(hipMemcpyAsync(nb.get(), buf.get(), (size_t)keep * bb, hipMemcpyDeviceToDevice, h->stream));
         RS_HIP(hipStreamSynchronize(h->stream));
-        RS_HIP(hipFree(*buf));
     }
-    *buf = nb;
+    buf = std::move(nb);
     return RS_OK;
 }
 
@@ -1735,25 +1736,10 @@ int vt_grow_lib(rs_vt* h, int64_t need_slots) {
     int64_t cap = h->localCap > 0 ? h->localCap : 64;
     while (cap < need_slots) cap *= 2;
     cap = (int64_t)rs::round_up((size_t)cap, 64);
-    uint4* nl = nullptr;
-    const size_t bytes = (size_t)(cap / 64) * tblock_bytes(h);
-    hipError_t e = hipMalloc(&nl, bytes);
-    if (e != hipSuccess) {
-        rs::set_error("template library growth to %lld slots (%zu bytes) failed: %s",
-                      (long long)cap, bytes, hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? RS_ERR_NOMEM : RS_ERR_HIP;
-    }
-    RS_HIP(hipMemsetAsync(nl, 0, bytes, h->stream));
-    if (h->dLib) {
-        RS_HIP(hipMemcpyAsync(nl, h->dLib, (size_t)(h->localCap / 64) * tblock_bytes(h),
-                              hipMemcpyDeviceToDevice, h->stream));
-        RS_HIP(hipStreamSynchronize(h->stream));
-        RS_HIP(hipFree(h->dLib));
-    }
-    h->dLib = nl;
+    RS_TRY(vt_realloc_blocks(h, h->dLib, h->localCap / 64, cap / 64, tblock_bytes(h), "template library growth"));
     if (h->planar) {
-        RS_TRY(vt_realloc_blocks(h, (void**)&h->dLibP, h->localCap / 64, cap / 64, pblock_bytes(h)));
-        RS_TRY(vt_realloc_blocks(h, (void**)&h->dLibTs, h->localCap / 64, cap / 64, TS_BLOCK_BYTES));
+        RS_TRY(vt_realloc_blocks(h, h->dLibP, h->localCap / 64, cap / 64, pblock_bytes(h)));
+        RS_TRY(vt_realloc_blocks(h, h->dLibTs, h->localCap / 64, cap / 64, TS_BLOCK_BYTES));
     }
     h->localCap = cap;
     return RS_OK;
@@ -1772,40 +1758,28 @@ int vt_qraw_idle(rs_vt* h) {
     return RS_OK;
 }
 
+constexpr unsigned VT_FINE = hipHostMallocMapped | hipHostMallocCoherent;
+
 int vt_grow_queries(rs_vt* h, int nq) {
     if (nq <= h->qCap) return RS_OK;
     int cap = h->qCap > 0 ? h->qCap : 64;
     while (cap < nq) cap *= 2;
     RS_TRY(vt_qraw_idle(h));
-    if (h->dQraw) RS_HIP(hipFree(h->dQraw));
-    if (h->hQraw) RS_HIP(hipHostFree(h->hQraw));
-    h->hQraw = h->hQrawDev = nullptr;
-    if (h->dQf) RS_HIP(hipFree(h->dQf));
-    if (h->dQsum) RS_HIP(hipFree(h->dQsum));
-    if (h->dBest) RS_HIP(hipFree(h->dBest));
-    if (h->hBest) RS_HIP(hipHostFree(h->hBest));
-    if (h->dQp) RS_HIP(hipFree(h->dQp));
-    if (h->dQsumRaw) RS_HIP(hipFree(h->dQsumRaw));
-    if (h->dQsj) RS_HIP(hipFree(h->dQsj));
-    if (h->dQc) RS_HIP(hipFree(h->dQc));
-    h->dQp = h->dQsumRaw = h->dQsj = h->dQc = nullptr;
-    const size_t qb = (size_t)h->H * h->W;
-    if (h->planar) {
-        RS_HIP(hipMalloc(&h->dQp, sizeof(uint32_t) * PL_CG * plane_ns(h) * 8 * (size_t)cap));
-        RS_HIP(hipMalloc(&h->dQsumRaw, sizeof(uint32_t) * cap));
-        if (h->prune) RS_HIP(hipMalloc(&h->dQsj, sizeof(uint32_t) * PF_NU * 16 * (size_t)cap));
-        if (h->prune) RS_HIP(hipMalloc(&h->dQc, sizeof(uint4) * QC_Q4 * (size_t)cap));
-    }
-    RS_HIP(hipMalloc(&h->dQraw, qb * cap));
-    RS_HIP(hipHostMalloc(&h->hQraw, qb * cap, hipHostMallocMapped | hipHostMallocCoherent));
-    RS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hQrawDev), h->hQraw, 0));
-    RS_HIP(hipMalloc(&h->dQf, sizeof(uint2) * (size_t)h->WD * h->H * cap));
-    RS_HIP(hipMalloc(&h->dQsum, sizeof(uint32_t) * cap));
-    RS_HIP(hipMalloc(&h->dBest, sizeof(unsigned long long) * cap));
-    // fine-grained (coherent): vt_fetch_keys polls the words the export kernel stores
-    RS_HIP(hipHostMalloc(&h->hBest, sizeof(unsigned long long) * cap, hipHostMallocMapped | hipHostMallocCoherent));
-    RS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hBestDev), h->hBest, 0));
+    h->qCap = 0;
     h->bestClean = h->bestPending = 0;
+    const size_t qb = (size_t)h->H * h->W, n = (size_t)cap;
+    if (h->planar) {
+        RS_TRY(h->dQp.reserve((size_t)PL_CG * plane_ns(h) * 8 * n));
+        RS_TRY(h->dQsumRaw.reserve(n));
+        if (h->prune) RS_TRY(h->dQsj.reserve((size_t)PF_NU * 16 * n));
+        if (h->prune) RS_TRY(h->dQc.reserve((size_t)QC_Q4 * 4 * n));
+    }
+    RS_TRY(h->dQraw.reserve(qb * n));
+    RS_TRY(h->hQraw.reserve(qb * n, VT_FINE));
+    RS_TRY(h->dQf.reserve((size_t)h->WD * h->H * n));
+    RS_TRY(h->dQsum.reserve(n));
+    RS_TRY(h->dBest.reserve(n));
+    RS_TRY(h->hBest.reserve(n, VT_FINE));
     h->qCap = cap;
     return RS_OK;
 }
@@ -1814,14 +1788,11 @@ int vt_grow_index(rs_vt* h, int n) {
     if (n <= h->idxCap) return RS_OK;
     int cap = h->idxCap > 0 ? h->idxCap : 64;
     while (cap < n) cap *= 2;
-    if (h->dSrc) RS_HIP(hipFree(h->dSrc));
-    if (h->dDst) RS_HIP(hipFree(h->dDst));
-    if (h->hSrc) RS_HIP(hipHostFree(h->hSrc));
-    if (h->hDst) RS_HIP(hipHostFree(h->hDst));
-    RS_HIP(hipMalloc(&h->dSrc, sizeof(int32_t) * cap));
-    RS_HIP(hipMalloc(&h->dDst, sizeof(int64_t) * cap));
-    RS_HIP(hipHostMalloc(&h->hSrc, sizeof(int32_t) * cap, hipHostMallocDefault));
-    RS_HIP(hipHostMalloc(&h->hDst, sizeof(int64_t) * cap, hipHostMallocDefault));
+    h->idxCap = 0;
+    RS_TRY(h->dSrc.reserve((size_t)cap));
+    RS_TRY(h->dDst.reserve((size_t)cap));
+    RS_TRY(h->hSrc.reserve((size_t)cap, hipHostMallocDefault));
+    RS_TRY(h->hDst.reserve((size_t)cap, hipHostMallocDefault));
     h->idxCap = cap;
     return RS_OK;
 }
@@ -1830,10 +1801,9 @@ int vt_grow_matrix(rs_vt* h, size_t elems) {
     if (elems <= h->matCap) return RS_OK;
     size_t cap = h->matCap > 0 ? h->matCap : 4096;
     while (cap < elems) cap *= 2;
-    if (h->dMat) RS_HIP(hipFree(h->dMat));
-    if (h->hMat) RS_HIP(hipHostFree(h->hMat));
-    RS_HIP(hipMalloc(&h->dMat, sizeof(uint32_t) * cap));
-    RS_HIP(hipHostMalloc(&h->hMat, sizeof(uint32_t) * cap, hipHostMallocDefault));
+    h->matCap = 0;
+    RS_TRY(h->dMat.reserve(cap));
+    RS_TRY(h->hMat.reserve(cap, hipHostMallocDefault));
     h->matCap = cap;
     return RS_OK;
 }
@@ -1842,28 +1812,41 @@ int vt_grow_cand(rs_vt* h, int64_t slots) {
     if (slots <= h->candCap) return RS_OK;
     int64_t cap = h->candCap > 0 ? h->candCap : 64;
     while (cap < slots) cap *= 2;
-    if (h->dCand) RS_HIP(hipFree(h->dCand));
-    RS_HIP(hipMalloc(&h->dCand, (size_t)(cap / 64) * tblock_bytes(h)));
+    h->candCap = 0;
+    RS_TRY(h->dCand.reserve((size_t)(cap / 64) * tblock_bytes(h) / sizeof(uint4)));
     if (h->planar) {
-        RS_TRY(vt_realloc_blocks(h, (void**)&h->dCandP, 0, cap / 64, pblock_bytes(h)));
-        RS_TRY(vt_realloc_blocks(h, (void**)&h->dCandTs, 0, cap / 64, TS_BLOCK_BYTES));
+        RS_TRY(vt_realloc_blocks(h, h->dCandP, 0, cap / 64, pblock_bytes(h)));
+        RS_TRY(vt_realloc_blocks(h, h->dCandTs, 0, cap / 64, TS_BLOCK_BYTES));
     }
     h->candCap = cap;
     return RS_OK;
 }
 
-int vt_build_forms(rs_vt* h, int nq);
+QueryForms vt_batch_view(const rs_vt* h) {
+    return {h->dQp.get(), h->dQsumRaw.get(), h->dQsj.get(), h->dQc.get()};
+}
+
+// The forms of rs_vt_match_stream's queries from query q0 on.
+QueryForms vt_stream_view(const rs_vt* h, size_t q0) {
+    const size_t qpq = (size_t)PL_CG * plane_ns(h) * 8;  // plane dwords per query
+    QueryForms v{h->dQpStream.get() + qpq * q0, h->dQsumStream.get() + q0, nullptr, nullptr};
+    if (h->dQsjStream.get()) v.qsj = h->dQsjStream.get() + (size_t)PF_NU * 16 * q0;
+    if (h->dQcStream.get()) v.qc = h->dQcStream.get() + (size_t)QC_Q4 * 4 * q0;
+    return v;
+}
+
+int vt_build_forms(rs_vt* h, const QueryForms& q, int nq);
 
 // Frozen key scans of at least this many queries prune (RS_VT_PRUNE=1, the default).
 constexpr int VT_PRUNE_MIN_Q = 512;
 
-// Whether a scan of nq queries against `count` slots from block tb0 takes the pruned path.
+// Whether a scan of nq queries (forms in q) against `count` slots from block tb0 takes the pruned path.
 // Below VT_PRUNE_MIN_Q queries the call is one latency-bound launch and the prefilter, the
 // list kernels and two scan passes cost more than they save; one template block has
 // nothing to prune.
-bool vt_prunes(const rs_vt* h, bool cand, int64_t tb0, int64_t count, int nq) {
+bool vt_prunes(const rs_vt* h, const QueryForms& q, bool cand, int64_t tb0, int64_t count, int nq) {
     const int64_t ntb = (count + 63) / 64;
-    return h->H == 64 && !cand && tb0 == 0 && h->dQsj && h->dQc && ntb <= 65535 &&
+    return h->H == 64 && !cand && tb0 == 0 && q.qsj && q.qc && ntb <= 65535 &&
            (h->prune == 2 || (h->prune == 1 && nq >= VT_PRUNE_MIN_Q && ntb >= 2));
 }
 // The plane build ahead of a key scan of the library: compact where that scan will prune.
@@ -1872,12 +1855,12 @@ bool vt_prunes(const rs_vt* h, bool cand, int64_t tb0, int64_t count, int nq) {
 // query measured faster than four and level with one (15.8, 12.9 and 13.7 us at the
 // headline shape).
 constexpr int VT_QC_THREADS = 128;
-uint32_t* vt_compact_for(rs_vt* h, int nq) {
+uint32_t* vt_compact_for(rs_vt* h, const QueryForms& q, int nq) {
     const int64_t lc = local_count_of(h, h->count);
-    const bool compact = h->planar && lc > 0 && vt_prunes(h, false, 0, lc, nq);
+    const bool compact = h->planar && lc > 0 && vt_prunes(h, q, false, 0, lc, nq);
     h->qpFull = !compact;
     h->qcValid = compact;
-    return compact ? h->dQc : nullptr;
+    return compact ? q.qc : nullptr;
 }
 
 // Batches of at most this many queries are read by the plane kernel straight from the
@@ -1893,10 +1876,11 @@ bool vt_zc_env() {
     return on;
 }
 
-// Upload nq raw queries and build their forms on the device.
+// Upload nq raw queries and build their forms (the batch view) on the device.
 int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
     RS_TRY(vt_grow_queries(h, nq));
     RS_TRY(vt_qraw_idle(h));
+    const QueryForms q = vt_batch_view(h);
     const size_t qb = (size_t)h->H * h->W * nq;
     // larger batches: HIP's own upload of the caller's (pageable) array, which returns
     // once the bytes are staged (per-batch PCIe-inclusive rate 4.04-4.12 against 3.44-3.54
@@ -1904,40 +1888,40 @@ int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
     // its keys, which the scan stores after the copy has run, so a pinned caller array is
     // no longer read when it returns.
     if (h->planar && nq <= VT_ZC_MAX && vt_zc_env()) {
-        std::memcpy(h->hQraw, queries, qb);
+        std::memcpy(h->hQraw.get(), queries, qb);
         h->qrawBusy = true;
-        uint32_t* const qc = vt_compact_for(h, nq);
-        hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(qc ? VT_QC_THREADS : 256), 0, h->stream, h->hQrawDev, h->H,
-                           h->M, h->dQp, h->dQsumRaw, h->dQraw, h->dQsj, qc);
+        uint32_t* const qc = vt_compact_for(h, q, nq);
+        hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(qc ? VT_QC_THREADS : 256), 0, h->stream, h->hQraw.dev(), h->H,
+                           h->M, q.qp, q.qsum, h->dQraw.get(), q.qsj, qc);
         RS_HIP(hipGetLastError());
         return RS_OK;
     }
-    RS_HIP(hipMemcpyAsync(h->dQraw, queries, qb, hipMemcpyHostToDevice, h->stream));
-    return vt_build_forms(h, nq);
+    RS_HIP(hipMemcpyAsync(h->dQraw.get(), queries, qb, hipMemcpyHostToDevice, h->stream));
+    return vt_build_forms(h, q, nq);
 }
 
-// Build the query forms of nq raw queries in device memory (default: dQraw).
+// Build the query forms of nq raw queries in device memory (default: dQraw) into the view q.
 // The plane scan reads only the planes; the byte-SWAR forms serve the other scans.
-int vt_build_forms(rs_vt* h, int nq, const uint8_t* src) {
+int vt_build_forms(rs_vt* h, const QueryForms& q, int nq, const uint8_t* src) {
     if (!h->planar)
         hipLaunchKernelGGL(vt_qform_kernel, dim3(nq), dim3(256), 0, h->stream, src, h->H, h->W,
-                           h->WD, h->M, h->dQf, h->dQsum);
+                           h->WD, h->M, h->dQf.get(), h->dQsum.get());
     else {
-        uint32_t* const qc = vt_compact_for(h, nq);
+        uint32_t* const qc = vt_compact_for(h, q, nq);
         hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(qc ? VT_QC_THREADS : 256), 0, h->stream, src, h->H,
-                           h->M, h->dQp, h->dQsumRaw, nullptr, h->dQsj, qc);
+                           h->M, q.qp, q.qsum, nullptr, q.qsj, qc);
     }
     RS_HIP(hipGetLastError());
     return RS_OK;
 }
 
-int vt_build_forms(rs_vt* h, int nq) { return vt_build_forms(h, nq, h->dQraw); }
+int vt_build_forms(rs_vt* h, const QueryForms& q, int nq) { return vt_build_forms(h, q, nq, h->dQraw.get()); }
 
 // Subsample nf frames on the device into the raw query buffer, then build the
 // forms.  Host frames go through a pinned staging buffer; device-resident frames
 // (a camera / decoder pipeline on the GPU) are gathered in place.
 int vt_stage_frames(rs_vt* h, int nf, const uint8_t* frames) {
-    RS_CHECK(h->dPix, RS_ERR_STATE, "no subsampling mask: call rs_vt_set_subsample first");
+    RS_CHECK(h->dPix.get(), RS_ERR_STATE, "no subsampling mask: call rs_vt_set_subsample first");
     RS_TRY(vt_grow_queries(h, nf));
     hipPointerAttribute_t attr{};
     const bool on_device = hipPointerGetAttributes(&attr, frames) == hipSuccess &&
@@ -1948,41 +1932,38 @@ int vt_stage_frames(rs_vt* h, int nf, const uint8_t* frames) {
         if (nf > h->frameCap) {
             int cap = h->frameCap > 0 ? h->frameCap : 16;
             while (cap < nf) cap *= 2;
-            if (h->dFrames) RS_HIP(hipFree(h->dFrames));
-            if (h->hFrames) RS_HIP(hipHostFree(h->hFrames));
-            h->dFrames = nullptr;
-            h->hFrames = nullptr;
-            RS_HIP(hipMalloc(&h->dFrames, (size_t)h->frameBytes * cap));
-            RS_HIP(hipHostMalloc(&h->hFrames, (size_t)h->frameBytes * cap, hipHostMallocDefault));
+            h->frameCap = 0;
+            RS_TRY(h->dFrames.reserve((size_t)h->frameBytes * cap));
+            RS_TRY(h->hFrames.reserve((size_t)h->frameBytes * cap, hipHostMallocDefault));
             h->frameCap = cap;
         }
         const size_t fb = (size_t)h->frameBytes * nf;
-        std::memcpy(h->hFrames, frames, fb);
-        RS_HIP(hipMemcpyAsync(h->dFrames, h->hFrames, fb, hipMemcpyHostToDevice, h->stream));
-        src = h->dFrames;
+        std::memcpy(h->hFrames.get(), frames, fb);
+        RS_HIP(hipMemcpyAsync(h->dFrames.get(), h->hFrames.get(), fb, hipMemcpyHostToDevice, h->stream));
+        src = h->dFrames.get();
     }
     hipLaunchKernelGGL(vt_gather_kernel, dim3(nf), dim3(256), 0, h->stream, src,
-                       (size_t)h->frameBytes, h->dPix, h->H * h->W, h->dQraw);
+                       (size_t)h->frameBytes, h->dPix.get(), h->H * h->W, h->dQraw.get());
     RS_HIP(hipGetLastError());
-    return vt_build_forms(h, nf);
+    return vt_build_forms(h, vt_batch_view(h), nf);
 }
 
 // Store raw staged queries src[i] into slots dst[i] of the library (or, with
 // `cand`, of the candidate buffer).
 int vt_store(rs_vt* h, bool cand, const uint8_t* d_raw, int n) {
     if (n == 0) return RS_OK;
-    uint4* lib = cand ? h->dCand : h->dLib;
-    RS_HIP(hipMemcpyAsync(h->dSrc, h->hSrc, sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
-    RS_HIP(hipMemcpyAsync(h->dDst, h->hDst, sizeof(int64_t) * n, hipMemcpyHostToDevice, h->stream));
+    uint4* lib = cand ? h->dCand.get() : h->dLib.get();
+    RS_HIP(hipMemcpyAsync(h->dSrc.get(), h->hSrc.get(), sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
+    RS_HIP(hipMemcpyAsync(h->dDst.get(), h->hDst.get(), sizeof(int64_t) * n, hipMemcpyHostToDevice, h->stream));
     h->stagingBusy = true;
     const int64_t total = (int64_t)n * h->WD * h->HQ;
     const int grid = (int)std::min<int64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(vt_store_kernel, dim3(grid), dim3(256), 0, h->stream, d_raw, h->dSrc,
-                       h->dDst, n, lib, h->H, h->W, h->WD, h->HQ);
+    hipLaunchKernelGGL(vt_store_kernel, dim3(grid), dim3(256), 0, h->stream, d_raw, h->dSrc.get(),
+                       h->dDst.get(), n, lib, h->H, h->W, h->WD, h->HQ);
     if (h->planar)
-        hipLaunchKernelGGL(vt_plane_store_kernel, dim3(n), dim3(256), 0, h->stream, d_raw, h->dSrc,
-                           h->dDst, h->H, h->M, cand ? h->dCandP : h->dLibP,
-                           cand ? h->dCandTs : h->dLibTs);
+        hipLaunchKernelGGL(vt_plane_store_kernel, dim3(n), dim3(256), 0, h->stream, d_raw, h->dSrc.get(),
+                           h->dDst.get(), h->H, h->M, cand ? h->dCandP.get() : h->dLibP.get(),
+                           cand ? h->dCandTs.get() : h->dLibTs.get());
     RS_HIP(hipGetLastError());
     return RS_OK;
 }
@@ -2009,85 +1990,67 @@ int plane_split(int ntb, int nbatch, int slots) {
     return nqc;
 }
 
-// Launch a scan of queries [0, nq) (forms in dQf) against `count` slots of lib.
+// Launch a scan of queries [0, nq) (forms in the view q) against `count` slots of lib.
 template <bool MATRIX>
-int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int rank,
+int vt_launch_plane(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int nq, ScanOut out, int rank,
                     int nranks, int64_t tb0) {
     const int ntb = (int)((count + 63) / 64);
     const int nqc = plane_split(ntb, (nq + PL_NB - 1) / PL_NB, h->planeSlots);
-    if (8 * ntb > h->ctrCap) {  // counters start at zero and every scan leaves them at zero
-        const int cap = std::max(8 * ntb, 2 * h->ctrCap);
-        if (h->dCtr) RS_HIP(hipFree(h->dCtr));
-        h->dCtr = nullptr;
-        h->ctrCap = 0;
-        RS_HIP(hipMalloc(&h->dCtr, sizeof(unsigned) * (size_t)cap));
-        RS_HIP(hipMemsetAsync(h->dCtr, 0, sizeof(unsigned) * (size_t)cap, h->stream));
-        h->ctrCap = cap;
+    if (8 * (size_t)ntb > h->dCtr.capacity()) {  // counters start at zero and every scan leaves them at zero
+        const size_t cap = std::max(8 * (size_t)ntb, 2 * h->dCtr.capacity());
+        RS_TRY(h->dCtr.reserve(cap));
+        RS_HIP(hipMemsetAsync(h->dCtr.get(), 0, sizeof(unsigned) * cap, h->stream));
     }
     RS_CHECK((int64_t)ntb * nqc < (1ll << 31), RS_ERR_ARG, "scan grid too large");
     const dim3 grid((unsigned)(ntb * nqc));
     const uint4* planes = reinterpret_cast<const uint4*>(
-        reinterpret_cast<const uint8_t*>(cand ? h->dCandP : h->dLibP) + (size_t)tb0 * pblock_bytes(h));
-    const uint32_t* ts = (cand ? h->dCandTs : h->dLibTs) + (size_t)tb0 * (TS_BLOCK_BYTES / 4);
+        reinterpret_cast<const uint8_t*>(cand ? h->dCandP.get() : h->dLibP.get()) + (size_t)tb0 * pblock_bytes(h));
+    const uint32_t* ts = (cand ? h->dCandTs.get() : h->dLibTs.get()) + (size_t)tb0 * (TS_BLOCK_BYTES / 4);
     if constexpr (!MATRIX) {
         // Pruned scan of the frozen library (vt_prunes).
-        if (vt_prunes(h, cand, tb0, count, nq)) {
+        if (vt_prunes(h, q, cand, tb0, count, nq)) {
             if (!h->qcValid) {   // the build before did not expect this scan to prune
                 hipLaunchKernelGGL(vt_qcompact_kernel, dim3((unsigned)nq), dim3(128), 0, h->stream,
-                                   reinterpret_cast<const uint4*>(h->dQp), reinterpret_cast<uint4*>(h->dQc));
+                                   reinterpret_cast<const uint4*>(q.qp), reinterpret_cast<uint4*>(q.qc));
                 h->qcValid = true;
             }
             const size_t pairs = (size_t)ntb * nq;
             if (pairs > h->pruneCap) {
                 const size_t cap = std::max(pairs, 2 * h->pruneCap);
-                if (h->dMinLB) RS_HIP(hipFree(h->dMinLB));
-                if (h->dSecond) RS_HIP(hipFree(h->dSecond));
-                if (h->dList) RS_HIP(hipFree(h->dList));
-                h->dMinLB = nullptr;
-                h->dSecond = nullptr;
-                h->dList = nullptr;
                 h->pruneCap = 0;
-                RS_HIP(hipMalloc(&h->dMinLB, sizeof(uint32_t) * cap));
-                RS_HIP(hipMalloc(&h->dSecond, sizeof(uint32_t) * cap));
-                RS_HIP(hipMalloc(&h->dList, sizeof(int) * 2 * cap));
+                RS_TRY(h->dMinLB.reserve(cap));
+                RS_TRY(h->dSecond.reserve(cap));
+                RS_TRY(h->dList.reserve(2 * cap));
                 h->pruneCap = cap;
             }
-            if (nq > h->tbStarCap) {
-                if (h->dTbStar) RS_HIP(hipFree(h->dTbStar));
-                h->dTbStar = nullptr;
-                h->tbStarCap = 0;
-                RS_HIP(hipMalloc(&h->dTbStar, sizeof(int) * (size_t)nq));
-                h->tbStarCap = nq;
-            }
+            RS_TRY(h->dTbStar.reserve((size_t)nq));  // (exact)
             if (ntb > h->listCntCap) {  // zero at first; the list kernels zero what they are about to fill
                 const int cap = std::max(ntb, 2 * h->listCntCap);
-                if (h->dListCnt) RS_HIP(hipFree(h->dListCnt));
-                h->dListCnt = nullptr;
                 h->listCntCap = 0;
-                RS_HIP(hipMalloc(&h->dListCnt, sizeof(unsigned) * (2 * (size_t)cap + 1)));
-                RS_HIP(hipMemsetAsync(h->dListCnt, 0, sizeof(unsigned) * (2 * (size_t)cap + 1), h->stream));
+                RS_TRY(h->dListCnt.reserve(2 * (size_t)cap + 1));
+                RS_HIP(hipMemsetAsync(h->dListCnt.get(), 0, sizeof(unsigned) * (2 * (size_t)cap + 1), h->stream));
                 h->listCntCap = cap;
             }
-            if (!h->dPruneStat) {
-                RS_HIP(hipMalloc(&h->dPruneStat, 3 * sizeof(unsigned long long)));
-                RS_HIP(hipMemsetAsync(h->dPruneStat, 0, 3 * sizeof(unsigned long long), h->stream));
+            if (!h->dPruneStat.get()) {
+                RS_TRY(h->dPruneStat.reserve(3));
+                RS_HIP(hipMemsetAsync(h->dPruneStat.get(), 0, 3 * sizeof(unsigned long long), h->stream));
             }
-            unsigned* cnt1 = h->dListCnt;
-            unsigned* cnt2 = h->dListCnt + h->listCntCap;
-            unsigned* verified = h->dListCnt + 2 * (size_t)h->listCntCap;
-            int* list1 = h->dList;
-            int* list2 = h->dList + pairs;
+            unsigned* cnt1 = h->dListCnt.get();
+            unsigned* cnt2 = h->dListCnt.get() + h->listCntCap;
+            unsigned* verified = h->dListCnt.get() + 2 * (size_t)h->listCntCap;
+            int* list1 = h->dList.get();
+            int* list2 = h->dList.get() + pairs;
             const int nqb = (nq + PF_NB - 1) / PF_NB, pfx = (ntb + PF_WAVES * PF_TPW - 1) / (PF_WAVES * PF_TPW);
             const dim3 pgrid((unsigned)pfx, (unsigned)std::min(nqb, std::max(1, VT_PF_GRID_CAP / pfx)));
             hipLaunchKernelGGL(vt_prefilter_kernel, pgrid, dim3(64 * PF_WAVES), 0, h->stream, planes, ntb, count,
-                               reinterpret_cast<const uint4*>(h->dQc), h->dQsj, nq, h->dMinLB,
-                               h->dSecond);
-            hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, h->dMinLB,
-                               h->dSecond, ntb, nq, planes, ts, reinterpret_cast<const uint4*>(h->dQc),
-                               reinterpret_cast<uint4*>(h->dQp), h->dQsumRaw,
-                               out.best, rank, nranks, h->dTbStar);
+                               reinterpret_cast<const uint4*>(q.qc), q.qsj, nq, h->dMinLB.get(),
+                               h->dSecond.get());
+            hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, h->dMinLB.get(),
+                               h->dSecond.get(), ntb, nq, planes, ts, reinterpret_cast<const uint4*>(q.qc),
+                               reinterpret_cast<uint4*>(q.qp), q.qsum,
+                               out.best, rank, nranks, h->dTbStar.get());
             const dim3 lgrid((unsigned)((nq + VT_LIST_T - 1) / VT_LIST_T), (unsigned)ntb);
-            hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar, cnt1,
+            hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar.get(), cnt1,
                                list1, verified, cnt2, ntb);
             // the passes min into the same keys; the folded export (out.host) needs one
             // launch to be the last, so a pruned call exports with vt_keys_export
@@ -2095,12 +2058,12 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
             po.host = nullptr;
             po.done = nullptr;
             hipLaunchKernelGGL((vt_scan_plane_kernel<64, false, true>), grid, dim3(64 * PL_CG * PL_SPLIT), 0,
-                               h->stream, planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, po, rank,
+                               h->stream, planes, ts, ntb, count, q.qp, q.qsum, nq, nqc, h->dCtr.get(), po, rank,
                                nranks, PlaneList{list1, cnt1, nq, VT_LIST_PER_B1});
-            hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB, nq,
-                               h->dTbStar, out.best, cnt2, list2, cnt1, verified, ntb, h->dPruneStat);
+            hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB.get(), nq,
+                               h->dTbStar.get(), out.best, cnt2, list2, cnt1, verified, ntb, h->dPruneStat.get());
             hipLaunchKernelGGL((vt_scan_plane_kernel<64, false, true>), grid, dim3(64 * PL_CG * PL_SPLIT), 0,
-                               h->stream, planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, po, rank,
+                               h->stream, planes, ts, ntb, count, q.qp, q.qsum, nq, nqc, h->dCtr.get(), po, rank,
                                nranks, PlaneList{list2, cnt2, nq, VT_LIST_PER});
             if (out.host)
                 hipLaunchKernelGGL(vt_keys_export, dim3((nq + 255) / 256 < 64 ? (nq + 255) / 256 : 64), dim3(256), 0,
@@ -2114,29 +2077,29 @@ int vt_launch_plane(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int
     }
     if (!h->qpFull) {   // a compact build, and a scan that reads every query's planes
         hipLaunchKernelGGL(vt_qexpand_kernel, dim3((unsigned)nq), dim3(256), 0, h->stream,
-                           reinterpret_cast<const uint4*>(h->dQc), reinterpret_cast<uint4*>(h->dQp));
+                           reinterpret_cast<const uint4*>(q.qc), reinterpret_cast<uint4*>(q.qp));
         h->qpFull = true;
     }
     if (h->H == 64)
         hipLaunchKernelGGL((vt_scan_plane_kernel<64, MATRIX>), grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream,
-                           planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, out, rank,
+                           planes, ts, ntb, count, q.qp, q.qsum, nq, nqc, h->dCtr.get(), out, rank,
                            nranks, PlaneList{});
     else
         hipLaunchKernelGGL((vt_scan_plane_kernel<32, MATRIX>), grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream,
-                           planes, ts, ntb, count, h->dQp, h->dQsumRaw, nq, nqc, h->dCtr, out, rank,
+                           planes, ts, ntb, count, q.qp, q.qsum, nq, nqc, h->dCtr.get(), out, rank,
                            nranks, PlaneList{});
     RS_HIP(hipGetLastError());
     return RS_OK;
 }
 
 // Launch a scan of queries [0, nq) against `count` slots of the library (or of
-// the candidate buffer), starting at 64-slot block tb0 of it.
+// the candidate buffer), starting at 64-slot block tb0 of it (q: the plane scan's forms).
 template <bool MATRIX>
-int vt_launch_scan(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int rank,
+int vt_launch_scan(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int nq, ScanOut out, int rank,
                    int nranks, int64_t tb0 = 0) {
     if (count <= 0 || nq <= 0) return RS_OK;
-    if (h->planar) return vt_launch_plane<MATRIX>(h, cand, count, nq, out, rank, nranks, tb0);
-    const uint4* lib = (cand ? h->dCand : h->dLib) + (size_t)tb0 * h->WD * h->HQ * 64;
+    if (h->planar) return vt_launch_plane<MATRIX>(h, q, cand, count, nq, out, rank, nranks, tb0);
+    const uint4* lib = (cand ? h->dCand.get() : h->dLib.get()) + (size_t)tb0 * h->WD * h->HQ * 64;
     const int ntb = (int)((count + 63) / 64);
     const bool fast = h->M == FAST_M && (h->H == 64 || h->H == 32);
     RS_CHECK((int64_t)ntb * nq < (1ll << 31), RS_ERR_ARG, "scan grid too large (%d x %d)", ntb, nq);
@@ -2145,25 +2108,25 @@ int vt_launch_scan(rs_vt* h, bool cand, int64_t count, int nq, ScanOut out, int 
         const dim3 grid((unsigned)((count + 7) / 8), nq);
         if (h->H == 64)
             hipLaunchKernelGGL((vt_scan_carry_col_kernel<64, 1>), grid, dim3(64), 0, h->stream,
-                               lib, count, h->WD, h->dQf, h->dQsum, nq, out, rank, nranks);
+                               lib, count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out, rank, nranks);
         else
             hipLaunchKernelGGL((vt_scan_carry_col_kernel<32, 1>), grid, dim3(64), 0, h->stream,
-                               lib, count, h->WD, h->dQf, h->dQsum, nq, out, rank, nranks);
+                               lib, count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out, rank, nranks);
     } else if (fast) {
         constexpr int NQ = 2;
         const int nqg = (nq + NQ - 1) / NQ;
         const dim3 grid((unsigned)(ntb * ((nqg + 7) / 8) * 8));
         if (h->H == 64)
             hipLaunchKernelGGL((vt_scan_carry_kernel<64, NQ, MATRIX>), grid, dim3(64), 0,
-                               h->stream, lib, ntb, count, h->WD, h->dQf, h->dQsum, nq, out,
+                               h->stream, lib, ntb, count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out,
                                rank, nranks);
         else
             hipLaunchKernelGGL((vt_scan_carry_kernel<32, NQ, MATRIX>), grid, dim3(64), 0,
-                               h->stream, lib, ntb, count, h->WD, h->dQf, h->dQsum, nq, out,
+                               h->stream, lib, ntb, count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out,
                                rank, nranks);
     } else {
         hipLaunchKernelGGL((vt_scan_generic_kernel<MATRIX>), dim3((unsigned)(ntb * nq)), dim3(64),
-                           0, h->stream, lib, ntb, count, h->H, h->M, h->WD, h->dQf, nq, out, rank,
+                           0, h->stream, lib, ntb, count, h->H, h->M, h->WD, h->dQf.get(), nq, out, rank,
                            nranks);
     }
     RS_HIP(hipGetLastError());
@@ -2212,11 +2175,11 @@ int vt_append_staged(rs_vt* h, const std::vector<std::pair<int, int64_t>>& news)
     RS_TRY(vt_grow_lib(h, local_count_of(h, new_count)));
     for (const auto& p : news) {
         if (p.second % h->nranks != h->rank) continue;
-        h->hSrc[mine] = p.first;
-        h->hDst[mine] = p.second / h->nranks;
+        h->hSrc.get()[mine] = p.first;
+        h->hDst.get()[mine] = p.second / h->nranks;
         ++mine;
     }
-    RS_TRY(vt_store(h, false, h->dQraw, mine));
+    RS_TRY(vt_store(h, false, h->dQraw.get(), mine));
     h->count = new_count;
     return RS_OK;
 }
@@ -2239,27 +2202,27 @@ int vt_scan_local_impl(rs_vt* h, int nq, const uint8_t* queries, bool frames = f
                  h->stagedQ);
     }
     if (h->bestClean < nq) {  // vt_keys_export resets the keys it hands over
-        RS_HIP(hipMemsetAsync(h->dBest, 0xFF, sizeof(unsigned long long) * nq, h->stream));
+        RS_HIP(hipMemsetAsync(h->dBest.get(), 0xFF, sizeof(unsigned long long) * nq, h->stream));
         h->bestClean = nq;
     }
     h->bestPending = h->bestClean;  // [0, nq) is dirty until exported; the rest stays clean
     h->bestClean = 0;
     const int64_t lc = local_count_of(h, h->count);
-    ScanOut out{h->dBest, nullptr, 0};
+    ScanOut out{h->dBest.get(), nullptr, 0};
     // a plane scan whose keys the host polls exports them itself (its last block): one
     // launch fewer per call.  Not when they are min-reduced over ranks first.
     h->keysFolded = fold_ok && h->planar && lc > 0 && vt_poll_env() && !h->timing && nq <= VT_POLL_MAX;
     if (h->keysFolded) {
-        if (!h->dDone) {
-            RS_HIP(hipMalloc(&h->dDone, sizeof(unsigned)));
-            RS_HIP(hipMemsetAsync(h->dDone, 0, sizeof(unsigned), h->stream));
+        if (!h->dDone.get()) {
+            RS_TRY(h->dDone.reserve(1));
+            RS_HIP(hipMemsetAsync(h->dDone.get(), 0, sizeof(unsigned), h->stream));
         }
-        for (int i = 0; i < nq; ++i) h->hBest[i] = KEY_PENDING;
-        out.host = h->hBestDev;
-        out.done = h->dDone;
+        for (int i = 0; i < nq; ++i) h->hBest.get()[i] = KEY_PENDING;
+        out.host = h->hBest.dev();
+        out.done = h->dDone.get();
     }
     if (h->timing) RS_HIP(hipEventRecord(h->ev0, h->stream));
-    RS_TRY(vt_launch_scan<false>(h, false, lc, nq, out, h->rank, h->nranks));
+    RS_TRY(vt_launch_scan<false>(h, vt_batch_view(h), false, lc, nq, out, h->rank, h->nranks));
     if (h->timing) RS_HIP(hipEventRecord(h->ev1, h->stream));
     h->timedScan = h->timing;
     h->stagedQ = nq;
@@ -2300,16 +2263,16 @@ int vt_resolve_impl(rs_vt* h, int nq, const unsigned long long* keys, int mode,
         RS_TRY(vt_grow_cand(h, (int64_t)rs::round_up((size_t)C, 64)));
         RS_TRY(vt_grow_index(h, (int)C));
         for (int64_t j = 0; j < C; ++j) {
-            h->hSrc[j] = cand[j];
-            h->hDst[j] = j;
+            h->hSrc.get()[j] = cand[j];
+            h->hDst.get()[j] = j;
             cpos[cand[j]] = (int)j;
         }
-        RS_TRY(vt_store(h, true, h->dQraw, (int)C));
+        RS_TRY(vt_store(h, true, h->dQraw.get(), (int)C));
         ldm = (int64_t)rs::round_up((size_t)C, 64);
         RS_TRY(vt_grow_matrix(h, (size_t)ldm * nq));
-        ScanOut mo{nullptr, h->dMat, ldm};
-        RS_TRY(vt_launch_scan<true>(h, true, C, nq, mo, 0, 1));
-        RS_HIP(hipMemcpyAsync(h->hMat, h->dMat, sizeof(uint32_t) * ldm * nq, hipMemcpyDeviceToHost,
+        ScanOut mo{nullptr, h->dMat.get(), ldm};
+        RS_TRY(vt_launch_scan<true>(h, vt_batch_view(h), true, C, nq, mo, 0, 1));
+        RS_HIP(hipMemcpyAsync(h->hMat.get(), h->dMat.get(), sizeof(uint32_t) * ldm * nq, hipMemcpyDeviceToHost,
                               h->stream));
         RS_HIP(hipStreamSynchronize(h->stream));
         h->stagingBusy = false;
@@ -2320,7 +2283,7 @@ int vt_resolve_impl(rs_vt* h, int nq, const unsigned long long* keys, int mode,
         for (size_t a = 0; a < news.size(); ++a) {
             const int j = news[a].first;
             const unsigned long long kj =
-                ((unsigned long long)h->hMat[(size_t)i * ldm + cpos[j]] << 32) |
+                ((unsigned long long)h->hMat.get()[(size_t)i * ldm + cpos[j]] << 32) |
                 (unsigned long long)news[a].second;
             k = kj < k ? kj : k;
         }
@@ -2343,7 +2306,7 @@ int vt_fetch_keys(rs_vt* h, int nq, bool allreduce) {
     if (allreduce && h->nranks > 1) {
         RS_CHECK(h->comm, RS_ERR_STATE, "sharded handle without a communicator: use "
                  "rs_vt_scan_local + an external min-reduction + rs_vt_resolve");
-        ncclResult_t r = ncclAllReduce(h->dBest, h->dBest, (size_t)nq, ncclUint64, ncclMin, h->comm,
+        ncclResult_t r = ncclAllReduce(h->dBest.get(), h->dBest.get(), (size_t)nq, ncclUint64, ncclMin, h->comm,
                                        h->stream);
         RS_CHECK(r == ncclSuccess, RS_ERR_RCCL, "ncclAllReduce(min) failed: %s",
                  ncclGetErrorString(r));
@@ -2353,12 +2316,12 @@ int vt_fetch_keys(rs_vt* h, int nq, bool allreduce) {
         h->keysFolded = false;
     } else {
         if (poll)
-            for (int i = 0; i < nq; ++i) h->hBest[i] = KEY_PENDING;
+            for (int i = 0; i < nq; ++i) h->hBest.get()[i] = KEY_PENDING;
         hipLaunchKernelGGL(vt_keys_export, dim3((nq + 255) / 256 < 64 ? (nq + 255) / 256 : 64), dim3(256), 0,
-                           h->stream, h->dBest, nq, h->hBestDev);
+                           h->stream, h->dBest.get(), nq, h->hBest.dev());
         RS_HIP(hipGetLastError());
     }
-    if (!(poll && vt_poll_keys(h->hBest, nq))) {
+    if (!(poll && vt_poll_keys(h->hBest.get(), nq))) {
         RS_HIP(hipStreamSynchronize(h->stream));
         h->stagingBusy = false;
     }
@@ -2395,13 +2358,9 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
     const size_t total = (size_t)nb * nq;
     RS_CHECK(total <= INT32_MAX, RS_ERR_ARG, "too many queries in one stream");
     if (total > h->streamCap) {
-        if (h->hStream) RS_HIP(hipHostFree(h->hStream));
-        if (h->dStream) RS_HIP(hipFree(h->dStream));
-        h->hStream = h->dStream = nullptr;
         h->streamCap = 0;
-        RS_HIP(hipHostMalloc(&h->hStream, sizeof(unsigned long long) * total, hipHostMallocDefault));
-        RS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hStreamDev), h->hStream, 0));
-        RS_HIP(hipMalloc(&h->dStream, sizeof(unsigned long long) * total));
+        RS_TRY(h->hStream.reserve(total, hipHostMallocDefault));
+        RS_TRY(h->dStream.reserve(total));
         h->streamCap = total;
         h->streamClean = false;
     }
@@ -2415,7 +2374,7 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
     // the keys start at UINT64_MAX: the export of the previous call reset them
     // (one memset after allocation, or after a call that did not reach its export)
     if (!h->streamClean)
-        RS_HIP(hipMemsetAsync(h->dStream, 0xFF, sizeof(unsigned long long) * h->streamCap, h->stream));
+        RS_HIP(hipMemsetAsync(h->dStream.get(), 0xFF, sizeof(unsigned long long) * h->streamCap, h->stream));
     h->streamClean = false;
     h->stagedQ = 0;  // the forms no longer match dQraw
     h->timedScan = false;
@@ -2434,40 +2393,22 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
     // upload in line (the earlier form) ran at 0.52 of the HBM-resident rate.
     const bool hostgroups = !on_device && h->planar;
     const bool allplanes = (on_device && h->planar && nb > 1) || hostgroups;
-    const size_t qpq = (size_t)PL_CG * plane_ns(h) * 8;  // plane dwords per query
-    struct PlaneBufRestore {  // h->dQp / dQsumRaw point at the per-batch buffers on return
-        rs_vt* h;
-        uint32_t* p;
-        uint32_t* q;
-        uint32_t* j;
-        uint32_t* c;
-        ~PlaneBufRestore() { h->dQp = p; h->dQsumRaw = q; h->dQsj = j; h->dQc = c; }
-    } restore{h, h->dQp, h->dQsumRaw, h->dQsj, h->dQc};
     if (allplanes) {
         if (total > h->qpStreamCap) {
-            if (h->dQpStream) RS_HIP(hipFree(h->dQpStream));
-            if (h->dQsumStream) RS_HIP(hipFree(h->dQsumStream));
-            if (h->dQsjStream) RS_HIP(hipFree(h->dQsjStream));
-            if (h->dQcStream) RS_HIP(hipFree(h->dQcStream));
-            h->dQpStream = h->dQsumStream = h->dQsjStream = h->dQcStream = nullptr;
             h->qpStreamCap = 0;
-            RS_HIP(hipMalloc(&h->dQpStream, sizeof(uint32_t) * qpq * total));
-            RS_HIP(hipMalloc(&h->dQsumStream, sizeof(uint32_t) * total));
-            if (h->prune) RS_HIP(hipMalloc(&h->dQsjStream, sizeof(uint32_t) * PF_NU * 16 * total));
-            if (h->prune) RS_HIP(hipMalloc(&h->dQcStream, sizeof(uint4) * QC_Q4 * total));
+            RS_TRY(h->dQpStream.reserve((size_t)PL_CG * plane_ns(h) * 8 * total));
+            RS_TRY(h->dQsumStream.reserve(total));
+            if (h->prune) RS_TRY(h->dQsjStream.reserve((size_t)PF_NU * 16 * total));
+            if (h->prune) RS_TRY(h->dQcStream.reserve((size_t)QC_Q4 * 4 * total));
             h->qpStreamCap = total;
         }
-        RS_CHECK(total <= INT32_MAX, RS_ERR_ARG, "too many queries in one stream");
-        h->dQp = h->dQpStream;
-        h->dQsumRaw = h->dQsumStream;
-        h->dQsj = h->dQsjStream;
-        h->dQc = h->dQcStream;
         if (!hostgroups) {
-            RS_TRY(vt_build_forms(h, (int)total, queries));
-            const ScanOut out{h->dStream, nullptr, 0};
+            const QueryForms q = vt_stream_view(h, 0);
+            RS_TRY(vt_build_forms(h, q, (int)total, queries));
+            const ScanOut out{h->dStream.get(), nullptr, 0};
             // the one scan of the call, bracketed by events when timing (rs_vt_last_ms)
             if (h->timing) RS_HIP(hipEventRecord(h->ev0, h->stream));
-            RS_TRY(vt_launch_scan<false>(h, false, lc, (int)total, out, h->rank, h->nranks));
+            RS_TRY(vt_launch_scan<false>(h, q, false, lc, (int)total, out, h->rank, h->nranks));
             if (h->timing) RS_HIP(hipEventRecord(h->ev1, h->stream));
             h->timedScan = h->timing;
         } else {
@@ -2488,12 +2429,8 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
             }
             if (qb * gb > h->upCap) {
                 RS_HIP(hipStreamSynchronize(h->ustream));
-                for (int i = 0; i < 2; ++i) {
-                    if (h->dUp[i]) RS_HIP(hipFree(h->dUp[i]));
-                    h->dUp[i] = nullptr;
-                }
                 h->upCap = 0;
-                for (int i = 0; i < 2; ++i) RS_HIP(hipMalloc(&h->dUp[i], qb * gb));
+                for (int i = 0; i < 2; ++i) RS_TRY(h->dUp[i].reserve(qb * gb));
                 h->upCap = qb * gb;
             }
             const int g1n = nb >= 4 ? 1 : gb;
@@ -2502,37 +2439,34 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
                 const int bi = g & 1;
                 // the buffer's group before last has had its planes built
                 if (g >= 2) RS_HIP(hipStreamWaitEvent(h->ustream, h->evUsed[bi], 0));
-                RS_HIP(hipMemcpyAsync(h->dUp[bi], queries + qb * b0, qb * n, hipMemcpyHostToDevice, h->ustream));
+                RS_HIP(hipMemcpyAsync(h->dUp[bi].get(), queries + qb * b0, qb * n, hipMemcpyHostToDevice, h->ustream));
                 RS_HIP(hipEventRecord(h->evUp[bi], h->ustream));
                 RS_HIP(hipStreamWaitEvent(h->stream, h->evUp[bi], 0));
-                h->dQp = h->dQpStream + qpq * (size_t)b0 * nq;
-                h->dQsumRaw = h->dQsumStream + (size_t)b0 * nq;
-                if (h->dQsjStream) h->dQsj = h->dQsjStream + (size_t)PF_NU * 16 * b0 * nq;
-                if (h->dQcStream) h->dQc = h->dQcStream + (size_t)QC_Q4 * 4 * b0 * nq;
-                RS_TRY(vt_build_forms(h, n * nq, h->dUp[bi]));
+                const QueryForms q = vt_stream_view(h, (size_t)b0 * nq);
+                RS_TRY(vt_build_forms(h, q, n * nq, h->dUp[bi].get()));
                 RS_HIP(hipEventRecord(h->evUsed[bi], h->stream));
-                const ScanOut out{h->dStream + (size_t)b0 * nq, nullptr, 0};
-                RS_TRY(vt_launch_scan<false>(h, false, lc, n * nq, out, h->rank, h->nranks));
+                const ScanOut out{h->dStream.get() + (size_t)b0 * nq, nullptr, 0};
+                RS_TRY(vt_launch_scan<false>(h, q, false, lc, n * nq, out, h->rank, h->nranks));
             }
             h->timedScan = false;   // scans interleaved with upload waits: no single duration
         }
         if (h->comm) {
-            ncclResult_t r = ncclAllReduce(h->dStream, h->dStream, total, ncclUint64, ncclMin, h->comm,
+            ncclResult_t r = ncclAllReduce(h->dStream.get(), h->dStream.get(), total, ncclUint64, ncclMin, h->comm,
                                            h->stream);
             RS_CHECK(r == ncclSuccess, RS_ERR_RCCL, "ncclAllReduce(min) failed: %s",
                      ncclGetErrorString(r));
         }
     }
     for (int b = 0; b < nb && !allplanes; ++b) {
-        unsigned long long* keys = h->dStream + (size_t)b * nq;
+        unsigned long long* keys = h->dStream.get() + (size_t)b * nq;
         const ScanOut out{keys, nullptr, 0};
         const uint8_t* src = queries + qb * b;
         if (!on_device) {
-            RS_HIP(hipMemcpyAsync(h->dQraw, src, qb, hipMemcpyHostToDevice, h->stream));
-            src = h->dQraw;
+            RS_HIP(hipMemcpyAsync(h->dQraw.get(), src, qb, hipMemcpyHostToDevice, h->stream));
+            src = h->dQraw.get();
         }
-        RS_TRY(vt_build_forms(h, nq, src));
-        RS_TRY(vt_launch_scan<false>(h, false, lc, nq, out, h->rank, h->nranks));
+        RS_TRY(vt_build_forms(h, vt_batch_view(h), nq, src));
+        RS_TRY(vt_launch_scan<false>(h, vt_batch_view(h), false, lc, nq, out, h->rank, h->nranks));
         if (h->comm) {
             // the batch's row is reduced on the collective stream while the next
             // batch's planes and scan run on the main stream (rows are distinct)
@@ -2551,14 +2485,14 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
     // keys -> pinned host memory and reset for the next call, in one queued launch
     // (in place of a device-to-host blit and a memset)
     hipLaunchKernelGGL(vt_keys_export, dim3(std::min<size_t>((total + 255) / 256, 256)), dim3(256), 0,
-                       h->stream, h->dStream, (int)total, h->hStreamDev);
+                       h->stream, h->dStream.get(), (int)total, h->hStream.dev());
     RS_HIP(hipGetLastError());
     RS_HIP(hipStreamSynchronize(h->stream));
     h->streamClean = true;
     if (!allplanes) h->timedScan = false;  // several scans: no single duration
     else if (h->timedScan) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
     for (size_t i = 0; i < total; ++i) {
-        const unsigned long long k = h->hStream[i];
+        const unsigned long long k = h->hStream.get()[i];
         if (best_index) best_index[i] = k == NO_KEY ? -1 : (int64_t)(k & 0xFFFFFFFFull);
         if (best_score) best_score[i] = k == NO_KEY ? UINT64_MAX : (k >> 32);
     }
@@ -2571,7 +2505,7 @@ int vt_match_impl(rs_vt* h, int nq, const uint8_t* queries, int mode, uint64_t* 
     RS_TRY(vt_scan_local_impl(h, nq, queries, frames, h->nranks == 1));
     if (nq == 0) return RS_OK;
     RS_TRY(vt_fetch_keys(h, nq, true));
-    return vt_resolve_impl(h, nq, h->hBest, mode, best_score, best_index, is_new);
+    return vt_resolve_impl(h, nq, h->hBest.get(), mode, best_score, best_index, is_new);
 }
 
 }  // namespace
@@ -2672,33 +2606,18 @@ int rs_vt_destroy(rs_vt* h) {
             if (se == hipSuccess) se = e;
         }
     if (h->comm) (void)ncclCommDestroy(h->comm);
-    for (void* p : {(void*)h->dLib, (void*)h->dQraw, (void*)h->dQf, (void*)h->dQsum, (void*)h->dBest,
-                    (void*)h->dSrc, (void*)h->dDst, (void*)h->dCand, (void*)h->dMat, (void*)h->dLibP,
-                    (void*)h->dLibTs, (void*)h->dCandP, (void*)h->dCandTs, (void*)h->dQp,
-                    (void*)h->dQsumRaw, (void*)h->dCtr, (void*)h->dDone, (void*)h->dPix, (void*)h->dFrames,
-                    (void*)h->dQsj, (void*)h->dQsjStream, (void*)h->dQc, (void*)h->dQcStream, (void*)h->dMinLB, (void*)h->dSecond, (void*)h->dList, (void*)h->dTbStar,
-                    (void*)h->dListCnt, (void*)h->dPruneStat})
-        if (p) (void)hipFree(p);
-    if (h->hStream) (void)hipHostFree(h->hStream);
-    if (h->dStream) (void)hipFree(h->dStream);
-    if (h->dQpStream) (void)hipFree(h->dQpStream);
-    if (h->dQsumStream) (void)hipFree(h->dQsumStream);
-    for (void* p : {(void*)h->hQraw, (void*)h->hBest, (void*)h->hSrc, (void*)h->hDst, (void*)h->hMat,
-                    (void*)h->hFrames})
-        if (p) (void)hipHostFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->evScan) (void)hipEventDestroy(h->evScan);
     if (h->evComm) (void)hipEventDestroy(h->evComm);
     if (h->cstream) (void)hipStreamDestroy(h->cstream);
     for (int i = 0; i < 2; ++i) {
-        if (h->dUp[i]) (void)hipFree(h->dUp[i]);
         if (h->evUp[i]) (void)hipEventDestroy(h->evUp[i]);
         if (h->evUsed[i]) (void)hipEventDestroy(h->evUsed[i]);
     }
     if (h->ustream) (void)hipStreamDestroy(h->ustream);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;  // (the buffers go with their members)
     RS_CHECK(se == hipSuccess, RS_ERR_HIP, "work queued before rs_vt_destroy failed: %s", hipGetErrorString(se));
     return RS_OK;
 }
@@ -2727,7 +2646,7 @@ int rs_vt_add(rs_vt* h, int n, const uint8_t* templates, int64_t* first_index) {
                             (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeDevice ||
                              attr.type == hipMemoryTypeManaged);
     (void)hipGetLastError();  // a pageable pointer is not an error
-    RS_HIP(hipMemcpyAsync(h->dQraw, templates, qb,
+    RS_HIP(hipMemcpyAsync(h->dQraw.get(), templates, qb,
                           attr.type == hipMemoryTypeDevice && direct_dma ? hipMemcpyDeviceToDevice
                                                                          : hipMemcpyHostToDevice,
                           h->stream));
@@ -2735,9 +2654,13 @@ int rs_vt_add(rs_vt* h, int n, const uint8_t* templates, int64_t* first_index) {
     std::vector<std::pair<int, int64_t>> news;
     news.reserve(n);
     for (int i = 0; i < n; ++i) news.emplace_back(i, h->count + i);
-    RS_TRY(vt_append_staged(h, news));   // (its copies guarded by vt_staging_idle, not a sync)
-    if (direct_dma) RS_HIP(hipStreamSynchronize(h->stream));
-    return RS_OK;
+    const int s = vt_append_staged(h, news);   // (its copies guarded by vt_staging_idle, not a sync)
+    // (on the error path as well: the upload above is queued either way)
+    if (direct_dma) {
+        const hipError_t e = hipStreamSynchronize(h->stream);
+        RS_CHECK(s != RS_OK || e == hipSuccess, RS_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    }
+    return s;
 }
 
 int rs_vt_read(rs_vt* h, int64_t index, uint8_t* out) {
@@ -2754,7 +2677,7 @@ int rs_vt_read(rs_vt* h, int64_t index, uint8_t* out) {
     for (int c = 0; c < h->WD; ++c)
         for (int q = 0; q < h->HQ; ++q)
             RS_HIP(hipMemcpyAsync(&chunks[(size_t)c * h->HQ + q],
-                                  h->dLib + ((tb * h->WD + c) * h->HQ + q) * 64 + tl, sizeof(uint4),
+                                  h->dLib.get() + ((tb * h->WD + c) * h->HQ + q) * 64 + tl, sizeof(uint4),
                                   hipMemcpyDeviceToHost, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     for (int r = 0; r < h->H; ++r)
@@ -2798,15 +2721,13 @@ int rs_vt_set_subsample(rs_vt* h, int64_t frame_bytes, const int32_t* pixels) {
                  "pixel offset %d of entry %d outside the %lld-byte frame", pixels[i], i,
                  (long long)frame_bytes);
     RS_HIP(hipSetDevice(h->device));
-    if (!h->dPix) RS_HIP(hipMalloc(&h->dPix, sizeof(int32_t) * npix));
-    RS_HIP(hipMemcpyAsync(h->dPix, pixels, sizeof(int32_t) * npix, hipMemcpyHostToDevice, h->stream));
+    RS_TRY(h->dPix.reserve((size_t)npix));
+    RS_HIP(hipMemcpyAsync(h->dPix.get(), pixels, sizeof(int32_t) * npix, hipMemcpyHostToDevice, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     if (frame_bytes != h->frameBytes) {  // staging buffers are sized per frame
-        if (h->dFrames) RS_HIP(hipFree(h->dFrames));
-        if (h->hFrames) RS_HIP(hipHostFree(h->hFrames));
-        h->dFrames = nullptr;
-        h->hFrames = nullptr;
         h->frameCap = 0;
+        h->dFrames.reset();
+        h->hFrames.reset();
     }
     h->frameBytes = frame_bytes;
     return RS_OK;
@@ -2824,7 +2745,7 @@ int rs_vt_scan_local(rs_vt* h, int nq, const uint8_t* queries, uint64_t* local_k
     RS_TRY(vt_scan_local_impl(h, nq, queries));
     if (nq == 0) return RS_OK;
     RS_TRY(vt_fetch_keys(h, nq, false));
-    if (local_keys) std::memcpy(local_keys, h->hBest, sizeof(uint64_t) * nq);
+    if (local_keys) std::memcpy(local_keys, h->hBest.get(), sizeof(uint64_t) * nq);
     return RS_OK;
 }
 
@@ -2871,16 +2792,16 @@ int rs_vt_scores(rs_vt* h, int nq, const uint8_t* queries, int64_t t0, int64_t n
     const int64_t tb0 = t0 / 64, lo = t0 - tb0 * 64, span = lo + nt;
     const int64_t ld = (int64_t)rs::round_up((size_t)span, 64);
     RS_TRY(vt_grow_matrix(h, (size_t)ld * nq));
-    ScanOut mo{nullptr, h->dMat, ld};
+    ScanOut mo{nullptr, h->dMat.get(), ld};
     RS_HIP(hipEventRecord(h->ev0, h->stream));
-    RS_TRY(vt_launch_scan<true>(h, false, span, nq, mo, 0, 1, tb0));
+    RS_TRY(vt_launch_scan<true>(h, vt_batch_view(h), false, span, nq, mo, 0, 1, tb0));
     RS_HIP(hipEventRecord(h->ev1, h->stream));
-    RS_HIP(hipMemcpy2DAsync(h->hMat, sizeof(uint32_t) * nt, h->dMat + lo, sizeof(uint32_t) * ld,
+    RS_HIP(hipMemcpy2DAsync(h->hMat.get(), sizeof(uint32_t) * nt, h->dMat.get() + lo, sizeof(uint32_t) * ld,
                             sizeof(uint32_t) * nt, nq, hipMemcpyDeviceToHost, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
     h->timedScan = true;
-    for (size_t i = 0; i < (size_t)nq * nt; ++i) scores[i] = h->hMat[i];
+    for (size_t i = 0; i < (size_t)nq * nt; ++i) scores[i] = h->hMat.get()[i];
     return RS_OK;
 }
 
@@ -2907,8 +2828,8 @@ int rs_vt_prune_stats(rs_vt* h, int64_t out[4]) {
     // the pairs of B2: list2's counters, which stay until the next pruned launch's lists
     unsigned long long s0 = 0ull;
     std::vector<unsigned> c2((size_t)h->pruneNtb);
-    RS_HIP(hipMemcpyAsync(&s0, h->dPruneStat, sizeof(s0), hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipMemcpyAsync(c2.data(), h->dListCnt + h->listCntCap, sizeof(unsigned) * c2.size(), hipMemcpyDeviceToHost,
+    RS_HIP(hipMemcpyAsync(&s0, h->dPruneStat.get(), sizeof(s0), hipMemcpyDeviceToHost, h->stream));
+    RS_HIP(hipMemcpyAsync(c2.data(), h->dListCnt.get() + h->listCntCap, sizeof(unsigned) * c2.size(), hipMemcpyDeviceToHost,
                           h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     out[0] = (int64_t)s0;
@@ -2925,7 +2846,7 @@ int rs_vt_prune_verified(rs_vt* h, int64_t* out) {
     if (h->prunePasses == 0) return RS_OK;
     RS_HIP(hipSetDevice(h->device));
     unsigned long long v = 0ull;
-    RS_HIP(hipMemcpyAsync(&v, h->dPruneStat + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+    RS_HIP(hipMemcpyAsync(&v, h->dPruneStat.get() + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     *out = (int64_t)v;
     return RS_OK;
@@ -3006,15 +2927,18 @@ int rs_sad_scores(int device, int dtype, int H, int W, int max_offset, int64_t n
     sad_program(0, (H - 2 * max_offset) * W, prog);
     const size_t es = dtype == RS_DT_F32 ? 4 : 8;
     const size_t tb = (size_t)nt * H * W * es, qb = (size_t)nq * H * W * es, ob = (size_t)nt * nq * es;
-    void *dT = nullptr, *dQ = nullptr, *dO = nullptr, *dP = nullptr;
+    rs::DevBuf<void> bT, bQ, bO;
+    rs::DevBuf<int2> bP;
     hipStream_t st = nullptr;
     int rc = RS_OK;
     auto run = [&]() -> int {
         RS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        RS_HIP(hipMalloc(&dT, tb));
-        RS_HIP(hipMalloc(&dQ, qb));
-        RS_HIP(hipMalloc(&dO, ob));
-        RS_HIP(hipMalloc(&dP, sizeof(int2) * prog.size()));
+        RS_TRY(bT.reserve(tb));
+        RS_TRY(bQ.reserve(qb));
+        RS_TRY(bO.reserve(ob));
+        RS_TRY(bP.reserve(prog.size()));
+        void *const dT = bT.get(), *const dQ = bQ.get(), *const dO = bO.get();
+        int2* const dP = bP.get();
         RS_HIP(hipMemcpyAsync(dT, templates, tb, hipMemcpyHostToDevice, st));
         RS_HIP(hipMemcpyAsync(dQ, queries, qb, hipMemcpyHostToDevice, st));
         RS_HIP(hipMemcpyAsync(dP, prog.data(), sizeof(int2) * prog.size(), hipMemcpyHostToDevice, st));
@@ -3024,12 +2948,12 @@ int rs_sad_scores(int device, int dtype, int H, int W, int max_offset, int64_t n
         if (dtype == RS_DT_F32)
             hipLaunchKernelGGL(vt_sad_float_kernel<float>, grid, dim3(64), 0, st,
                                static_cast<const float*>(dT), nt, static_cast<const float*>(dQ), nq,
-                               H, W, max_offset, static_cast<const int2*>(dP), (int)prog.size(),
+                               H, W, max_offset, dP, (int)prog.size(),
                                static_cast<float*>(dO));
         else
             hipLaunchKernelGGL(vt_sad_float_kernel<double>, grid, dim3(64), 0, st,
                                static_cast<const double*>(dT), nt, static_cast<const double*>(dQ),
-                               nq, H, W, max_offset, static_cast<const int2*>(dP), (int)prog.size(),
+                               nq, H, W, max_offset, dP, (int)prog.size(),
                                static_cast<double*>(dO));
         RS_HIP(hipGetLastError());
         RS_HIP(hipMemcpyAsync(scores, dO, ob, hipMemcpyDeviceToHost, st));
@@ -3037,8 +2961,6 @@ int rs_sad_scores(int device, int dtype, int H, int W, int max_offset, int64_t n
         return RS_OK;
     };
     rc = run();
-    for (void* p : {dT, dQ, dO, dP})
-        if (p) (void)hipFree(p);
     if (st) (void)hipStreamDestroy(st);
     return rc;
 }

@@ -303,25 +303,26 @@ constexpr size_t LDS_BUDGET = 64 * 1024;
 // ===========================================================================
 // Host side
 // ===========================================================================
+// The buffers are rs::DevBuf members (rs_common.h; untyped ones count bytes, the element
+// being es wide).  Group capacity: qCap (dQ, dIn, dBest, dBidx).
 struct rs_vtf {
     int H = 0, W = 0, M = 0, dtype = 0, device = 0;
     size_t es = 0;            // element size
-    int64_t count = 0, cap = 0;
-    void* dLib = nullptr;
+    int64_t count = 0, cap = 0;   // templates stored, and templates dLib holds
+    rs::DevBuf<void> dLib;
     hipStream_t stream = nullptr;
     SadPlan plan;
-    int2* dProg = nullptr;
+    rs::DevBuf<int2> dProg;
     // launch shape of the score kernel
     bool staged = false;      // template and query tiles fit the LDS budget
     int tsize = 0;            // elements of the padded template tile (tile_at)
     // staged queries and results
     int qCap = 0, nqStaged = 0;
-    void* dQ = nullptr;
-    void* dIn = nullptr;      // [qCap][qCap] in-batch scores
-    void* dBest = nullptr;    // [qCap]
-    int64_t* dBidx = nullptr; // [qCap]
-    size_t scoreCap = 0;      // elements
-    void* dScores = nullptr;
+    rs::DevBuf<void> dQ;
+    rs::DevBuf<void> dIn;        // [qCap][qCap] in-batch scores
+    rs::DevBuf<void> dBest;      // [qCap]
+    rs::DevBuf<int64_t> dBidx;   // [qCap]
+    rs::DevBuf<void> dScores;    // (its capacity in bytes)
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double lastMs = -1.0;
@@ -342,8 +343,6 @@ int free_handle(rs_vtf* h) {
         rs::set_error("queued work of the float library failed");
         rc = RS_ERR_HIP;
     }
-    for (void* p : {h->dLib, (void*)h->dProg, h->dQ, h->dIn, h->dBest, (void*)h->dBidx, h->dScores})
-        if (p) (void)hipFree(p);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -356,30 +355,14 @@ int ensure_lib(rs_vtf* h, int64_t want) {
     int64_t cap = h->cap > 0 ? h->cap : 1;
     while (cap < want) cap *= 2;
     const size_t tb = (size_t)h->H * h->W * h->es;
-    void* p = nullptr;
-    if (hipMalloc(&p, (size_t)cap * tb) != hipSuccess) {
-        (void)hipGetLastError();
-        rs::set_error("no device memory for %lld float templates", (long long)cap);
-        return RS_ERR_NOMEM;
-    }
+    rs::DevBuf<void> nl;   // the library is copied: the new block before the old one goes
+    RS_TRY(nl.reserve((size_t)cap * tb, "float template library"));
     if (h->count > 0) {
-        RS_HIP(hipMemcpyAsync(p, h->dLib, (size_t)h->count * tb, hipMemcpyDeviceToDevice, h->stream));
+        RS_HIP(hipMemcpyAsync(nl.get(), h->dLib.get(), (size_t)h->count * tb, hipMemcpyDeviceToDevice, h->stream));
         RS_HIP(hipStreamSynchronize(h->stream));
     }
-    if (h->dLib) RS_HIP(hipFree(h->dLib));
-    h->dLib = p;
+    h->dLib = std::move(nl);
     h->cap = cap;
-    return RS_OK;
-}
-
-int regrow(void** p, size_t bytes) {
-    if (*p) RS_HIP(hipFree(*p));
-    *p = nullptr;
-    if (hipMalloc(p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        rs::set_error("no device memory (%zu bytes)", bytes);
-        return RS_ERR_NOMEM;
-    }
     return RS_OK;
 }
 
@@ -390,26 +373,23 @@ int ensure_queries(rs_vtf* h, int nq) {
     while (cap < nq) cap *= 2;
     h->qCap = 0;
     h->nqStaged = 0;
-    RS_TRY(regrow(&h->dQ, (size_t)cap * h->H * h->W * h->es));
-    RS_TRY(regrow(&h->dIn, (size_t)cap * cap * h->es));
-    RS_TRY(regrow(&h->dBest, (size_t)cap * h->es));
-    RS_TRY(regrow(reinterpret_cast<void**>(&h->dBidx), (size_t)cap * sizeof(int64_t)));
+    RS_TRY(h->dQ.reserve((size_t)cap * h->H * h->W * h->es));
+    RS_TRY(h->dIn.reserve((size_t)cap * cap * h->es));
+    RS_TRY(h->dBest.reserve((size_t)cap * h->es));
+    RS_TRY(h->dBidx.reserve((size_t)cap));
     h->qCap = cap;
     return RS_OK;
 }
 
 int ensure_scores(rs_vtf* h, size_t elems) {
-    if (elems <= h->scoreCap) return RS_OK;
+    if (elems * h->es <= h->dScores.capacity()) return RS_OK;
     RS_HIP(hipStreamSynchronize(h->stream));
-    h->scoreCap = 0;
-    RS_TRY(regrow(&h->dScores, elems * h->es));
-    h->scoreCap = elems;
-    return RS_OK;
+    return h->dScores.reserve(elems * h->es);
 }
 
 int stage_queries(rs_vtf* h, int nq, const void* queries) {
     RS_TRY(ensure_queries(h, nq));
-    RS_HIP(hipMemcpyAsync(h->dQ, queries, (size_t)nq * h->H * h->W * h->es, hipMemcpyHostToDevice,
+    RS_HIP(hipMemcpyAsync(h->dQ.get(), queries, (size_t)nq * h->H * h->W * h->es, hipMemcpyHostToDevice,
                           h->stream));
     h->nqStaged = nq;
     return RS_OK;
@@ -437,13 +417,13 @@ int launch_scores(rs_vtf* h, const void* lib, int64_t nt, int nq, int lower, voi
     const int n_prog = (int)h->plan.prog.size();
     if (h->staged)
         hipLaunchKernelGGL((vtf_score_kernel<T, true>), grid, dim3(threads), lds, h->stream,
-                           static_cast<const T*>(lib), nt, static_cast<const T*>(h->dQ), nq, qchunk,
-                           h->H, h->W, h->M, h->tsize, qt, h->plan.depth, h->dProg, n_prog, lower, nt,
+                           static_cast<const T*>(lib), nt, static_cast<const T*>(h->dQ.get()), nq, qchunk,
+                           h->H, h->W, h->M, h->tsize, qt, h->plan.depth, h->dProg.get(), n_prog, lower, nt,
                            static_cast<T*>(out));
     else
         hipLaunchKernelGGL((vtf_score_kernel<T, false>), grid, dim3(threads), lds, h->stream,
-                           static_cast<const T*>(lib), nt, static_cast<const T*>(h->dQ), nq, qchunk,
-                           h->H, h->W, h->M, 0, qt, h->plan.depth, h->dProg, n_prog, lower, nt,
+                           static_cast<const T*>(lib), nt, static_cast<const T*>(h->dQ.get()), nq, qchunk,
+                           h->H, h->W, h->M, 0, qt, h->plan.depth, h->dProg.get(), n_prog, lower, nt,
                            static_cast<T*>(out));
     RS_HIP(hipGetLastError());
     return RS_OK;
@@ -457,12 +437,12 @@ int launch_scores(rs_vtf* h, const void* lib, int64_t nt, int nq, int lower, voi
 int launch_argmin(rs_vtf* h, int nq, int64_t nt) {
     if (h->dtype == RS_DT_F32)
         hipLaunchKernelGGL(vtf_argmin_kernel<float>, dim3(nq), dim3(256), 0, h->stream,
-                           static_cast<const float*>(h->dScores), nt, static_cast<float*>(h->dBest),
-                           h->dBidx);
+                           static_cast<const float*>(h->dScores.get()), nt, static_cast<float*>(h->dBest.get()),
+                           h->dBidx.get());
     else
         hipLaunchKernelGGL(vtf_argmin_kernel<double>, dim3(nq), dim3(256), 0, h->stream,
-                           static_cast<const double*>(h->dScores), nt,
-                           static_cast<double*>(h->dBest), h->dBidx);
+                           static_cast<const double*>(h->dScores.get()), nt,
+                           static_cast<double*>(h->dBest.get()), h->dBidx.get());
     RS_HIP(hipGetLastError());
     return RS_OK;
 }
@@ -505,8 +485,8 @@ int rs_vtf_create(int H, int W, int max_offset, int dtype, int64_t capacity, int
         RS_CHECK(lds_bytes(h, 256, 2, false) <= LDS_BUDGET, RS_ERR_ARG,
                  "window too deep for the scan's LDS stack");
         RS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        RS_HIP(hipMalloc(reinterpret_cast<void**>(&h->dProg), sizeof(int2) * h->plan.prog.size()));
-        RS_HIP(hipMemcpyAsync(h->dProg, h->plan.prog.data(), sizeof(int2) * h->plan.prog.size(),
+        RS_TRY(h->dProg.reserve(h->plan.prog.size()));
+        RS_HIP(hipMemcpyAsync(h->dProg.get(), h->plan.prog.data(), sizeof(int2) * h->plan.prog.size(),
                               hipMemcpyHostToDevice, h->stream));
         RS_HIP(hipStreamSynchronize(h->stream));
         RS_HIP(hipEventCreate(&h->ev0));
@@ -546,7 +526,7 @@ int rs_vtf_add(rs_vtf* h, int n, const void* templates, int64_t* first_index) {
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(ensure_lib(h, h->count + n));
     const size_t tb = (size_t)h->H * h->W * h->es;
-    RS_HIP(hipMemcpyAsync(static_cast<char*>(h->dLib) + (size_t)h->count * tb, templates,
+    RS_HIP(hipMemcpyAsync(static_cast<char*>(h->dLib.get()) + (size_t)h->count * tb, templates,
                           (size_t)n * tb, hipMemcpyHostToDevice, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     h->count += n;
@@ -560,7 +540,7 @@ int rs_vtf_read(rs_vtf* h, int64_t index, void* out) {
              (long long)index, (long long)h->count);
     RS_HIP(hipSetDevice(h->device));
     const size_t tb = (size_t)h->H * h->W * h->es;
-    RS_HIP(hipMemcpyAsync(out, static_cast<char*>(h->dLib) + (size_t)index * tb, tb,
+    RS_HIP(hipMemcpyAsync(out, static_cast<char*>(h->dLib.get()) + (size_t)index * tb, tb,
                           hipMemcpyDeviceToHost, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     return RS_OK;
@@ -578,8 +558,8 @@ int rs_vtf_scores(rs_vtf* h, int nq, const void* queries, int64_t t0, int64_t nt
     RS_TRY(stage_queries(h, nq, queries));
     RS_TRY(ensure_scores(h, (size_t)nq * nt));
     const size_t tb = (size_t)h->H * h->W * h->es;
-    RS_TRY(launch_scores(h, static_cast<char*>(h->dLib) + (size_t)t0 * tb, nt, nq, 0, h->dScores));
-    RS_HIP(hipMemcpyAsync(scores, h->dScores, (size_t)nq * nt * h->es, hipMemcpyDeviceToHost,
+    RS_TRY(launch_scores(h, static_cast<char*>(h->dLib.get()) + (size_t)t0 * tb, nt, nq, 0, h->dScores.get()));
+    RS_HIP(hipMemcpyAsync(scores, h->dScores.get(), (size_t)nq * nt * h->es, hipMemcpyDeviceToHost,
                           h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     return RS_OK;
@@ -600,17 +580,17 @@ int rs_vtf_scan(rs_vtf* h, int nq, const void* queries, int want_inbatch, void* 
     if (nt > 0) {
         RS_TRY(ensure_scores(h, (size_t)nq * nt));
         if (h->timing) RS_HIP(hipEventRecord(h->ev0, h->stream));
-        RS_TRY(launch_scores(h, h->dLib, nt, nq, 0, h->dScores));
+        RS_TRY(launch_scores(h, h->dLib.get(), nt, nq, 0, h->dScores.get()));
         RS_TRY(launch_argmin(h, nq, nt));
         if (h->timing) RS_HIP(hipEventRecord(h->ev1, h->stream));
-        RS_HIP(hipMemcpyAsync(best_score, h->dBest, (size_t)nq * h->es, hipMemcpyDeviceToHost,
+        RS_HIP(hipMemcpyAsync(best_score, h->dBest.get(), (size_t)nq * h->es, hipMemcpyDeviceToHost,
                               h->stream));
-        RS_HIP(hipMemcpyAsync(best_index, h->dBidx, (size_t)nq * sizeof(int64_t),
+        RS_HIP(hipMemcpyAsync(best_index, h->dBidx.get(), (size_t)nq * sizeof(int64_t),
                               hipMemcpyDeviceToHost, h->stream));
     }
     if (want_inbatch) {
-        RS_TRY(launch_scores(h, h->dQ, nq, nq, 1, h->dIn));
-        RS_HIP(hipMemcpyAsync(inbatch, h->dIn, (size_t)nq * nq * h->es, hipMemcpyDeviceToHost,
+        RS_TRY(launch_scores(h, h->dQ.get(), nq, nq, 1, h->dIn.get()));
+        RS_HIP(hipMemcpyAsync(inbatch, h->dIn.get(), (size_t)nq * nq * h->es, hipMemcpyDeviceToHost,
                               h->stream));
     }
     RS_HIP(hipStreamSynchronize(h->stream));
@@ -641,8 +621,8 @@ int rs_vtf_append_staged(rs_vtf* h, int n, const int32_t* which, int64_t* first_
     for (int i = 0; i < n;) {
         int run = 1;   // consecutive staged queries go as one copy
         while (i + run < n && which[i + run] == which[i] + run) ++run;
-        RS_HIP(hipMemcpyAsync(static_cast<char*>(h->dLib) + (size_t)(h->count + i) * tb,
-                              static_cast<char*>(h->dQ) + (size_t)which[i] * tb, (size_t)run * tb,
+        RS_HIP(hipMemcpyAsync(static_cast<char*>(h->dLib.get()) + (size_t)(h->count + i) * tb,
+                              static_cast<char*>(h->dQ.get()) + (size_t)which[i] * tb, (size_t)run * tb,
                               hipMemcpyDeviceToDevice, h->stream));
         i += run;
     }

@@ -229,6 +229,8 @@ int vo_check_params(int im_h, int im_w, const rs_vo_params* p) {
 
 }  // namespace
 
+// The buffers are rs::DevBuf / rs::PinnedBuf members (rs_common.h).  Group capacities, in
+// frames: cap (dProf, dTab, hTab) and frameCap (dFrames, hFrames).
 struct rs_vo {
     int device = 0, H = 0, W = 0, S = 0;
     rs_vo_params p{};
@@ -237,9 +239,11 @@ struct rs_vo {
     bool same = false;
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    uint8_t *dFrames = nullptr, *hFrames = nullptr;
+    rs::DevBuf<uint8_t> dFrames;
+    rs::PinnedBuf<uint8_t> hFrames;
     int frameCap = 0;
-    uint32_t *dProf = nullptr, *dTab = nullptr, *hTab = nullptr, *dCarry = nullptr;
+    rs::DevBuf<uint32_t> dProf, dTab, dCarry;
+    rs::PinnedBuf<uint32_t> hTab;
     int cap = 0;
     bool hasCarry = false, timing = false, timed = false;
     float ms[2] = {0, 0};
@@ -252,26 +256,19 @@ int vo_grow(rs_vo* h, int n, bool staging) {
     if (n > h->cap) {
         int cap = h->cap > 0 ? h->cap : 1;
         while (cap < n) cap *= 2;
-        if (h->dProf) RS_HIP(hipFree(h->dProf));
-        if (h->dTab) RS_HIP(hipFree(h->dTab));
-        if (h->hTab) RS_HIP(hipHostFree(h->hTab));
-        h->dProf = h->dTab = h->hTab = nullptr;
         h->cap = 0;
-        RS_HIP(hipMalloc(&h->dProf, sizeof(uint32_t) * ps * cap));
-        RS_HIP(hipMalloc(&h->dTab, sizeof(uint32_t) * nt * cap));
-        RS_HIP(hipHostMalloc(&h->hTab, sizeof(uint32_t) * nt * cap, hipHostMallocDefault));
+        RS_TRY(h->dProf.reserve(ps * cap));
+        RS_TRY(h->dTab.reserve(nt * cap));
+        RS_TRY(h->hTab.reserve(nt * cap, hipHostMallocDefault));
         h->cap = cap;
     }
     if (staging && n > h->frameCap) {
         int cap = h->frameCap > 0 ? h->frameCap : 1;
         while (cap < n) cap *= 2;
         const size_t fb = (size_t)h->H * h->W;
-        if (h->dFrames) RS_HIP(hipFree(h->dFrames));
-        if (h->hFrames) RS_HIP(hipHostFree(h->hFrames));
-        h->dFrames = h->hFrames = nullptr;
         h->frameCap = 0;
-        RS_HIP(hipMalloc(&h->dFrames, fb * cap));
-        RS_HIP(hipHostMalloc(&h->hFrames, fb * cap, hipHostMallocDefault));
+        RS_TRY(h->dFrames.reserve(fb * cap));
+        RS_TRY(h->hFrames.reserve(fb * cap, hipHostMallocDefault));
         h->frameCap = cap;
     }
     return RS_OK;
@@ -290,24 +287,24 @@ int vo_launch(rs_vo* h, int n, const uint8_t* src, bool timed) {
             tiles = std::max(tiles, (G + VO_GROUPS - 1) / VO_GROUPS);
         }
         hipLaunchKernelGGL(vo_profile_kernel, dim3(n, tiles, nreg), dim3(VO_THREADS), 0, h->stream, src,
-                           fb, h->W, h->reg[0], h->reg[1], (int)h->same, h->dProf, ps);
+                           fb, h->W, h->reg[0], h->reg[1], (int)h->same, h->dProf.get(), ps);
     } else {
         const int wmax = std::max(h->wd[0], h->wd[1]);
         hipLaunchKernelGGL(vo_profile_bytes_kernel, dim3(n, (wmax + VO_THREADS - 1) / VO_THREADS, nreg),
                            dim3(VO_THREADS), 0, h->stream, src, fb, h->W, h->reg[0], h->reg[1],
-                           (int)h->same, h->dProf, ps);
+                           (int)h->same, h->dProf.get(), ps);
     }
     RS_HIP(hipGetLastError());
     if (timed) RS_HIP(hipEventRecord(h->ev[1], h->stream));
-    const uint32_t* carry = h->hasCarry ? h->dCarry : nullptr;
+    const uint32_t* carry = h->hasCarry ? h->dCarry.get() : nullptr;
     const int wmax = std::max(h->wd[0], h->wd[1]);
     if (wmax <= VO_LDS_WIDTH)
         hipLaunchKernelGGL(vo_shift_kernel<true>, dim3(n, nreg), dim3(VO_THREADS),
-                           sizeof(uint32_t) * 2 * wmax, h->stream, h->dProf, ps, carry, h->wd[0],
-                           h->wd[1], h->S, (int)h->same, h->dTab);
+                           sizeof(uint32_t) * 2 * wmax, h->stream, h->dProf.get(), ps, carry, h->wd[0],
+                           h->wd[1], h->S, (int)h->same, h->dTab.get());
     else
         hipLaunchKernelGGL(vo_shift_kernel<false>, dim3(n, nreg), dim3(VO_THREADS), 0, h->stream,
-                           h->dProf, ps, carry, h->wd[0], h->wd[1], h->S, (int)h->same, h->dTab);
+                           h->dProf.get(), ps, carry, h->wd[0], h->wd[1], h->S, (int)h->same, h->dTab.get());
     RS_HIP(hipGetLastError());
     if (timed) RS_HIP(hipEventRecord(h->ev[2], h->stream));
     return RS_OK;
@@ -348,13 +345,13 @@ int rs_vo_create(int im_h, int im_w, const rs_vo_params* params, int device, rs_
     h->same = std::memcmp(&h->reg[0], &h->reg[1], sizeof(VoRegion)) == 0;
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
-    if (e == hipSuccess) e = hipMalloc(&h->dCarry, sizeof(uint32_t) * ((size_t)h->wd[0] + h->wd[1]));
     if (e != hipSuccess) {
-        rs::set_error("odometer stream/event/buffer creation failed: %s", hipGetErrorString(e));
+        rs::set_error("odometer stream/event creation failed: %s", hipGetErrorString(e));
         rs_vo_destroy(h);
         return RS_ERR_HIP;
     }
-    const int s = vo_grow(h, 1, true);
+    int s = h->dCarry.reserve((size_t)h->wd[0] + h->wd[1]);
+    if (s == RS_OK) s = vo_grow(h, 1, true);
     if (s != RS_OK) {
         rs_vo_destroy(h);
         return s;
@@ -368,14 +365,10 @@ int rs_vo_destroy(rs_vo* h) {
     (void)hipSetDevice(h->device);
     // queued work that failed after a call returned is reported here, not dropped
     const hipError_t se = h->stream ? hipStreamSynchronize(h->stream) : hipSuccess;
-    for (void* p : {(void*)h->dFrames, (void*)h->dProf, (void*)h->dTab, (void*)h->dCarry})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)h->hFrames, (void*)h->hTab})
-        if (p) (void)hipHostFree(p);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;  // (the buffers go with their members)
     RS_CHECK(se == hipSuccess, RS_ERR_HIP, "work queued before rs_vo_destroy failed: %s", hipGetErrorString(se));
     return RS_OK;
 }
@@ -411,16 +404,16 @@ int rs_vo_run(rs_vo* h, int nf, const uint8_t* frames, double* deltas, uint32_t*
         const int n = std::min(chunk, nf - c0);
         const uint8_t* src = frames + fb * c0;
         if (!on_device) {
-            std::memcpy(h->hFrames, src, fb * n);
-            RS_HIP(hipMemcpyAsync(h->dFrames, h->hFrames, fb * n, hipMemcpyHostToDevice, h->stream));
-            src = h->dFrames;
+            std::memcpy(h->hFrames.get(), src, fb * n);
+            RS_HIP(hipMemcpyAsync(h->dFrames.get(), h->hFrames.get(), fb * n, hipMemcpyHostToDevice, h->stream));
+            src = h->dFrames.get();
         }
         const bool first = !h->hasCarry;  // frame c0 has no predecessor
         RS_TRY(vo_launch(h, n, src, timed));
-        RS_HIP(hipMemcpyAsync(h->dCarry, h->dProf + ps * (n - 1), sizeof(uint32_t) * ps,
+        RS_HIP(hipMemcpyAsync(h->dCarry.get(), h->dProf.get() + ps * (n - 1), sizeof(uint32_t) * ps,
                               hipMemcpyDeviceToDevice, h->stream));
         h->hasCarry = true;
-        RS_HIP(hipMemcpyAsync(h->hTab, h->dTab, sizeof(uint32_t) * 2 * nt * n, hipMemcpyDeviceToHost,
+        RS_HIP(hipMemcpyAsync(h->hTab.get(), h->dTab.get(), sizeof(uint32_t) * 2 * nt * n, hipMemcpyDeviceToHost,
                               h->stream));
         RS_HIP(hipStreamSynchronize(h->stream));
         if (timed) {
@@ -429,8 +422,8 @@ int rs_vo_run(rs_vo* h, int nf, const uint8_t* frames, double* deltas, uint32_t*
             h->timed = true;
         }
         if (profiles)
-            RS_HIP(hipMemcpy(profiles + ps * c0, h->dProf, sizeof(uint32_t) * ps * n, hipMemcpyDeviceToHost));
-        if (tables) std::memcpy(tables + 2 * nt * c0, h->hTab, sizeof(uint32_t) * 2 * nt * n);
+            RS_HIP(hipMemcpy(profiles + ps * c0, h->dProf.get(), sizeof(uint32_t) * ps * n, hipMemcpyDeviceToHost));
+        if (tables) std::memcpy(tables + 2 * nt * c0, h->hTab.get(), sizeof(uint32_t) * 2 * nt * n);
         for (int i = 0; i < n; ++i) {
             double* d = deltas + 2 * (size_t)(c0 + i);
             if (i == 0 && first) {
@@ -438,7 +431,7 @@ int rs_vo_run(rs_vo* h, int nf, const uint8_t* frames, double* deltas, uint32_t*
                 d[1] = 0.0;
                 continue;
             }
-            const uint32_t* t = h->hTab + 2 * nt * i;
+            const uint32_t* t = h->hTab.get() + 2 * nt * i;
             int st = 0, sr = 0;
             double bt = 0.0, br = 0.0;
             vo_select(h->S, h->wd[0], h->rows[0], t, &st, &bt);

@@ -1,0 +1,226 @@
+// Stand-alone host test of rs::DevBuf / rs::PinnedBuf (rs_common.h) and of the growth idiom
+// the handles write with them.  It links its own definitions of the four allocation
+// functions -- malloc-backed, counting live blocks, able to refuse the k-th allocation --
+// in place of rs_common.cpp, so it needs no GPU; tests/test_host_buffers.py builds it with
+// -fsanitize=address,undefined and runs it.  Exit status 0: every check held.
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "rs_common.h"
+
+namespace {
+
+int g_live = 0;       // blocks allocated and not yet released
+int g_allocs = 0;     // allocation calls so far
+int g_frees = 0;      // release calls so far
+int g_fail_at = -1;   // the allocation call (0-based, counted from arm()) to refuse
+int g_checks = 0, g_failed = 0;
+char g_error[256] = {0};
+
+void arm(int k) { g_allocs = 0; g_fail_at = k; }
+
+hipError_t test_alloc(void** ptr, size_t bytes) {
+    *ptr = nullptr;
+    if (g_allocs++ == g_fail_at) return hipErrorOutOfMemory;
+    *ptr = std::malloc(bytes ? bytes : 1);
+    std::memset(*ptr, 0xA5, bytes);   // the whole block is writable
+    ++g_live;
+    return hipSuccess;
+}
+
+hipError_t test_free(void* ptr) {
+    std::free(ptr);   // (a second release of one block is the sanitizer's to report)
+    --g_live;
+    ++g_frees;
+    return hipSuccess;
+}
+
+#define CHECK(cond)                                                        \
+    do {                                                                   \
+        ++g_checks;                                                        \
+        if (!(cond)) {                                                     \
+            ++g_failed;                                                    \
+            std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond); \
+        }                                                                  \
+    } while (0)
+
+}  // namespace
+
+namespace rs {
+
+void set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_error, sizeof(g_error), fmt, ap);
+    va_end(ap);
+}
+void clear_error() { g_error[0] = 0; }
+
+hipError_t dev_alloc(void** ptr, size_t bytes) { return test_alloc(ptr, bytes); }
+hipError_t dev_free(void* ptr) { return test_free(ptr); }
+hipError_t pinned_alloc(void** ptr, void** dev, size_t bytes, unsigned) {
+    const hipError_t e = test_alloc(ptr, bytes);
+    *dev = *ptr;
+    return e;
+}
+hipError_t pinned_free(void* ptr) { return test_free(ptr); }
+
+}  // namespace rs
+
+// HIP's error text: the one HIP symbol the header's failure path refers to.
+extern "C" const char* hipGetErrorString(hipError_t e) {
+    return e == hipErrorOutOfMemory ? "out of memory" : "error";
+}
+
+namespace {
+
+// A group of buffers under one capacity, grown the way the handles grow theirs: the
+// capacity is zero from before the first buffer is touched until the last has succeeded.
+struct Group {
+    int cap = 0;
+    rs::DevBuf<uint32_t> a;
+    rs::PinnedBuf<unsigned long long> b;
+    rs::DevBuf<void> c;
+    rs::DevBuf<uint8_t> d;
+};
+constexpr int GROUP_BUFS = 4;
+
+int grow(Group* g, int n) {
+    if (n <= g->cap) return RS_OK;
+    int cap = g->cap > 0 ? g->cap : 16;
+    while (cap < n) cap *= 2;
+    g->cap = 0;
+    RS_TRY(g->a.reserve((size_t)cap));
+    RS_TRY(g->b.reserve((size_t)cap, hipHostMallocDefault));
+    RS_TRY(g->c.reserve(3 * (size_t)cap));
+    RS_TRY(g->d.reserve(64 * (size_t)cap));
+    g->cap = cap;
+    return RS_OK;
+}
+
+void check_group(const Group& g) {   // a non-zero capacity: every buffer holds that much
+    if (g.cap == 0) return;
+    CHECK(g.a.get() && g.a.capacity() >= (size_t)g.cap);
+    CHECK(g.b.get() && g.b.dev() && g.b.capacity() >= (size_t)g.cap);
+    CHECK(g.c.get() && g.c.capacity() >= 3 * (size_t)g.cap);
+    CHECK(g.d.get() && g.d.capacity() >= 64 * (size_t)g.cap);
+    g.a.get()[g.cap - 1] = 1u;       // the last element is the block's (the sanitizer checks)
+    g.b.get()[g.cap - 1] = 1ull;
+    g.d.get()[64 * (size_t)g.cap - 1] = 1;
+}
+
+void test_reserve() {
+    arm(-1);
+    rs::DevBuf<uint32_t> b;
+    CHECK(b.get() == nullptr && b.capacity() == 0);
+    CHECK(b.reserve(100) == RS_OK && b.get() && b.capacity() == 100 && g_live == 1);
+    uint32_t* const p = b.get();
+    const int allocs = g_allocs;
+    CHECK(b.reserve(100) == RS_OK && b.reserve(1) == RS_OK && b.reserve(0) == RS_OK);
+    CHECK(g_allocs == allocs && b.get() == p && b.capacity() == 100);   // within capacity: nothing
+    CHECK(b.reserve(101) == RS_OK && b.capacity() == 101 && g_live == 1);  // exactly n, old block gone
+    b.reset();
+    CHECK(b.get() == nullptr && b.capacity() == 0 && g_live == 0);
+    b.reset();
+    CHECK(g_live == 0);
+
+    rs::DevBuf<void> v;   // untyped: bytes
+    CHECK(v.reserve(7) == RS_OK && v.capacity() == 7);
+    static_cast<char*>(v.get())[6] = 0;
+
+    rs::PinnedBuf<double> h;
+    CHECK(h.reserve(8, hipHostMallocMapped | hipHostMallocCoherent) == RS_OK);
+    CHECK(h.get() && h.dev() == h.get() && h.capacity() == 8 && g_live == 2);
+    h.get()[7] = 1.0;
+    h.reset();
+    CHECK(h.get() == nullptr && h.dev() == nullptr && h.capacity() == 0 && g_live == 1);
+}
+
+void test_failed_reserve() {
+    rs::DevBuf<uint64_t> b;
+    rs::PinnedBuf<uint8_t> h;
+    arm(-1);
+    CHECK(b.reserve(10) == RS_OK && h.reserve(10, hipHostMallocDefault) == RS_OK && g_live == 2);
+    arm(0);
+    rs::clear_error();
+    CHECK(b.reserve(20, "test buffer") == RS_ERR_NOMEM);
+    CHECK(b.get() == nullptr && b.capacity() == 0 && g_live == 1);   // the old block went first
+    CHECK(std::strstr(g_error, "test buffer") && std::strstr(g_error, "out of memory"));
+    arm(0);
+    CHECK(h.reserve(20, hipHostMallocDefault) == RS_ERR_NOMEM);
+    CHECK(h.get() == nullptr && h.dev() == nullptr && h.capacity() == 0 && g_live == 0);
+    arm(-1);
+    CHECK(b.reserve(20) == RS_OK && b.capacity() == 20 && g_live == 1);   // and grows again
+}
+
+void test_group_growth() {
+    for (int first = 0; first < 2; ++first)          // from empty, and from a grown group
+        for (int k = 0; k < GROUP_BUFS; ++k) {
+            Group g;
+            arm(-1);
+            if (first) {
+                CHECK(grow(&g, 20) == RS_OK && g.cap == 32);
+                check_group(g);
+            }
+            const int want = first ? 70 : 20;
+            arm(k);
+            CHECK(grow(&g, want) == RS_ERR_NOMEM);
+            CHECK(g.cap == 0);
+            // no member points at a released block: each is empty or holds what it says
+            CHECK((g.a.get() == nullptr) == (g.a.capacity() == 0));
+            CHECK((g.b.get() == nullptr) == (g.b.capacity() == 0));
+            CHECK((g.c.get() == nullptr) == (g.c.capacity() == 0));
+            CHECK((g.d.get() == nullptr) == (g.d.capacity() == 0));
+            int held = 0;
+            for (const bool has : {g.a.get() != nullptr, g.b.get() != nullptr, g.c.get() != nullptr,
+                                   g.d.get() != nullptr})
+                held += has;
+            CHECK(g_live == held);
+            arm(-1);
+            CHECK(grow(&g, 5) == RS_OK && g.cap == 16);   // a small call after the failure
+            check_group(g);
+            CHECK(grow(&g, want) == RS_OK && g.cap >= want && g_live == GROUP_BUFS);
+            check_group(g);
+        }
+    CHECK(g_live == 0);
+}
+
+void test_move() {
+    arm(-1);
+    rs::DevBuf<int> a, b;
+    CHECK(a.reserve(4) == RS_OK && b.reserve(9) == RS_OK && g_live == 2);
+    int* const pb = b.get();
+    const int frees = g_frees;
+    a = std::move(b);   // copy-on-grow: a fresh buffer replaces the old one
+    CHECK(g_frees == frees + 1 && g_live == 1);   // the target's old block, exactly once
+    CHECK(a.get() == pb && a.capacity() == 9 && b.get() == nullptr && b.capacity() == 0);
+    rs::DevBuf<int>& self = a;
+    a = std::move(self);
+    CHECK(a.get() == pb && g_live == 1);
+    rs::DevBuf<int> c(std::move(a));
+    CHECK(c.get() == pb && a.get() == nullptr && g_frees == frees + 1);
+
+    rs::PinnedBuf<int> x, y;
+    CHECK(x.reserve(4, hipHostMallocDefault) == RS_OK && y.reserve(9, hipHostMallocDefault) == RS_OK);
+    int* const py = y.get();
+    const int frees2 = g_frees;
+    x = std::move(y);
+    CHECK(g_frees == frees2 + 1 && x.get() == py && x.dev() == py && x.capacity() == 9);
+    CHECK(y.get() == nullptr && y.dev() == nullptr && y.capacity() == 0);
+}
+
+}  // namespace
+
+int main() {
+    test_reserve();
+    CHECK(g_live == 0);
+    test_failed_reserve();
+    CHECK(g_live == 0);
+    test_group_growth();
+    test_move();
+    CHECK(g_live == 0);   // at exit nothing is live
+    std::printf("%d checks, %d failed, %d live\n", g_checks, g_failed, g_live);
+    return g_failed == 0 && g_live == 0 ? 0 : 1;
+}

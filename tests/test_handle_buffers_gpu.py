@@ -1,0 +1,160 @@
+"""The handles' device and pinned buffers (rs::DevBuf / rs::PinnedBuf members) through their
+growth sites, on a 64 x 32 library of 130 templates (three blocks, the last partial), dense
+and with RS_VT_PRUNE=force: one handle's query buffers grown twice by match_batch, its
+stream buffers by host and device-resident match_stream, its candidate, matrix and index
+buffers by a sequential batch that appends; every index and score against the C oracle for
+the library as it stood at that call, and the batch matched before the streams matched
+again after them bit for bit (the streams read their own view of the query forms and leave
+the batch's alone).  Then every handle kind created and destroyed 20 times, and a library
+too large for the device refused with MemoryError, after which a fresh handle matches."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import view_templates as V
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+T, THR = 130, 45000
+
+# RS_VT_PRUNE is the child's environment, as in test_wait_paths_gpu.py
+CHILD = r'''
+import sys
+import numpy as np
+sys.path.insert(0, %(root)r)
+from pyratslam_amd import _lib
+from pyratslam_amd.view_templates import ViewTemplates
+d = np.load(%(inp)r)
+h = ViewTemplates._from_shape((64, 32), %(thr)d)
+assert h.scan_form() == %(form)r, h.scan_form()
+h.add(d['lib'])
+out = {}
+def keep(name, idx, score):
+    out[name + '_idx'], out[name + '_score'] = idx, score
+i, s, _ = h.match_templates(d['q300'][:70], mode=0); keep('s1', i, s)
+keep('s2', *h.match_stream(d['qs']))
+buf = _lib.DeviceBuffer(d['qd'].nbytes).upload(d['qd'])
+keep('s3', *h.match_stream((3, 40, buf)))
+buf.close()
+i, s, _ = h.match_templates(d['q300'][:70], mode=0); keep('s4', i, s)
+i, s, _ = h.match_templates(d['q300'], mode=0); keep('s5', i, s)
+i, s, n = h.match_templates(d['q20'], mode=1); keep('s6', i, s)
+out['s6_new'] = n
+out['count'] = np.int64(h.count())
+h.close()
+np.savez(%(out)r, **out)
+'''
+
+
+@pytest.fixture(scope='module')
+def built():
+    from pyratslam_amd import _build
+    _build.build()
+
+
+def data():
+    lib = V.synthetic_library(T, 64, 32, seed=301)
+    q300, _ = V.synthetic_queries(lib, 300, seed=302, hit_frac=0.8)
+    qs, _ = V.synthetic_queries(lib, 120, seed=303, hit_frac=0.8)
+    qd, _ = V.synthetic_queries(lib, 120, seed=304, hit_frac=0.8)
+    q20, _ = V.synthetic_queries(lib, 20, seed=305, hit_frac=0.5)
+    return dict(lib=lib, q300=q300, qs=qs.reshape(3, 40, 64, 32), qd=qd.reshape(3, 40, 64, 32), q20=q20)
+
+
+def oracle_sequential(lib, queries):
+    """ViewTemplates.match query by query through the C oracle: (index, score, is_new)."""
+    from oracle import c_oracle as C
+    lib = list(lib)
+    idx, score, new = [], [], []
+    for q in queries:
+        s, i = C.vt_best(np.stack(lib), q[None])
+        miss = float(s[0]) > THR
+        idx.append(len(lib) if miss else int(i[0]))
+        score.append(int(s[0]))
+        new.append(miss)
+        if miss:
+            lib.append(q)
+    return np.array(idx), np.array(score, dtype=np.uint64), np.array(new)
+
+
+@pytest.mark.parametrize('prune', [None, 'force'], ids=['dense', 'pruned'])
+def test_growth_across_capacities_and_the_stream_view(built, tmp_path, prune):
+    from oracle import c_oracle as C
+    d = data()
+    inp, outp = str(tmp_path / 'in.npz'), str(tmp_path / 'out.npz')
+    np.savez(inp, **d)
+    env = {k: v for k, v in os.environ.items() if k != 'RS_VT_PRUNE'}
+    if prune:
+        env['RS_VT_PRUNE'] = prune
+    # (unset: the pruned form, which prunes only large calls -- these all take the dense launch)
+    script = CHILD % {'root': ROOT, 'inp': inp, 'out': outp, 'thr': THR, 'form': 'plane-pruned'}
+    subprocess.run([sys.executable, '-c', script], env=env, check=True, timeout=120)
+    r = np.load(outp)
+
+    def check(name, queries):
+        score, idx = C.vt_best(d['lib'], queries.reshape(-1, 64, 32))
+        got_i, got_s = r[name + '_idx'].reshape(-1), r[name + '_score'].reshape(-1)
+        print(name, 'mismatches: index', int((got_i != idx).sum()), 'score', int((got_s != score).sum()))
+        assert np.array_equal(got_i, idx), name
+        assert np.array_equal(got_s, score), name
+
+    check('s1', d['q300'][:70])
+    check('s2', d['qs'])
+    check('s3', d['qd'])
+    check('s4', d['q300'][:70])
+    assert np.array_equal(r['s4_idx'], r['s1_idx']) and np.array_equal(r['s4_score'], r['s1_score'])
+    check('s5', d['q300'])
+    idx, score, new = oracle_sequential(d['lib'], d['q20'])
+    assert 0 < new.sum() < len(new)
+    assert np.array_equal(r['s6_idx'], idx)
+    assert np.array_equal(r['s6_score'], score)
+    assert np.array_equal(r['s6_new'], new)
+    assert int(r['count']) == T + int(new.sum())
+
+
+def test_create_and_destroy_every_handle_kind_20_times(built):
+    """close() raises unless rs_*_destroy returned RS_OK."""
+    import pyratslam_amd.view_templates as vt
+    from pyratslam_amd.posecell_network import PoseCellNetwork
+    from pyratslam_amd.visual_odometer import SimpleVisualOdometer
+    lib = V.synthetic_library(T, 64, 32, seed=301)
+    q, _ = V.synthetic_queries(lib, 4, seed=306, hit_frac=1.0)
+    frames = np.random.default_rng(307).integers(0, 256, size=(3, 48, 64), dtype=np.uint8)
+    for k in range(20):
+        h = vt.ViewTemplates._from_shape((64, 32), THR)          # rs_vt
+        h.add(lib)
+        idx, _, new = h.match_templates(q, mode=0)
+        assert not new.any() and idx.shape == (4,)
+        h.close()
+        f = vt.ViewTemplates._from_shape((64, 32), 1e9)          # rs_vtf, made by the first float batch
+        fq = q.astype(np.float32)
+        fi, _, fn = f.match_templates(fq)
+        assert f._vtf is not None and fn[0] and f.count() == int(fn.sum())
+        f.close()
+        vo = SimpleVisualOdometer()                              # rs_vo
+        assert vo.run(frames).shape == (3, 2)
+        vo.close()
+        pc = PoseCellNetwork((32, 32, 18), precision='float32' if k % 2 == 0 else 'float64')   # rs_pc
+        pc.inject(1.0, (5, 6, 7))
+        assert len(pc.update((0.2, 0.01))) == 3
+        pc.close()
+
+
+def test_a_refused_allocation_is_a_memory_error(built):
+    """2^40 slots of 2 KiB: refused by the runtime, before any kernel."""
+    from oracle import c_oracle as C
+    import pyratslam_amd.view_templates as vt
+    with pytest.raises(MemoryError):
+        vt.ViewTemplates._from_shape((64, 32), THR, capacity=1 << 40)
+    lib = V.synthetic_library(T, 64, 32, seed=301)
+    q, _ = V.synthetic_queries(lib, 4, seed=308, hit_frac=1.0)
+    h = vt.ViewTemplates._from_shape((64, 32), THR)
+    h.add(lib)
+    idx, score, new = h.match_templates(q, mode=0)
+    want_s, want_i = C.vt_best(lib, q)
+    assert np.array_equal(idx, want_i) and np.array_equal(score, want_s) and not new.any()
+    h.close()

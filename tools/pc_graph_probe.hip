@@ -73,7 +73,7 @@ int main(int argc, char** argv) {
     // the same n steps captured (ring control uploaded once, outside the graph)
     if (pc_grow_steps(h, n) != RS_OK) return 1;
     pc_pack_ctl(h, n, ox.data(), oy.data(), f.data(), zf.data());
-    CK(hipMemcpy(h->dCtl, h->hCtl, h->ctlStride * n, hipMemcpyHostToDevice));
+    CK(hipMemcpy(h->dCtl.get(), h->hCtl.get(), h->ctlStride * n, hipMemcpyHostToDevice));
     hipGraph_t g;
     hipGraphExec_t ge;
     CK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeGlobal));
@@ -81,7 +81,7 @@ int main(int argc, char** argv) {
         const PcCtlRing c = make_ctl_ring(h, s);
         if (pc_launch_step<float, PcCtlRing>(h, step_out(h, s), &c, -1) != RS_OK) return 1;
     }
-    hipLaunchKernelGGL(pc_res_export, dim3(n), dim3(64), 0, h->stream, h->dRes, n, h->hResDev);
+    hipLaunchKernelGGL(pc_res_export, dim3(n), dim3(64), 0, h->stream, h->dRes.get(), n, h->hRes.dev());
     CK(hipStreamEndCapture(h->stream, &g));
     fprintf(stderr, "captured\n");
     double ti = now_us();
@@ -100,7 +100,7 @@ int main(int argc, char** argv) {
             const PcCtlRing c = make_ctl_ring(h, s);
             if (pc_launch_step<float, PcCtlRing>(h, step_out(h, s), &c, -1) != RS_OK) return 1;
         }
-        hipLaunchKernelGGL(pc_res_export, dim3(n), dim3(64), 0, h->stream, h->dRes, n, h->hResDev);
+        hipLaunchKernelGGL(pc_res_export, dim3(n), dim3(64), 0, h->stream, h->dRes.get(), n, h->hRes.dev());
     }
     CK(hipStreamSynchronize(h->stream));
     const double ring = (now_us() - t0) / (reps * n);

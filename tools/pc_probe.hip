@@ -245,10 +245,10 @@ int main(int argc, char** argv) {
         make_ctl_halo(h, 0, ox.data(), oy.data(), f.data(), zf.data(), &c);
         CK(hipEventRecord(c0, h->stream));
         for (int i = 0; i < reps; ++i)
-            hf_launch<false>(h->TH, g, h->stream, (const float*)h->dP, hf_pack(X, Y),
+            hf_launch<false>(h->TH, g, h->stream, (const float*)h->dP.get(), hf_pack(X, Y),
                                hf_pack(h->cgx, g.x), hf_pack(c.ux, c.uy), hf_pack(c.uw, c.uh), hf_magic(h->cgx),
-                               hf_magic(c.uh), h->dPart, h->nPart, (float*)h->dQ, h->dPart + h->nPart, h->dRes, h->dRes + RES_SLOTS,
-                               (const float*)h->dFilt, h->nf, c, h->kf, nullptr);
+                               hf_magic(c.uh), h->dPart.get(), h->nPart, (float*)h->dQ.get(), h->dPart.get() + h->nPart, h->dRes.get(), h->dRes.get() + RES_SLOTS,
+                               (const float*)h->dFilt.get(), h->nf, c, h->kf, nullptr);
         CK(hipEventRecord(c1, h->stream));
         CK(hipEventSynchronize(c1));
         CK(hipEventElapsedTime(&t, c0, c1));
@@ -280,8 +280,8 @@ int main(int argc, char** argv) {
         CK(hipEventRecord(c0, h->stream));
         for (int i = 0; i < reps; ++i)
             hipLaunchKernelGGL((pc_excite_cols<float, CO_TX, CO_TY, CO_NW, THF, false>), g, b, 0, h->stream,
-                               (const float*)h->dP, X, Y, TH, h->cgx, h->cgy, (int)g.x, (float*)h->dQ,
-                               h->dPart, h->dRes, h->coKC, h->kf);
+                               (const float*)h->dP.get(), X, Y, TH, h->cgx, h->cgy, (int)g.x, (float*)h->dQ.get(),
+                               h->dPart.get(), h->dRes.get(), h->coKC, h->kf);
         CK(hipEventRecord(c1, h->stream));
         CK(hipEventSynchronize(c1));
         CK(hipEventElapsedTime(&t, c0, c1));
@@ -289,8 +289,8 @@ int main(int argc, char** argv) {
         CK(hipEventRecord(c0, h->stream));
         for (int i = 0; i < reps; ++i)
             hipLaunchKernelGGL((pc_path_cols<float, CO_TX, CO_TY, CO_NW, THF, false, PcCtlRing>), g, bp, 0, h->stream,
-                               (const float*)h->dQ, X, Y, TH, h->cgx, h->cgy, (int)g.x, (float*)h->dP, h->dPart,
-                               h->nPart, (const float*)h->dFilt, h->nf, ctl, h->dRes, (float*)nullptr,
+                               (const float*)h->dQ.get(), X, Y, TH, h->cgx, h->cgy, (int)g.x, (float*)h->dP.get(), h->dPart.get(),
+                               h->nPart, (const float*)h->dFilt.get(), h->nf, ctl, h->dRes.get(), (float*)nullptr,
                                (unsigned*)nullptr, h->coKC);
         CK(hipEventRecord(c1, h->stream));
         CK(hipEventSynchronize(c1));
@@ -325,7 +325,7 @@ int main(int argc, char** argv) {
     CK(hipEventRecord(e0, h->stream));
     for (int i = 0; i < reps; ++i)
         hipLaunchKernelGGL((pc_excite_rows<float, 64>), g, dim3(RT_NT), 0, h->stream,
-                           (const float*)h->dP, (float*)h->dQ, h->dPart, h->dRes, X, Y, TH, h->kf);
+                           (const float*)h->dP.get(), (float*)h->dQ.get(), h->dPart.get(), h->dRes.get(), X, Y, TH, h->kf);
     CK(hipEventRecord(e1, h->stream));
     CK(hipEventSynchronize(e1));
     CK(hipEventElapsedTime(&t, e0, e1));
@@ -333,8 +333,8 @@ int main(int argc, char** argv) {
     CK(hipEventRecord(e0, h->stream));
     for (int i = 0; i < reps; ++i)
         hipLaunchKernelGGL((pc_path_rows<float, 64, PcCtlRing>), g, dim3(RT_NT), 0, h->stream,
-                           (const float*)h->dQ, (float*)h->dP, h->dPart, h->nPart,
-                           (const float*)h->dFilt, h->nf, ctl, h->dRes, (float*)nullptr,
+                           (const float*)h->dQ.get(), (float*)h->dP.get(), h->dPart.get(), h->nPart,
+                           (const float*)h->dFilt.get(), h->nf, ctl, h->dRes.get(), (float*)nullptr,
                            (unsigned*)nullptr, X, Y, TH);
     CK(hipEventRecord(e1, h->stream));
     CK(hipEventSynchronize(e1));

@@ -83,9 +83,9 @@ int main(int argc, char** argv) {
         }
         if (pc_grow_steps(h, steps) != RS_OK) return 1;   // the argmax slots exist now
         const size_t nres = sizeof(unsigned long long) * RES_SLOTS * h->resCap;
-        CK(hipMemsetAsync(h->dQ, v == 1 ? 0xFF : 0, h->n * h->esz, h->stream));
-        CK(hipMemsetAsync(h->dPart, v == 2 ? 0xFF : 0, sizeof(double) * h->nPart, h->stream));
-        CK(hipMemsetAsync(h->dRes, v == 3 ? 0xFF : 0, nres, h->stream));
+        CK(hipMemsetAsync(h->dQ.get(), v == 1 ? 0xFF : 0, h->n * h->esz, h->stream));
+        CK(hipMemsetAsync(h->dPart.get(), v == 2 ? 0xFF : 0, sizeof(double) * h->nPart, h->stream));
+        CK(hipMemsetAsync(h->dRes.get(), v == 3 ? 0xFF : 0, nres, h->stream));
         CK(hipStreamSynchronize(h->stream));
         rs_pc_inject(h, 1.0, X / 2, Y / 2, TH / 2);
         for (int s = 0; s < steps; ++s)
@@ -93,7 +93,7 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "update: %s\n", rs_last_error());
                 return 1;
             }
-        CK(hipMemcpy(got.data(), h->dP, h->n * h->esz, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(got.data(), h->dP.get(), h->n * h->esz, hipMemcpyDeviceToHost));
         int nan = 0;
         for (float x : got) nan += std::isnan(x);
         if (v == 0) {
@@ -121,7 +121,7 @@ int main(int argc, char** argv) {
         int stale = 0;
         const int n = 20000;
         for (int i = 0; i < n; ++i) {
-            h->hRes[0] = fake;
+            h->hRes.get()[0] = fake;
             const int s = i % steps;
             if (rs_pc_update(h, &ox[s * TH], &oy[s * TH], &fi[s * TH], &zf[s * 7], &pk[0]) != RS_OK) {
                 fprintf(stderr, "update: %s\n", rs_last_error());
