@@ -56,6 +56,8 @@
  *   rs_vo_run       vis_odom.update(im) per frame ros_simulate.py:119-122, the (vtrans, vrot)
  *                   deltas the main loop feeds to update_posecells, :163-165
  *   rs_vo_select    the shift choice inside update(), on the host alone
+ *   rs_em_*         (new) ExperienceMap with the linking the reference leaves as a TODO,
+ *                   experience_map.py:58; rs_em_relax_host is the same rule on the host alone
  */
 #ifndef RATSLAM_ABI_H
 #define RATSLAM_ABI_H
@@ -453,6 +455,63 @@ int rs_vo_select(int max_shift, int width, int rows, const uint32_t* table, int*
  * untimed or in several chunks */
 int rs_vo_set_timing(rs_vo* h, int enable);
 int rs_vo_last_ms(rs_vo* h, double ms[2]);
+
+/* ------------------------------------------------------------------------ */
+/* Linked experience map                                                     */
+/* ------------------------------------------------------------------------ */
+/* The map the reference leaves at "TODO: linking will go here" (experience_map.py:58):
+ * experiences with a pose (x, y, th), an append-only list of links l = (a -> b, d, h, f)
+ * -- distance, heading and facing of b as measured from a -- and a damped-Jacobi
+ * relaxation over the links.  All float64, correctly rounded, no contraction:
+ *   wrap(t)  = t - 2pi * rint(t / 2pi)
+ *   link     ex = x_b - (x_a + d * cos(th_a + h)), ey the same with sin,
+ *            df = wrap(th_b - (th_a + f))
+ *   sweep    (reads the previous iterate only) experience i sums from +0.0, in order, its
+ *            links with i == a by ascending link id, each (+ex, +ey, +df), then its links
+ *            with i == b by ascending link id, each (-ex, -ey, -df);  w = correction / deg_i;
+ *            x' = x + w * sx;  y' = y + w * sy;  th' = wrap(th + w * st);
+ *            an experience without links keeps its pose
+ * The poses live on the device; the link list and the bookkeeping of which template owns
+ * which experience stay with the caller (pyratslam_amd/linked_experience_map.py).
+ * Kernel form: "lds" (one workgroup, both iterates in LDS, all sweeps in one launch) while
+ * the map has at most 768 experiences, "sweep" (one launch per sweep over two global
+ * buffers) above, each where it measured faster; both give the same bits.
+ * RS_EM_FORM=lds|sweep, read at rs_em_create, forces one -- the lds form holds 3,072
+ * experiences, and forced beyond that rs_em_relax returns RS_ERR_ARG. */
+typedef struct rs_em rs_em;
+
+/* capacity: experiences allocated at once (>= 1; the map grows by doubling);
+ * correction in (0, 1] */
+int rs_em_create(int capacity, double correction, int device, rs_em** out);
+/* synchronises and reports an error of queued work, like rs_vt_destroy */
+int rs_em_destroy(rs_em* h);
+int rs_em_count(rs_em* h, int* nexp, int* nlinks);
+/* a new experience reached from experience `from` by the measurement (d, heading, facing):
+ * (x + d * cos(th + heading), y + d * sin(th + heading), wrap(th + facing)), computed on the
+ * device from `from`'s current pose (queued); from == -1: the origin (0, 0, facing).  It
+ * adds no link. */
+int rs_em_add_experience(rs_em* h, int from, double d, double heading, double facing, int* id);
+/* append the link from -> to; RS_ERR_ARG for ids out of range and for from == to */
+int rs_em_add_link(rs_em* h, int from, int to, double d, double heading, double facing, int* id);
+/* `loops` sweeps over all links, queued on the handle's stream: does not synchronise.  The
+ * incidence lists are rebuilt on the host and uploaded only when experiences or links were
+ * added since the last relax. */
+int rs_em_relax(rs_em* h, int loops);
+/* poses [first, first + n) as xyth[3 * n], after everything queued before */
+int rs_em_read(rs_em* h, int first, int n, double* xyth);
+int rs_em_write(rs_em* h, int first, int n, const double* xyth);
+/* HIP events around the launches of every later rs_em_relax (default off); rs_em_last_ms
+ * waits for the last relax and gives its device time, -1 when it ran untimed */
+int rs_em_set_timing(rs_em* h, int enable);
+int rs_em_last_ms(rs_em* h, double* ms);
+/* "lds" or "sweep": the form rs_em_relax takes at the map's present size */
+const char* rs_em_form(rs_em* h);
+/* the same sweeps on the host alone (no handle, no device), through the library's own
+ * incidence-list builder: nlinks links (from, to, d, heading, facing) over nexp experiences,
+ * xyth[3 * nexp] relaxed in place */
+int rs_em_relax_host(int nexp, int nlinks, const int32_t* from, const int32_t* to, const double* d,
+                     const double* heading, const double* facing, double* xyth, int loops,
+                     double correction);
 
 /* Multi-GPU: one process per GPU, library sharded round-robin (template g lives
  * on rank g % nranks at slot g / nranks); per query the local first-argmin keys

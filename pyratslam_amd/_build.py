@@ -13,7 +13,7 @@ INCLUDE = os.path.join(ROOT, 'include')
 LIB = os.path.join(HERE, 'libratslam_hip.so')
 OBJDIR = os.path.join(HERE, 'build')
 SOURCES = ['rs_common.cpp', 'posecell.hip', 'view_templates.hip', 'view_templates_float.hip',
-           'visual_odometer.hip']
+           'visual_odometer.hip', 'experience_map.hip']
 # per-source flags: the plane scan's batch takes are single-lane atomics; the
 # wave-aggregating atomic optimizer only adds a readfirstlane round trip to them.
 # The pose-cell stencils keep scalar FMAs: SLP packing into v_pk_fma_f32 pairs the
@@ -25,8 +25,12 @@ EXTRA = {'view_templates.hip': ['-mllvm', '-amdgpu-atomic-optimizer-strategy=Non
                                 '-mllvm', '-amdgpu-sched-strategy=max-ilp'],
          # pc_step_halo's first 9 arguments (the union image's addresses, the partial sums) preloaded
          # into scalar registers (posecell.hip, before pc_step_halo)
-         'posecell.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-kernarg-preload-count=9']}
-HEADERS = [os.path.join(CSRC, 'rs_common.h'), os.path.join(INCLUDE, 'ratslam_abi.h')]
+         'posecell.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-kernarg-preload-count=9'],
+         # the linked map's float64 rule is defined operation by operation (em_rule.h): a
+         # fused multiply-add would round x + w * sx once where NumPy rounds twice
+         'experience_map.hip': ['-ffp-contract=off']}
+HEADERS = [os.path.join(CSRC, 'rs_common.h'), os.path.join(CSRC, 'em_rule.h'),
+           os.path.join(INCLUDE, 'ratslam_abi.h')]
 ARCH = os.environ.get('PYRATSLAM_ARCH', 'gfx950')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 

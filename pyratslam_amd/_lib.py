@@ -149,6 +149,21 @@ SIGNATURES = {
     'rs_vo_select': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _u32p, _c_int_p, _f64p]),
     'rs_vo_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
     'rs_vo_last_ms': (ctypes.c_int, [_vp, _f64p]),
+    'rs_em_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(_vp)]),
+    'rs_em_destroy': (ctypes.c_int, [_vp]),
+    'rs_em_count': (ctypes.c_int, [_vp, _c_int_p, _c_int_p]),
+    'rs_em_add_experience': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, _c_int_p]),
+    'rs_em_add_link': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_double, _c_int_p]),
+    'rs_em_relax': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'rs_em_read': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _f64p]),
+    'rs_em_write': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _f64p]),
+    'rs_em_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'rs_em_last_ms': (ctypes.c_int, [_vp, _f64p]),
+    'rs_em_form': (ctypes.c_char_p, [_vp]),
+    'rs_em_relax_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i32p, _i32p, _f64p, _f64p, _f64p,
+                                        _f64p, ctypes.c_int, ctypes.c_double]),
     'rs_comm_unique_id': (ctypes.c_int, [_u8p]),
     'rs_vt_attach_comm': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _u8p]),
     'rs_vt_set_shard': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),

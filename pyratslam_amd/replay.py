@@ -34,7 +34,9 @@ same pipeline over an array of frames, batched on the GPU.
 
 ``python -m pyratslam_amd.replay --bag FILE`` replays a bag;
 ``--synthetic N`` writes and replays a synthetic one (``synthetic.ros_stream``);
-``--visual-odometry`` replays either from the camera alone.
+``--visual-odometry`` replays either from the camera alone; ``--loop-closure`` keeps a
+``LinkedExperienceMap`` (every matched frame goes to ``em.on_template``, which links the
+experiences and relaxes the map on the GPU) in place of the dead-reckoned ``ExperienceMap``.
 """
 import argparse
 import json
@@ -89,6 +91,7 @@ class RatslamReplay:
                                 device=device)
         self.pcn, self.vts = pcn, vts
         self.em = em if em is not None else ExperienceMap()
+        self._em_links = hasattr(self.em, 'on_template')   # (LinkedExperienceMap)
         self.odom_freq = odom_freq
         self.feedback_energy = feedback_energy
         self.batch = batch and hasattr(pcn, 'run') and not publish
@@ -120,6 +123,8 @@ class RatslamReplay:
         pc_max = self.pcn.get_pc_max()
         template_match = self.vts.match(input=im, pc_x=pc_max[0], pc_y=pc_max[1], pc_th=pc_max[2])
         self.template_index.append(int(template_match.get_index()))
+        if self._em_links:   # a linked map learns which place the frame was recognised as
+            self.em.on_template(self.template_index[-1])
         if self.feedback_energy:
             self.pcn.inject(self.feedback_energy, tuple(template_match.location()))
         if self.use_visual_odometry:   # ros_simulate.py:119-122
@@ -241,7 +246,9 @@ class RatslamReplay:
                 pcs = [peak] + [tuple(int(v) for v in m) for m in maxes[:-1]]
                 idx, _, _ = self.vts.match_frames((n, buf), pcs)
                 self.template_index.extend(int(j) for j in idx)
-                for (vt, vr), m in zip(deltas, maxes):
+                for (vt, vr), m, j in zip(deltas, maxes, idx):
+                    if self._em_links:   # the frame's match, then its step: the per-frame order
+                        self.em.on_template(int(j))
                     self.deltas.append((float(vt), float(vr)))
                     self._record(float(vt), float(vr), m)
         finally:
@@ -287,9 +294,17 @@ def main(argv=None):
                     help='camera-only replay (USE_VISUAL_ODOMETRY, ros_simulate.py:81): odometry '
                          'messages are ignored, every frame goes through SimpleVisualOdometer; '
                          'each rank runs its own odometer replica')
+    ap.add_argument('--loop-closure', action='store_true',
+                    help='keep a LinkedExperienceMap: one experience per view template, links '
+                         'from odometry, relaxed on the GPU after every frame; each rank keeps '
+                         'its own replica')
+    ap.add_argument('--exp-loops', type=int, default=None, metavar='N',
+                    help='relaxation sweeps per frame under --loop-closure (default 100)')
     ap.add_argument('--host-reduce', action='store_true',
                     help='combine the ranks\' keys on the host (several ranks on one GPU)')
     args = ap.parse_args(argv)
+    if args.exp_loops is not None and not args.loop_closure:
+        ap.error('--exp-loops needs --loop-closure')
     from . import launch
     if args.gpus > 1 and not launch.under_launcher():
         return launch.spawn(args.gpus, ['-m', 'pyratslam_amd.replay'] + list(
@@ -298,8 +313,13 @@ def main(argv=None):
     d = Dist(args.gpus)
     dev = d.local if args.device is None else args.device
     vts = sharded_templates(d, dev, args.host_reduce) if d.world > 1 else None
+    em = None
+    if args.loop_closure:
+        from .linked_experience_map import EXP_LOOPS, LinkedExperienceMap
+        em = LinkedExperienceMap(exp_loops=EXP_LOOPS if args.exp_loops is None else args.exp_loops,
+                                 device=dev)
     r = RatslamReplay(device=dev, precision=args.precision, feedback_energy=args.feedback, vts=vts,
-                      use_visual_odometry=args.visual_odometry)
+                      use_visual_odometry=args.visual_odometry, em=em)
     d.barrier()
     t0 = time.perf_counter()
     if args.bag:
@@ -314,7 +334,10 @@ def main(argv=None):
                           'frames': len(res['template_index']), 'templates': res['templates'],
                           'seconds': dt, 'pc_max': res['pc_max'].tolist(),
                           'template_index': res['template_index'].tolist(),
-                          'em_points': res['em_points'].tolist()}))
+                          'em_points': res['em_points'].tolist(),
+                          **({'experiences': r.em.poses().tolist(),
+                              'links': [list(map(float, l)) for l in r.em.links().tolist()]}
+                             if em is not None else {})}))
     d.close()
     return 0
 

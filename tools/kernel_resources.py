@@ -14,7 +14,8 @@ src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ''
 extra = {'posecell.hip': ['-fno-slp-vectorize'],
          'view_templates.hip': ['-mllvm', '-amdgpu-atomic-optimizer-strategy=None',
-                                '-mllvm', '-amdgpu-sched-strategy=max-ilp']}
+                                '-mllvm', '-amdgpu-sched-strategy=max-ilp'],
+         'experience_map.hip': ['-ffp-contract=off']}
 cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-x', 'hip',
        f'-I{ROOT}/include', f'-I{ROOT}/pyratslam_amd/csrc', '--cuda-device-only', '-c', src,
        '-o', '/dev/null', '-Rpass-analysis=kernel-resource-usage', *extra.get(os.path.basename(src), [])]
