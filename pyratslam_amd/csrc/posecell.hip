@@ -42,11 +42,10 @@
 #include <vector>
 
 #include "rs_common.h"
+#include "pc_ctl.h"  // FL, HALF, the control structs and their constants, the result-word sentinels
 
 namespace {
 
-constexpr int FL = RS_FILTER_LEN;  // 7 taps
-constexpr int HALF = FL / 2;       // 3
 constexpr int NT = 256;            // threads per block (4 waves)
 constexpr int FT = FL * FL;        // 49 taps of a 2-D filter
 
@@ -105,21 +104,8 @@ struct PcNorm<double> {
     __device__ double operator()(double x) const { return x / t; }
 };
 
-// Per-step control of the path-integration kernel: inline by value (one launch
-// carries its step's shifts, filter rows and theta filter; no copy, no extra
-// dependency) when TH <= CTL_INLINE_MAX, else pointers into a device ring.
-constexpr int CTL_INLINE_MAX = 128;
-struct PcCtlInline {     // single update(): the launch carries the control (~700 B kernarg)
-    short iox[CTL_INLINE_MAX];
-    short ioy[CTL_INLINE_MAX];
-    unsigned char ifi[CTL_INLINE_MAX];
-    double izf[FL];
-    // the union of the step's per-layer shifted windows (column form, whole theta
-    // extent: every block holds every layer, so it is the same for all blocks):
-    // smallest centred shifts and the union's extent in cells, formed on the host
-    // (make_ctl_inline) so the path kernel issues its window loads first thing
-    short umx, umy, uwx, uwy;
-};
+// Per-step control of the path-integration kernel: PcCtlInline (pc_ctl.h), or pointers
+// into a device ring.
 struct PcCtlRing {       // batched run(): one record per step, uploaded once per batch
     const int* ox;
     const int* oy;
@@ -142,11 +128,6 @@ __device__ inline double ctl_zf(const PcCtlRing& c, int z) { return c.zf[z]; }
 // held each step's end back: 64x64x36 13.35 -> 12.32 us per batched step,
 // 128x128x72 27.7 -> 26.8, tools/pc_ab.py).
 constexpr int RES_SLOTS = 256;
-// No step's packed key is ever 0: float32 keys are (value bits << 32 | ~lin) and
-// float64 keys ~lin, with lin < X*Y*TH < 2^32 - 1 (rs_pc_create).  The host writes
-// RES_NONE into each step's result word before the launch and refuses a result
-// still holding it after the stream has synchronised.
-constexpr unsigned long long RES_NONE = 0ull;
 // Step outputs are >= 0 or NaN (every step ends in a clamp), so the value bits order
 // like the values (-0 taken as +0); every NaN is given one bit pattern above +inf, so
 // that, as in numpy's argmax, a NaN beats every number and the first NaN wins.
@@ -1019,7 +1000,7 @@ __global__ __launch_bounds__(64 * WR * WC) PC_ST_WAVES void pc_path_stream(
 // ---------------------------------------------------------------------------
 // 12 waves per block (768 threads; 9, 10, 11, 13, 14, 16: 20.6, 20.3, 20.2, 20.5,
 // 20.3, 20.2 us vs 19.8 per 128x128x72 step)
-constexpr int CO_TX = 8, CO_TY = 8, CO_NW = 12;
+constexpr int CO_NW = 12;  // (the tile, CO_TX x CO_TY: pc_ctl.h)
 // float64 whole-extent blocks: 8 waves (2 per SIMD), so the path kernel's 7x7 filter
 // taps and its window loads fit the 256 VGPRs per wave without spilling
 template <typename T>
@@ -1366,12 +1347,6 @@ constexpr int CO_WIN_BYTES = 128 * 1024, CO_WIN_BYTES_CHUNK = 56 * 1024;
 // theta extent of the path kernel's LDS-DMA window instance (float32, whole extent,
 // control as kernel arguments): BASELINE configs[3]'s 72 layers
 constexpr int CO_DMA_TH = 72;
-
-// signed shift in (-n/2, n/2] (control shifts may exceed the grid: vtrans large)
-__host__ __device__ inline int co_centre(int o, int n) {
-    o = rs::wrapi(o, n);
-    return o > n / 2 ? o - n : o;
-}
 
 // wave min / max of an int by DPP row operations and readlanes (as co_wave_max)
 template <bool MAX>
@@ -1880,12 +1855,9 @@ __global__ __launch_bounds__(64 * NW) void pc_path_cols(
 //    shift (the centre of its Q window): those shifted tiles partition each layer as
 //    the tiles do.
 // ---------------------------------------------------------------------------
-constexpr int HF_T = 4;                       // tile: HF_T x HF_T cells through all layers
-constexpr int HF_W = HF_T + 4 * HALF;         // 16: a layer's excitation window
+// (HF_T, the 4 x 4 tile, HF_W = 16, a layer's excitation window, HF_TH, HF_UMAX and HF_NEAR: pc_ctl.h)
 constexpr int HF_Q = HF_T + 2 * HALF;         // 10: a layer's excited (Q) window
 constexpr int HF_NW = 9, HF_NT = 64 * HF_NW;  // 576 threads: one task per (layer, window row) at TH = 36
-constexpr int HF_TH = 36;                     // the theta extent instantiated (configs[1], the ROS node)
-constexpr int HF_UMAX = 22 * 22;              // union cells staged by LDS-DMA (|shifts| spread <= 6)
 // theta-pass windows, (e, i) pairs [j][rx][ry], row pitch 18 pairs: the y pass's 16-byte
 // row reads (16 lanes on consecutive rows, 36 dwords apart) are conflict-free
 constexpr int HF_WP = 18, HF_WJ = HF_W * HF_WP;
@@ -1893,32 +1865,13 @@ constexpr int HF_YC = HF_W + 4;               // y-pass outputs per Q column (16
 constexpr int HF_YL = HF_Q * HF_YC;           // ... per layer, [qc][rx]
 constexpr int HF_QJ = HF_Q * HF_Q + 4;        // Q window per layer
 constexpr int HF_EXP_MAX = 64;                // steps whose keys pc_halo_finish exports itself
-constexpr float HF_NEAR = 0x1p-20f;           // relative margin of a possible rounding tie (pc_halo_export)
-// A step's result word when its last-step records cannot settle the first maximum of the
-// scaled state (a cell within HF_NEAR of the maximum): never a valid key (a key's low
-// word is ~lin >= 2, lin < X*Y*TH < 2^32 - 1, rs_pc_create)
-constexpr unsigned long long RES_AMBIG = 1ull;
-constexpr unsigned long long REC_SET = 1ull << 63;   // a record's count word: REC_SET | count
 // calls of at most this many steps poll their result words (pc_poll_words); longer ones
 // wait in the stream synchronisation with the CPU idle (a 4,000-step run: 9.13 polled vs
 // 9.02 us per step synchronised, tools/pc_ab.py, round 5)
 constexpr int HF_POLL_MAX = 64;
 constexpr int HF_FLAGS = 1024;   // pc_halo_finish blocks' flags in pinned host memory
 
-// One step's control, a kernel argument (formed on the host by make_ctl_halo).
-struct PcCtlHalo {
-    short sx[HF_TH], sy[HF_TH];  // layer j's 16 x 16 window starts at union row sx[j], column sy[j]
-    unsigned char fo[HF_TH];     // layer j's path filter (row of the filter table)
-    float zf[FL];                // theta filter (posecell_network.py:308)
-    short ux, uy;                // union origin = tile origin - 6 + the smallest centred shift
-    short uw, uh;                // union extent in cells (at most X, Y)
-    int wrap;                    // the union is a whole period in x or y (windows wrap inside it)
-};
 typedef float hf_f2 __attribute__((ext_vector_type(2)));  // (excitatory, inhibitory) pairs: packed FMAs
-// two 16-bit fields in one kernel argument (pc_step_halo's preloaded union origin / extent)
-inline int hf_pack(short lo, short hi) {
-    return (int)((unsigned)(unsigned short)lo | ((unsigned)(unsigned short)hi << 16));
-}
 
 // The normalisation total of a step from its per-block partials, formed by every wave
 // itself in one fixed order (so every block gets the same bits): 4 per lane, then DPP.
@@ -1942,10 +1895,7 @@ __device__ inline double pc_partials_total(const double* __restrict__ part, int 
     pc_partials_issue(part, npart, pt);
     return pc_partials_sum(part, npart, pt);
 }
-// q = n / d for n, d < 2^16, d >= 2, by one high multiply with m = hf_magic(d): the error
-// of m / 2^32 against 1 / d is below 2^-32, so n * m / 2^32 stays below the next integer
-// when n < 2^32 / d
-inline unsigned hf_magic(int d) { return (unsigned)(0xFFFFFFFFull / (unsigned)d + 1ull); }
+// (hf_pack and hf_magic, the host's forming of the preloaded arguments below: pc_ctl.h)
 
 // EXC: excitation only (rs_pc_excite, the step the reference runs before a LUT
 // KeyError): zero shifts, Q of the own cells stored into Uo (theta-fastest), partials.
@@ -2966,6 +2916,13 @@ struct OdoTables {
     std::vector<double> own;        // owned copies when held by a handle
     std::vector<int32_t> ownRows;
 };
+static void fill_odo(OdoTables& o, int TH, double vt_scale, double vr_scale, const double* cos_a, const double* sin_a,
+                     int key_min, int nkeys, const int32_t* key_rows, int z_min, int nz, const double* zf_table) {
+    o.TH = TH; o.vtScale = vt_scale; o.vrScale = vr_scale;
+    o.cosA = cos_a; o.sinA = sin_a;
+    o.keyMin = key_min; o.nKeys = nkeys; o.keyRows = key_rows;
+    o.zMin = z_min; o.nZ = nz; o.zfTab = zf_table;
+}
 
 // The step-kernel family of a handle (the file's header comment; rs_pc_step_form names it).
 enum class PcForm { Rows, Stream, Cols, Halo };
@@ -3025,7 +2982,6 @@ struct rs_pc {
     std::vector<int32_t> cOx, cOy, cRows;
     std::vector<double> cZf;
     bool dbgSkipExport = false;  // rs_pc_debug(RS_PC_DBG_SKIP_EXPORT): the next run leaves hRes unwritten
-    double* exportDev = nullptr;  // rs_pc_update_odom_read: the state export queued behind the step
     rs::PinnedBuf<double> hRead; // rs_pc_read: pinned float64 volume the export kernel writes in place
 };
 
@@ -3034,6 +2990,16 @@ namespace {
 // P (and Q) theta-fastest, the reference's C order (x, y, th): the column and halo
 // forms; the others keep P layer-major
 inline bool pc_thfast(const rs_pc* h) { return h->form == PcForm::Cols || h->form == PcForm::Halo; }
+
+// The handle's precision as a type: f(T{}) with T float or double (f a generic lambda
+// that takes `auto t` and names the type decltype(t); both results of one type).
+template <typename F>
+__attribute__((always_inline)) inline auto pc_by_prec(const rs_pc* h, F&& f) {
+    return h->prec == RS_PREC_F32 ? f(float{}) : f(double{});
+}
+// A kernel instance's integer parameter chosen at run time, passed on as a type.
+template <int N>
+using Int = std::integral_constant<int, N>;
 
 // Per-step buffers of a call of n steps, grown in powers of two: the result slots and
 // words always; the control ring (pinned staging + device copy, ctlStride bytes a step)
@@ -3122,77 +3088,22 @@ const SepKernel<float>& sep_of<float>(const rs_pc* h) { return h->kf; }
 template <>
 const SepKernel<double>& sep_of<double>(const rs_pc* h) { return h->kd; }
 
-// Control of step s as a kernel argument (TH <= CTL_INLINE_MAX) ...
-void make_ctl_inline(const rs_pc* h, int s, const int32_t* ox, const int32_t* oy,
-                     const int32_t* fidx, const double* zf, PcCtlInline* c) {
-    const size_t b = (size_t)s * h->TH;
-    int mnx = INT_MAX, mxx = INT_MIN, mny = INT_MAX, mxy = INT_MIN;
-    for (int k = 0; k < h->TH; ++k) {
-        c->iox[k] = (short)ox[b + k];
-        c->ioy[k] = (short)oy[b + k];
-        c->ifi[k] = (unsigned char)fidx[b + k];
-        const int cx = co_centre(ox[b + k], h->X), cy = co_centre(oy[b + k], h->Y);
-        mnx = std::min(mnx, cx);
-        mxx = std::max(mxx, cx);
-        mny = std::min(mny, cy);
-        mxy = std::max(mxy, cy);
-    }
-    for (int z = 0; z < FL; ++z) c->izf[z] = zf[(size_t)s * FL + z];
-    c->umx = (short)mnx;
-    c->umy = (short)mny;
-    c->uwx = (short)(CO_TX + 2 * HALF + mxx - mnx);
-    c->uwy = (short)(CO_TY + 2 * HALF + mxy - mny);
-}
-
-// ... or as pointers into the device ring record of step s.
-PcCtlRing make_ctl_ring(const rs_pc* h, int s, const unsigned char* ring = nullptr) {
-    const unsigned char* rec = (ring ? ring : h->dCtl.get()) + (size_t)s * h->ctlStride;
+// Control of step s as pointers into its device ring record (as a kernel argument,
+// TH <= CTL_INLINE_MAX: make_ctl_inline, pc_ctl.h).
+PcCtlRing make_ctl_ring(const rs_pc* h, int s) {
+    const unsigned char* rec = h->dCtl.get() + (size_t)s * h->ctlStride;
     return PcCtlRing{reinterpret_cast<const int*>(rec),
                      reinterpret_cast<const int*>(rec + ctl_off_oy(h)),
                      reinterpret_cast<const int*>(rec + ctl_off_f(h)),
                      reinterpret_cast<const double*>(rec + ctl_off_zf(h))};
 }
 
-void decode_xyz(const rs_pc* h, unsigned long long key, int32_t* out);
-
-// Control of step s for the halo form: the layers' centred shifts as window starts in
-// the union of the step's shifted 16 x 16 windows (the same for every block), which the
-// kernel loads first thing.
-void make_ctl_halo(const rs_pc* h, int s, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
-                   const double* zf, PcCtlHalo* c) {
-    const size_t b = (size_t)s * h->TH;
-    int mnx = INT_MAX, mxx = INT_MIN, mny = INT_MAX, mxy = INT_MIN;
-    for (int k = 0; k < h->TH; ++k) {
-        const int cx = co_centre(ox[b + k], h->X), cy = co_centre(oy[b + k], h->Y);
-        mnx = std::min(mnx, cx);
-        mxx = std::max(mxx, cx);
-        mny = std::min(mny, cy);
-        mxy = std::max(mxy, cy);
-    }
-    const int uw = std::min(HF_W + mxx - mnx, h->X);
-    int uy = mny, uh = std::min(HF_W + mxy - mny, h->Y);
-    const bool wrap = HF_W + mxx - mnx > h->X || HF_W + mxy - mny > h->Y;
-    // theta extents that are not whole 16-byte pieces (pc_step_halo loads the image in
-    // 16-byte pieces of cell pairs then): an even start column and width, one column more
-    // on either side where needed, when that stays a union the image holds
-    if (h->TH % 4 != 0 && h->Y % 2 == 0 && !wrap) {
-        const int py = uy - (uy & 1), ph = (uh + (uy & 1) + 1) & ~1;
-        if (ph <= h->Y && uw * ph <= HF_UMAX) {
-            uy = py;
-            uh = ph;
-        }
-    }
-    for (int k = 0; k < h->TH; ++k) {
-        c->sx[k] = (short)(co_centre(ox[b + k], h->X) - mnx);
-        c->sy[k] = (short)(co_centre(oy[b + k], h->Y) - uy);
-        c->fo[k] = (unsigned char)fidx[b + k];
-    }
-    for (int z = 0; z < FL; ++z) c->zf[z] = (float)zf[(size_t)s * FL + z];
-    c->ux = (short)mnx;
-    c->uy = (short)uy;
-    c->uw = (short)uw;
-    c->uh = (short)uh;
-    c->wrap = wrap;
+void decode_xyz(const rs_pc* h, unsigned long long key, int32_t* out) {
+    const unsigned lin = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+    out[2] = (int32_t)(lin % (unsigned)h->TH);
+    const unsigned xy = lin / (unsigned)h->TH;
+    out[1] = (int32_t)(xy % (unsigned)h->Y);
+    out[0] = (int32_t)(xy / (unsigned)h->Y);
 }
 
 // Where step s of a launch sequence leaves its results: its RES_SLOTS argmax
@@ -3210,48 +3121,28 @@ inline StepOut step_out(const rs_pc* h, int s) {
 
 // Wait for a call's result words (pinned host memory, each one 8-byte system-scope store
 // by the call's last kernel) instead of the stream's completion signal: a bounded spin
-// that returns true once every word of steps [s0, s1) holds a key, false when it runs
-// out (the caller then synchronises the stream, which returns any error).  Safe for the
-// same reason as the halo form's record polling (pc_run_halo): the host reads nothing
-// else the call wrote, and every later device access is ordered on the stream.
+// (rs::spin_until) that returns true once every word of steps [s0, s1) holds a key, false
+// when it runs out (the caller then synchronises the stream, which returns any error).
+// Safe for the same reason as the halo form's record polling (pc_run_halo): the host reads
+// nothing else the call wrote, and every later device access is ordered on the stream.
 bool pc_poll_words(const rs_pc* h, int s0, int s1) {
-    const volatile unsigned long long* w = h->hRes.get();
-    int s = s0;
-    for (long spin = 0; spin < 4000000 && s < s1; ++spin)
-        while (s < s1 && w[s] != RES_NONE) ++s;
-    return s == s1;
+    const volatile unsigned long long* w = h->hRes.get() + s0;
+    return rs::spin_until(s1 - s0, [w](int s) { return w[s] != RES_NONE; });
 }
 
 // An eager halo call (the volume written into the caller's pinned array) polls the
 // finishing blocks' flags instead of the stream's completion when it is short and not
 // profiled; RS_PC_HALO_FLAGS=0 keeps the stream synchronisation for it.
-bool halo_poll_env() {
-    static const bool on = [] {
-        const char* e = std::getenv("RS_PC_HALO_POLL");
-        return !(e && std::strcmp(e, "0") == 0);
-    }();
-    return on;
-}
-bool halo_flags_env() {
-    static const bool on = [] {
-        const char* e = std::getenv("RS_PC_HALO_FLAGS");
-        return !(e && std::strcmp(e, "0") == 0);
-    }();
-    return on;
-}
-bool xp_poll_ok(const rs_pc* h, int n, bool poll_env) {
-    return poll_env && halo_flags_env() && h->exportDev && h->hFlag.get() && !h->profiling && !h->dbgSkipExport &&
-           n <= HF_POLL_MAX && (int)std::min<size_t>(1024, (h->n / 4 + 255) / 256) <= HF_FLAGS;
-}
+bool halo_poll_env() { static const bool on = rs::env_on("RS_PC_HALO_POLL"); return on; }
+bool halo_flags_env() { static const bool on = rs::env_on("RS_PC_HALO_FLAGS"); return on; }
+// pc_halo_finish's grid: 256 threads, a float4 each per pass
+inline int hf_finish_blocks(const rs_pc* h) { return (int)std::min<size_t>(1024, (h->n / 4 + 255) / 256); }
 
-// Spin until pc_halo_finish's nb blocks have each stored flag value seq (bounded; false
-// when the spin runs out and the caller must synchronise the stream instead).
+// Spin until a volume-writing launch's nb blocks have each stored flag value seq (bounded;
+// false when the spin runs out and the caller must synchronise the stream instead).
 bool pc_poll_flags(const rs_pc* h, int nb, unsigned seq) {
     const volatile unsigned* f = h->hFlag.get();
-    int b = 0;
-    for (long spin = 0; spin < 4000000 && b < nb; ++spin)
-        while (b < nb && f[b] == seq) ++b;
-    return b == nb;
+    return rs::spin_until(nb, [f, seq](int b) { return f[b] == seq; });
 }
 
 // The next flag value of a volume-writing launch the host will poll (0 is the flags'
@@ -3264,34 +3155,85 @@ unsigned pc_next_seq(rs_pc* h) {
 bool pc_flags_ok(const rs_pc* h, int nb) {
     return halo_poll_env() && halo_flags_env() && h->hFlag.get() && !h->profiling && nb <= HF_FLAGS;
 }
-// The export kernel's grid when its flags are polled: at most 128 blocks, each thread
-// storing a few 16-byte pieces (fewer blocks, fewer flags; 64x64x36 rows-form read 32-36
-// us at 32-128 blocks against 36-37 at 289, within the boxes' spread, tools/node_step.py,
-// round 5)
-int pc_xflag_nb(int nb) { return std::min(nb, 128); }
+// ... and whether an n-step halo call with an eager readback (xp) may poll its finishing pass
+bool xp_poll_ok(const rs_pc* h, int n, const double* xp) {
+    return xp && pc_flags_ok(h, hf_finish_blocks(h)) && !h->dbgSkipExport && n <= HF_POLL_MAX;
+}
 
-// pc_halo_export's last-step rule on the host, over records in pinned host memory: the
-// largest key, or RES_AMBIG when another cell may round to the same scaled value; RES_NONE
-// when a block's record is missing (a record's key is never 0).
-unsigned long long halo_key_from_records(const unsigned long long* rec, int nrec) {
-    unsigned long long m = 0ull;
-    for (int b = 0; b < nrec; ++b) {
-        if (rec[2 * b] == 0ull || rec[2 * b + 1] == 0ull) return RES_NONE;
-        m = std::max(m, rec[2 * b]);
-    }
-    auto val = [](unsigned long long k) {
-        const unsigned u = (unsigned)(k >> 32);
-        float f;
-        std::memcpy(&f, &u, sizeof(f));
-        return f;
-    };
-    const float gv = val(m), thr = gv - gv * HF_NEAR;
-    if (!(gv > 0.f) || std::isinf(gv) || std::isnan(gv)) return m;   // 0, inf, NaN maxima are exact
-    for (int b = 0; b < nrec; ++b) {
-        const unsigned long long kb = rec[2 * b];
-        if (kb == m ? (rec[2 * b + 1] & ~REC_SET) > 1ull : val(kb) >= thr) return RES_AMBIG;
-    }
-    return m;
+// The only launch of pc_halo_finish: U in buffer src_buf (0 dP, 1 dQ), its partial sums in
+// half part_half of dPart, normalised into dP; the handle's state is settled after it.
+// What else the pass leaves is the caller's choice:
+struct HaloFinishOut {
+    unsigned long long* slot = nullptr;  // the last step's slots: every block max-reduces its key into them
+    int nexp = 0;           // > 0, the call's own key export: block 0 stores the words of steps 0 .. nexp-2
+                            // into hRes, every block its key of step nexp-1 into hKey (zeroed here)
+    double* xp = nullptr;   // the float64 C-order volume (a pinned array's device address)
+    unsigned* flag = nullptr;  // per-block flags set to seq behind the block's volume stores
+    unsigned seq = 0u;
+};
+int pc_launch_halo_finish(rs_pc* h, int src_buf, int part_half, const HaloFinishOut& o = {}) {
+    float* buf[2] = {static_cast<float*>(h->dP.get()), static_cast<float*>(h->dQ.get())};
+    const int n4 = (int)(h->n / 4), nb = hf_finish_blocks(h);
+    if (o.nexp > 0) std::memset(h->hKey.get(), 0, sizeof(unsigned long long) * nb);
+    hipLaunchKernelGGL(pc_halo_finish, dim3(nb), dim3(256), 0, h->stream, buf[src_buf], buf[0], n4,
+                       h->dPart.get() + (size_t)part_half * h->nPart, h->nPart, o.slot, h->dRes.get(), o.nexp,
+                       h->hRes.dev(), o.nexp > 0 ? h->hKey.dev() : nullptr, o.xp, (int)(h->n * sizeof(float)),
+                       o.flag, o.seq);
+    RS_HIP(hipGetLastError());
+    h->haloPend = false;
+    h->haloCur = 0;
+    return RS_OK;
+}
+
+// The only launch of pc_step_halo (EXC: its excitation-only instance), forming the
+// arguments the kernel has preloaded: the grid, the tile counts and the union's origin and
+// extent as 16-bit pairs, and the two high-multiply divisors.
+template <bool EXC>
+int pc_launch_halo_step(rs_pc* h, const float* src, float* dst, const double* part_in, int npart_in,
+                        double* part_out, unsigned long long* prev_slot, unsigned long long* slot,
+                        const PcCtlHalo& c, unsigned long long* rec) {
+    const int nblk = h->cgx * h->cgy;
+    hf_launch<EXC>(h->TH, dim3(nblk), h->stream, src, hf_pack(h->X, h->Y), hf_pack(h->cgx, nblk),
+                   hf_pack(c.ux, c.uy), hf_pack(c.uw, c.uh), hf_magic(h->cgx), hf_magic(c.uh), part_in, npart_in, dst,
+                   part_out, prev_slot, slot, static_cast<const float*>(h->dFilt.get()), h->nf, c, h->kf, rec);
+    RS_HIP(hipGetLastError());
+    return RS_OK;
+}
+
+// The only launch of pc_export2_kernel: the float64 C-order volume into pinned host
+// memory (dst: its device address).  *seq != 0: the launch's *nb blocks each set their
+// flag to it and the host may poll them (pc_poll_flags); the grid is then at most 128
+// blocks, each thread storing a few 16-byte pieces (fewer blocks, fewer flags; 64x64x36
+// rows-form read 32-36 us at 32-128 blocks against 36-37 at 289, within the boxes'
+// spread, tools/node_step.py, round 5).
+int pc_launch_export(rs_pc* h, double* dst, bool may_poll, int* nb, unsigned* seq) {
+    int xnb = (int)std::min<size_t>(1024, (h->n / 2 + NT - 1) / NT + 1);
+    const bool fl = may_poll && pc_flags_ok(h, xnb);
+    if (fl) xnb = std::min(xnb, 128);
+    *nb = xnb;
+    *seq = fl ? pc_next_seq(h) : 0u;
+    pc_by_prec(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pc_export2_kernel<T>), dim3(xnb), dim3(NT), 0, h->stream,
+                           static_cast<const T*>(h->dP.get()), dst, h->X, h->Y, h->TH, (int)pc_thfast(h),
+                           fl ? h->hFlag.dev() : nullptr, *seq);
+    });
+    RS_HIP(hipGetLastError());
+    return RS_OK;
+}
+
+// The end of a call of n steps, either run path: no result word may still hold the
+// sentinel once the call has been waited for; the call's device time; the keys decoded.
+int pc_end_call(rs_pc* h, int n, int32_t* out_xyz) {
+    for (int s = 0; s < n; ++s)
+        RS_CHECK(h->hRes.get()[s] != RES_NONE, RS_ERR_HIP,
+                 "step %d of %d: its argmax key did not reach the host result buffer after the "
+                 "stream synchronised", s, n);
+    if (h->profiling) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
+    else h->lastMs = 0.f;  // the call-bracketing events are recorded only while profiling
+    if (out_xyz)
+        for (int s = 0; s < n; ++s) decode_xyz(h, h->hRes.get()[s], out_xyz + 3 * (size_t)s);
+    return RS_OK;
 }
 
 // The halo form's state left unnormalised by a call (U in buffer haloCur, its partial
@@ -3299,16 +3241,7 @@ unsigned long long halo_key_from_records(const unsigned long long* rec, int nrec
 // change the state directly (read, write, inject, get_max, total, excite, debug) settle
 // it first.  (The next call's first launch consumes it as it is: it scales on load.)
 int pc_halo_settle(rs_pc* h) {
-    if (!h->haloPend) return RS_OK;
-    float* buf[2] = {static_cast<float*>(h->dP.get()), static_cast<float*>(h->dQ.get())};
-    const int n4 = (int)(h->n / 4), nb = std::min(1024, (n4 + 255) / 256);
-    hipLaunchKernelGGL(pc_halo_finish, dim3(nb), dim3(256), 0, h->stream, buf[h->haloCur], buf[0], n4,
-                       h->dPart.get() + (size_t)h->haloPart * h->nPart, h->nPart, nullptr, nullptr, 0, nullptr,
-                       nullptr, nullptr, (int)(h->n * sizeof(float)), nullptr, 0u);
-    RS_HIP(hipGetLastError());
-    h->haloPend = false;
-    h->haloCur = 0;
-    return RS_OK;
+    return h->haloPend ? pc_launch_halo_finish(h, h->haloCur, h->haloPart) : RS_OK;
 }
 
 // A volume read of a state a halo call left unnormalised (the ROS node's `.posecells`
@@ -3323,20 +3256,19 @@ int pc_halo_settle(rs_pc* h) {
 int pc_halo_settle_read(rs_pc* h, double* xp_dev, bool* done) {
     *done = false;
     if (!h->haloPend) return RS_OK;
-    float* buf[2] = {static_cast<float*>(h->dP.get()), static_cast<float*>(h->dQ.get())};
-    const int n4 = (int)(h->n / 4), nb = std::min(1024, (n4 + 255) / 256);
+    const int nb = hf_finish_blocks(h);
     const bool fl = pc_flags_ok(h, nb);
     const unsigned seq = fl ? pc_next_seq(h) : 0u;
-    hipLaunchKernelGGL(pc_halo_finish, dim3(nb), dim3(256), 0, h->stream, buf[h->haloCur], buf[0], n4,
-                       h->dPart.get() + (size_t)h->haloPart * h->nPart, h->nPart, nullptr, nullptr, 0, nullptr,
-                       nullptr, xp_dev, (int)(h->n * sizeof(float)), fl ? h->hFlag.dev() : nullptr, seq);
-    RS_HIP(hipGetLastError());
-    h->haloPend = false;
-    h->haloCur = 0;
+    RS_TRY(pc_launch_halo_finish(h, h->haloCur, h->haloPart, {nullptr, 0, xp_dev, fl ? h->hFlag.dev() : nullptr, seq}));
     if (!(fl && pc_poll_flags(h, nb, seq))) RS_HIP(hipStreamSynchronize(h->stream));
     *done = true;
     return RS_OK;
 }
+
+// How a halo-form call ends (pc_run_halo): the last launch's per-block records of U in pinned
+// host memory, reduced by the host after its wait (a one-step call: no export launch); the
+// records on the device and pc_halo_export; or the finishing pass, pc_halo_finish.
+enum class HaloEnd { HostRecords, DevRecords, Finish };
 
 // n steps of the halo form: one launch each (step s reads the state in one buffer,
 // scaled by the partials of the step before, and writes U into the other; the partial
@@ -3345,13 +3277,13 @@ int pc_halo_settle_read(rs_pc* h, double* xp_dev, bool* done) {
 // steps 0 .. n-2 keyed by the launch after each, step n-1 from the last launch's
 // per-block records of U -- the finishing pass over the volume (pc_halo_finish) is off
 // the per-call path (update() at 64x64x36: about 4 us of device time per call).  With an
-// eager readback (the float64 volume into the caller's pinned array), or when the
+// eager readback (xp: the float64 volume into the caller's pinned array), or when the
 // records cannot settle the last step's first maximum (RES_AMBIG: a cell within
 // HF_NEAR of the peak), pc_halo_finish normalises the state into dP, keys it and
 // exports.  One host sync (two for RES_AMBIG).  rs_pc_debug(RS_PC_DBG_HALO_SETTLE) makes
 // every later call finish.
 int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
-                const double* zf, int32_t* out_xyz) {
+                const double* zf, int32_t* out_xyz, double* xp) {
     RS_TRY(pc_grow_steps(h, n, false));   // (the control travels as kernel arguments)
     const bool pk = h->profiling && h->profKernels;
     if (pk) RS_TRY(pc_ensure_events(h, (size_t)2 * n + 2));
@@ -3359,77 +3291,69 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     // RS_PC_HALO_POLL=0: a one-step call waits for the kernel's completion signal instead
     // of returning once every block's record has reached host memory (below)
     const bool poll_env = halo_poll_env();
-    const bool lazy = h->exportDev == nullptr && !h->haloSettleAlways;
-    // a one-step call: the blocks' records go straight to pinned host memory and the host
-    // reduces them after its wait (no export launch)
-    const bool host_rec = lazy && n == 1 && h->hRec.get();
-    if (host_rec) std::memset(h->hRec.get(), 0, sizeof(unsigned long long) * 2 * h->nPart);
+    const HaloEnd end = xp || h->haloSettleAlways     ? HaloEnd::Finish
+                        : n == 1 && h->hRec.get()     ? HaloEnd::HostRecords
+                                                      : HaloEnd::DevRecords;
+    const bool lazy = end != HaloEnd::Finish;
+    if (end == HaloEnd::HostRecords) std::memset(h->hRec.get(), 0, sizeof(unsigned long long) * 2 * h->nPart);
     if (h->profiling) RS_HIP(hipEventRecord(h->ev0, h->stream));
+
+    // 1. the steps
     float* buf[2] = {static_cast<float*>(h->dP.get()), static_cast<float*>(h->dQ.get())};
-    const dim3 grid(h->cgx * h->cgy);
+    double* part[2] = {h->dPart.get(), h->dPart.get() + h->nPart};
     const bool pend = h->haloPend;
     const int c0 = pend ? h->haloCur : 0;          // the buffer step 0 reads
     const int p0 = pend ? (h->haloPart ^ 1) : 0;   // the partials half step 0 writes
+    unsigned long long* const last_slot = h->dRes.get() + (size_t)(n - 1) * RES_SLOTS;
     for (int s = 0; s < n; ++s) {
         PcCtlHalo c;
-        make_ctl_halo(h, s, ox, oy, fidx, zf, &c);
-        const double* part_in = s > 0 ? h->dPart.get() + (size_t)((p0 + s - 1) & 1) * h->nPart
-                                      : h->dPart.get() + (size_t)(pend ? h->haloPart : 0) * h->nPart;
-        const int npart_in = s > 0 || pend ? h->nPart : 0;
+        make_ctl_halo(h->X, h->Y, h->TH, ox + (size_t)s * h->TH, oy + (size_t)s * h->TH, fidx + (size_t)s * h->TH,
+                      zf + (size_t)s * FL, &c);
+        unsigned long long* const slot = h->dRes.get() + (size_t)s * RES_SLOTS;
+        unsigned long long* rec = nullptr;   // the last launch's records, where the ending reads them
+        if (lazy && s == n - 1) rec = end == HaloEnd::HostRecords ? h->hRec.dev() : h->dRec.get();
         if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s], h->stream));
-        hf_launch<false>(h->TH, grid, h->stream, static_cast<const float*>(buf[(c0 + s) & 1]),
-                           hf_pack(h->X, h->Y), hf_pack(h->cgx, grid.x), hf_pack(c.ux, c.uy), hf_pack(c.uw, c.uh),
-                           hf_magic(h->cgx), hf_magic(c.uh), part_in, npart_in, buf[(c0 + s + 1) & 1],
-                           h->dPart.get() + (size_t)((p0 + s) & 1) * h->nPart,
-                           s == 0 ? nullptr : h->dRes.get() + (size_t)(s - 1) * RES_SLOTS,
-                           h->dRes.get() + (size_t)s * RES_SLOTS, static_cast<const float*>(h->dFilt.get()), h->nf, c, h->kf,
-                           lazy && s == n - 1 ? (host_rec ? h->hRec.dev() : h->dRec.get()) : nullptr);
-        RS_HIP(hipGetLastError());
+        RS_TRY(pc_launch_halo_step<false>(h, buf[(c0 + s) & 1], buf[(c0 + s + 1) & 1],
+                                          part[s > 0 ? (p0 + s - 1) & 1 : pend ? h->haloPart : 0],
+                                          s > 0 || pend ? h->nPart : 0, part[(p0 + s) & 1],
+                                          s == 0 ? nullptr : slot - RES_SLOTS, slot, c, rec));
         if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s + 1], h->stream));
     }
     const int cl = (c0 + n) & 1, pl = (p0 + n - 1) & 1;   // where the last U and its partials are
-    const int n4 = (int)(h->n / 4), nb = std::min(1024, (n4 + 255) / 256);
+
+    // 2. the ending
+    const int nb = hf_finish_blocks(h);
     // an eager readback the host may poll for (per-block flags behind a system-scope release)
-    const bool flag_poll = xp_poll_ok(h, n, poll_env);
+    const bool flag_poll = xp_poll_ok(h, n, xp);
     const unsigned seq = flag_poll ? pc_next_seq(h) : 0u;
-    // own export: block 0 stores the words of steps 0 .. n-2, every block its key of step
-    // n-1 into hKey, reduced here once the launch has been waited for
-    auto finish = [&](int nexp_own, double* xp) -> int {
-        const bool fl = flag_poll && xp != nullptr;
-        if (nexp_own > 0) std::memset(h->hKey.get(), 0, sizeof(unsigned long long) * nb);
-        hipLaunchKernelGGL(pc_halo_finish, dim3(nb), dim3(256), 0, h->stream, buf[cl], buf[0], n4,
-                           h->dPart.get() + (size_t)pl * h->nPart, h->nPart, h->dRes.get() + (size_t)(n - 1) * RES_SLOTS,
-                           h->dRes.get(), nexp_own, h->hRes.dev(), nexp_own > 0 ? h->hKey.dev() : nullptr, xp,
-                           (int)(h->n * sizeof(float)), fl ? h->hFlag.dev() : nullptr, seq);
-        RS_HIP(hipGetLastError());
-        h->haloPend = false;
-        h->haloCur = 0;
-        return RS_OK;
-    };
+    const bool skipped = h->dbgSkipExport;
+    // own export: pc_halo_finish stores the words of steps 0 .. n-2 itself, and every block
+    // its key of step n-1 into hKey, reduced below once the launch has been waited for
+    const bool own_export = end == HaloEnd::Finish && !skipped && n <= HF_EXP_MAX;
     if (pk) RS_HIP(hipEventRecord(h->evPool[2 * n], h->stream));
-    bool own_export = false;
-    if (lazy) {
-        if (!h->dbgSkipExport && !host_rec) {
-            hipLaunchKernelGGL(pc_halo_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes.get(), n,
-                               h->dRec.get(), (int)grid.x, h->hRes.dev());
-            RS_HIP(hipGetLastError());
-        }
-        h->haloPend = true;
-        h->haloCur = cl;
-        h->haloPart = pl;
-    } else {
-        own_export = !h->dbgSkipExport && n <= HF_EXP_MAX;
-        RS_TRY(finish(own_export ? n : 0, h->exportDev));
-        if (!h->dbgSkipExport && !own_export) {
+    if (end == HaloEnd::DevRecords && !skipped) {
+        hipLaunchKernelGGL(pc_halo_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes.get(), n,
+                           h->dRec.get(), h->nPart, h->hRes.dev());
+        RS_HIP(hipGetLastError());
+    }
+    if (end == HaloEnd::Finish) {
+        RS_TRY(pc_launch_halo_finish(h, cl, pl, {last_slot, own_export ? n : 0, xp, flag_poll ? h->hFlag.dev() : nullptr, seq}));
+        if (!skipped && !own_export) {
             hipLaunchKernelGGL(pc_res_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes.get(), n,
                                h->hRes.dev());
             RS_HIP(hipGetLastError());
         }
     }
-    const bool skipped = h->dbgSkipExport;
+    if (lazy) {
+        h->haloPend = true;
+        h->haloCur = cl;
+        h->haloPart = pl;
+    }
     h->dbgSkipExport = false;
     if (pk) RS_HIP(hipEventRecord(h->evPool[2 * n + 1], h->stream));
     if (h->profiling) RS_HIP(hipEventRecord(h->ev1, h->stream));
+
+    // 3. the wait
     // A one-step call returns as soon as every block's record has reached the pinned host
     // array, without waiting for the kernel's completion signal and the host's wake-up
     // (update() at 64x64x36: 22.5-24.3 -> 16.8-18.9 us, tools/pc_ab.py --mode update,
@@ -3442,25 +3366,21 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     // A spin that runs out (a slow or faulted kernel) falls back to the stream
     // synchronisation, which returns any error.
     bool polled = false;
-    if (flag_poll && !lazy && !skipped) {
+    if (flag_poll) {
         // the eager readback: every finishing block's flag (its volume slice released at
         // system scope before it), then every step's key word
         polled = pc_poll_flags(h, nb, seq) && pc_poll_words(h, 0, n - 1);
-    }
-    if (lazy && !skipped && poll_env && !h->profiling && n <= HF_POLL_MAX) {
-        if (host_rec) {
-            const volatile unsigned long long* r = h->hRec.get();
-            const int nr = (int)grid.x;
-            int b = 0;
-            for (long spin = 0; spin < 4000000 && b < nr; ++spin)
-                while (b < nr && r[2 * b] != 0ull && r[2 * b + 1] != 0ull) ++b;
-            polled = b == nr;
-        } else {
-            polled = pc_poll_words(h, 0, n);   // the export kernel's words
-        }
+    } else if (lazy && !skipped && poll_env && !h->profiling && n <= HF_POLL_MAX) {
+        const volatile unsigned long long* r = h->hRec.get();
+        polled = end == HaloEnd::HostRecords
+                     ? rs::spin_until(h->nPart, [r](int b) { return r[2 * b] != 0ull && r[2 * b + 1] != 0ull; })
+                     : pc_poll_words(h, 0, n);   // the export kernel's words
     }
     if (!polled) RS_HIP(hipStreamSynchronize(h->stream));
-    if (host_rec && !skipped) h->hRes.get()[n - 1] = halo_key_from_records(h->hRec.get(), (int)grid.x);
+
+    // 4. the last step's key
+    unsigned long long& last = h->hRes.get()[n - 1];
+    if (end == HaloEnd::HostRecords && !skipped) last = halo_key_from_records(h->hRec.get(), h->nPart);
     if (own_export) {   // the finishing blocks' keys of the last step (a key is never 0)
         unsigned long long m = 0ull;
         bool all = true;
@@ -3468,25 +3388,19 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
             all &= h->hKey.get()[b] != 0ull;
             m = std::max(m, h->hKey.get()[b]);
         }
-        h->hRes.get()[n - 1] = all ? m : RES_NONE;
+        last = all ? m : RES_NONE;
     }
-    if (lazy && !skipped && h->hRes.get()[n - 1] == RES_AMBIG) {
+    if (lazy && !skipped && last == RES_AMBIG) {
         // a cell within HF_NEAR of the last step's peak: key the normalised state itself
         // (its slots were zeroed by the last launch and nothing has reduced into them)
-        h->hRes.get()[n - 1] = RES_NONE;
-        RS_TRY(finish(0, nullptr));
-        hipLaunchKernelGGL(pc_res_export, dim3(1), dim3(64), 0, h->stream, h->dRes.get() + (size_t)(n - 1) * RES_SLOTS, 1,
-                           h->hRes.dev() + (n - 1));
+        last = RES_NONE;
+        RS_TRY(pc_launch_halo_finish(h, cl, pl, {last_slot}));
+        hipLaunchKernelGGL(pc_res_export, dim3(1), dim3(64), 0, h->stream, last_slot, 1, h->hRes.dev() + (n - 1));
         RS_HIP(hipGetLastError());
         if (!(poll_env && pc_poll_words(h, n - 1, n))) RS_HIP(hipStreamSynchronize(h->stream));
         ++h->haloAmbig;
     }
-    for (int s = 0; s < n; ++s)
-        RS_CHECK(h->hRes.get()[s] != RES_NONE, RS_ERR_HIP,
-                 "step %d of %d: its argmax key did not reach the host result buffer after the "
-                 "stream synchronised", s, n);
-    if (h->profiling) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
-    else h->lastMs = 0.f;  // the call-bracketing events are recorded only while profiling
+    RS_TRY(pc_end_call(h, n, out_xyz));
     if (pk) {
         h->kernelMs[0] = h->kernelMs[1] = 0.0;
         for (int s = 0; s < n; ++s) {
@@ -3498,156 +3412,108 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         RS_HIP(hipEventElapsedTime(&b, h->evPool[2 * n], h->evPool[2 * n + 1]));
         h->kernelMs[1] = b;
     }
-    if (out_xyz)
-        for (int s = 0; s < n; ++s) decode_xyz(h, h->hRes.get()[s], out_xyz + 3 * (size_t)s);
     return RS_OK;
 }
 
 // Streaming variants instantiated: (BX rows per wave, WR row groups, WC column tiles of 64).
 #define PC_STREAM_VARIANTS(X_) X_(1, 8, 1) X_(2, 8, 1)
 
-template <typename T, typename CTL>
-int pc_launch_stream(rs_pc* h, const T* P, T* Q, unsigned long long* slot, T* bmax, unsigned* bidx,
-                     const CTL* ctl, int prof_base) {
-    const StreamGrid G = h->sg;
-    const dim3 grid(G.gx * G.gy * G.gz), block(64 * h->swr * h->swc);
-    const SepKernel<T>& k = sep_of<T>(h);
-    const T* filt = static_cast<const T*>(h->dFilt.get());
-    bool done = false;
-#define PC_EXCITE_CASE(bx_, wr_, wc_)                                                         \
-    if (!done && h->sbx == bx_ && h->swr == wr_ && h->swc == wc_) {                           \
-        hipLaunchKernelGGL((pc_excite_stream<T, bx_, wr_, wc_>), grid, block, 0, h->stream, P, \
-                           Q,                                                                 \
-                           h->dPart.get(), slot, h->X, h->Y, h->TH, G, k);                          \
-        done = true;                                                                          \
-    }
-    PC_STREAM_VARIANTS(PC_EXCITE_CASE)
-#undef PC_EXCITE_CASE
-    RS_CHECK(done, RS_ERR_STATE, "no streaming variant BX=%d WR=%d WC=%d", h->sbx, h->swr, h->swc);
-    RS_HIP(hipGetLastError());
-    if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 1], h->stream));
-    if (!ctl) return RS_OK;
-    if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 2], h->stream));
-    done = false;
-#define PC_PATH_CASE(bx_, wr_, wc_)                                                              \
-    if (!done && h->sbx == bx_ && h->swr == wr_ && h->swc == wc_) {                              \
-        hipLaunchKernelGGL((pc_path_stream<T, bx_, wr_, wc_, CTL>), grid, block, 0, h->stream, Q, \
-                           static_cast<T*>(h->dP.get()), h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot,  \
-                           bmax, bidx, h->X, h->Y, h->TH, G);                                    \
-        done = true;                                                                             \
-    }
-    PC_STREAM_VARIANTS(PC_PATH_CASE)
-#undef PC_PATH_CASE
-    RS_HIP(hipGetLastError());
-    return RS_OK;
+// f(Int<BX>, Int<WR>, Int<WC>) for the instantiated variant (bx, wr, wc), the tile as
+// types; RS_ERR_ARG where no such variant is instantiated.
+template <typename F>
+int with_stream_variant(int bx, int wr, int wc, F&& f) {
+#define PC_VARIANT(bx_, wr_, wc_) \
+    if (bx == bx_ && wr == wr_ && wc == wc_) return f(Int<bx_>{}, Int<wr_>{}, Int<wc_>{});
+    PC_STREAM_VARIANTS(PC_VARIANT)
+#undef PC_VARIANT
+    RS_CHECK(false, RS_ERR_ARG, "no streaming variant BX=%d WR=%d WC=%d", bx, wr, wc);
 }
 
+// A step of the rows, stream and cols forms: the form's kernel instance is chosen once,
+// and its excitation and path launches go out from that choice (two, below).
 template <typename T, typename CTL>
 int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
     const T* P = static_cast<const T*>(h->dP.get());
     T* Q = static_cast<T*>(h->dQ.get());
+    T* Pn = static_cast<T*>(h->dP.get());
+    double* part = h->dPart.get();
     const SepKernel<T>& k = sep_of<T>(h);
     unsigned long long* slot = so.slot;
     T* bmax = static_cast<T*>(so.bmax);
     unsigned* bidx = so.bidx;
     const T* filt = static_cast<const T*>(h->dFilt.get());
-    if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base], h->stream));
-    switch (h->form) {
-    case PcForm::Cols: {
-        const dim3 g(h->cgx * h->cgy * h->coNch);
-        const bool whole = h->coKC >= h->TH;
-        constexpr int THF = co_thmax<T>(), THC = co_thmax_chunk<T>();
-        bool fixed = false;
-        if constexpr (std::is_same<T, float>::value) {
-            if (whole && h->TH == CO_DMA_TH) {  // configs[3]'s theta extent
-                hipLaunchKernelGGL((pc_excite_cols<float, CO_TX, CO_TY, CO_NW, CO_DMA_TH, false, CO_DMA_TH>), g,
-                                   dim3(64 * CO_NW), 0, h->stream, P, h->X, h->Y, h->TH, h->cgx, h->cgy,
-                                   (int)g.x, Q, h->dPart.get(), slot, h->coKC, k);
-                fixed = true;
-            }
-        }
-        if (fixed) {
-        } else if (whole)
-            hipLaunchKernelGGL((pc_excite_cols<T, CO_TX, CO_TY, co_nw<T>(), THF, false>), g, dim3(64 * co_nw<T>()), 0,
-                               h->stream, P, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x, Q, h->dPart.get(), slot,
-                               h->coKC, k);
-        else
-            hipLaunchKernelGGL((pc_excite_cols<T, CO_TX, CO_TY, CO_NW_CHUNK, THC, true>), g,
-                               dim3(64 * CO_NW_CHUNK), 0, h->stream, P, h->X, h->Y, h->TH, h->cgx, h->cgy,
-                               (int)g.x, Q, h->dPart.get(), slot, h->coKC, k);
+    // excitation, then path integration, each between its profiling events; without a
+    // control the excitation alone (rs_pc_excite() normalises with pc_scale_kernel)
+    auto two = [&](auto&& excite, auto&& path) -> int {
+        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base], h->stream));
+        excite();
         RS_HIP(hipGetLastError());
         if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 1], h->stream));
         if (!ctl) return RS_OK;
         if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 2], h->stream));
-        bool launched = false;
-        if constexpr (std::is_same<T, float>::value && std::is_same<CTL, PcCtlInline>::value) {
-            // TH == 72 (configs[3]): the LDS-DMA window instance
-            if (whole && h->TH == CO_DMA_TH) {
-                hipLaunchKernelGGL((pc_path_cols<float, CO_TX, CO_TY, CO_NW, CO_DMA_TH, false, PcCtlInline, CO_DMA_TH>),
-                                   g, dim3(64 * CO_NW), 0, h->stream, Q, h->X, h->Y, h->TH, h->cgx, h->cgy,
-                                   (int)g.x, static_cast<T*>(h->dP.get()), h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot,
-                                   bmax, bidx, h->coKC);
-                launched = true;
-            }
-        }
-        if (launched) {
-        } else if (whole)
-            hipLaunchKernelGGL((pc_path_cols<T, CO_TX, CO_TY, co_nw<T>(), THF, false, CTL>), g, dim3(64 * co_nw<T>()), 0,
-                               h->stream, Q, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x, static_cast<T*>(h->dP.get()),
-                               h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot, bmax, bidx, h->coKC);
-        else
-            hipLaunchKernelGGL((pc_path_cols<T, CO_TX, CO_TY, CO_NW_CHUNK, THC, true, CTL>), g,
-                               dim3(64 * CO_NW_CHUNK), 0, h->stream, Q, h->X, h->Y, h->TH, h->cgx, h->cgy,
-                               (int)g.x, static_cast<T*>(h->dP.get()), h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot,
-                               bmax, bidx, h->coKC);
-        break;
+        path();
+        RS_HIP(hipGetLastError());
+        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 3], h->stream));
+        return RS_OK;
+    };
+    switch (h->form) {
+    case PcForm::Cols: {
+        const dim3 g(h->cgx * h->cgy * h->coNch);
+        // an instance: NW waves, a window of THM layers, theta-chunked or whole, and FIX, the
+        // fixed theta extent of the LDS-DMA kernels (0: any).  The path kernel has its LDS-DMA
+        // window instance only with the control as kernel arguments; with the ring it is
+        // the whole-extent one
+        auto cols = [&](auto nw, auto thm, auto chunk, auto fix) -> int {
+            constexpr int NW = decltype(nw)::value, THM = decltype(thm)::value, FIX = decltype(fix)::value;
+            constexpr bool CHUNK = decltype(chunk)::value;
+            constexpr bool DMA = FIX != 0 && std::is_same<CTL, PcCtlInline>::value;
+            constexpr int PTHM = FIX != 0 && !DMA ? co_thmax<T>() : THM;
+            return two([&] { hipLaunchKernelGGL((pc_excite_cols<T, CO_TX, CO_TY, NW, THM, CHUNK, FIX>), g, dim3(64 * NW), 0,
+                                                h->stream, P, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x, Q, part, slot,
+                                                h->coKC, k); },
+                       [&] { hipLaunchKernelGGL((pc_path_cols<T, CO_TX, CO_TY, NW, PTHM, CHUNK, CTL, DMA ? FIX : 0>), g,
+                                                dim3(64 * NW), 0, h->stream, Q, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x,
+                                                Pn, part, h->nPart, filt, h->nf, *ctl, slot, bmax, bidx, h->coKC); });
+        };
+        const bool whole = h->coKC >= h->TH;
+        if constexpr (std::is_same<T, float>::value)
+            if (whole && h->TH == CO_DMA_TH)  // configs[3]'s theta extent
+                return cols(Int<CO_NW>{}, Int<CO_DMA_TH>{}, std::false_type{}, Int<CO_DMA_TH>{});
+        if (whole) return cols(Int<co_nw<T>()>{}, Int<co_thmax<T>()>{}, std::false_type{}, Int<0>{});
+        return cols(Int<CO_NW_CHUNK>{}, Int<co_thmax_chunk<T>()>{}, std::true_type{}, Int<0>{});
     }
-    case PcForm::Stream:
-        RS_TRY((pc_launch_stream<T, CTL>(h, P, Q, slot, bmax, bidx, ctl, prof_base)));
-        break;
+    case PcForm::Stream: {
+        const StreamGrid G = h->sg;
+        const dim3 grid(G.gx * G.gy * G.gz), block(64 * h->swr * h->swc);
+        return with_stream_variant(h->sbx, h->swr, h->swc, [&](auto bx, auto wr, auto wc) -> int {
+            constexpr int BX = decltype(bx)::value, WR = decltype(wr)::value, WC = decltype(wc)::value;
+            return two([&] { hipLaunchKernelGGL((pc_excite_stream<T, BX, WR, WC>), grid, block, 0, h->stream, P, Q, part,
+                                                slot, h->X, h->Y, h->TH, G, k); },
+                       [&] { hipLaunchKernelGGL((pc_path_stream<T, BX, WR, WC, CTL>), grid, block, 0, h->stream, Q, Pn, part,
+                                                h->nPart, filt, h->nf, *ctl, slot, bmax, bidx, h->X, h->Y, h->TH, G); });
+        });
+    }
     case PcForm::Rows: {
         const dim3 g((h->X + RT_BX - 1) / RT_BX, (h->TH + RT_BK - 1) / RT_BK);
-        if (h->rowsYP == 64)
-            hipLaunchKernelGGL((pc_excite_rows<T, 64>), g, dim3(RT_NT), 0, h->stream, P, Q,
-                               h->dPart.get(), slot, h->X, h->Y, h->TH, k);
-        else
-            hipLaunchKernelGGL((pc_excite_rows<T, 128>), g, dim3(RT_NT), 0, h->stream, P, Q,
-                               h->dPart.get(), slot, h->X, h->Y, h->TH, k);
-        RS_HIP(hipGetLastError());
-        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 1], h->stream));
-        if (!ctl) return RS_OK;  // rs_pc_excite() normalises with pc_scale_kernel
-        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 2], h->stream));
-        if (h->rowsYP == 64)
-            hipLaunchKernelGGL((pc_path_rows<T, 64, CTL>), g, dim3(RT_NT), 0, h->stream, Q,
-                               static_cast<T*>(h->dP.get()), h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot,
-                               bmax, bidx, h->X, h->Y, h->TH);
-        else
-            hipLaunchKernelGGL((pc_path_rows<T, 128, CTL>), g, dim3(RT_NT), 0, h->stream, Q,
-                               static_cast<T*>(h->dP.get()), h->dPart.get(), h->nPart, filt, h->nf, *ctl, slot,
-                               bmax, bidx, h->X, h->Y, h->TH);
-        break;
+        auto rows = [&](auto yp) -> int {
+            constexpr int YP = decltype(yp)::value;
+            return two([&] { hipLaunchKernelGGL((pc_excite_rows<T, YP>), g, dim3(RT_NT), 0, h->stream, P, Q, part, slot,
+                                                h->X, h->Y, h->TH, k); },
+                       [&] { hipLaunchKernelGGL((pc_path_rows<T, YP, CTL>), g, dim3(RT_NT), 0, h->stream, Q, Pn, part,
+                                                h->nPart, filt, h->nf, *ctl, slot, bmax, bidx, h->X, h->Y, h->TH); });
+        };
+        return h->rowsYP == 64 ? rows(Int<64>{}) : rows(Int<128>{});
     }
-    case PcForm::Halo:  // one launch per step: pc_run_halo, rs_pc_excite
-        RS_CHECK(false, RS_ERR_STATE, "the halo form has no two-launch step");
+    case PcForm::Halo: break;  // one launch per step: pc_run_halo, rs_pc_excite
     }
-    RS_HIP(hipGetLastError());
-    if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 3], h->stream));
-    return RS_OK;
-}
-
-void decode_xyz(const rs_pc* h, unsigned long long key, int32_t* out) {
-    const unsigned lin = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-    out[2] = (int32_t)(lin % (unsigned)h->TH);
-    const unsigned xy = lin / (unsigned)h->TH;
-    out[1] = (int32_t)(xy % (unsigned)h->Y);
-    out[0] = (int32_t)(xy / (unsigned)h->Y);
+    RS_CHECK(false, RS_ERR_STATE, "the halo form has no two-launch step");
 }
 
 // n steps launched one by one on the handle's stream, then one export and a sync.
 int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
-                  const double* zf, int32_t* out_xyz) {
+                  const double* zf, int32_t* out_xyz, double* xp) {
     if (n == 0) return RS_OK;
-    if (h->form == PcForm::Halo) return pc_run_halo(h, n, ox, oy, fidx, zf, out_xyz);
+    if (h->form == PcForm::Halo) return pc_run_halo(h, n, ox, oy, fidx, zf, out_xyz, xp);
     // Batches: the column form takes each step's control as kernel arguments too (its
     // path kernel then starts its window loads without a global round trip for the
     // shifts: 128x128x72 27.5 -> 27.1 us per step with the filter table staged behind
@@ -3664,19 +3530,14 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     if (h->profiling) RS_HIP(hipEventRecord(h->ev0, h->stream));
     for (int s = 0; s < n; ++s) {
         const int pb = pk ? 4 * s : -1;
+        const size_t b = (size_t)s * h->TH;
         if (inline_ctl) {
             PcCtlInline c;
-            make_ctl_inline(h, s, ox, oy, fidx, zf, &c);
-            if (h->prec == RS_PREC_F32)
-                RS_TRY((pc_launch_step<float, PcCtlInline>(h, step_out(h, s), &c, pb)));
-            else
-                RS_TRY((pc_launch_step<double, PcCtlInline>(h, step_out(h, s), &c, pb)));
+            make_ctl_inline(h->X, h->Y, h->TH, ox + b, oy + b, fidx + b, zf + (size_t)s * FL, &c);
+            RS_TRY(pc_by_prec(h, [&](auto t) { return pc_launch_step<decltype(t), PcCtlInline>(h, step_out(h, s), &c, pb); }));
         } else {
             const PcCtlRing c = make_ctl_ring(h, s);
-            if (h->prec == RS_PREC_F32)
-                RS_TRY((pc_launch_step<float, PcCtlRing>(h, step_out(h, s), &c, pb)));
-            else
-                RS_TRY((pc_launch_step<double, PcCtlRing>(h, step_out(h, s), &c, pb)));
+            RS_TRY(pc_by_prec(h, [&](auto t) { return pc_launch_step<decltype(t), PcCtlRing>(h, step_out(h, s), &c, pb); }));
         }
     }
     if (h->prec == RS_PREC_F64) {
@@ -3697,36 +3558,16 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     const bool may_poll = halo_poll_env() && !h->profiling && !skipped && n <= HF_POLL_MAX;
     int xnb = 0;
     unsigned seq = 0u;
-    if (h->exportDev) {
-        xnb = (int)std::min<size_t>(1024, (h->n / 2 + NT - 1) / NT + 1);
-        const bool fl = may_poll && pc_flags_ok(h, xnb);
-        if (fl) xnb = pc_xflag_nb(xnb);
-        seq = fl ? pc_next_seq(h) : 0u;
-        unsigned* flag = fl ? h->hFlag.dev() : nullptr;
-        if (h->prec == RS_PREC_F32)
-            hipLaunchKernelGGL((pc_export2_kernel<float>), dim3(xnb), dim3(NT), 0, h->stream,
-                               static_cast<const float*>(h->dP.get()), h->exportDev, h->X, h->Y, h->TH, (int)pc_thfast(h),
-                               flag, seq);
-        else
-            hipLaunchKernelGGL((pc_export2_kernel<double>), dim3(xnb), dim3(NT), 0, h->stream,
-                               static_cast<const double*>(h->dP.get()), h->exportDev, h->X, h->Y, h->TH, (int)pc_thfast(h),
-                               flag, seq);
-        RS_HIP(hipGetLastError());
-    }
+    if (xp) RS_TRY(pc_launch_export(h, xp, may_poll, &xnb, &seq));
     if (h->profiling) RS_HIP(hipEventRecord(h->ev1, h->stream));
     // the result words polled (pc_poll_words), and with an eager readback the volume's
     // flags first (each block's stores released at system scope before its flag), unless
     // the call is profiled, long or its export was withheld (RS_PC_HALO_POLL=0: always the
     // stream synchronisation; RS_PC_HALO_FLAGS=0: for an eager readback)
-    const bool polled = may_poll && (h->exportDev ? seq != 0u && pc_poll_flags(h, xnb, seq) : true) &&
+    const bool polled = may_poll && (xp ? seq != 0u && pc_poll_flags(h, xnb, seq) : true) &&
                         pc_poll_words(h, 0, n);
     if (!polled) RS_HIP(hipStreamSynchronize(h->stream));
-    for (int s = 0; s < n; ++s)
-        RS_CHECK(h->hRes.get()[s] != RES_NONE, RS_ERR_HIP,
-                 "step %d of %d: its argmax key did not reach the host result buffer after the "
-                 "stream synchronised", s, n);
-    if (h->profiling) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
-    else h->lastMs = 0.f;  // the step-bracketing events are recorded only while profiling
+    RS_TRY(pc_end_call(h, n, out_xyz));
     if (pk) {
         h->kernelMs[0] = h->kernelMs[1] = 0.0;
         for (int s = 0; s < n; ++s) {
@@ -3737,20 +3578,19 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
             h->kernelMs[1] += b;
         }
     }
-    if (out_xyz)
-        for (int s = 0; s < n; ++s)
-            decode_xyz(h, h->hRes.get()[s], out_xyz + 3 * (size_t)s);
     return RS_OK;
 }
 
+// xp: an eager readback, the float64 volume after the last step into the caller's
+// pinned array (its device address), queued behind the steps; else null.
 int pc_run_impl(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
-                const double* zf, int32_t* out_xyz) {
+                const double* zf, int32_t* out_xyz, double* xp = nullptr) {
     RS_CHECK(h, RS_ERR_STATE, "null pose-cell handle");
     RS_CHECK(n >= 0, RS_ERR_ARG, "negative step count");
     if (n == 0) return RS_OK;
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(pc_check_ctl(h, n, ox, oy, fidx, zf));
-    return pc_run_direct(h, n, ox, oy, fidx, zf, out_xyz);
+    return pc_run_direct(h, n, ox, oy, fidx, zf, out_xyz, xp);
 }
 
 // path_integration's control for one step (posecell_network.py:252-308) in the
@@ -3870,30 +3710,28 @@ int pc_rows_set(rs_pc* h) {
 // pipeline: pc_stream_set refuses a variant that spills.
 template <typename T>
 int pc_stream_scratch(int bx, int wr, int wc, size_t* bytes) {
-    hipFuncAttributes a{};
     *bytes = 0;
-    bool done = false;
-#define PC_SCRATCH(bx_, wr_, wc_)                                                                      \
-    if (!done && bx == bx_ && wr == wr_ && wc == wc_) {                                                \
-        const void* fns[3] = {                                                                         \
-            reinterpret_cast<const void*>(&pc_excite_stream<T, bx_, wr_, wc_>),                        \
-            reinterpret_cast<const void*>(&pc_path_stream<T, bx_, wr_, wc_, PcCtlRing>),               \
-            reinterpret_cast<const void*>(&pc_path_stream<T, bx_, wr_, wc_, PcCtlInline>)};            \
-        for (const void* f : fns) {                                                          \
-            RS_HIP(hipFuncGetAttributes(&a, f));                                             \
-            *bytes += a.localSizeBytes;                                                      \
-        }                                                                                    \
-        done = true;                                                                         \
-    }
-    PC_STREAM_VARIANTS(PC_SCRATCH)
-#undef PC_SCRATCH
-    return RS_OK;
+    return with_stream_variant(bx, wr, wc, [&](auto b, auto r, auto c) -> int {
+        constexpr int BX = decltype(b)::value, WR = decltype(r)::value, WC = decltype(c)::value;
+        const void* fns[3] = {reinterpret_cast<const void*>(&pc_excite_stream<T, BX, WR, WC>),
+                              reinterpret_cast<const void*>(&pc_path_stream<T, BX, WR, WC, PcCtlRing>),
+                              reinterpret_cast<const void*>(&pc_path_stream<T, BX, WR, WC, PcCtlInline>)};
+        hipFuncAttributes a{};
+        for (const void* f : fns) {
+            RS_HIP(hipFuncGetAttributes(&a, f));
+            *bytes += a.localSizeBytes;
+        }
+        return RS_OK;
+    });
 }
 
 // The column kernels' limits: single-conditional wraps, the window in LDS, the
 // filter table in LDS.
+int pc_cols_vec(const rs_pc* h) {
+    return pc_by_prec(h, [](auto t) { return co_vec<decltype(t)>(); });
+}
 bool pc_cols_fit(const rs_pc* h) {
-    const int vec = h->esz == 4 ? co_vec<float>() : co_vec<double>();
+    const int vec = pc_cols_vec(h);
     return h->X >= CO_TX + 2 * HALF && h->Y >= CO_TY + 2 * HALF + 4 && h->Y % vec == 0 &&
            h->TH >= CO_CH + 2 && h->nf <= RT_NFMAX;
 }
@@ -3902,8 +3740,8 @@ bool pc_cols_fit(const rs_pc* h) {
 // block per CU when it fits the LDS window (no halo layers); KC < TH puts KC + 6
 // layers in each of two blocks per CU.
 int pc_cols_set(rs_pc* h, int kc) {
-    const int thf = h->esz == 4 ? co_thmax<float>() : co_thmax<double>();
-    const int thc = h->esz == 4 ? co_thmax_chunk<float>() : co_thmax_chunk<double>();
+    const int thf = pc_by_prec(h, [](auto t) { return co_thmax<decltype(t)>(); });
+    const int thc = pc_by_prec(h, [](auto t) { return co_thmax_chunk<decltype(t)>(); });
     if (kc <= 0) {
         kc = h->TH;
         if (h->TH > thf) {  // more layers than one block holds: the fewest chunks that fit
@@ -3959,16 +3797,8 @@ bool pc_stream_fit(const rs_pc* h) { return h->nf <= RT_NFMAX; }
 // bx rows.  kc (layers per block) = 0 picks the smallest chunk that keeps the grid
 // within one block per CU.
 int pc_stream_set(rs_pc* h, int bx, int wr, int wc, int kc) {
-    bool known = false;
-#define PC_KNOWN(bx_, wr_, wc_) known = known || (bx == bx_ && wr == wr_ && wc == wc_);
-    PC_STREAM_VARIANTS(PC_KNOWN)
-#undef PC_KNOWN
-    RS_CHECK(known, RS_ERR_ARG, "no streaming variant BX=%d WR=%d WC=%d", bx, wr, wc);
-    size_t scratch = 0;
-    if (h->esz == 4)
-        RS_TRY(pc_stream_scratch<float>(bx, wr, wc, &scratch));
-    else
-        RS_TRY(pc_stream_scratch<double>(bx, wr, wc, &scratch));
+    size_t scratch = 0;   // (a variant that is not instantiated is refused here: with_stream_variant)
+    RS_TRY(pc_by_prec(h, [&](auto t) { return pc_stream_scratch<decltype(t)>(bx, wr, wc, &scratch); }));
     RS_CHECK(scratch == 0, RS_ERR_ARG,
              "streaming variant BX=%d WR=%d WC=%d spills %zu B to scratch at this precision", bx, wr,
              wc, scratch);
@@ -4018,7 +3848,7 @@ int pc_choose_form(rs_pc* h) {
         RS_CHECK(pc_cols_fit(h), RS_ERR_ARG,
                  "RS_PC_FORM=cols needs X >= %d, Y >= %d and a multiple of %d, TH >= %d and at most %d "
                  "path filters",
-                 CO_TX + 2 * HALF, CO_TY + 2 * HALF + 4, h->esz == 4 ? co_vec<float>() : co_vec<double>(),
+                 CO_TX + 2 * HALF, CO_TY + 2 * HALF + 4, pc_cols_vec(h),
                  CO_CH + 2, RT_NFMAX);
         return pc_cols_set(h, env[4] == ':' ? std::atoi(env + 5) : 0);
     }
@@ -4186,23 +4016,18 @@ int rs_pc_excite(rs_pc* h) {
         PcCtlHalo c{};
         c.uw = (short)HF_W;
         c.uh = (short)HF_W;
-        hf_launch<true>(h->TH, dim3(h->cgx * h->cgy), h->stream,
-                           static_cast<const float*>(h->dP.get()), hf_pack(h->X, h->Y), hf_pack(h->cgx, h->cgx * h->cgy),
-                           hf_pack(c.ux, c.uy), hf_pack(c.uw, c.uh), hf_magic(h->cgx), hf_magic(c.uh), h->dPart.get(), 0,
-                           static_cast<float*>(h->dQ.get()), h->dPart.get(), nullptr, nullptr, static_cast<const float*>(h->dFilt.get()), h->nf, c, h->kf,
-                           nullptr);
-        RS_HIP(hipGetLastError());
-    } else if (h->prec == RS_PREC_F32) {
-        RS_TRY((pc_launch_step<float, PcCtlRing>(h, step_out(h, 0), nullptr, -1)));
+        RS_TRY(pc_launch_halo_step<true>(h, static_cast<const float*>(h->dP.get()), static_cast<float*>(h->dQ.get()),
+                                         h->dPart.get(), 0, h->dPart.get(), nullptr, nullptr, c, nullptr));
     } else {
-        RS_TRY((pc_launch_step<double, PcCtlRing>(h, step_out(h, 0), nullptr, -1)));
+        RS_TRY(pc_by_prec(h, [&](auto t) {
+            return pc_launch_step<decltype(t), PcCtlRing>(h, step_out(h, 0), nullptr, -1);
+        }));
     }
-    if (h->prec == RS_PREC_F32)
-        hipLaunchKernelGGL((pc_scale_kernel<float>), dim3(64), dim3(NT), 0, h->stream,
-                           static_cast<float*>(h->dQ.get()), h->n, h->dPart.get(), h->nPart);
-    else
-        hipLaunchKernelGGL((pc_scale_kernel<double>), dim3(64), dim3(NT), 0, h->stream,
-                           static_cast<double*>(h->dQ.get()), h->n, h->dPart.get(), h->nPart);
+    pc_by_prec(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pc_scale_kernel<T>), dim3(64), dim3(NT), 0, h->stream, static_cast<T*>(h->dQ.get()),
+                           h->n, h->dPart.get(), h->nPart);
+    });
     RS_HIP(hipGetLastError());
     // Q has P's layout in every form (the column form: both theta-fastest)
     RS_HIP(hipMemcpyAsync(h->dP.get(), h->dQ.get(), h->n * h->esz, hipMemcpyDeviceToDevice, h->stream));
@@ -4222,22 +4047,13 @@ int rs_pc_set_odometry_tables(rs_pc* h, double vtrans_scale, double vrot_scale,
     for (int i = 0; i < nkeys; ++i)
         RS_CHECK(key_rows[i] >= 0 && key_rows[i] < h->nf, RS_ERR_ARG,
                  "key row %d outside the %d-filter table", key_rows[i], h->nf);
-    OdoTables& o = h->odo;
-    o.TH = h->TH;
-    o.vtScale = vtrans_scale;
-    o.vrScale = vrot_scale;
+    OdoTables& o = h->odo;   // (the handle keeps its own copies)
     o.own.assign(cos_a, cos_a + h->TH);
     o.own.insert(o.own.end(), sin_a, sin_a + h->TH);
     o.own.insert(o.own.end(), zf_table, zf_table + (size_t)nz * FL);
     o.ownRows.assign(key_rows, key_rows + nkeys);
-    o.cosA = o.own.data();
-    o.sinA = o.own.data() + h->TH;
-    o.zfTab = o.own.data() + 2 * (size_t)h->TH;
-    o.keyMin = key_min;
-    o.nKeys = nkeys;
-    o.keyRows = o.ownRows.data();
-    o.zMin = zorig_min;
-    o.nZ = nz;
+    fill_odo(o, h->TH, vtrans_scale, vrot_scale, o.own.data(), o.own.data() + h->TH, key_min, nkeys,
+             o.ownRows.data(), zorig_min, nz, o.own.data() + 2 * (size_t)h->TH);
     h->odoReady = true;
     return RS_OK;
 }
@@ -4251,24 +4067,15 @@ int rs_pc_odom_control(int TH, double vtrans_scale, double vrot_scale, const dou
     RS_CHECK(cos_a && sin_a && key_rows && zf_table && (n == 0 || (odom && ox && oy && fidx && zf &&
              status)), RS_ERR_ARG, "null argument");
     OdoTables o;
-    o.TH = TH;
-    o.vtScale = vtrans_scale;
-    o.vrScale = vrot_scale;
-    o.cosA = cos_a;
-    o.sinA = sin_a;
-    o.keyMin = key_min;
-    o.nKeys = nkeys;
-    o.keyRows = key_rows;
-    o.zMin = zorig_min;
-    o.nZ = nz;
-    o.zfTab = zf_table;
+    fill_odo(o, TH, vtrans_scale, vrot_scale, cos_a, sin_a, key_min, nkeys, key_rows, zorig_min, nz, zf_table);
     for (int s = 0; s < n; ++s)
         status[s] = pc_odom_control(&o, odom[2 * s], odom[2 * s + 1], ox + (size_t)TH * s,
                                     oy + (size_t)TH * s, fidx + (size_t)TH * s, zf + (size_t)FL * s);
     return RS_OK;
 }
 
-int rs_pc_update_odom(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[3]) {
+// One step from an odometry sample; xp: the volume after it into a pinned array (pc_run_impl).
+static int pc_update_odom(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[3], double* xp) {
     rs::clear_error();
     RS_CHECK(h, RS_ERR_STATE, "null pose-cell handle");
     RS_CHECK(h->odoReady, RS_ERR_STATE, "rs_pc_set_odometry_tables has not been called");
@@ -4285,7 +4092,11 @@ int rs_pc_update_odom(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[3]) 
                  "(posecell_network.py:249)");
     }
     RS_CHECK(st == RS_OK, st, "odometry (%g, %g) outside the control tables", vtrans, vrot);
-    return pc_run_impl(h, 1, h->cOx.data(), h->cOy.data(), h->cRows.data(), h->cZf.data(), out_xyz);
+    return pc_run_impl(h, 1, h->cOx.data(), h->cOy.data(), h->cRows.data(), h->cZf.data(), out_xyz, xp);
+}
+
+int rs_pc_update_odom(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[3]) {
+    return pc_update_odom(h, vtrans, vrot, out_xyz, nullptr);
 }
 
 int rs_pc_update_odom_read(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[3], double* pinned) {
@@ -4293,10 +4104,9 @@ int rs_pc_update_odom_read(rs_pc* h, double vtrans, double vrot, int32_t out_xyz
     RS_CHECK(h && pinned, RS_ERR_ARG, "null argument");
     RS_CHECK(reinterpret_cast<uintptr_t>(pinned) % 16 == 0, RS_ERR_ARG, "pinned buffer not 16-byte aligned");
     RS_HIP(hipSetDevice(h->device));
-    RS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->exportDev), pinned, 0));
-    const int st = rs_pc_update_odom(h, vtrans, vrot, out_xyz);
-    h->exportDev = nullptr;
-    return st;
+    double* xp = nullptr;   // the state export queued behind the step
+    RS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&xp), pinned, 0));
+    return pc_update_odom(h, vtrans, vrot, out_xyz, xp);
 }
 
 int rs_pc_run_odom(rs_pc* h, int n, const double* odom, int32_t* out_xyz, int* first_bad) {
@@ -4375,12 +4185,11 @@ int rs_pc_inject(rs_pc* h, double energy, int x, int y, int th) {
     RS_TRY(pc_halo_settle(h));  // (halo: a state a call left unnormalised)
     // the column form keeps P theta-fastest (C order); the others layer-major
     const size_t idx = pc_thfast(h) ? ((size_t)x * h->Y + y) * h->TH + th : ((size_t)th * h->X + x) * h->Y + y;
-    if (h->prec == RS_PREC_F32)
-        hipLaunchKernelGGL((pc_inject_kernel<float>), dim3(1), dim3(64), 0, h->stream,
-                           static_cast<float*>(h->dP.get()), idx, energy);
-    else
-        hipLaunchKernelGGL((pc_inject_kernel<double>), dim3(1), dim3(64), 0, h->stream,
-                           static_cast<double*>(h->dP.get()), idx, energy);
+    pc_by_prec(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pc_inject_kernel<T>), dim3(1), dim3(64), 0, h->stream, static_cast<T*>(h->dP.get()), idx,
+                           energy);
+    });
     RS_HIP(hipGetLastError());
     // no host sync: the add is ordered on the handle's stream before the next step,
     // read or argmax (template -> pose-cell feedback costs one queued launch)
@@ -4392,8 +4201,7 @@ int rs_pc_get_max(rs_pc* h, int32_t out_xyz[3]) {
     RS_CHECK(h && out_xyz, RS_ERR_ARG, "null argument");
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(pc_halo_settle(h));  // (halo: a state a call left unnormalised)
-    if (h->prec == RS_PREC_F32) return pc_argmax_impl<float>(h, out_xyz);
-    return pc_argmax_impl<double>(h, out_xyz);
+    return pc_by_prec(h, [&](auto t) { return pc_argmax_impl<decltype(t)>(h, out_xyz); });
 }
 
 // The float64 C-order volume into pinned host memory (dst: its device pointer) and the
@@ -4404,19 +4212,10 @@ int pc_read_volume(rs_pc* h, double* dst) {
     bool done = false;
     RS_TRY(pc_halo_settle_read(h, dst, &done));
     if (done) return RS_OK;
-    int nb = (int)std::min<size_t>(1024, (h->n / 2 + NT - 1) / NT + 1);
-    const bool fl = pc_flags_ok(h, nb);
-    if (fl) nb = pc_xflag_nb(nb);
-    const unsigned seq = fl ? pc_next_seq(h) : 0u;
-    unsigned* flag = fl ? h->hFlag.dev() : nullptr;
-    if (h->prec == RS_PREC_F32)
-        hipLaunchKernelGGL((pc_export2_kernel<float>), dim3(nb), dim3(NT), 0, h->stream,
-                           static_cast<const float*>(h->dP.get()), dst, h->X, h->Y, h->TH, (int)pc_thfast(h), flag, seq);
-    else
-        hipLaunchKernelGGL((pc_export2_kernel<double>), dim3(nb), dim3(NT), 0, h->stream,
-                           static_cast<const double*>(h->dP.get()), dst, h->X, h->Y, h->TH, (int)pc_thfast(h), flag, seq);
-    RS_HIP(hipGetLastError());
-    if (!(fl && pc_poll_flags(h, nb, seq))) RS_HIP(hipStreamSynchronize(h->stream));
+    int nb = 0;
+    unsigned seq = 0u;
+    RS_TRY(pc_launch_export(h, dst, true, &nb, &seq));
+    if (!(seq != 0u && pc_poll_flags(h, nb, seq))) RS_HIP(hipStreamSynchronize(h->stream));
     return RS_OK;
 }
 
@@ -4450,12 +4249,11 @@ int rs_pc_write(rs_pc* h, const double* host) {
     h->haloPend = false;  // (halo: the whole state is replaced)
     h->haloCur = 0;
     RS_HIP(hipMemcpyAsync(h->dTmp.get(), host, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
-    if (h->prec == RS_PREC_F32)
-        hipLaunchKernelGGL((pc_import_kernel<float>), dim3(256), dim3(NT), 0, h->stream, h->dTmp.get(),
-                           static_cast<float*>(h->dP.get()), h->X, h->Y, h->TH, (int)pc_thfast(h));
-    else
-        hipLaunchKernelGGL((pc_import_kernel<double>), dim3(256), dim3(NT), 0, h->stream, h->dTmp.get(),
-                           static_cast<double*>(h->dP.get()), h->X, h->Y, h->TH, (int)pc_thfast(h));
+    pc_by_prec(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pc_import_kernel<T>), dim3(256), dim3(NT), 0, h->stream, h->dTmp.get(),
+                           static_cast<T*>(h->dP.get()), h->X, h->Y, h->TH, (int)pc_thfast(h));
+    });
     RS_HIP(hipGetLastError());
     RS_HIP(hipStreamSynchronize(h->stream));
     return RS_OK;
@@ -4466,12 +4264,11 @@ int rs_pc_total(rs_pc* h, double* total) {
     RS_CHECK(h && total, RS_ERR_ARG, "null argument");
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(pc_halo_settle(h));  // (halo: a state a call left unnormalised)
-    if (h->prec == RS_PREC_F32)
-        hipLaunchKernelGGL((pc_total_kernel<float>), dim3(1), dim3(NT), 0, h->stream,
-                           static_cast<const float*>(h->dP.get()), h->n, h->dScalar.get());
-    else
-        hipLaunchKernelGGL((pc_total_kernel<double>), dim3(1), dim3(NT), 0, h->stream,
-                           static_cast<const double*>(h->dP.get()), h->n, h->dScalar.get());
+    pc_by_prec(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pc_total_kernel<T>), dim3(1), dim3(NT), 0, h->stream, static_cast<const T*>(h->dP.get()),
+                           h->n, h->dScalar.get());
+    });
     RS_HIP(hipGetLastError());
     RS_HIP(hipMemcpyAsync(total, h->dScalar.get(), sizeof(double), hipMemcpyDeviceToHost, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));

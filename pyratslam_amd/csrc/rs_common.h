@@ -7,6 +7,8 @@
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <utility>
 
@@ -49,6 +51,22 @@ __host__ __device__ inline int wrapi(int v, int n) {
 }
 
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
+
+// A switch read from the environment: on unless the variable is set to "0".
+inline bool env_on(const char* name) { const char* e = std::getenv(name); return !(e && std::strcmp(e, "0") == 0); }
+
+// The host's bounded wait for n items a kernel stores into pinned memory one by one:
+// arrived(i) reads item i (through the caller's volatile pointer).  True once all n have
+// arrived, false when the spin runs out (a slow or faulted kernel): the caller then
+// synchronises the stream, which returns any error.
+constexpr long SPIN_LIMIT = 4'000'000;
+template <class Arrived>
+__attribute__((always_inline)) inline bool spin_until(int n, Arrived arrived) {
+    int i = 0;
+    for (long spin = 0; spin < SPIN_LIMIT && i < n; ++spin)
+        while (i < n && arrived(i)) ++i;
+    return i == n;
+}
 
 // The library's only allocation and release calls (rs_common.cpp): hipMalloc, hipFree,
 // hipHostMalloc (with the block's device address, hipHostGetDevicePointer) and hipHostFree.

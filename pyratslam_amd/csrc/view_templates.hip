@@ -1868,13 +1868,7 @@ uint32_t* vt_compact_for(rs_vt* h, const QueryForms& q, int nq) {
 // the kernel leaves the raw bytes in dQraw for the template stores); RS_VT_ZC=0: always
 // the copy.
 constexpr int VT_ZC_MAX = 64;
-bool vt_zc_env() {
-    static const bool on = [] {
-        const char* e = std::getenv("RS_VT_ZC");
-        return !(e && std::strcmp(e, "0") == 0);
-    }();
-    return on;
-}
+bool vt_zc_env() { static const bool on = rs::env_on("RS_VT_ZC"); return on; }
 
 // Upload nq raw queries and build their forms (the batch view) on the device.
 int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
@@ -2141,19 +2135,10 @@ int vt_launch_scan(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int 
 // falls back to the stream synchronisation.  RS_VT_POLL=0: always synchronise.
 constexpr unsigned long long KEY_PENDING = 0xFFFFFFFF00000000ull;  // score 2^32-1: never a key
 constexpr int VT_POLL_MAX = 4096;
-bool vt_poll_env() {
-    static const bool on = [] {
-        const char* e = std::getenv("RS_VT_POLL");
-        return !(e && std::strcmp(e, "0") == 0);
-    }();
-    return on;
-}
+bool vt_poll_env() { static const bool on = rs::env_on("RS_VT_POLL"); return on; }
 bool vt_poll_keys(const unsigned long long* w_, int n) {
     const volatile unsigned long long* w = w_;
-    int i = 0;
-    for (long spin = 0; spin < 4000000 && i < n; ++spin)
-        while (i < n && w[i] != KEY_PENDING) ++i;
-    return i == n;
+    return rs::spin_until(n, [w](int i) { return w[i] != KEY_PENDING; });
 }
 
 // The pinned staging arrays hSrc / hDst are read by asynchronous copies (vt_store):

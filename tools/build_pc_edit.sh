@@ -1,7 +1,9 @@
 #!/bin/bash
 # A/B variant of the library from an edited copy of posecell.hip (the product source
 # stays untouched): abtmp/<name>.so, with each "old=>new" argument applied as a
-# literal substitution (python str.replace, must match) to the copy.
+# literal substitution (python str.replace, must match) to the copy.  (The control-forming
+# code -- make_ctl_halo, make_ctl_inline, halo_key_from_records and their constants -- lives
+# in csrc/pc_ctl.h, which the copy includes as it is: out of reach of the substitution.)
 # usage: tools/build_pc_edit.sh <name> 'old=>new' ['old=>new' ...]
 set -euo pipefail
 cd "$(dirname "$0")/.."

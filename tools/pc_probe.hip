@@ -242,7 +242,7 @@ int main(int argc, char** argv) {
         CK(hipEventElapsedTime(&t, c0, c1));
         printf("empty kernel, same grid: %.2f us/launch\n", 1e3 * t / reps);
         PcCtlHalo c;
-        make_ctl_halo(h, 0, ox.data(), oy.data(), f.data(), zf.data(), &c);
+        make_ctl_halo(X, Y, h->TH, ox.data(), oy.data(), f.data(), zf.data(), &c);
         CK(hipEventRecord(c0, h->stream));
         for (int i = 0; i < reps; ++i)
             hf_launch<false>(h->TH, g, h->stream, (const float*)h->dP.get(), hf_pack(X, Y),
