@@ -182,6 +182,39 @@ int rs_pc_excite(rs_pc* h);
  * host sync), ordered before the next update / read / argmax */
 int rs_pc_inject(rs_pc* h, double energy, int x, int y, int th);
 int rs_pc_get_max(rs_pc* h, int32_t out_xyz[3]);
+/* Sub-cell pose: the activity packet's circular centroid round the first maximum, the
+ * estimate ratslam-python and OpenRatSLAM return where the reference's get_pc_max is a
+ * placeholder (posecell_network.py:316-320).  The library returns six float64 sums per
+ * step, (S_x, C_x, S_y, C_y, S_th, C_th), over the wrapped box of (2r+1)^3 cells round
+ * the step's argmax cell, by the rule of csrc/pc_peak_rule.h (every operation correctly
+ * rounded, in a fixed order); the caller forms pose_a = atan2(S_a, C_a) * N_a / 2pi mod N_a.
+ * The sums belong to the stored state, which may carry one positive factor common to all
+ * cells (the halo form keeps it unnormalised between steps): only atan2 of a pair is
+ * defined.  Where the stored state is what rs_pc_write wrote they are exactly the rule's.
+ *   rs_pc_set_peak_tables  r = cells_to_avg in 1 .. 3 with 2r+1 <= min(X, Y, TH) (else
+ *                          RS_ERR_ARG, before any device call); sc_a[2 N_a]: the axis's
+ *                          sin weights sin(2 pi c / N_a), c = 0 .. N_a-1, then its cos
+ *                          weights, as the caller's own math library evaluates them.
+ *                          The calls below return RS_ERR_STATE before it.
+ *   rs_pc_get_peak         the stored state's argmax cell and its sums (settles a pending
+ *                          halo state as rs_pc_get_max does); one host sync.
+ *   rs_pc_update_odom_peak, rs_pc_run_odom_peaks, rs_pc_run_peaks
+ *                          rs_pc_update_odom, rs_pc_run_odom and rs_pc_run with each
+ *                          step's sums (out_sums[n*6]) computed on the device behind the
+ *                          step; the same statuses, *first_bad and state as those calls,
+ *                          and the sums of the steps before a failing one are valid.
+ *                          They wait for the stream's completion, never for polled words.
+ *   rs_pc_peak_host        the rule on the host alone (no handle, no device) for the box
+ *                          round cell xyz of a float64 C-order (X, Y, TH) volume. */
+int rs_pc_set_peak_tables(rs_pc* h, int r, const double* sc_x, const double* sc_y, const double* sc_th);
+int rs_pc_get_peak(rs_pc* h, int32_t xyz[3], double sums[6]);
+int rs_pc_update_odom_peak(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[3], double sums[6]);
+int rs_pc_run_odom_peaks(rs_pc* h, int n, const double* odom, int32_t* out_xyz, double* out_sums,
+                         int* first_bad);
+int rs_pc_run_peaks(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
+                    const double* zf, int32_t* out_xyz, double* out_sums);
+int rs_pc_peak_host(int X, int Y, int TH, int r, const double* volume_xyth, const int32_t xyz[3],
+                    const double* sc_x, const double* sc_y, const double* sc_th, double sums[6]);
 /* whole volume as float64, C order (X, Y, TH) -- the reference's .posecells */
 int rs_pc_read(rs_pc* h, double* host_xyth);
 /* the same volume written by the GPU straight into pinned host memory from

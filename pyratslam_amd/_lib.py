@@ -96,6 +96,13 @@ SIGNATURES = {
     'rs_pc_excite': (ctypes.c_int, [_vp]),
     'rs_pc_inject': (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'rs_pc_get_max': (ctypes.c_int, [_vp, _i32p]),
+    'rs_pc_set_peak_tables': (ctypes.c_int, [_vp, ctypes.c_int, _f64p, _f64p, _f64p]),
+    'rs_pc_get_peak': (ctypes.c_int, [_vp, _i32p, _f64p]),
+    'rs_pc_update_odom_peak': (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _i32p, _f64p]),
+    'rs_pc_run_odom_peaks': (ctypes.c_int, [_vp, ctypes.c_int, _f64p, _i32p, _f64p, _c_int_p]),
+    'rs_pc_run_peaks': (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _i32p, _f64p, _i32p, _f64p]),
+    'rs_pc_peak_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p, _i32p,
+                                       _f64p, _f64p, _f64p, _f64p]),
     'rs_pc_read': (ctypes.c_int, [_vp, _f64p]),
     'rs_pc_read_pinned': (ctypes.c_int, [_vp, _vp]),
     'rs_pc_update_odom_read': (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _i32p, _vp]),

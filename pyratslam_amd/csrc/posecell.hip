@@ -43,6 +43,7 @@
 
 #include "rs_common.h"
 #include "pc_ctl.h"  // FL, HALF, the control structs and their constants, the result-word sentinels
+#include "pc_peak_rule.h"  // the packet's circular centroid: the six sums of a wrapped box
 
 namespace {
 
@@ -2897,6 +2898,84 @@ __global__ __launch_bounds__(NT) void pc_total_kernel(const T* __restrict__ P, s
     if (threadIdx.x == 0) *out = s;
 }
 
+// The activity packet's circular centroid round a step's first maximum (pc_peak_rule.h,
+// DESIGN section 24): one wave per launch, queued where the step's state and its argmax key
+// are both on the device.  The wave reduces the key itself -- a float32 step's RES_SLOTS
+// slot words (slot), else nb (value, index) block partials (bmax, bidx: a float64 step's,
+// or pc_argmax_blocks' of the stored state) -- decodes the cell as decode_xyz does, gathers
+// the wrapped box of (2r+1)^3 cells from P (layer-major, or theta-fastest: thfast) into LDS
+// as float64, and takes the rule's stages on at most 49 lanes each: R and C, the three
+// marginals, the six dot products with the uploaded weights.  The rule fixes the order of
+// every sum, so the bits do not depend on the lane mapping.  Six plain 8-byte stores.
+template <typename T>
+__global__ __launch_bounds__(64) void pc_peak_kernel(const T* __restrict__ P, int X, int Y, int TH, int thfast,
+                                                     int r, const unsigned long long* __restrict__ slot,
+                                                     const T* __restrict__ bmax, const unsigned* __restrict__ bidx,
+                                                     int nb, const double* __restrict__ tabs,
+                                                     double* __restrict__ out) {
+    constexpr int W = rs::PC_PEAK_WMAX;
+    __shared__ double s_v[W * W * W];
+    __shared__ double s_R[W * W], s_C[W * W], s_m[3 * W], s_t[6 * W];
+    const int lane = threadIdx.x, w = 2 * r + 1;
+    unsigned lin;
+    if (slot) {
+        unsigned long long m = slot[lane];
+#pragma unroll
+        for (int q = 1; q < RES_SLOTS / 64; ++q) m = max(m, slot[lane + 64 * q]);
+        lin = 0xFFFFFFFFu - (unsigned)(co_wave_max(m) & 0xFFFFFFFFull);
+    } else {
+        T bv = -std::numeric_limits<T>::infinity();
+        unsigned bl = 0xFFFFFFFFu;
+        for (int i = lane; i < nb; i += 64) {
+            const T v = bmax[i];
+            const unsigned l = bidx[i];
+            if (pc_better(v, l, bv, bl)) {
+                bv = v;
+                bl = l;
+            }
+        }
+        // (value, index) pairs are totally ordered, so every lane ends on the same pair
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const T v = __shfl_xor(bv, off);
+            const unsigned l = __shfl_xor(bl, off);
+            if (pc_better(v, l, bv, bl)) {
+                bv = v;
+                bl = l;
+            }
+        }
+        lin = bl;
+    }
+    if (lin >= (unsigned)X * Y * TH) lin = 0u;   // (a key no step wrote: never an address outside P)
+    const int pth = (int)(lin % (unsigned)TH);
+    const unsigned xy = lin / (unsigned)TH;
+    const int py = (int)(xy % (unsigned)Y), px = (int)(xy / (unsigned)Y);
+    // the six rows of weights the last stage multiplies by (row q: axis q / 2, sin then cos),
+    // loaded with the box: one memory round trip behind the key, not one more behind the sums
+    double tw = 0.0;
+    if (lane < 6 * w) {
+        const int q = lane / w, a = q >> 1;
+        const int n = a == 0 ? X : a == 1 ? Y : TH, p = a == 0 ? px : a == 1 ? py : pth;
+        tw = tabs[(a == 0 ? 0 : a == 1 ? 2 * X : 2 * (X + Y)) + (q & 1) * n + rs::pc_peak_wrap(p, lane % w, r, n)];
+    }
+    for (int e = lane; e < w * w * w; e += 64) {
+        const int k = e % w, ij = e / w, j = ij % w, i = ij / w;
+        const size_t cx = rs::pc_peak_wrap(px, i, r, X), cy = rs::pc_peak_wrap(py, j, r, Y),
+                     ck = rs::pc_peak_wrap(pth, k, r, TH);
+        s_v[e] = (double)P[thfast ? (cx * Y + cy) * TH + ck : (ck * X + cx) * Y + cy];
+    }
+    if (lane < 6 * w) s_t[lane] = tw;
+    __syncthreads();
+    if (lane < w * w) {
+        s_R[lane] = rs::pc_peak_R(s_v, w, lane / w, lane % w);
+        s_C[lane] = rs::pc_peak_C(s_v, w, lane / w, lane % w);
+    }
+    __syncthreads();
+    if (lane < 3 * w) s_m[lane] = rs::pc_peak_marginal(s_R, s_C, w, lane / w, lane % w);
+    __syncthreads();
+    if (lane < 6) out[lane] = rs::pc_peak_dot_w(s_m + (lane >> 1) * w, s_t + lane * w, w);
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -2983,6 +3062,11 @@ struct rs_pc {
     std::vector<double> cZf;
     bool dbgSkipExport = false;  // rs_pc_debug(RS_PC_DBG_SKIP_EXPORT): the next run leaves hRes unwritten
     rs::PinnedBuf<double> hRead; // rs_pc_read: pinned float64 volume the export kernel writes in place
+    // sub-cell peak (rs_pc_set_peak_tables): the box radius (0: no tables yet), the axes' sin | cos
+    // weights, and six sums per step where pc_peak_kernel stores them (pinned; dev(): its address)
+    int peakR = 0;
+    rs::DevBuf<double> dPeakTab;
+    rs::PinnedBuf<double> hPeak;
 };
 
 namespace {
@@ -3222,6 +3306,28 @@ int pc_launch_export(rs_pc* h, double* dst, bool may_poll, int* nb, unsigned* se
     return RS_OK;
 }
 
+// Room for the six sums of each of a peaks call's n steps (grown in powers of two; every
+// earlier peaks call has synchronised the stream, so no launch still stores into the old block).
+int pc_grow_peaks(rs_pc* h, int n) {
+    size_t cap = 16;
+    while (cap < (size_t)n) cap *= 2;
+    return h->hPeak.reserve(6 * cap, PC_FINE);
+}
+
+// The only launch of pc_peak_kernel: the sums of step s of a peaks call (hPeak[6s ..]) from the
+// state in P, keyed by the step's slot words (slot) or by nb block partials (bmax, bidx).
+int pc_launch_peak(rs_pc* h, const void* P, const unsigned long long* slot, const void* bmax,
+                   const unsigned* bidx, int nb, int s) {
+    pc_by_prec(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pc_peak_kernel<T>), dim3(1), dim3(64), 0, h->stream, static_cast<const T*>(P), h->X,
+                           h->Y, h->TH, (int)pc_thfast(h), h->peakR, slot, static_cast<const T*>(bmax), bidx, nb,
+                           h->dPeakTab.get(), h->hPeak.dev() + 6 * (size_t)s);
+    });
+    RS_HIP(hipGetLastError());
+    return RS_OK;
+}
+
 // The end of a call of n steps, either run path: no result word may still hold the
 // sentinel once the call has been waited for; the call's device time; the keys decoded.
 int pc_end_call(rs_pc* h, int n, int32_t* out_xyz) {
@@ -3283,15 +3389,18 @@ enum class HaloEnd { HostRecords, DevRecords, Finish };
 // exports.  One host sync (two for RES_AMBIG).  rs_pc_debug(RS_PC_DBG_HALO_SETTLE) makes
 // every later call finish.
 int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
-                const double* zf, int32_t* out_xyz, double* xp) {
+                const double* zf, int32_t* out_xyz, double* xp, double* sums) {
     RS_TRY(pc_grow_steps(h, n, false));   // (the control travels as kernel arguments)
+    if (sums) RS_TRY(pc_grow_peaks(h, n));
     const bool pk = h->profiling && h->profKernels;
     if (pk) RS_TRY(pc_ensure_events(h, (size_t)2 * n + 2));
     for (int s = 0; s < n; ++s) h->hRes.get()[s] = RES_NONE;
     // RS_PC_HALO_POLL=0: a one-step call waits for the kernel's completion signal instead
     // of returning once every block's record has reached host memory (below)
     const bool poll_env = halo_poll_env();
-    const HaloEnd end = xp || h->haloSettleAlways     ? HaloEnd::Finish
+    // A peaks call (sums) finishes too: its last step is then keyed in last_slot from the
+    // normalised state in dP, where the step's peak launch finds both (never RES_AMBIG)
+    const HaloEnd end = xp || sums || h->haloSettleAlways ? HaloEnd::Finish
                         : n == 1 && h->hRec.get()     ? HaloEnd::HostRecords
                                                       : HaloEnd::DevRecords;
     const bool lazy = end != HaloEnd::Finish;
@@ -3318,13 +3427,17 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
                                           s > 0 || pend ? h->nPart : 0, part[(p0 + s) & 1],
                                           s == 0 ? nullptr : slot - RES_SLOTS, slot, c, rec));
         if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s + 1], h->stream));
+        // step s-1's key is complete now (this launch reduced it into slot - RES_SLOTS from the
+        // state it loaded), and its U stays in the buffer this launch read until launch s+1
+        // overwrites it: the peak launch of step s-1 goes between the two
+        if (sums && s > 0) RS_TRY(pc_launch_peak(h, buf[(c0 + s) & 1], slot - RES_SLOTS, nullptr, nullptr, 0, s - 1));
     }
     const int cl = (c0 + n) & 1, pl = (p0 + n - 1) & 1;   // where the last U and its partials are
 
     // 2. the ending
     const int nb = hf_finish_blocks(h);
     // an eager readback the host may poll for (per-block flags behind a system-scope release)
-    const bool flag_poll = xp_poll_ok(h, n, xp);
+    const bool flag_poll = !sums && xp_poll_ok(h, n, xp);
     const unsigned seq = flag_poll ? pc_next_seq(h) : 0u;
     const bool skipped = h->dbgSkipExport;
     // own export: pc_halo_finish stores the words of steps 0 .. n-2 itself, and every block
@@ -3338,6 +3451,8 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     }
     if (end == HaloEnd::Finish) {
         RS_TRY(pc_launch_halo_finish(h, cl, pl, {last_slot, own_export ? n : 0, xp, flag_poll ? h->hFlag.dev() : nullptr, seq}));
+        // the last step's peak: the normalised state in dP, its keys in last_slot
+        if (sums) RS_TRY(pc_launch_peak(h, buf[0], last_slot, nullptr, nullptr, 0, n - 1));
         if (!skipped && !own_export) {
             hipLaunchKernelGGL(pc_res_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes.get(), n,
                                h->hRes.dev());
@@ -3376,7 +3491,11 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
                      ? rs::spin_until(h->nPart, [r](int b) { return r[2 * b] != 0ull && r[2 * b + 1] != 0ull; })
                      : pc_poll_words(h, 0, n);   // the export kernel's words
     }
+    // (A peaks call never polls: the early returns above are safe only because the host reads
+    // nothing but the key words or flagged volume slices, and the sums are plain stores of the
+    // peak launches, visible to the host once the stream has synchronised.)
     if (!polled) RS_HIP(hipStreamSynchronize(h->stream));
+    if (sums) std::memcpy(sums, h->hPeak.get(), sizeof(double) * 6 * (size_t)n);
 
     // 4. the last step's key
     unsigned long long& last = h->hRes.get()[n - 1];
@@ -3511,9 +3630,10 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
 
 // n steps launched one by one on the handle's stream, then one export and a sync.
 int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
-                  const double* zf, int32_t* out_xyz, double* xp) {
+                  const double* zf, int32_t* out_xyz, double* xp, double* sums) {
     if (n == 0) return RS_OK;
-    if (h->form == PcForm::Halo) return pc_run_halo(h, n, ox, oy, fidx, zf, out_xyz, xp);
+    if (h->form == PcForm::Halo) return pc_run_halo(h, n, ox, oy, fidx, zf, out_xyz, xp, sums);
+    if (sums) RS_TRY(pc_grow_peaks(h, n));
     // Batches: the column form takes each step's control as kernel arguments too (its
     // path kernel then starts its window loads without a global round trip for the
     // shifts: 128x128x72 27.5 -> 27.1 us per step with the filter table staged behind
@@ -3539,6 +3659,14 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
             const PcCtlRing c = make_ctl_ring(h, s);
             RS_TRY(pc_by_prec(h, [&](auto t) { return pc_launch_step<decltype(t), PcCtlRing>(h, step_out(h, s), &c, pb); }));
         }
+        // the step's state is in dP and its key on the device (float32: its slot words;
+        // float64: its block partials, pc_argmax_steps runs only after the last step) until
+        // the next step's launches: the step's peak launch goes here
+        if (sums) {
+            const StepOut so = step_out(h, s);
+            const bool f32 = h->prec == RS_PREC_F32;
+            RS_TRY(pc_launch_peak(h, h->dP.get(), f32 ? so.slot : nullptr, so.bmax, so.bidx, h->nPart, s));
+        }
     }
     if (h->prec == RS_PREC_F64) {
         hipLaunchKernelGGL((pc_argmax_steps<double>), dim3(n), dim3(NT), 0, h->stream,
@@ -3555,7 +3683,9 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     h->dbgSkipExport = false;
     // the volume after the last step, into the caller's pinned array (the eager
     // readback), its blocks' flags polled when the call may return early
-    const bool may_poll = halo_poll_env() && !h->profiling && !skipped && n <= HF_POLL_MAX;
+    // (a peaks call synchronises the stream: the polled words' early return is safe only
+    // because the host reads nothing else, and the sums are plain stores of other launches)
+    const bool may_poll = halo_poll_env() && !h->profiling && !skipped && n <= HF_POLL_MAX && !sums;
     int xnb = 0;
     unsigned seq = 0u;
     if (xp) RS_TRY(pc_launch_export(h, xp, may_poll, &xnb, &seq));
@@ -3567,6 +3697,7 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     const bool polled = may_poll && (xp ? seq != 0u && pc_poll_flags(h, xnb, seq) : true) &&
                         pc_poll_words(h, 0, n);
     if (!polled) RS_HIP(hipStreamSynchronize(h->stream));
+    if (sums) std::memcpy(sums, h->hPeak.get(), sizeof(double) * 6 * (size_t)n);
     RS_TRY(pc_end_call(h, n, out_xyz));
     if (pk) {
         h->kernelMs[0] = h->kernelMs[1] = 0.0;
@@ -3582,15 +3713,17 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
 }
 
 // xp: an eager readback, the float64 volume after the last step into the caller's
-// pinned array (its device address), queued behind the steps; else null.
+// pinned array (its device address), queued behind the steps; else null.  sums: a peaks
+// call, six sums per step (pc_peak_kernel, queued behind each step) into this host array.
 int pc_run_impl(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
-                const double* zf, int32_t* out_xyz, double* xp = nullptr) {
+                const double* zf, int32_t* out_xyz, double* xp = nullptr, double* sums = nullptr) {
     RS_CHECK(h, RS_ERR_STATE, "null pose-cell handle");
     RS_CHECK(n >= 0, RS_ERR_ARG, "negative step count");
+    RS_CHECK(!sums || h->peakR > 0, RS_ERR_STATE, "rs_pc_set_peak_tables has not been called");
     if (n == 0) return RS_OK;
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(pc_check_ctl(h, n, ox, oy, fidx, zf));
-    return pc_run_direct(h, n, ox, oy, fidx, zf, out_xyz, xp);
+    return pc_run_direct(h, n, ox, oy, fidx, zf, out_xyz, xp, sums);
 }
 
 // path_integration's control for one step (posecell_network.py:252-308) in the
@@ -3652,9 +3785,12 @@ int pc_odom_control(const OdoTables* h, double vtrans, double vrot, int32_t* ox,
                  : pc_odom_control_base(h, vtrans, vrot, ox, oy, rows, zf);
 }
 
+// The stored state's argmax, queued: its block partials in dBmax / dBidx (*nb of them), the
+// key into dRes[0] and from there into hRes[0] once the stream has synchronised.
 template <typename T>
-int pc_argmax_impl(rs_pc* h, int32_t* out) {
+int pc_argmax_queue(rs_pc* h, int* nb_out) {
     const int nb = h->nBmaxCap < 1024 ? h->nBmaxCap : 1024;
+    *nb_out = nb;
     hipLaunchKernelGGL((pc_argmax_blocks<T>), dim3(nb), dim3(NT), 0, h->stream,
                        static_cast<const T*>(h->dP.get()), h->X, h->Y, h->TH, static_cast<T*>(h->dBmax.get()),
                        h->dBidx.get(), (int)pc_thfast(h));
@@ -3664,6 +3800,13 @@ int pc_argmax_impl(rs_pc* h, int32_t* out) {
     RS_HIP(hipGetLastError());
     RS_HIP(hipMemcpyAsync(h->hRes.get(), h->dRes.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost,
                           h->stream));
+    return RS_OK;
+}
+
+template <typename T>
+int pc_argmax_impl(rs_pc* h, int32_t* out) {
+    int nb = 0;
+    RS_TRY(pc_argmax_queue<T>(h, &nb));
     RS_HIP(hipStreamSynchronize(h->stream));
     decode_xyz(h, h->hRes.get()[0], out);
     return RS_OK;
@@ -4074,11 +4217,14 @@ int rs_pc_odom_control(int TH, double vtrans_scale, double vrot_scale, const dou
     return RS_OK;
 }
 
-// One step from an odometry sample; xp: the volume after it into a pinned array (pc_run_impl).
-static int pc_update_odom(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[3], double* xp) {
+// One step from an odometry sample; xp: the volume after it into a pinned array; sums: the
+// step's six peak sums (pc_run_impl).
+static int pc_update_odom(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[3], double* xp,
+                          double* sums = nullptr) {
     rs::clear_error();
     RS_CHECK(h, RS_ERR_STATE, "null pose-cell handle");
     RS_CHECK(h->odoReady, RS_ERR_STATE, "rs_pc_set_odometry_tables has not been called");
+    RS_CHECK(!sums || h->peakR > 0, RS_ERR_STATE, "rs_pc_set_peak_tables has not been called");
     h->cOx.resize(h->TH);
     h->cOy.resize(h->TH);
     h->cRows.resize(h->TH);
@@ -4092,7 +4238,7 @@ static int pc_update_odom(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[
                  "(posecell_network.py:249)");
     }
     RS_CHECK(st == RS_OK, st, "odometry (%g, %g) outside the control tables", vtrans, vrot);
-    return pc_run_impl(h, 1, h->cOx.data(), h->cOy.data(), h->cRows.data(), h->cZf.data(), out_xyz, xp);
+    return pc_run_impl(h, 1, h->cOx.data(), h->cOy.data(), h->cRows.data(), h->cZf.data(), out_xyz, xp, sums);
 }
 
 int rs_pc_update_odom(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[3]) {
@@ -4109,10 +4255,12 @@ int rs_pc_update_odom_read(rs_pc* h, double vtrans, double vrot, int32_t out_xyz
     return pc_update_odom(h, vtrans, vrot, out_xyz, xp);
 }
 
-int rs_pc_run_odom(rs_pc* h, int n, const double* odom, int32_t* out_xyz, int* first_bad) {
+// A batch of steps from odometry samples; sums: six peak sums per step (pc_run_impl).
+static int pc_run_odom(rs_pc* h, int n, const double* odom, int32_t* out_xyz, int* first_bad, double* sums) {
     rs::clear_error();
     RS_CHECK(h, RS_ERR_STATE, "null pose-cell handle");
     RS_CHECK(h->odoReady, RS_ERR_STATE, "rs_pc_set_odometry_tables has not been called");
+    RS_CHECK(!sums || h->peakR > 0, RS_ERR_STATE, "rs_pc_set_peak_tables has not been called");
     RS_CHECK(n >= 0 && (odom || n == 0), RS_ERR_ARG, "bad odometry batch");
     if (first_bad) *first_bad = -1;
     const size_t th = h->TH;
@@ -4166,13 +4314,87 @@ int rs_pc_run_odom(rs_pc* h, int n, const double* odom, int32_t* out_xyz, int* f
         else RS_CHECK(false, fail_st, "odometry of step %d outside the control tables", fail);
     }
     RS_TRY(pc_run_impl(h, todo, h->cOx.data(), h->cOy.data(), h->cRows.data(), h->cZf.data(),
-                       out_xyz));
+                       out_xyz, nullptr, sums));
     if (todo < n) {
         RS_TRY(rs_pc_excite(h));
         if (first_bad) *first_bad = todo;
         RS_CHECK(false, RS_ERR_LUT_KEY, "path-integration LUT key outside the table at step %d "
                  "(posecell_network.py:249)", todo);
     }
+    return RS_OK;
+}
+
+int rs_pc_run_odom(rs_pc* h, int n, const double* odom, int32_t* out_xyz, int* first_bad) {
+    return pc_run_odom(h, n, odom, out_xyz, first_bad, nullptr);
+}
+
+int rs_pc_set_peak_tables(rs_pc* h, int r, const double* sc_x, const double* sc_y, const double* sc_th) {
+    rs::clear_error();
+    RS_CHECK(h, RS_ERR_STATE, "null pose-cell handle");
+    RS_CHECK(sc_x && sc_y && sc_th, RS_ERR_ARG, "null table");
+    RS_CHECK(r >= 1 && r <= rs::PC_PEAK_RMAX, RS_ERR_ARG, "peak radius %d outside 1 .. %d", r, rs::PC_PEAK_RMAX);
+    RS_CHECK(rs::pc_peak_fits(h->X, h->Y, h->TH, r), RS_ERR_ARG,
+             "grid (%d, %d, %d) does not hold a box of %d cells along every axis", h->X, h->Y, h->TH, 2 * r + 1);
+    RS_HIP(hipSetDevice(h->device));
+    const size_t nx = 2 * (size_t)h->X, ny = 2 * (size_t)h->Y, nth = 2 * (size_t)h->TH;
+    std::vector<double> tab(sc_x, sc_x + nx);
+    tab.insert(tab.end(), sc_y, sc_y + ny);
+    tab.insert(tab.end(), sc_th, sc_th + nth);
+    h->peakR = 0;
+    RS_TRY(h->dPeakTab.reserve(tab.size()));
+    // (ordered behind any peak launch still queued on the handle's stream)
+    RS_HIP(hipMemcpyAsync(h->dPeakTab.get(), tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream));
+    h->peakR = r;
+    return RS_OK;
+}
+
+int rs_pc_get_peak(rs_pc* h, int32_t xyz[3], double sums[6]) {
+    rs::clear_error();
+    RS_CHECK(h && xyz && sums, RS_ERR_ARG, "null argument");
+    RS_CHECK(h->peakR > 0, RS_ERR_STATE, "rs_pc_set_peak_tables has not been called");
+    RS_HIP(hipSetDevice(h->device));
+    RS_TRY(pc_halo_settle(h));  // (halo: a state a call left unnormalised)
+    RS_TRY(pc_grow_peaks(h, 1));
+    int nb = 0;
+    RS_TRY(pc_by_prec(h, [&](auto t) { return pc_argmax_queue<decltype(t)>(h, &nb); }));
+    RS_TRY(pc_launch_peak(h, h->dP.get(), nullptr, h->dBmax.get(), h->dBidx.get(), nb, 0));
+    // the stream's completion, not a polled word: the sums are plain stores (pc_run_direct)
+    RS_HIP(hipStreamSynchronize(h->stream));
+    decode_xyz(h, h->hRes.get()[0], xyz);
+    std::memcpy(sums, h->hPeak.get(), sizeof(double) * 6);
+    return RS_OK;
+}
+
+int rs_pc_update_odom_peak(rs_pc* h, double vtrans, double vrot, int32_t out_xyz[3], double sums[6]) {
+    rs::clear_error();
+    RS_CHECK(sums, RS_ERR_ARG, "null sums");
+    return pc_update_odom(h, vtrans, vrot, out_xyz, nullptr, sums);
+}
+
+int rs_pc_run_odom_peaks(rs_pc* h, int n, const double* odom, int32_t* out_xyz, double* out_sums, int* first_bad) {
+    rs::clear_error();
+    RS_CHECK(out_sums || n <= 0, RS_ERR_ARG, "null sums");
+    return pc_run_odom(h, n, odom, out_xyz, first_bad, out_sums);
+}
+
+int rs_pc_run_peaks(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx, const double* zf,
+                    int32_t* out_xyz, double* out_sums) {
+    rs::clear_error();
+    RS_CHECK(out_sums || n <= 0, RS_ERR_ARG, "null sums");
+    return pc_run_impl(h, n, ox, oy, fidx, zf, out_xyz, nullptr, out_sums);
+}
+
+int rs_pc_peak_host(int X, int Y, int TH, int r, const double* volume, const int32_t xyz[3], const double* sc_x,
+                    const double* sc_y, const double* sc_th, double sums[6]) {
+    rs::clear_error();
+    RS_CHECK(volume && xyz && sums, RS_ERR_ARG, "null argument");
+    RS_CHECK(sc_x && sc_y && sc_th, RS_ERR_ARG, "null table");
+    RS_CHECK(r >= 1 && r <= rs::PC_PEAK_RMAX, RS_ERR_ARG, "peak radius %d outside 1 .. %d", r, rs::PC_PEAK_RMAX);
+    RS_CHECK(X > 0 && Y > 0 && TH > 0 && rs::pc_peak_fits(X, Y, TH, r), RS_ERR_ARG,
+             "grid (%d, %d, %d) does not hold a box of %d cells along every axis", X, Y, TH, 2 * r + 1);
+    RS_CHECK(rs::pc_peak_host(X, Y, TH, r, volume, xyz, sc_x, sc_y, sc_th, sums), RS_ERR_ARG,
+             "cell (%d, %d, %d) outside grid (%d, %d, %d)", xyz[0], xyz[1], xyz[2], X, Y, TH);
     return RS_OK;
 }
 

@@ -5,7 +5,9 @@ API of ``/root/reference/ratslam/posecell_network.py:22-353``: ``PoseCellNetwork
 ``get_pc_max()``, ``.posecells`` (float64 ndarray, C order (X, Y, TH)), ``.shape``,
 plus the filter helpers the reference exposes.  ``step(v)`` is an alias of
 ``update`` (the name BASELINE.json's north_star uses) and ``run(odometry)``
-performs many updates with one host round trip.
+performs many updates with one host round trip.  ``get_pc_pose()``, ``update_pose(v)`` and
+``run(odometry, poses=True)`` add the sub-cell pose ratslam-python returns where the
+reference's ``get_pc_max`` is a placeholder: the packet's circular centroid (``pc_peak``).
 
 The pose-cell volume lives on the GPU; ``.posecells`` copies it to the host
 on access (and uploads on assignment).  The per-step control scalars are
@@ -21,6 +23,7 @@ import numpy as np
 
 from . import _lib
 from . import filters as F
+from . import pc_peak
 
 PC_DIM_XY = 21           # posecell_network.py:8 (unused by the reference too)
 PC_DIM_TH = 36
@@ -106,13 +109,24 @@ class PoseCellNetwork:
     ``update()`` also exports the new volume into a pinned array before its one host
     sync, and the next ``.posecells`` read returns that array: the ROS node's
     update-then-publish step, ros_simulate.py:134-145, as one round trip).
+    ``cells_to_avg``: radius (1 .. 3) of the wrapped box the sub-cell pose is averaged over
+    (``get_pc_pose``, ``update_pose``, ``run(poses=True)``; ratslam-python's PC_CELLS_TO_AVG);
+    a grid too small for the box raises ValueError when a pose is first asked for.
     Extra keyword arguments are accepted and ignored, like the reference (:24).
     """
 
-    def __init__(self, shape, precision='float32', device=0, readback='lazy', **kwargs):
+    def __init__(self, shape, precision='float32', device=0, readback='lazy',
+                 cells_to_avg=pc_peak.CELLS_TO_AVG, **kwargs):
         if readback not in ('lazy', 'eager'):
             raise ValueError("readback must be 'lazy' or 'eager', got %r" % (readback,))
         self._eager = readback == 'eager'
+        if int(cells_to_avg) != cells_to_avg or not 1 <= cells_to_avg <= pc_peak.MAX_CELLS_TO_AVG:
+            raise ValueError('cells_to_avg must be 1, 2 or 3, got %r' % (cells_to_avg,))
+        self.cells_to_avg = int(cells_to_avg)
+        self._peak_ready = False   # the weights are uploaded when a pose is first asked for
+        # run(poses=True) that raised the reference's LUT KeyError at step s: the (s, 3) poses
+        # of the steps before it (the call's return value is lost to the exception)
+        self.last_poses = None
         self._fresh = None   # eager: the volume exported by the last update()
         if len(shape) != 3:
             raise TypeError('PoseCellNetwork shape must be (X, Y, TH), got %r' % (shape,))
@@ -259,6 +273,60 @@ class PoseCellNetwork:
             _lib.check(self._lib.rs_pc_get_max(self._h, _lib.ptr(out, ctypes.c_int32)))
         return tuple(int(v) for v in out)
 
+    # -- sub-cell pose (pc_peak) --------------------------------
+    def _peak_tables(self):
+        """Upload the centroid's sin / cos weights on first use (under the mutex)."""
+        if not self._peak_ready:
+            pc_peak.check_radius(self.shape, self.cells_to_avg)   # ValueError before any device call
+            tabs = pc_peak.peak_tables(self.shape)
+            _lib.check(self._lib.rs_pc_set_peak_tables(
+                self._h, self.cells_to_avg, *(_lib.ptr(t, ctypes.c_double) for t in tabs)))
+            self._peak_sums = np.empty(6, dtype=np.float64)
+            self._peak_ready = True
+
+    def get_pc_peak(self):
+        """``(cell, sums)``: the stored state's first maximum and the rule's six sums of the
+        box round it (rs_pc_get_peak)."""
+        out = np.empty(3, dtype=np.int32)
+        sums = np.empty(6, dtype=np.float64)
+        with self._mutex:
+            self._peak_tables()
+            _lib.check(self._lib.rs_pc_get_peak(self._h, _lib.ptr(out, ctypes.c_int32),
+                                                _lib.ptr(sums, ctypes.c_double)))
+        return tuple(int(v) for v in out), sums
+
+    def get_pc_pose(self):
+        """Sub-cell pose ``(x, y, th)`` in cell units: the circular centroid of the activity
+        within ``cells_to_avg`` cells of the first maximum."""
+        cell, sums = self.get_pc_peak()
+        return pc_peak.pose_from_sums(sums, cell, self.shape)
+
+    def update_pose(self, v=(0.0, 0.0)):
+        """``update(v)`` that returns the sub-cell pose after the step (and sets ``max_pc``):
+        the centroid is taken on the GPU behind the step, one host round trip."""
+        vtrans, vrot = float(v[0]), float(v[1])
+        with self._mutex:
+            self._peak_tables()
+            self._fresh = None
+            st = self._lib.rs_pc_update_odom_peak(self._h, vtrans, vrot, _lib.ptr(self._out3, ctypes.c_int32),
+                                                  _lib.ptr(self._peak_sums, ctypes.c_double))
+            if st == _lib.RS_OK:
+                self.max_pc = tuple(int(x) for x in self._out3)
+                self._max_valid = True
+                return pc_peak.pose_from_sums(self._peak_sums, self.max_pc, self.shape)
+            if st == _lib.RS_ERR_LUT_KEY:
+                self._max_valid = False
+                F.step_control(vtrans, vrot, self.shape[2], self.filter_table)
+                raise KeyError('path-integration LUT miss')  # pragma: no cover
+            if st != _lib.RS_ERR_CTL_RANGE:
+                _lib.check(st)
+        _, poses = self._run_host_control(np.array([[vtrans, vrot]]), poses=True)
+        return tuple(float(x) for x in poses[0])
+
+    def _poses(self, maxes, sums):
+        return np.array([pc_peak.pose_from_sums(s, m, self.shape) for m, s in zip(maxes, sums)],
+                        dtype=np.float64).reshape(-1, 3)
+
     def update(self, v=(0.0, 0.0)):
         """One network step (posecell_network.py:326-353); returns and stores max_pc.
 
@@ -311,14 +379,18 @@ class PoseCellNetwork:
 
     step = update
 
-    def run(self, odometry):
+    def run(self, odometry, poses=False):
         """``update`` for every row (vtrans, vrot) of ``odometry``; one host round trip.
 
-        Returns an int32 array (n, 3) of max_pc per step.  A LUT KeyError at step
-        s leaves the state the reference would (steps < s done, then steps 1-4 of s).
+        Returns an int32 array (n, 3) of max_pc per step; with ``poses=True``,
+        ``(maxes, poses)``, poses a float64 (n, 3) array of each step's sub-cell pose.
+        A LUT KeyError at step s leaves the state the reference would (steps < s done,
+        then steps 1-4 of s).
         """
         od = np.ascontiguousarray(np.asarray(odometry, dtype=np.float64).reshape(-1, 2))
         n = od.shape[0]
+        if poses:
+            return self._run_poses(od)
         if n == 1 and not self._eager:
             # one step (the ROS node's queue drain, usually): update()'s prebound call,
             # the same library step and the same KeyError / host-control fallbacks
@@ -345,28 +417,67 @@ class PoseCellNetwork:
             raise KeyError('LUT miss at step %d' % bad.value)  # pragma: no cover
         return out
 
-    def _run_host_control(self, od):
+    def _run_poses(self, od):
+        """run(poses=True): rs_pc_run_odom_peaks, with run()'s KeyError and host-control paths."""
+        n = od.shape[0]
+        out = np.empty((n, 3), dtype=np.int32)
+        sums = np.empty((n, 6), dtype=np.float64)
+        bad = ctypes.c_int(-1)
+        with self._mutex:
+            self._peak_tables()
+            self._fresh = None
+            st = self._lib.rs_pc_run_odom_peaks(self._h, n, _lib.ptr(od, ctypes.c_double),
+                                                _lib.ptr(out, ctypes.c_int32), _lib.ptr(sums, ctypes.c_double),
+                                                ctypes.byref(bad))
+            if st in (_lib.RS_OK, _lib.RS_ERR_LUT_KEY):
+                todo = n if st == _lib.RS_OK else bad.value
+                if todo > 0:
+                    self.max_pc = tuple(int(v) for v in out[todo - 1])
+                self._max_valid = st == _lib.RS_OK and todo > 0
+            elif st != _lib.RS_ERR_CTL_RANGE:
+                _lib.check(st)
+        if st == _lib.RS_ERR_CTL_RANGE:
+            return self._run_host_control(od, poses=True)
+        if st == _lib.RS_ERR_LUT_KEY:
+            # (the poses of the steps before the failing one stay readable)
+            self.last_poses = self._poses(out[:bad.value], sums[:bad.value])
+            F.step_control(od[bad.value, 0], od[bad.value, 1], self.shape[2], self.filter_table)
+            raise KeyError('LUT miss at step %d' % bad.value)  # pragma: no cover
+        return out, self._poses(out, sums)
+
+    def _run_host_control(self, od, poses=False):
         """run() with the control computed here (filters.batch_control) and handed to
-        rs_pc_run: for odometry outside the library's control tables."""
+        rs_pc_run (rs_pc_run_peaks with ``poses``): for odometry outside the library's
+        control tables."""
         n = od.shape[0]
         ox, oy, rows, zf, first_bad = F.batch_control(od, self.shape[2], self.filter_table)
         todo = n if first_bad is None else first_bad
         out = np.empty((n, 3), dtype=np.int32)
+        sums = np.empty((n, 6), dtype=np.float64) if poses else None
         with self._mutex:
-            if todo > 0:
+            if todo > 0 and poses:
+                self._peak_tables()
+                _lib.check(self._lib.rs_pc_run_peaks(
+                    self._h, todo, _lib.ptr(ox, ctypes.c_int32), _lib.ptr(oy, ctypes.c_int32),
+                    _lib.ptr(rows, ctypes.c_int32), _lib.ptr(zf, ctypes.c_double),
+                    _lib.ptr(out, ctypes.c_int32), _lib.ptr(sums, ctypes.c_double)))
+            elif todo > 0:
                 _lib.check(self._lib.rs_pc_run(
                     self._h, todo, _lib.ptr(ox, ctypes.c_int32), _lib.ptr(oy, ctypes.c_int32),
                     _lib.ptr(rows, ctypes.c_int32), _lib.ptr(zf, ctypes.c_double),
                     _lib.ptr(out, ctypes.c_int32)))
+            if todo > 0:
                 self.max_pc = tuple(int(v) for v in out[todo - 1])
                 self._max_valid = True
             if first_bad is not None:
                 _lib.check(self._lib.rs_pc_excite(self._h))
                 self._max_valid = False
         if first_bad is not None:
+            if poses:
+                self.last_poses = self._poses(out[:todo], sums[:todo])
             F.step_control(od[first_bad, 0], od[first_bad, 1], self.shape[2], self.filter_table)
             raise KeyError('LUT miss at step %d' % first_bad)  # pragma: no cover
-        return out
+        return (out, self._poses(out, sums)) if poses else out
 
     def device_ms(self):
         """Device time (HIP events) of the last update/run, in ms; recorded only while

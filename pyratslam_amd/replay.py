@@ -36,7 +36,10 @@ same pipeline over an array of frames, batched on the GPU.
 ``--synthetic N`` writes and replays a synthetic one (``synthetic.ros_stream``);
 ``--visual-odometry`` replays either from the camera alone; ``--loop-closure`` keeps a
 ``LinkedExperienceMap`` (every matched frame goes to ``em.on_template``, which links the
-experiences and relaxes the map on the GPU) in place of the dead-reckoned ``ExperienceMap``.
+experiences and relaxes the map on the GPU) in place of the dead-reckoned ``ExperienceMap``;
+``--subcell-peak`` also records the sub-cell pose of every update (``pc_pose``: the activity
+packet's circular centroid, ``PoseCellNetwork.update_pose`` / ``run(poses=True)``), while the
+view templates, the feedback injection and both maps still receive the integer peak cell.
 """
 import argparse
 import json
@@ -75,7 +78,7 @@ class RatslamReplay:
                  x_step=X_STEP, y_step=Y_STEP, match_threshold=MATCH_THRESHOLD,
                  odom_freq=ODOM_FREQ, feedback_energy=None, pcn=None, vts=None, em=None,
                  device=0, precision='float32', batch=True, publish=False,
-                 use_visual_odometry=False, vo=None):
+                 use_visual_odometry=False, vo=None, subcell_peak=False):
         # publish: the node's per-step work in full -- every update reads the whole
         # .posecells volume, as ros_simulate.py:140-145 does to publish it -- so steps
         # go one by one (no batched run()) and the network exports eagerly
@@ -109,6 +112,9 @@ class RatslamReplay:
         # ros_simulate.py:56-57 (Python-2 int / 2, then math.floor)
         self.pcn.inject(1, tuple(int(math.floor(s // 2)) for s in pose_size))
         self.pc_max, self.em_points, self.template_index = [], [], []
+        # the sub-cell pose of every update, recorded next to pc_max (results()['pc_pose'])
+        self.subcell_peak = bool(subcell_peak)
+        self.pc_pose = []
 
     # -- callbacks ---------------------------------------------------------------
     def odom_callback(self, twist):
@@ -135,7 +141,10 @@ class RatslamReplay:
     def update_posecells(self, vtrans, vrot):
         """ros_simulate.py:134-146 (publishing reduced to recording; with publish=True
         the volume is read as the node reads it to publish, :140)."""
-        self.pcn.update((vtrans, vrot))
+        if self.subcell_peak:
+            self.pc_pose.append(tuple(self.pcn.update_pose((vtrans, vrot))))
+        else:
+            self.pcn.update((vtrans, vrot))
         self._record(vtrans, vrot, self.pcn.get_pc_max())
         if self.publish:
             pc = self.pcn.posecells
@@ -160,12 +169,20 @@ class RatslamReplay:
         if not steps:
             return
         if self.batch:
-            maxes = self.pcn.run(np.array(steps, dtype=np.float64))
+            maxes = self._run(np.array(steps, dtype=np.float64))
             for (vt, vr), m in zip(steps, maxes):
                 self._record(vt, vr, m)
         else:
             for vt, vr in steps:
                 self.update_posecells(vt, vr)
+
+    def _run(self, odometry):
+        """``pcn.run``; with ``subcell_peak`` the poses come back with the peaks and are recorded."""
+        if not self.subcell_peak:
+            return self.pcn.run(odometry)
+        maxes, poses = self.pcn.run(odometry, poses=True)
+        self.pc_pose.extend(tuple(float(v) for v in p) for p in poses)
+        return maxes
 
     # -- drivers -----------------------------------------------------------------
     def replay_events(self, events):
@@ -242,7 +259,7 @@ class RatslamReplay:
                 buf.upload(chunk)
                 deltas = self.vo.run((n, buf))
                 peak = tuple(int(v) for v in self.pcn.get_pc_max())
-                maxes = self.pcn.run(deltas)
+                maxes = self._run(deltas)
                 pcs = [peak] + [tuple(int(v) for v in m) for m in maxes[:-1]]
                 idx, _, _ = self.vts.match_frames((n, buf), pcs)
                 self.template_index.extend(int(j) for j in idx)
@@ -256,7 +273,9 @@ class RatslamReplay:
         return self
 
     def results(self):
-        return {'pc_max': np.array(self.pc_max, dtype=np.int64).reshape(-1, 3),
+        return {**({'pc_pose': np.array(self.pc_pose, dtype=np.float64).reshape(-1, 3)}
+                   if self.subcell_peak else {}),
+                'pc_max': np.array(self.pc_max, dtype=np.int64).reshape(-1, 3),
                 'em_points': np.array(self.em_points, dtype=np.float64).reshape(-1, 2),
                 'template_index': np.array(self.template_index, dtype=np.int64),
                 'templates': len(self.vts.templates)}
@@ -300,6 +319,9 @@ def main(argv=None):
                          'its own replica')
     ap.add_argument('--exp-loops', type=int, default=None, metavar='N',
                     help='relaxation sweeps per frame under --loop-closure (default 100)')
+    ap.add_argument('--subcell-peak', action='store_true',
+                    help='record the sub-cell pose of every update (pc_pose): the activity '
+                         'packet\'s circular centroid, computed on the GPU behind each step')
     ap.add_argument('--host-reduce', action='store_true',
                     help='combine the ranks\' keys on the host (several ranks on one GPU)')
     args = ap.parse_args(argv)
@@ -319,7 +341,7 @@ def main(argv=None):
         em = LinkedExperienceMap(exp_loops=EXP_LOOPS if args.exp_loops is None else args.exp_loops,
                                  device=dev)
     r = RatslamReplay(device=dev, precision=args.precision, feedback_energy=args.feedback, vts=vts,
-                      use_visual_odometry=args.visual_odometry, em=em)
+                      use_visual_odometry=args.visual_odometry, em=em, subcell_peak=args.subcell_peak)
     d.barrier()
     t0 = time.perf_counter()
     if args.bag:
@@ -335,6 +357,7 @@ def main(argv=None):
                           'seconds': dt, 'pc_max': res['pc_max'].tolist(),
                           'template_index': res['template_index'].tolist(),
                           'em_points': res['em_points'].tolist(),
+                          **({'pc_pose': res['pc_pose'].tolist()} if args.subcell_peak else {}),
                           **({'experiences': r.em.poses().tolist(),
                               'links': [list(map(float, l)) for l in r.em.links().tolist()]}
                              if em is not None else {})}))
