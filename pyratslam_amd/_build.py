@@ -31,6 +31,7 @@ EXTRA = {'view_templates.hip': ['-mllvm', '-amdgpu-atomic-optimizer-strategy=Non
          'experience_map.hip': ['-ffp-contract=off']}
 HEADERS = [os.path.join(CSRC, 'rs_common.h'), os.path.join(CSRC, 'em_rule.h'),
            os.path.join(CSRC, 'pc_ctl.h'), os.path.join(CSRC, 'pc_peak_rule.h'),
+           os.path.join(CSRC, 'vt_plan.h'),
            os.path.join(INCLUDE, 'ratslam_abi.h')]
 ARCH = os.environ.get('PYRATSLAM_ARCH', 'gfx950')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

@@ -115,8 +115,7 @@ int em_form_for(const rs_em* h, int n) {
 // Room for n experiences; the poses move with a fresh pair of buffers.
 int em_grow_pose(rs_em* h, int n) {
     if (n <= h->cap) return RS_OK;
-    int cap = h->cap > 0 ? h->cap : 1;
-    while (cap < n) cap *= 2;
+    const int cap = rs::grown(h->cap, n, 1);
     RS_HIP(hipStreamSynchronize(h->stream));
     rs::DevBuf<double> a, b;
     RS_TRY(a.reserve(3 * (size_t)cap, "experience poses"));
@@ -143,8 +142,7 @@ int em_upload_topology(rs_em* h) {
     RS_TRY(h->dOff.reserve(noff, "incidence offsets"));
     RS_TRY(h->hOff.reserve(noff, hipHostMallocDefault, "incidence offsets"));
     if ((int64_t)L > h->lcap) {
-        int lcap = h->lcap > 0 ? h->lcap : 16;
-        while ((size_t)lcap < L) lcap *= 2;
+        const int lcap = rs::grown(h->lcap, (int)L, 16);
         h->lcap = 0;
         h->uploaded = 0;                            // the records are sent again, not copied
         RS_TRY(h->dLinks.reserve(lcap, "link records"));

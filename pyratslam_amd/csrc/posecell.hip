@@ -3081,9 +3081,7 @@ template <typename F>
 __attribute__((always_inline)) inline auto pc_by_prec(const rs_pc* h, F&& f) {
     return h->prec == RS_PREC_F32 ? f(float{}) : f(double{});
 }
-// A kernel instance's integer parameter chosen at run time, passed on as a type.
-template <int N>
-using Int = std::integral_constant<int, N>;
+using rs::Int;
 
 // Per-step buffers of a call of n steps, grown in powers of two: the result slots and
 // words always; the control ring (pinned staging + device copy, ctlStride bytes a step)
@@ -3094,8 +3092,7 @@ constexpr unsigned PC_FINE = hipHostMallocMapped | hipHostMallocCoherent;
 
 int pc_grow_steps(rs_pc* h, int n, bool ctl = true) {
     if (n > h->resCap) {
-        int cap = h->resCap > 0 ? h->resCap : 16;
-        while (cap < n) cap *= 2;
+        const int cap = rs::grown(h->resCap, n, 16);
         h->resCap = 0;
         RS_TRY(h->dRes.reserve((size_t)RES_SLOTS * cap));
         // every slot starts zeroed (the excitation's block 0 zeroes a step's slots again
@@ -3113,8 +3110,7 @@ int pc_grow_steps(rs_pc* h, int n, bool ctl = true) {
         h->resCap = cap;
     }
     if (ctl && n > h->ctlCap) {
-        int cap = h->ctlCap > 0 ? h->ctlCap : 16;
-        while (cap < n) cap *= 2;
+        const int cap = rs::grown(h->ctlCap, n, 16);
         h->ctlCap = 0;
         RS_TRY(h->dCtl.reserve(h->ctlStride * cap));
         RS_TRY(h->hCtl.reserve(h->ctlStride * cap, hipHostMallocDefault));
@@ -3309,9 +3305,7 @@ int pc_launch_export(rs_pc* h, double* dst, bool may_poll, int* nb, unsigned* se
 // Room for the six sums of each of a peaks call's n steps (grown in powers of two; every
 // earlier peaks call has synchronised the stream, so no launch still stores into the old block).
 int pc_grow_peaks(rs_pc* h, int n) {
-    size_t cap = 16;
-    while (cap < (size_t)n) cap *= 2;
-    return h->hPeak.reserve(6 * cap, PC_FINE);
+    return h->hPeak.reserve(6 * rs::grown<size_t>(0, (size_t)n, 16), PC_FINE);
 }
 
 // The only launch of pc_peak_kernel: the sums of step s of a peaks call (hPeak[6s ..]) from the

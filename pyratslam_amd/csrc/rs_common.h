@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <utility>
 
 #include "ratslam_abi.h"
@@ -51,6 +52,29 @@ __host__ __device__ inline int wrapi(int v, int n) {
 }
 
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
+
+// The capacity a buffer group of capacity old_cap grows to for `need` elements: old_cap while
+// it suffices, otherwise old_cap (`first` for an empty group) doubled until it does.  How to
+// grow (zeroing the group capacity first, fills, flags, synchronises) stays with the caller.
+template <class T>
+constexpr T grown(T old_cap, T need, T first) {
+    if (need <= old_cap) return old_cap;
+    T cap = old_cap > 0 ? old_cap : first;
+    while (cap < need) cap *= 2;
+    return cap;
+}
+
+// A kernel instance's integer parameter chosen at run time, passed on as a type.
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// Whether p is device memory (hipMemoryTypeDevice exactly); a host pointer is not an error.
+inline bool on_device(const void* p) {
+    hipPointerAttribute_t attr{};
+    const bool dev = hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();
+    return dev;
+}
 
 // A switch read from the environment: on unless the variable is set to "0".
 inline bool env_on(const char* name) { const char* e = std::getenv(name); return !(e && std::strcmp(e, "0") == 0); }

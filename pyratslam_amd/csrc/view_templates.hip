@@ -30,9 +30,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "rs_common.h"
+#include "vt_plan.h"
 
 namespace {
 
@@ -1089,12 +1091,6 @@ constexpr int PF_WAVES = 4;   // waves per thread block
 #define VT_PF_TPW (VT_PF_UNITS == 1 ? 8 / (VT_PF_CGS) : 1)
 #endif
 constexpr int PF_TPW = VT_PF_TPW;
-// 1: the staged planes of the next step are read while this step's chains run.  Kept for
-// A/B builds: measured no faster at two or at four blocks per wave.
-#ifndef VT_PF_AHEAD
-#define VT_PF_AHEAD 0
-#endif
-constexpr bool PF_AHEAD = VT_PF_AHEAD != 0;
 // Column groups per step of the walk: PF_TPW * PF_CPS independent borrow chains, four as
 // the whole unit's two blocks had (two groups of four blocks at once: 117 VGPRs, and
 // measured slower).
@@ -1199,8 +1195,6 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
                     q[i][4] = hi.x; q[i][5] = hi.y; q[i][6] = hi.z; q[i][7] = hi.w;
                 }
             };
-            uint32_t qn[PF_CPS][8];   // (PF_AHEAD) the step after this one's
-            if (PF_AHEAD) read_q(0, 0, 0, qn);
 #pragma unroll
             for (int x = 0; x < PL_NO; ++x) {   // offset o = x - (M-1): start row 4J - o
                 uint32_t lb[PF_TPW];
@@ -1214,16 +1208,7 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
 #pragma unroll
                     for (int cp = 0; cp < PF_CGS; cp += PF_CPS) {
                         uint32_t q[PF_CPS][8], b[PF_TPW][PF_CPS];
-                        if (!PF_AHEAD) {
-                            read_q(x, u, cp, q);
-                        } else {
-#pragma unroll
-                            for (int i = 0; i < PF_CPS; ++i)
-#pragma unroll
-                                for (int k = 0; k < 8; ++k) q[i][k] = qn[i][k];
-                            const bool cw = cp + PF_CPS >= PF_CGS, uw = cw && u + 1 >= PF_NU;
-                            if (!uw || x + 1 < PL_NO) read_q(uw ? x + 1 : x, uw ? 0 : (cw ? u + 1 : u), cw ? 0 : cp + PF_CPS, qn);
-                        }
+                        read_q(x, u, cp, q);
 #pragma unroll
                         for (int k = 0; k < 8; ++k)
 #pragma unroll
@@ -1727,15 +1712,12 @@ int vt_realloc_blocks(rs_vt* h, rs::DevBuf<T>& buf, int64_t keep, int64_t blocks
 }
 
 int64_t local_count_of(const rs_vt* h, int64_t global_count) {
-    if (global_count <= h->rank) return 0;
-    return (global_count - h->rank + h->nranks - 1) / h->nranks;
+    return vt_plan::local_count_of(h->rank, h->nranks, global_count);
 }
 
 int vt_grow_lib(rs_vt* h, int64_t need_slots) {
     if (need_slots <= h->localCap) return RS_OK;
-    int64_t cap = h->localCap > 0 ? h->localCap : 64;
-    while (cap < need_slots) cap *= 2;
-    cap = (int64_t)rs::round_up((size_t)cap, 64);
+    const int64_t cap = (int64_t)rs::round_up((size_t)rs::grown<int64_t>(h->localCap, need_slots, 64), 64);
     RS_TRY(vt_realloc_blocks(h, h->dLib, h->localCap / 64, cap / 64, tblock_bytes(h), "template library growth"));
     if (h->planar) {
         RS_TRY(vt_realloc_blocks(h, h->dLibP, h->localCap / 64, cap / 64, pblock_bytes(h)));
@@ -1762,8 +1744,7 @@ constexpr unsigned VT_FINE = hipHostMallocMapped | hipHostMallocCoherent;
 
 int vt_grow_queries(rs_vt* h, int nq) {
     if (nq <= h->qCap) return RS_OK;
-    int cap = h->qCap > 0 ? h->qCap : 64;
-    while (cap < nq) cap *= 2;
+    const int cap = rs::grown(h->qCap, nq, 64);
     RS_TRY(vt_qraw_idle(h));
     h->qCap = 0;
     h->bestClean = h->bestPending = 0;
@@ -1786,8 +1767,7 @@ int vt_grow_queries(rs_vt* h, int nq) {
 
 int vt_grow_index(rs_vt* h, int n) {
     if (n <= h->idxCap) return RS_OK;
-    int cap = h->idxCap > 0 ? h->idxCap : 64;
-    while (cap < n) cap *= 2;
+    const int cap = rs::grown(h->idxCap, n, 64);
     h->idxCap = 0;
     RS_TRY(h->dSrc.reserve((size_t)cap));
     RS_TRY(h->dDst.reserve((size_t)cap));
@@ -1799,8 +1779,7 @@ int vt_grow_index(rs_vt* h, int n) {
 
 int vt_grow_matrix(rs_vt* h, size_t elems) {
     if (elems <= h->matCap) return RS_OK;
-    size_t cap = h->matCap > 0 ? h->matCap : 4096;
-    while (cap < elems) cap *= 2;
+    const size_t cap = rs::grown<size_t>(h->matCap, elems, 4096);
     h->matCap = 0;
     RS_TRY(h->dMat.reserve(cap));
     RS_TRY(h->hMat.reserve(cap, hipHostMallocDefault));
@@ -1810,8 +1789,7 @@ int vt_grow_matrix(rs_vt* h, size_t elems) {
 
 int vt_grow_cand(rs_vt* h, int64_t slots) {
     if (slots <= h->candCap) return RS_OK;
-    int64_t cap = h->candCap > 0 ? h->candCap : 64;
-    while (cap < slots) cap *= 2;
+    const int64_t cap = rs::grown<int64_t>(h->candCap, slots, 64);
     h->candCap = 0;
     RS_TRY(h->dCand.reserve((size_t)(cap / 64) * tblock_bytes(h) / sizeof(uint4)));
     if (h->planar) {
@@ -1837,17 +1815,10 @@ QueryForms vt_stream_view(const rs_vt* h, size_t q0) {
 
 int vt_build_forms(rs_vt* h, const QueryForms& q, int nq);
 
-// Frozen key scans of at least this many queries prune (RS_VT_PRUNE=1, the default).
-constexpr int VT_PRUNE_MIN_Q = 512;
-
-// Whether a scan of nq queries (forms in q) against `count` slots from block tb0 takes the pruned path.
-// Below VT_PRUNE_MIN_Q queries the call is one latency-bound launch and the prefilter, the
-// list kernels and two scan passes cost more than they save; one template block has
-// nothing to prune.
+// Whether a scan of nq queries (forms in q) against `count` slots from block tb0 takes the
+// pruned path (vt_plan::prunes).
 bool vt_prunes(const rs_vt* h, const QueryForms& q, bool cand, int64_t tb0, int64_t count, int nq) {
-    const int64_t ntb = (count + 63) / 64;
-    return h->H == 64 && !cand && tb0 == 0 && q.qsj && q.qc && ntb <= 65535 &&
-           (h->prune == 2 || (h->prune == 1 && nq >= VT_PRUNE_MIN_Q && ntb >= 2));
+    return vt_plan::prunes(h->H, cand, tb0, q.qsj && q.qc, (count + 63) / 64, h->prune, nq);
 }
 // The plane build ahead of a key scan of the library: compact where that scan will prune.
 // A wrong guess costs a conversion launch (vt_launch_plane), never a result.
@@ -1863,11 +1834,7 @@ uint32_t* vt_compact_for(rs_vt* h, const QueryForms& q, int nq) {
     return compact ? q.qc : nullptr;
 }
 
-// Batches of at most this many queries are read by the plane kernel straight from the
-// pinned staging array (one launch in place of a host-to-device copy and the launch;
-// the kernel leaves the raw bytes in dQraw for the template stores); RS_VT_ZC=0: always
-// the copy.
-constexpr int VT_ZC_MAX = 64;
+// RS_VT_ZC=0: no batch is read in place from the pinned staging array (vt_plan::stages_in_place).
 bool vt_zc_env() { static const bool on = rs::env_on("RS_VT_ZC"); return on; }
 
 // Upload nq raw queries and build their forms (the batch view) on the device.
@@ -1881,7 +1848,7 @@ int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
     // G compares/s through our memcpy into pinned staging, round 5).  The call waits for
     // its keys, which the scan stores after the copy has run, so a pinned caller array is
     // no longer read when it returns.
-    if (h->planar && nq <= VT_ZC_MAX && vt_zc_env()) {
+    if (vt_plan::stages_in_place(h->planar, nq, vt_zc_env())) {
         std::memcpy(h->hQraw.get(), queries, qb);
         h->qrawBusy = true;
         uint32_t* const qc = vt_compact_for(h, q, nq);
@@ -1917,15 +1884,11 @@ int vt_build_forms(rs_vt* h, const QueryForms& q, int nq) { return vt_build_form
 int vt_stage_frames(rs_vt* h, int nf, const uint8_t* frames) {
     RS_CHECK(h->dPix.get(), RS_ERR_STATE, "no subsampling mask: call rs_vt_set_subsample first");
     RS_TRY(vt_grow_queries(h, nf));
-    hipPointerAttribute_t attr{};
-    const bool on_device = hipPointerGetAttributes(&attr, frames) == hipSuccess &&
-                           attr.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();  // a host pointer is not an error
+    const bool on_device = rs::on_device(frames);
     const uint8_t* src = frames;
     if (!on_device) {
         if (nf > h->frameCap) {
-            int cap = h->frameCap > 0 ? h->frameCap : 16;
-            while (cap < nf) cap *= 2;
+            const int cap = rs::grown(h->frameCap, nf, 16);
             h->frameCap = 0;
             RS_TRY(h->dFrames.reserve((size_t)h->frameBytes * cap));
             RS_TRY(h->hFrames.reserve((size_t)h->frameBytes * cap, hipHostMallocDefault));
@@ -1962,26 +1925,112 @@ int vt_store(rs_vt* h, bool cand, const uint8_t* d_raw, int n) {
     return RS_OK;
 }
 
-// Blocks per template block (nqc) for the plane scan.  A block's fixed cost
-// (its template planes, 128 KiB, into VGPRs) is small next to its query batches,
-// and the nqc blocks of a template block balance their batches dynamically, so
-// finer splits fill the last round of resident blocks better; measured on
-// MI355X (tools/scan_split.py, 1,024 queries): nqc = 32 is within 2% of the best
-// split from 12.5k to 100k templates (100k: 18.6 ms at nqc = 1, the previous
-// choice there, vs 15.0 ms), and small libraries gain from up to 4 rounds of
-// blocks (1k: 128 -> 0.183 ms vs 0.199 ms at 32).  nqc >= 8 is a multiple of 8
-// (the XCD query groups).  RS_VT_NQC overrides (A/B).
-int plane_split(int ntb, int nbatch, int slots) {
-    int nqc;
-    if (const char* e = std::getenv("RS_VT_NQC")) {
-        nqc = std::max(1, std::atoi(e));
-    } else {
-        const int fill = (slots + ntb - 1) / ntb;  // blocks per template block for one round
-        nqc = std::max(32, std::min(4 * fill, std::max(128, fill)));
+// f(Int<64>{}) or f(Int<32>{}): the kernel instance for the handle's template height
+// (the scans with an H parameter exist for these two; every other shape is generic).
+template <class F>
+__attribute__((always_inline)) inline auto vt_by_h(const rs_vt* h, F&& f) {
+    return h->H == 64 ? f(rs::Int<64>{}) : f(rs::Int<32>{});
+}
+
+// RS_VT_NQC (A/B, read at every launch): blocks per template block in place of
+// vt_plan::plane_split's model; 0: unset.
+int vt_nqc_env() {
+    const char* e = std::getenv("RS_VT_NQC");
+    return e ? std::max(1, std::atoi(e)) : 0;
+}
+
+// The only launch of vt_keys_export: n keys -> host (pinned, device address), reset behind it.
+void vt_launch_keys_export(rs_vt* h, unsigned long long* keys, int n, unsigned long long* host, int max_blocks) {
+    hipLaunchKernelGGL(vt_keys_export, dim3((unsigned)vt_plan::export_grid(n, max_blocks)), dim3(256), 0, h->stream,
+                       keys, n, host);
+}
+
+// One plane scan launch: its grid, the template planes and sums from block tb0 on, the queries.
+struct PlaneScan {
+    dim3 grid;
+    const uint4* planes;
+    const uint32_t* ts;
+    int ntb;
+    int64_t count;
+    const QueryForms& q;
+    int nq, nqc, rank, nranks;
+};
+template <int H, bool MATRIX, bool LIST>
+void vt_launch_plane_scan(rs_vt* h, const PlaneScan& s, const ScanOut& out, const PlaneList& list) {
+    hipLaunchKernelGGL((vt_scan_plane_kernel<H, MATRIX, LIST>), s.grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream,
+                       s.planes, s.ts, s.ntb, s.count, s.q.qp, s.q.qsum, s.nq, s.nqc, h->dCtr.get(), out, s.rank,
+                       s.nranks, list);
+}
+
+// The pruned scan's buffers for ntb template blocks x nq queries.
+int vt_ensure_prune_buffers(rs_vt* h, int ntb, int nq) {
+    const size_t pairs = (size_t)ntb * nq;
+    if (pairs > h->pruneCap) {
+        const size_t cap = std::max(pairs, 2 * h->pruneCap);
+        h->pruneCap = 0;
+        RS_TRY(h->dMinLB.reserve(cap));
+        RS_TRY(h->dSecond.reserve(cap));
+        RS_TRY(h->dList.reserve(2 * cap));
+        h->pruneCap = cap;
     }
-    nqc = std::min(nqc, std::max(1, nbatch));
-    if (nqc >= 8) nqc &= ~7;
-    return nqc;
+    RS_TRY(h->dTbStar.reserve((size_t)nq));  // (exact)
+    if (ntb > h->listCntCap) {  // zero at first; the list kernels zero what they are about to fill
+        const int cap = std::max(ntb, 2 * h->listCntCap);
+        h->listCntCap = 0;
+        RS_TRY(h->dListCnt.reserve(2 * (size_t)cap + 1));
+        RS_HIP(hipMemsetAsync(h->dListCnt.get(), 0, sizeof(unsigned) * (2 * (size_t)cap + 1), h->stream));
+        h->listCntCap = cap;
+    }
+    if (!h->dPruneStat.get()) {
+        RS_TRY(h->dPruneStat.reserve(3));
+        RS_HIP(hipMemsetAsync(h->dPruneStat.get(), 0, 3 * sizeof(unsigned long long), h->stream));
+    }
+    return RS_OK;
+}
+
+// Pruned scan of the frozen library (vt_prunes): prefilter, verification, then the scan of
+// each query's candidate block (list 1, pass B1) and of the blocks its bound leaves (list 2,
+// pass B2).
+int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
+    const QueryForms& q = s.q;
+    const int ntb = s.ntb, nq = s.nq;
+    if (!h->qcValid) {   // the build before did not expect this scan to prune
+        hipLaunchKernelGGL(vt_qcompact_kernel, dim3((unsigned)nq), dim3(128), 0, h->stream,
+                           reinterpret_cast<const uint4*>(q.qp), reinterpret_cast<uint4*>(q.qc));
+        h->qcValid = true;
+    }
+    RS_TRY(vt_ensure_prune_buffers(h, ntb, nq));
+    const size_t pairs = (size_t)ntb * nq;
+    unsigned* cnt1 = h->dListCnt.get();
+    unsigned* cnt2 = h->dListCnt.get() + h->listCntCap;
+    unsigned* verified = h->dListCnt.get() + 2 * (size_t)h->listCntCap;
+    int* list1 = h->dList.get();
+    int* list2 = h->dList.get() + pairs;
+    const vt_plan::Grid2 pf = vt_plan::prefilter_grid(ntb, nq, PF_WAVES * PF_TPW, PF_NB, VT_PF_GRID_CAP);
+    hipLaunchKernelGGL(vt_prefilter_kernel, dim3((unsigned)pf.x, (unsigned)pf.y), dim3(64 * PF_WAVES), 0, h->stream,
+                       s.planes, ntb, s.count, reinterpret_cast<const uint4*>(q.qc), q.qsj, nq, h->dMinLB.get(),
+                       h->dSecond.get());
+    hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, h->dMinLB.get(),
+                       h->dSecond.get(), ntb, nq, s.planes, s.ts, reinterpret_cast<const uint4*>(q.qc),
+                       reinterpret_cast<uint4*>(q.qp), q.qsum, out.best, s.rank, s.nranks, h->dTbStar.get());
+    const dim3 lgrid((unsigned)((nq + VT_LIST_T - 1) / VT_LIST_T), (unsigned)ntb);
+    hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar.get(), cnt1,
+                       list1, verified, cnt2, ntb);
+    // the passes min into the same keys; the folded export (out.host) needs one
+    // launch to be the last, so a pruned call exports with vt_keys_export
+    ScanOut po = out;
+    po.host = nullptr;
+    po.done = nullptr;
+    vt_launch_plane_scan<64, false, true>(h, s, po, PlaneList{list1, cnt1, nq, VT_LIST_PER_B1});
+    hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB.get(), nq,
+                       h->dTbStar.get(), out.best, cnt2, list2, cnt1, verified, ntb, h->dPruneStat.get());
+    vt_launch_plane_scan<64, false, true>(h, s, po, PlaneList{list2, cnt2, nq, VT_LIST_PER});
+    if (out.host) vt_launch_keys_export(h, out.best, nq, out.host, vt_plan::VT_EXPORT_BLOCKS);
+    RS_HIP(hipGetLastError());
+    h->prunePairs = (int64_t)pairs;
+    h->prunePasses = 2;
+    h->pruneNtb = ntb;
+    return RS_OK;
 }
 
 // Launch a scan of queries [0, nq) (forms in the view q) against `count` slots of lib.
@@ -1989,99 +2038,25 @@ template <bool MATRIX>
 int vt_launch_plane(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int nq, ScanOut out, int rank,
                     int nranks, int64_t tb0) {
     const int ntb = (int)((count + 63) / 64);
-    const int nqc = plane_split(ntb, (nq + PL_NB - 1) / PL_NB, h->planeSlots);
+    const int nqc = vt_plan::plane_split(ntb, (nq + PL_NB - 1) / PL_NB, h->planeSlots, vt_nqc_env());
     if (8 * (size_t)ntb > h->dCtr.capacity()) {  // counters start at zero and every scan leaves them at zero
         const size_t cap = std::max(8 * (size_t)ntb, 2 * h->dCtr.capacity());
         RS_TRY(h->dCtr.reserve(cap));
         RS_HIP(hipMemsetAsync(h->dCtr.get(), 0, sizeof(unsigned) * cap, h->stream));
     }
     RS_CHECK((int64_t)ntb * nqc < (1ll << 31), RS_ERR_ARG, "scan grid too large");
-    const dim3 grid((unsigned)(ntb * nqc));
     const uint4* planes = reinterpret_cast<const uint4*>(
         reinterpret_cast<const uint8_t*>(cand ? h->dCandP.get() : h->dLibP.get()) + (size_t)tb0 * pblock_bytes(h));
     const uint32_t* ts = (cand ? h->dCandTs.get() : h->dLibTs.get()) + (size_t)tb0 * (TS_BLOCK_BYTES / 4);
-    if constexpr (!MATRIX) {
-        // Pruned scan of the frozen library (vt_prunes).
-        if (vt_prunes(h, q, cand, tb0, count, nq)) {
-            if (!h->qcValid) {   // the build before did not expect this scan to prune
-                hipLaunchKernelGGL(vt_qcompact_kernel, dim3((unsigned)nq), dim3(128), 0, h->stream,
-                                   reinterpret_cast<const uint4*>(q.qp), reinterpret_cast<uint4*>(q.qc));
-                h->qcValid = true;
-            }
-            const size_t pairs = (size_t)ntb * nq;
-            if (pairs > h->pruneCap) {
-                const size_t cap = std::max(pairs, 2 * h->pruneCap);
-                h->pruneCap = 0;
-                RS_TRY(h->dMinLB.reserve(cap));
-                RS_TRY(h->dSecond.reserve(cap));
-                RS_TRY(h->dList.reserve(2 * cap));
-                h->pruneCap = cap;
-            }
-            RS_TRY(h->dTbStar.reserve((size_t)nq));  // (exact)
-            if (ntb > h->listCntCap) {  // zero at first; the list kernels zero what they are about to fill
-                const int cap = std::max(ntb, 2 * h->listCntCap);
-                h->listCntCap = 0;
-                RS_TRY(h->dListCnt.reserve(2 * (size_t)cap + 1));
-                RS_HIP(hipMemsetAsync(h->dListCnt.get(), 0, sizeof(unsigned) * (2 * (size_t)cap + 1), h->stream));
-                h->listCntCap = cap;
-            }
-            if (!h->dPruneStat.get()) {
-                RS_TRY(h->dPruneStat.reserve(3));
-                RS_HIP(hipMemsetAsync(h->dPruneStat.get(), 0, 3 * sizeof(unsigned long long), h->stream));
-            }
-            unsigned* cnt1 = h->dListCnt.get();
-            unsigned* cnt2 = h->dListCnt.get() + h->listCntCap;
-            unsigned* verified = h->dListCnt.get() + 2 * (size_t)h->listCntCap;
-            int* list1 = h->dList.get();
-            int* list2 = h->dList.get() + pairs;
-            const int nqb = (nq + PF_NB - 1) / PF_NB, pfx = (ntb + PF_WAVES * PF_TPW - 1) / (PF_WAVES * PF_TPW);
-            const dim3 pgrid((unsigned)pfx, (unsigned)std::min(nqb, std::max(1, VT_PF_GRID_CAP / pfx)));
-            hipLaunchKernelGGL(vt_prefilter_kernel, pgrid, dim3(64 * PF_WAVES), 0, h->stream, planes, ntb, count,
-                               reinterpret_cast<const uint4*>(q.qc), q.qsj, nq, h->dMinLB.get(),
-                               h->dSecond.get());
-            hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, h->dMinLB.get(),
-                               h->dSecond.get(), ntb, nq, planes, ts, reinterpret_cast<const uint4*>(q.qc),
-                               reinterpret_cast<uint4*>(q.qp), q.qsum,
-                               out.best, rank, nranks, h->dTbStar.get());
-            const dim3 lgrid((unsigned)((nq + VT_LIST_T - 1) / VT_LIST_T), (unsigned)ntb);
-            hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar.get(), cnt1,
-                               list1, verified, cnt2, ntb);
-            // the passes min into the same keys; the folded export (out.host) needs one
-            // launch to be the last, so a pruned call exports with vt_keys_export
-            ScanOut po = out;
-            po.host = nullptr;
-            po.done = nullptr;
-            hipLaunchKernelGGL((vt_scan_plane_kernel<64, false, true>), grid, dim3(64 * PL_CG * PL_SPLIT), 0,
-                               h->stream, planes, ts, ntb, count, q.qp, q.qsum, nq, nqc, h->dCtr.get(), po, rank,
-                               nranks, PlaneList{list1, cnt1, nq, VT_LIST_PER_B1});
-            hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB.get(), nq,
-                               h->dTbStar.get(), out.best, cnt2, list2, cnt1, verified, ntb, h->dPruneStat.get());
-            hipLaunchKernelGGL((vt_scan_plane_kernel<64, false, true>), grid, dim3(64 * PL_CG * PL_SPLIT), 0,
-                               h->stream, planes, ts, ntb, count, q.qp, q.qsum, nq, nqc, h->dCtr.get(), po, rank,
-                               nranks, PlaneList{list2, cnt2, nq, VT_LIST_PER});
-            if (out.host)
-                hipLaunchKernelGGL(vt_keys_export, dim3((nq + 255) / 256 < 64 ? (nq + 255) / 256 : 64), dim3(256), 0,
-                                   h->stream, out.best, nq, out.host);
-            RS_HIP(hipGetLastError());
-            h->prunePairs = (int64_t)pairs;
-            h->prunePasses = 2;
-            h->pruneNtb = ntb;
-            return RS_OK;
-        }
-    }
+    const PlaneScan s{dim3((unsigned)(ntb * nqc)), planes, ts, ntb, count, q, nq, nqc, rank, nranks};
+    if constexpr (!MATRIX)
+        if (vt_prunes(h, q, cand, tb0, count, nq)) return vt_launch_pruned(h, s, out);
     if (!h->qpFull) {   // a compact build, and a scan that reads every query's planes
         hipLaunchKernelGGL(vt_qexpand_kernel, dim3((unsigned)nq), dim3(256), 0, h->stream,
                            reinterpret_cast<const uint4*>(q.qc), reinterpret_cast<uint4*>(q.qp));
         h->qpFull = true;
     }
-    if (h->H == 64)
-        hipLaunchKernelGGL((vt_scan_plane_kernel<64, MATRIX>), grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream,
-                           planes, ts, ntb, count, q.qp, q.qsum, nq, nqc, h->dCtr.get(), out, rank,
-                           nranks, PlaneList{});
-    else
-        hipLaunchKernelGGL((vt_scan_plane_kernel<32, MATRIX>), grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream,
-                           planes, ts, ntb, count, q.qp, q.qsum, nq, nqc, h->dCtr.get(), out, rank,
-                           nranks, PlaneList{});
+    vt_by_h(h, [&](auto H) { vt_launch_plane_scan<decltype(H)::value, MATRIX, false>(h, s, out, PlaneList{}); });
     RS_HIP(hipGetLastError());
     return RS_OK;
 }
@@ -2100,24 +2075,18 @@ int vt_launch_scan(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int 
     if (fast && !MATRIX && (int64_t)ntb * nq < 2048 && h->WD <= 8) {
         // few waves of work: spread each template over 8 column lanes
         const dim3 grid((unsigned)((count + 7) / 8), nq);
-        if (h->H == 64)
-            hipLaunchKernelGGL((vt_scan_carry_col_kernel<64, 1>), grid, dim3(64), 0, h->stream,
-                               lib, count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out, rank, nranks);
-        else
-            hipLaunchKernelGGL((vt_scan_carry_col_kernel<32, 1>), grid, dim3(64), 0, h->stream,
-                               lib, count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out, rank, nranks);
+        vt_by_h(h, [&](auto H) {
+            hipLaunchKernelGGL((vt_scan_carry_col_kernel<decltype(H)::value, 1>), grid, dim3(64), 0, h->stream, lib,
+                               count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out, rank, nranks);
+        });
     } else if (fast) {
         constexpr int NQ = 2;
         const int nqg = (nq + NQ - 1) / NQ;
         const dim3 grid((unsigned)(ntb * ((nqg + 7) / 8) * 8));
-        if (h->H == 64)
-            hipLaunchKernelGGL((vt_scan_carry_kernel<64, NQ, MATRIX>), grid, dim3(64), 0,
-                               h->stream, lib, ntb, count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out,
-                               rank, nranks);
-        else
-            hipLaunchKernelGGL((vt_scan_carry_kernel<32, NQ, MATRIX>), grid, dim3(64), 0,
-                               h->stream, lib, ntb, count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out,
-                               rank, nranks);
+        vt_by_h(h, [&](auto H) {
+            hipLaunchKernelGGL((vt_scan_carry_kernel<decltype(H)::value, NQ, MATRIX>), grid, dim3(64), 0, h->stream,
+                               lib, ntb, count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out, rank, nranks);
+        });
     } else {
         hipLaunchKernelGGL((vt_scan_generic_kernel<MATRIX>), dim3((unsigned)(ntb * nq)), dim3(64),
                            0, h->stream, lib, ntb, count, h->H, h->M, h->WD, h->dQf.get(), nq, out, rank,
@@ -2134,7 +2103,6 @@ int vt_launch_scan(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int 
 // arrays a call's copies read are guarded by vt_staging_idle).  A spin that runs out
 // falls back to the stream synchronisation.  RS_VT_POLL=0: always synchronise.
 constexpr unsigned long long KEY_PENDING = 0xFFFFFFFF00000000ull;  // score 2^32-1: never a key
-constexpr int VT_POLL_MAX = 4096;
 bool vt_poll_env() { static const bool on = rs::env_on("RS_VT_POLL"); return on; }
 bool vt_poll_keys(const unsigned long long* w_, int n) {
     const volatile unsigned long long* w = w_;
@@ -2149,6 +2117,33 @@ int vt_staging_idle(rs_vt* h) {
         h->stagingBusy = false;
     }
     return RS_OK;
+}
+
+// Min-reduce n keys in place over the handle's communicator, queued on `stream`.
+int vt_allreduce_min(rs_vt* h, unsigned long long* buf, size_t n, hipStream_t stream) {
+    ncclResult_t r = ncclAllReduce(buf, buf, n, ncclUint64, ncclMin, h->comm, stream);
+    RS_CHECK(r == ncclSuccess, RS_ERR_RCCL, "ncclAllReduce(min) failed: %s", ncclGetErrorString(r));
+    return RS_OK;
+}
+
+// run() between the events ev0 and ev1 when `timed` (rs_vt_last_ms reads them once the
+// stream has run); timedScan says whether the last scan was.
+template <class Run>
+int vt_timed_scan(rs_vt* h, bool timed, Run run) {
+    if (timed) RS_HIP(hipEventRecord(h->ev0, h->stream));
+    RS_TRY(run());
+    if (timed) RS_HIP(hipEventRecord(h->ev1, h->stream));
+    h->timedScan = timed;
+    return RS_OK;
+}
+
+// Packed keys -> (index, score) of a frozen match; NO_KEY (an empty library): (-1, UINT64_MAX).
+void vt_decode_keys(const unsigned long long* key, size_t n, uint64_t* best_score, int64_t* best_index) {
+    for (size_t i = 0; i < n; ++i) {
+        const unsigned long long k = key[i];   // (read once: the outputs may alias it for all the compiler knows)
+        if (best_index) best_index[i] = k == NO_KEY ? -1 : (int64_t)(k & 0xFFFFFFFFull);
+        if (best_score) best_score[i] = k == NO_KEY ? UINT64_MAX : (k >> 32);
+    }
 }
 
 int vt_append_staged(rs_vt* h, const std::vector<std::pair<int, int64_t>>& news) {
@@ -2194,9 +2189,8 @@ int vt_scan_local_impl(rs_vt* h, int nq, const uint8_t* queries, bool frames = f
     h->bestClean = 0;
     const int64_t lc = local_count_of(h, h->count);
     ScanOut out{h->dBest.get(), nullptr, 0};
-    // a plane scan whose keys the host polls exports them itself (its last block): one
-    // launch fewer per call.  Not when they are min-reduced over ranks first.
-    h->keysFolded = fold_ok && h->planar && lc > 0 && vt_poll_env() && !h->timing && nq <= VT_POLL_MAX;
+    // a plane scan whose keys the host polls exports them itself (vt_plan::folds_keys)
+    h->keysFolded = vt_plan::folds_keys(fold_ok, h->planar, lc, vt_poll_env(), h->timing, nq);
     if (h->keysFolded) {
         if (!h->dDone.get()) {
             RS_TRY(h->dDone.reserve(1));
@@ -2206,10 +2200,9 @@ int vt_scan_local_impl(rs_vt* h, int nq, const uint8_t* queries, bool frames = f
         out.host = h->hBest.dev();
         out.done = h->dDone.get();
     }
-    if (h->timing) RS_HIP(hipEventRecord(h->ev0, h->stream));
-    RS_TRY(vt_launch_scan<false>(h, vt_batch_view(h), false, lc, nq, out, h->rank, h->nranks));
-    if (h->timing) RS_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timedScan = h->timing;
+    RS_TRY(vt_timed_scan(h, h->timing, [&] {
+        return vt_launch_scan<false>(h, vt_batch_view(h), false, lc, nq, out, h->rank, h->nranks);
+    }));
     h->stagedQ = nq;
     return RS_OK;
 }
@@ -2226,11 +2219,8 @@ int vt_resolve_impl(rs_vt* h, int nq, const unsigned long long* keys, int mode,
     RS_HIP(hipSetDevice(h->device));
     std::vector<unsigned long long> key(keys, keys + nq);
     if (mode == RS_VT_FROZEN) {
-        for (int i = 0; i < nq; ++i) {
-            if (is_new) is_new[i] = 0;
-            if (best_index) best_index[i] = key[i] == NO_KEY ? -1 : (int64_t)(key[i] & 0xFFFFFFFFull);
-            if (best_score) best_score[i] = key[i] == NO_KEY ? UINT64_MAX : (key[i] >> 32);
-        }
+        if (is_new) std::memset(is_new, 0, (size_t)nq);
+        vt_decode_keys(key.data(), (size_t)nq, best_score, best_index);
         return RS_OK;
     }
     // Candidates: queries that miss the stored library.  Only they can become
@@ -2291,19 +2281,15 @@ int vt_fetch_keys(rs_vt* h, int nq, bool allreduce) {
     if (allreduce && h->nranks > 1) {
         RS_CHECK(h->comm, RS_ERR_STATE, "sharded handle without a communicator: use "
                  "rs_vt_scan_local + an external min-reduction + rs_vt_resolve");
-        ncclResult_t r = ncclAllReduce(h->dBest.get(), h->dBest.get(), (size_t)nq, ncclUint64, ncclMin, h->comm,
-                                       h->stream);
-        RS_CHECK(r == ncclSuccess, RS_ERR_RCCL, "ncclAllReduce(min) failed: %s",
-                 ncclGetErrorString(r));
+        RS_TRY(vt_allreduce_min(h, h->dBest.get(), (size_t)nq, h->stream));
     }
-    const bool poll = vt_poll_env() && !h->timedScan && nq <= VT_POLL_MAX;
+    const bool poll = vt_plan::polls_keys(vt_poll_env(), h->timedScan, nq);
     if (h->keysFolded) {   // the scan's last block exports them (vt_scan_local_impl)
         h->keysFolded = false;
     } else {
         if (poll)
             for (int i = 0; i < nq; ++i) h->hBest.get()[i] = KEY_PENDING;
-        hipLaunchKernelGGL(vt_keys_export, dim3((nq + 255) / 256 < 64 ? (nq + 255) / 256 : 64), dim3(256), 0,
-                           h->stream, h->dBest.get(), nq, h->hBest.dev());
+        vt_launch_keys_export(h, h->dBest.get(), nq, h->hBest.dev(), vt_plan::VT_EXPORT_BLOCKS);
         RS_HIP(hipGetLastError());
     }
     if (!(poll && vt_poll_keys(h->hBest.get(), nq))) {
@@ -2318,15 +2304,106 @@ int vt_fetch_keys(rs_vt* h, int nq, bool allreduce) {
     return RS_OK;
 }
 
-// nb frozen-library batches queued back to back with one host synchronisation:
-// per batch the forms are built straight from the raw queries (device-resident
-// ones in place; host ones through dQraw) and the library is scanned into that
-// batch's row of keys; with a communicator the row is min-reduced over the ranks
-// on a second stream, overlapped with the next batch; one copy brings all rows back.
-constexpr int VT_UP_GROUP = 16;  // host batches per upload group of rs_vt_match_stream
+// nb frozen-library batches queued back to back with one host synchronisation, their keys
+// the rows of dStream; one export launch brings all rows back.  Three paths
+// (vt_plan::StreamPath); each queues its scans and the min-reduction over the ranks of a
+// handle with a communicator.
+
+// Room for the forms of all `total` queries of a call (the fused and host-group paths).
+int vt_grow_stream_forms(rs_vt* h, size_t total) {
+    if (total <= h->qpStreamCap) return RS_OK;
+    h->qpStreamCap = 0;
+    RS_TRY(h->dQpStream.reserve((size_t)PL_CG * plane_ns(h) * 8 * total));
+    RS_TRY(h->dQsumStream.reserve(total));
+    if (h->prune) RS_TRY(h->dQsjStream.reserve((size_t)PF_NU * 16 * total));
+    if (h->prune) RS_TRY(h->dQcStream.reserve((size_t)QC_Q4 * 4 * total));
+    h->qpStreamCap = total;
+    return RS_OK;
+}
+
+// Device-resident batches: one build, one scan (timed when timing is on), one collective.
+int vt_stream_fused(rs_vt* h, size_t total, const uint8_t* queries, int64_t lc) {
+    RS_TRY(vt_grow_stream_forms(h, total));
+    const QueryForms q = vt_stream_view(h, 0);
+    RS_TRY(vt_build_forms(h, q, (int)total, queries));
+    const ScanOut out{h->dStream.get(), nullptr, 0};
+    RS_TRY(vt_timed_scan(h, h->timing, [&] {
+        return vt_launch_scan<false>(h, q, false, lc, (int)total, out, h->rank, h->nranks);
+    }));
+    if (h->comm) RS_TRY(vt_allreduce_min(h, h->dStream.get(), total, h->stream));
+    return RS_OK;
+}
+
+// Host batches in upload groups (vt_plan::host_groups), double-buffered on the upload
+// stream; one collective.  Scans interleaved with upload waits have no single duration:
+// timedScan stays false.
+int vt_stream_host_groups(rs_vt* h, int nb, int nq, const uint8_t* queries, int64_t lc) {
+    const size_t total = (size_t)nb * nq, qb = (size_t)h->H * h->W * nq;
+    RS_TRY(vt_grow_stream_forms(h, total));
+    const vt_plan::HostGroups plan = vt_plan::host_groups(nb);
+    if (!h->ustream) {
+        RS_HIP(hipStreamCreateWithFlags(&h->ustream, hipStreamNonBlocking));
+        for (int i = 0; i < 2; ++i) {
+            RS_HIP(hipEventCreateWithFlags(&h->evUp[i], hipEventDisableTiming));
+            RS_HIP(hipEventCreateWithFlags(&h->evUsed[i], hipEventDisableTiming));
+        }
+    }
+    if (qb * plan.gb > h->upCap) {
+        RS_HIP(hipStreamSynchronize(h->ustream));
+        h->upCap = 0;
+        for (int i = 0; i < 2; ++i) RS_TRY(h->dUp[i].reserve(qb * plan.gb));
+        h->upCap = qb * plan.gb;
+    }
+    for (int g = 0;; ++g) {
+        const vt_plan::HostGroup grp = plan.group(g);
+        if (grp.n == 0) break;
+        const int bi = grp.buf;
+        if (grp.waits) RS_HIP(hipStreamWaitEvent(h->ustream, h->evUsed[bi], 0));
+        RS_HIP(hipMemcpyAsync(h->dUp[bi].get(), queries + qb * grp.b0, qb * grp.n, hipMemcpyHostToDevice, h->ustream));
+        RS_HIP(hipEventRecord(h->evUp[bi], h->ustream));
+        RS_HIP(hipStreamWaitEvent(h->stream, h->evUp[bi], 0));
+        const QueryForms q = vt_stream_view(h, (size_t)grp.b0 * nq);
+        RS_TRY(vt_build_forms(h, q, grp.n * nq, h->dUp[bi].get()));
+        RS_HIP(hipEventRecord(h->evUsed[bi], h->stream));
+        const ScanOut out{h->dStream.get() + (size_t)grp.b0 * nq, nullptr, 0};
+        RS_TRY(vt_launch_scan<false>(h, q, false, lc, grp.n * nq, out, h->rank, h->nranks));
+    }
+    if (h->comm) RS_TRY(vt_allreduce_min(h, h->dStream.get(), total, h->stream));
+    return RS_OK;
+}
+
+// A build and a scan per batch through the batch view (host batches through dQraw).  With a
+// communicator each batch's row is reduced on the collective stream while the next batch's
+// forms and scan run on the main stream (rows are distinct), and the main stream waits for
+// the last.  Several scans: no single duration, timedScan stays false.
+int vt_stream_per_batch(rs_vt* h, int nb, int nq, const uint8_t* queries, bool on_device, int64_t lc) {
+    const size_t qb = (size_t)h->H * h->W * nq;
+    for (int b = 0; b < nb; ++b) {
+        unsigned long long* keys = h->dStream.get() + (size_t)b * nq;
+        const ScanOut out{keys, nullptr, 0};
+        const uint8_t* src = queries + qb * b;
+        if (!on_device) {
+            RS_HIP(hipMemcpyAsync(h->dQraw.get(), src, qb, hipMemcpyHostToDevice, h->stream));
+            src = h->dQraw.get();
+        }
+        RS_TRY(vt_build_forms(h, vt_batch_view(h), nq, src));
+        RS_TRY(vt_launch_scan<false>(h, vt_batch_view(h), false, lc, nq, out, h->rank, h->nranks));
+        if (h->comm) {
+            RS_HIP(hipEventRecord(h->evScan, h->stream));
+            RS_HIP(hipStreamWaitEvent(h->cstream, h->evScan, 0));
+            RS_TRY(vt_allreduce_min(h, keys, (size_t)nq, h->cstream));
+        }
+    }
+    if (h->comm) {
+        RS_HIP(hipEventRecord(h->evComm, h->cstream));
+        RS_HIP(hipStreamWaitEvent(h->stream, h->evComm, 0));
+    }
+    return RS_OK;
+}
 
 int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint64_t* best_score,
                          int64_t* best_index) {
+    // arguments, streams and room for the keys
     RS_CHECK(h, RS_ERR_STATE, "null view-template handle");
     RS_CHECK(nb >= 0 && nq >= 0, RS_ERR_ARG, "negative batch or query count");
     if (nb == 0 || nq == 0) return RS_OK;
@@ -2349,138 +2426,31 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
         h->streamCap = total;
         h->streamClean = false;
     }
-    hipPointerAttribute_t attr{};
-    const bool on_device = hipPointerGetAttributes(&attr, queries) == hipSuccess &&
-                           attr.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();  // a host pointer is not an error
+    const bool on_device = rs::on_device(queries);
     RS_CHECK(!on_device || reinterpret_cast<uintptr_t>(queries) % 8 == 0, RS_ERR_ARG,
              "device-resident queries must be 8-byte aligned");
-    const size_t qb = (size_t)h->H * h->W * nq;
     // the keys start at UINT64_MAX: the export of the previous call reset them
     // (one memset after allocation, or after a call that did not reach its export)
     if (!h->streamClean)
         RS_HIP(hipMemsetAsync(h->dStream.get(), 0xFF, sizeof(unsigned long long) * h->streamCap, h->stream));
     h->streamClean = false;
     h->stagedQ = 0;  // the forms no longer match dQraw
-    h->timedScan = false;
+    h->timedScan = false;  // (only the fused path's one scan is timed)
     const int64_t lc = local_count_of(h, h->count);
-    // Device-resident batches of the plane scan: one launch builds every batch's
-    // planes (nb * nq blocks) and ONE scan launch covers all nb * nq queries (the
-    // batches are independent against a frozen library, and their keys are rows of
-    // one array), so the scan's fixed costs -- each block's template planes into
-    // VGPRs, the last partial round of blocks -- are paid once per call instead of
-    // once per batch; a sharded handle then min-reduces all rows in one collective.
-    // Host batches of the plane scan take the same fused path in groups of up to
-    // VT_UP_GROUP batches: a group is uploaded on the upload stream into one of two
-    // device buffers while the previous group's planes and scan run on the main stream
-    // (the upload of pageable memory holds the host, not the GPU), then its planes are
-    // built in one launch and scanned in one launch.  One batch per launch with its
-    // upload in line (the earlier form) ran at 0.52 of the HBM-resident rate.
-    const bool hostgroups = !on_device && h->planar;
-    const bool allplanes = (on_device && h->planar && nb > 1) || hostgroups;
-    if (allplanes) {
-        if (total > h->qpStreamCap) {
-            h->qpStreamCap = 0;
-            RS_TRY(h->dQpStream.reserve((size_t)PL_CG * plane_ns(h) * 8 * total));
-            RS_TRY(h->dQsumStream.reserve(total));
-            if (h->prune) RS_TRY(h->dQsjStream.reserve((size_t)PF_NU * 16 * total));
-            if (h->prune) RS_TRY(h->dQcStream.reserve((size_t)QC_Q4 * 4 * total));
-            h->qpStreamCap = total;
-        }
-        if (!hostgroups) {
-            const QueryForms q = vt_stream_view(h, 0);
-            RS_TRY(vt_build_forms(h, q, (int)total, queries));
-            const ScanOut out{h->dStream.get(), nullptr, 0};
-            // the one scan of the call, bracketed by events when timing (rs_vt_last_ms)
-            if (h->timing) RS_HIP(hipEventRecord(h->ev0, h->stream));
-            RS_TRY(vt_launch_scan<false>(h, q, false, lc, (int)total, out, h->rank, h->nranks));
-            if (h->timing) RS_HIP(hipEventRecord(h->ev1, h->stream));
-            h->timedScan = h->timing;
-        } else {
-            // a first group of one batch (its upload is the only one not hidden behind a
-            // scan), then groups of about a third of the rest (2 .. VT_UP_GROUP batches: a
-            // scan launch of >= 2 batches keeps the fused launch's efficiency).  10 batches
-            // of 1,024 queries from a pageable array: groups (1, 3, 3, 3) 1.674 ms per call
-            // against 1.745 for (2, 2, 2, 2, 2), 1.759 for threes, 1.762 for fives, 1.920 for
-            // ones, and 1.757 with the caller's array page-locked for the call
-            // (hipHostRegister): the uploads are not the bound (tools/stream_ab.py --host)
-            const int gb = std::min(nb, std::max(2, std::min(VT_UP_GROUP, (nb - 1) / 3)));
-            if (!h->ustream) {
-                RS_HIP(hipStreamCreateWithFlags(&h->ustream, hipStreamNonBlocking));
-                for (int i = 0; i < 2; ++i) {
-                    RS_HIP(hipEventCreateWithFlags(&h->evUp[i], hipEventDisableTiming));
-                    RS_HIP(hipEventCreateWithFlags(&h->evUsed[i], hipEventDisableTiming));
-                }
-            }
-            if (qb * gb > h->upCap) {
-                RS_HIP(hipStreamSynchronize(h->ustream));
-                h->upCap = 0;
-                for (int i = 0; i < 2; ++i) RS_TRY(h->dUp[i].reserve(qb * gb));
-                h->upCap = qb * gb;
-            }
-            const int g1n = nb >= 4 ? 1 : gb;
-            for (int g = 0, b0 = 0, n = 0; b0 < nb; ++g, b0 += n) {
-                n = std::min(g == 0 ? g1n : gb, nb - b0);
-                const int bi = g & 1;
-                // the buffer's group before last has had its planes built
-                if (g >= 2) RS_HIP(hipStreamWaitEvent(h->ustream, h->evUsed[bi], 0));
-                RS_HIP(hipMemcpyAsync(h->dUp[bi].get(), queries + qb * b0, qb * n, hipMemcpyHostToDevice, h->ustream));
-                RS_HIP(hipEventRecord(h->evUp[bi], h->ustream));
-                RS_HIP(hipStreamWaitEvent(h->stream, h->evUp[bi], 0));
-                const QueryForms q = vt_stream_view(h, (size_t)b0 * nq);
-                RS_TRY(vt_build_forms(h, q, n * nq, h->dUp[bi].get()));
-                RS_HIP(hipEventRecord(h->evUsed[bi], h->stream));
-                const ScanOut out{h->dStream.get() + (size_t)b0 * nq, nullptr, 0};
-                RS_TRY(vt_launch_scan<false>(h, q, false, lc, n * nq, out, h->rank, h->nranks));
-            }
-            h->timedScan = false;   // scans interleaved with upload waits: no single duration
-        }
-        if (h->comm) {
-            ncclResult_t r = ncclAllReduce(h->dStream.get(), h->dStream.get(), total, ncclUint64, ncclMin, h->comm,
-                                           h->stream);
-            RS_CHECK(r == ncclSuccess, RS_ERR_RCCL, "ncclAllReduce(min) failed: %s",
-                     ncclGetErrorString(r));
-        }
-    }
-    for (int b = 0; b < nb && !allplanes; ++b) {
-        unsigned long long* keys = h->dStream.get() + (size_t)b * nq;
-        const ScanOut out{keys, nullptr, 0};
-        const uint8_t* src = queries + qb * b;
-        if (!on_device) {
-            RS_HIP(hipMemcpyAsync(h->dQraw.get(), src, qb, hipMemcpyHostToDevice, h->stream));
-            src = h->dQraw.get();
-        }
-        RS_TRY(vt_build_forms(h, vt_batch_view(h), nq, src));
-        RS_TRY(vt_launch_scan<false>(h, vt_batch_view(h), false, lc, nq, out, h->rank, h->nranks));
-        if (h->comm) {
-            // the batch's row is reduced on the collective stream while the next
-            // batch's planes and scan run on the main stream (rows are distinct)
-            RS_HIP(hipEventRecord(h->evScan, h->stream));
-            RS_HIP(hipStreamWaitEvent(h->cstream, h->evScan, 0));
-            ncclResult_t r = ncclAllReduce(keys, keys, (size_t)nq, ncclUint64, ncclMin, h->comm,
-                                           h->cstream);
-            RS_CHECK(r == ncclSuccess, RS_ERR_RCCL, "ncclAllReduce(min) failed: %s",
-                     ncclGetErrorString(r));
-        }
-    }
-    if (h->comm && !allplanes) {
-        RS_HIP(hipEventRecord(h->evComm, h->cstream));
-        RS_HIP(hipStreamWaitEvent(h->stream, h->evComm, 0));
+    // the path's scans and its min-reduction
+    switch (vt_plan::stream_path(on_device, h->planar, nb)) {
+    case vt_plan::StreamPath::Fused: RS_TRY(vt_stream_fused(h, total, queries, lc)); break;
+    case vt_plan::StreamPath::HostGroups: RS_TRY(vt_stream_host_groups(h, nb, nq, queries, lc)); break;
+    case vt_plan::StreamPath::PerBatch: RS_TRY(vt_stream_per_batch(h, nb, nq, queries, on_device, lc)); break;
     }
     // keys -> pinned host memory and reset for the next call, in one queued launch
     // (in place of a device-to-host blit and a memset)
-    hipLaunchKernelGGL(vt_keys_export, dim3(std::min<size_t>((total + 255) / 256, 256)), dim3(256), 0,
-                       h->stream, h->dStream.get(), (int)total, h->hStream.dev());
+    vt_launch_keys_export(h, h->dStream.get(), (int)total, h->hStream.dev(), vt_plan::VT_EXPORT_BLOCKS_STREAM);
     RS_HIP(hipGetLastError());
     RS_HIP(hipStreamSynchronize(h->stream));
     h->streamClean = true;
-    if (!allplanes) h->timedScan = false;  // several scans: no single duration
-    else if (h->timedScan) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
-    for (size_t i = 0; i < total; ++i) {
-        const unsigned long long k = h->hStream.get()[i];
-        if (best_index) best_index[i] = k == NO_KEY ? -1 : (int64_t)(k & 0xFFFFFFFFull);
-        if (best_score) best_score[i] = k == NO_KEY ? UINT64_MAX : (k >> 32);
-    }
+    if (h->timedScan) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
+    vt_decode_keys(h->hStream.get(), total, best_score, best_index);
     return RS_OK;
 }
 
@@ -2511,7 +2481,9 @@ int rs_vt_create(int H, int W, int max_offset, uint64_t thr, int64_t capacity, i
     RS_HIP(hipGetDeviceCount(&ndev));
     RS_CHECK(device >= 0 && device < ndev, RS_ERR_ARG, "device %d not in [0, %d)", device, ndev);
     RS_HIP(hipSetDevice(device));
-    rs_vt* h = new rs_vt();
+    // one failure exit: rs_vt_destroy takes a handle at any stage (null streams and events)
+    std::unique_ptr<rs_vt, int (*)(rs_vt*)> owner(new rs_vt(), rs_vt_destroy);
+    rs_vt* const h = owner.get();
     h->H = H; h->W = W; h->M = max_offset; h->thr = (double)thr; h->device = device;
     h->WD = (W + 3) / 4;
     h->HQ = (H + 3) / 4;
@@ -2520,11 +2492,7 @@ int rs_vt_create(int H, int W, int max_offset, uint64_t thr, int64_t capacity, i
         // A/B switch: "carry" forces the byte-SWAR carry-count scan; "plane" (or
         // unset) keeps the default
         if (std::strcmp(e, "carry") == 0) h->planar = false;
-        else if (std::strcmp(e, "plane") != 0 && e[0] != 0) {
-            rs::set_error("RS_VT_SCAN='%s': expected plane or carry", e);
-            delete h;
-            return RS_ERR_ARG;
-        }
+        else RS_CHECK(std::strcmp(e, "plane") == 0 || e[0] == 0, RS_ERR_ARG, "RS_VT_SCAN='%s': expected plane or carry", e);
     }
     if (h->planar && h->H == 64) {
         // A/B switch: "0" keeps the dense launch everywhere, "force" prunes at any size
@@ -2532,27 +2500,20 @@ int rs_vt_create(int H, int W, int max_offset, uint64_t thr, int64_t capacity, i
         const char* e = std::getenv("RS_VT_PRUNE");
         if (!e || e[0] == 0 || std::strcmp(e, "1") == 0) h->prune = 1;
         else if (std::strcmp(e, "force") == 0) h->prune = 2;
-        else if (std::strcmp(e, "0") != 0) {
-            rs::set_error("RS_VT_PRUNE='%s': expected 0, 1 or force", e);
-            delete h;
-            return RS_ERR_ARG;
-        }
+        else RS_CHECK(std::strcmp(e, "0") == 0, RS_ERR_ARG, "RS_VT_PRUNE='%s': expected 0, 1 or force", e);
     }
     if (h->planar) {
         // resident blocks per CU: the occupancy API, capped by the kernel's own VGPR and
         // LDS arithmetic (the API has read one block high on gfx950 for some SGPR counts)
         int per_cu = 0, cus = 0;
         hipFuncAttributes fa{};
-        const void* fn = h->H == 64 ? reinterpret_cast<const void*>(vt_scan_plane_kernel<64, false>)
-                                    : reinterpret_cast<const void*>(vt_scan_plane_kernel<32, false>);
+        const void* fn = vt_by_h(h, [](auto H) {
+            return reinterpret_cast<const void*>(vt_scan_plane_kernel<decltype(H)::value, false>);
+        });
         hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * PL_CG * PL_SPLIT, 0);
         if (oe == hipSuccess) oe = hipFuncGetAttributes(&fa, fn);
         if (oe == hipSuccess) oe = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-        if (oe != hipSuccess) {
-            rs::set_error("occupancy query failed: %s", hipGetErrorString(oe));
-            delete h;
-            return RS_ERR_HIP;
-        }
+        RS_CHECK(oe == hipSuccess, RS_ERR_HIP, "occupancy query failed: %s", hipGetErrorString(oe));
         const int vg = std::max(8, (fa.numRegs + 7) / 8 * 8);
         const int by_vgpr = (512 / vg) * 4 / (PL_CG * PL_SPLIT);  // waves/SIMD x 4 SIMDs / waves/block
         const int by_lds = fa.sharedSizeBytes > 0 ? (int)(160 * 1024 / fa.sharedSizeBytes) : per_cu;
@@ -2563,19 +2524,11 @@ int rs_vt_create(int H, int W, int max_offset, uint64_t thr, int64_t capacity, i
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&h->ev0);
     if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-    if (e != hipSuccess) {
-        rs::set_error("stream/event creation failed: %s", hipGetErrorString(e));
-        rs_vt_destroy(h);
-        return RS_ERR_HIP;
-    }
-    int s = vt_grow_lib(h, capacity > 0 ? capacity : 64);
-    if (s == RS_OK) s = vt_grow_queries(h, 64);
-    if (s == RS_OK) s = vt_grow_index(h, 64);
-    if (s != RS_OK) {
-        rs_vt_destroy(h);
-        return s;
-    }
-    *out = h;
+    RS_CHECK(e == hipSuccess, RS_ERR_HIP, "stream/event creation failed: %s", hipGetErrorString(e));
+    RS_TRY(vt_grow_lib(h, capacity > 0 ? capacity : 64));
+    RS_TRY(vt_grow_queries(h, 64));
+    RS_TRY(vt_grow_index(h, 64));
+    *out = owner.release();
     return RS_OK;
 }
 
@@ -2778,14 +2731,13 @@ int rs_vt_scores(rs_vt* h, int nq, const uint8_t* queries, int64_t t0, int64_t n
     const int64_t ld = (int64_t)rs::round_up((size_t)span, 64);
     RS_TRY(vt_grow_matrix(h, (size_t)ld * nq));
     ScanOut mo{nullptr, h->dMat.get(), ld};
-    RS_HIP(hipEventRecord(h->ev0, h->stream));
-    RS_TRY(vt_launch_scan<true>(h, vt_batch_view(h), false, span, nq, mo, 0, 1, tb0));
-    RS_HIP(hipEventRecord(h->ev1, h->stream));
+    RS_TRY(vt_timed_scan(h, true, [&] {   // (always timed: rs_vt_last_ms after rs_vt_scores)
+        return vt_launch_scan<true>(h, vt_batch_view(h), false, span, nq, mo, 0, 1, tb0);
+    }));
     RS_HIP(hipMemcpy2DAsync(h->hMat.get(), sizeof(uint32_t) * nt, h->dMat.get() + lo, sizeof(uint32_t) * ld,
                             sizeof(uint32_t) * nt, nq, hipMemcpyDeviceToHost, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));
     RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
-    h->timedScan = true;
     for (size_t i = 0; i < (size_t)nq * nt; ++i) scores[i] = h->hMat.get()[i];
     return RS_OK;
 }

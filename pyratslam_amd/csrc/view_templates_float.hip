@@ -352,8 +352,7 @@ int free_handle(rs_vtf* h) {
 
 int ensure_lib(rs_vtf* h, int64_t want) {
     if (want <= h->cap) return RS_OK;
-    int64_t cap = h->cap > 0 ? h->cap : 1;
-    while (cap < want) cap *= 2;
+    const int64_t cap = rs::grown<int64_t>(h->cap, want, 1);
     const size_t tb = (size_t)h->H * h->W * h->es;
     rs::DevBuf<void> nl;   // the library is copied: the new block before the old one goes
     RS_TRY(nl.reserve((size_t)cap * tb, "float template library"));
@@ -369,8 +368,7 @@ int ensure_lib(rs_vtf* h, int64_t want) {
 int ensure_queries(rs_vtf* h, int nq) {
     if (nq <= h->qCap) return RS_OK;
     RS_HIP(hipStreamSynchronize(h->stream));
-    int cap = h->qCap > 0 ? h->qCap : 1;
-    while (cap < nq) cap *= 2;
+    const int cap = rs::grown(h->qCap, nq, 1);
     h->qCap = 0;
     h->nqStaged = 0;
     RS_TRY(h->dQ.reserve((size_t)cap * h->H * h->W * h->es));

@@ -254,8 +254,7 @@ namespace {
 int vo_grow(rs_vo* h, int n, bool staging) {
     const size_t ps = (size_t)h->wd[0] + h->wd[1], nt = 2 * (size_t)(2 * h->S - 1);
     if (n > h->cap) {
-        int cap = h->cap > 0 ? h->cap : 1;
-        while (cap < n) cap *= 2;
+        const int cap = rs::grown(h->cap, n, 1);
         h->cap = 0;
         RS_TRY(h->dProf.reserve(ps * cap));
         RS_TRY(h->dTab.reserve(nt * cap));
@@ -263,8 +262,7 @@ int vo_grow(rs_vo* h, int n, bool staging) {
         h->cap = cap;
     }
     if (staging && n > h->frameCap) {
-        int cap = h->frameCap > 0 ? h->frameCap : 1;
-        while (cap < n) cap *= 2;
+        const int cap = rs::grown(h->frameCap, n, 1);
         const size_t fb = (size_t)h->H * h->W;
         h->frameCap = 0;
         RS_TRY(h->dFrames.reserve(fb * cap));
@@ -388,10 +386,7 @@ int rs_vo_run(rs_vo* h, int nf, const uint8_t* frames, double* deltas, uint32_t*
     if (nf == 0) return RS_OK;
     RS_CHECK(frames && deltas, RS_ERR_ARG, "null argument");
     RS_HIP(hipSetDevice(h->device));
-    hipPointerAttribute_t attr{};
-    const bool on_device = hipPointerGetAttributes(&attr, frames) == hipSuccess &&
-                           attr.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();  // a host pointer is not an error
+    const bool on_device = rs::on_device(frames);
     // device-resident frames are read in place in one pass; host frames are staged
     // through the pinned buffer VO_CHUNK_FRAMES at a time
     const int chunk = on_device ? nf : std::min(nf, VO_CHUNK_FRAMES);

@@ -1,0 +1,136 @@
+// What the view-template matcher's host side decides before it launches: which scan, how
+// many blocks, which path through rs_vt_match_stream, how its host batches are grouped.
+// Pure functions of integers and booleans, shared by view_templates.hip and by
+// tests/vt_plan_main.cpp (built with the plain host compiler: no HIP include here).  The
+// kernels' own constants (queries per staged batch, template blocks per thread block, the
+// grid cap) come in as arguments.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+
+namespace vt_plan {
+
+// Templates of a library of global_count that live on `rank` of nranks (template g on rank g % nranks).
+inline int64_t local_count_of(int rank, int nranks, int64_t global_count) {
+    if (global_count <= rank) return 0;
+    return (global_count - rank + nranks - 1) / nranks;
+}
+
+// Blocks per template block (nqc) for the plane scan.  A block's fixed cost
+// (its template planes, 128 KiB, into VGPRs) is small next to its query batches,
+// and the nqc blocks of a template block balance their batches dynamically, so
+// finer splits fill the last round of resident blocks better; measured on
+// MI355X (tools/scan_split.py, 1,024 queries): nqc = 32 is within 2% of the best
+// split from 12.5k to 100k templates (100k: 18.6 ms at nqc = 1, the previous
+// choice there, vs 15.0 ms), and small libraries gain from up to 4 rounds of
+// blocks (1k: 128 -> 0.183 ms vs 0.199 ms at 32).  nqc >= 8 is a multiple of 8
+// (the XCD query groups).  nqc_override > 0 (RS_VT_NQC, A/B) replaces the model.
+inline int plane_split(int ntb, int nbatch, int slots, int nqc_override) {
+    int nqc = nqc_override;
+    if (nqc_override <= 0) {
+        const int fill = (slots + ntb - 1) / ntb;  // blocks per template block for one round
+        nqc = std::max(32, std::min(4 * fill, std::max(128, fill)));
+    }
+    nqc = std::min(nqc, std::max(1, nbatch));
+    if (nqc >= 8) nqc &= ~7;
+    return nqc;
+}
+
+// Frozen key scans of at least this many queries prune (RS_VT_PRUNE=1, the default).
+constexpr int VT_PRUNE_MIN_Q = 512;
+constexpr int64_t VT_PRUNE_MAX_TB = 65535;  // the list kernels' grid.y
+
+// Whether a scan of nq queries against ntb template blocks from block tb0 takes the pruned
+// path (forms: the view holds QS_J and compact planes; prune: 0 never, 1 the large scans,
+// 2 "force").  Below VT_PRUNE_MIN_Q queries the call is one latency-bound launch and the
+// prefilter, the list kernels and two scan passes cost more than they save; one template
+// block has nothing to prune.
+inline bool prunes(int H, bool cand, int64_t tb0, bool forms, int64_t ntb, int prune, int nq) {
+    return H == 64 && !cand && tb0 == 0 && forms && ntb <= VT_PRUNE_MAX_TB &&
+           (prune == 2 || (prune == 1 && nq >= VT_PRUNE_MIN_Q && ntb >= 2));
+}
+
+// The prefilter's grid: x covers the template blocks, tb_per_block to a thread block; y the
+// batches of q_per_batch queries, as many as keep the grid within `cap` thread blocks (at
+// least one: the kernel strides over the rest).
+struct Grid2 {
+    int x, y;
+};
+inline Grid2 prefilter_grid(int ntb, int nq, int tb_per_block, int q_per_batch, int cap) {
+    const int nqb = (nq + q_per_batch - 1) / q_per_batch, pfx = (ntb + tb_per_block - 1) / tb_per_block;
+    return {pfx, std::min(nqb, std::max(1, cap / pfx))};
+}
+
+// Thread blocks of 256 of a key export of n keys (the kernel strides): a batch's keys, and
+// the rows of rs_vt_match_stream.
+constexpr int VT_EXPORT_BLOCKS = 64, VT_EXPORT_BLOCKS_STREAM = 256;
+inline int export_grid(int64_t n, int max_blocks) { return (int)std::min<int64_t>((n + 255) / 256, max_blocks); }
+
+// Batches of at most this many queries are read by the plane kernel straight from the
+// pinned staging array (one launch in place of a host-to-device copy and the launch;
+// the kernel leaves the raw bytes in dQraw for the template stores); RS_VT_ZC=0: always
+// the copy.
+constexpr int VT_ZC_MAX = 64;
+inline bool stages_in_place(bool planar, int nq, bool zc_on) { return planar && nq <= VT_ZC_MAX && zc_on; }
+
+// The host polls a call's keys in pinned memory instead of synchronising the stream
+// (RS_VT_POLL=0: never), unless events time the scan or the keys are too many to spin on.
+constexpr int VT_POLL_MAX = 4096;
+inline bool polls_keys(bool poll_on, bool timed, int nq) { return poll_on && !timed && nq <= VT_POLL_MAX; }
+// A plane scan whose keys the host polls exports them itself (its last block): one
+// launch fewer per call.  Not when they are min-reduced over ranks first (fold_ok).
+inline bool folds_keys(bool fold_ok, bool planar, int64_t local_count, bool poll_on, bool timing, int nq) {
+    return fold_ok && planar && local_count > 0 && polls_keys(poll_on, timing, nq);
+}
+
+// rs_vt_match_stream's three ways through nb batches.
+//   Fused: device-resident batches of the plane scan.  One launch builds every batch's
+//     planes and ONE scan launch covers all nb * nq queries (the batches are independent
+//     against a frozen library, and their keys are rows of one array), so the scan's fixed
+//     costs -- each block's template planes into VGPRs, the last partial round of blocks --
+//     are paid once per call instead of once per batch; a sharded handle then min-reduces
+//     all rows in one collective.
+//   HostGroups: host batches of the plane scan take the same path in groups (below).
+//   PerBatch: every other handle, and one device-resident batch: a build and a scan per
+//     batch, each row min-reduced on the collective stream.
+enum class StreamPath { Fused, HostGroups, PerBatch };
+inline StreamPath stream_path(bool on_device, bool planar, int nb) {
+    if (!planar) return StreamPath::PerBatch;
+    if (!on_device) return StreamPath::HostGroups;
+    return nb > 1 ? StreamPath::Fused : StreamPath::PerBatch;
+}
+
+// Host batches in upload groups: a group is uploaded on the upload stream into one of two
+// device buffers while the previous group's planes and scan run on the main stream (the
+// upload of pageable memory holds the host, not the GPU), then its planes are built in one
+// launch and scanned in one launch.  One batch per launch with its upload in line (the
+// earlier form) ran at 0.52 of the HBM-resident rate.
+// A first group of one batch (its upload is the only one not hidden behind a scan), then
+// groups of about a third of the rest (2 .. VT_UP_GROUP batches: a scan launch of >= 2
+// batches keeps the fused launch's efficiency).  10 batches of 1,024 queries from a
+// pageable array: groups (1, 3, 3, 3) 1.674 ms per call against 1.745 for (2, 2, 2, 2, 2),
+// 1.759 for threes, 1.762 for fives, 1.920 for ones, and 1.757 with the caller's array
+// page-locked for the call (hipHostRegister): the uploads are not the bound
+// (tools/stream_ab.py --host).
+constexpr int VT_UP_GROUP = 16;  // host batches per upload group, at most
+struct HostGroup {
+    int b0, n;   // batches [b0, b0 + n); n == 0: past the last group
+    int buf;     // which of the two upload buffers
+    bool waits;  // the buffer's group before last must have had its planes built (evUsed)
+};
+struct HostGroups {
+    int gb;      // batches per group (the capacity of an upload buffer)
+    int first;   // batches of group 0
+    int nb;
+    HostGroup group(int g) const {
+        const int b0 = g == 0 ? 0 : std::min(nb, first + (g - 1) * gb);
+        return {b0, std::min(g == 0 ? first : gb, nb - b0), g & 1, g >= 2};
+    }
+};
+inline HostGroups host_groups(int nb) {
+    const int gb = std::min(nb, std::max(2, std::min(VT_UP_GROUP, (nb - 1) / 3)));
+    return {gb, nb >= 4 ? 1 : gb, nb};
+}
+
+}  // namespace vt_plan

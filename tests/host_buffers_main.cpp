@@ -1,5 +1,5 @@
-// Stand-alone host test of rs::DevBuf / rs::PinnedBuf (rs_common.h) and of the growth idiom
-// the handles write with them.  It links its own definitions of the four allocation
+// Stand-alone host test of rs::DevBuf / rs::PinnedBuf and rs::grown (rs_common.h) and of the
+// growth idiom the handles write with them.  It links its own definitions of the four allocation
 // functions -- malloc-backed, counting live blocks, able to refuse the k-th allocation --
 // in place of rs_common.cpp, so it needs no GPU; tests/test_host_buffers.py builds it with
 // -fsanitize=address,undefined and runs it.  Exit status 0: every check held.
@@ -89,8 +89,7 @@ constexpr int GROUP_BUFS = 4;
 
 int grow(Group* g, int n) {
     if (n <= g->cap) return RS_OK;
-    int cap = g->cap > 0 ? g->cap : 16;
-    while (cap < n) cap *= 2;
+    const int cap = rs::grown(g->cap, n, 16);
     g->cap = 0;
     RS_TRY(g->a.reserve((size_t)cap));
     RS_TRY(g->b.reserve((size_t)cap, hipHostMallocDefault));
@@ -211,9 +210,42 @@ void test_move() {
     CHECK(y.get() == nullptr && y.dev() == nullptr && y.capacity() == 0);
 }
 
+// rs::grown against the loop every growth site wrote out before it, for the first
+// capacities the handles start from (1, 16, 64, 4096) and the three integer types they use.
+template <class T>
+T doubling_loop(T old_cap, T need, T first) {
+    if (need <= old_cap) return old_cap;
+    T cap = old_cap > 0 ? old_cap : first;
+    while (cap < need) cap *= 2;
+    return cap;
+}
+template <class T>
+void test_grown_as() {
+    for (const T first : {(T)1, (T)16, (T)64, (T)4096})
+        for (T old_cap = 0; old_cap <= 64 * first; old_cap = old_cap ? 2 * old_cap : first)
+            for (const T need : {(T)0, (T)1, first - 1, first, first + 1, old_cap, old_cap + 1, 2 * old_cap,
+                                 2 * old_cap + 1, (T)1000, (T)4097, (T)100000, (T)((1 << 30) - 1), (T)(1 << 30)}) {
+                const T cap = rs::grown<T>(old_cap, need, first);
+                CHECK(cap == doubling_loop<T>(old_cap, need, first));
+                CHECK(cap >= need && cap >= old_cap);
+                CHECK(need > old_cap || cap == old_cap);          // within capacity: unchanged
+                CHECK(need <= old_cap || cap / 2 < need || cap == first);   // no further than needed
+                T p = cap;   // first times a power of two, from such a capacity
+                while (p > first && p % 2 == 0) p /= 2;
+                CHECK(cap == 0 || p == first);
+            }
+    static_assert(rs::grown(0, 5, 16) == 16 && rs::grown(16, 17, 16) == 32 && rs::grown(64, 64, 16) == 64, "");
+}
+void test_grown() {
+    test_grown_as<int>();
+    test_grown_as<int64_t>();
+    test_grown_as<size_t>();
+}
+
 }  // namespace
 
 int main() {
+    test_grown();
     test_reserve();
     CHECK(g_live == 0);
     test_failed_reserve();

@@ -285,6 +285,33 @@ def test_match_stream_per_batch_loop(vtmod, shape, t, nb, q):
     assert lib.count() == t
 
 
+def test_match_stream_per_batch_collective_one_rank(vtmod):
+    """A handle without planes and a 1-rank RCCL communicator: rs_vt_match_stream's per-batch
+    path with each batch's row min-reduced on the collective stream (evScan, evComm) while
+    the next batch is built and scanned, the main stream joined before the export.  Twice,
+    so the collective stream and its events are reused: equal to a plain handle's
+    match_stream and to the oracle's minimum and first argmin on every query."""
+    shape, t, nb, q = (32, 30), 70, 3, 33
+    lib_np = V.synthetic_library(t, *shape, seed=t + 5)
+    batches = np.stack([V.synthetic_queries(lib_np, q, seed=100 + b)[0] for b in range(nb)])
+    uid = vtmod.ShardedViewTemplates.unique_id()
+    s = vtmod.ShardedViewTemplates.from_shape(shape, 45000, 0, 1, reducer='rccl', unique_id=uid)
+    plain = new_handle(vtmod, shape, 45000)
+    assert s.scan_form() == 'carry' and plain.scan_form() == 'carry'
+    s.add(lib_np)
+    plain.add(lib_np)
+    ref = np.stack([[V.vt_scores_library(lib_np, x) for x in batch] for batch in batches])
+    ref_idx, ref_score = plain.match_stream(batches)
+    for _ in range(2):
+        idx, score = s.match_stream(batches)
+        assert np.array_equal(idx, ref_idx) and np.array_equal(score, ref_score)
+        assert np.array_equal(score, ref.min(axis=2))
+        assert np.array_equal(idx, ref.argmin(axis=2))
+    assert s.count() == t
+    s.close()
+    plain.close()
+
+
 # --- e. match_frames through the public constructor ---------------------------
 @pytest.mark.parametrize('geom,shape', [(((0, 128), (0, 96), 2, 2, 128, 128), (64, 48)),
                                         (((0, 64), (0, 40), 2, 2, 64, 64), (32, 20))])

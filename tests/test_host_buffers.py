@@ -1,4 +1,4 @@
-"""rs::DevBuf / rs::PinnedBuf (csrc/rs_common.h) and the handles' growth idiom, on the host:
+"""rs::DevBuf / rs::PinnedBuf, rs::grown (csrc/rs_common.h) and the handles' growth idiom, on the host:
 tests/host_buffers_main.cpp defines the four allocation functions itself (malloc-backed,
 counting live blocks, refusing the k-th call) in place of rs_common.cpp, is built with the
 host compiler and -fsanitize=address,undefined, and run as a child process.  The sanitizer

@@ -600,9 +600,11 @@ def test_match_stream_refuses_host_reduced_shards(vtmod):
 
 
 def test_match_stream_collective_path_one_rank(vtmod):
-    """A 1-rank RCCL communicator runs rs_vt_match_stream's collective path on one
-    GPU (each batch's allreduce on the second stream, overlapped with the next
-    batch, then joined): results equal the plain frozen matching."""
+    """A 1-rank RCCL communicator runs rs_vt_match_stream's collective on one GPU.  On a
+    plane-scan handle host batches take the upload-group path: one allreduce over every
+    row on the main stream, after the last group's scan (the per-batch collectives on the
+    second stream are test_byte_scans_gpu's test_match_stream_per_batch_collective_one_rank).
+    Results equal the plain frozen matching."""
     lib_np = V.synthetic_library(700, 64, 32, seed=9)
     batches = np.stack([V.synthetic_queries(lib_np, 300, seed=40 + b)[0] for b in range(6)])
     uid = vtmod.ShardedViewTemplates.unique_id()
