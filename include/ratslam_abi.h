@@ -111,12 +111,19 @@ typedef struct rs_pc_params {
     int precision;              /* RS_PREC_F32 (default) or RS_PREC_F64          */
     double global_inhibition;   /* PC_GLOBAL_INHIB = 0.2 (posecell_network.py:15) */
     /* 3-D excitation kernel K = (ge x ge x ge - gi x gi x gi) * k_scale, the exact
-     * rank-2 form of diff_gaussian(order=3) (posecell_network.py:97-113). */
+     * rank-2 form of diff_gaussian(order=3) (posecell_network.py:97-113).
+     * The excitation is the periodic correlation out[i] = sum_t g[t] * P[i + t - 3] along
+     * each axis, t = 0 .. 6 (the reference's kernel `conv`, convolution.py:228-246): tap t
+     * reads the cell t - 3 places further on, so reversed taps are another kernel. */
     double ge[RS_FILTER_LEN];
     double gi[RS_FILTER_LEN];
     double k_scale;             /* 1 / |sum(ge^3 - gi^3)|                         */
     /* table of 7x7 path-integration filters (posecell_network.py:47,50-59),
      * row-major [nfilters][7][7], F[x][y] with x along the first grid axis.
+     * The path step of layer k, with F = table[fidx[k]], is
+     *   out[i][j][k] = sum_{x,y} F[x][y] * P[(i + x - 3 + ox[k]) % X][(j + y - 3 + oy[k]) % Y][k]
+     * (convolution.py:320-340), and the theta pass that follows it is the same
+     * correlation with zf: out[k] = sum_t zf[t] * P[(k + t - 3) % TH].
      * A table of more than 8 filters needs Y <= 128 (only the "rows" step kernels read
      * a table that is not staged in LDS); on a wider grid rs_pc_create returns
      * RS_ERR_ARG */

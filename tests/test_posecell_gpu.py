@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import _pc_asym
 from conftest import dense_state, load_golden
 from oracle import posecell as P
 
@@ -421,22 +422,8 @@ def test_default_form_by_grid_size(pcn, monkeypatch):
         pcn((64, 64, 36))
 
 
-def _create_with_table(lib, shape, precision, table):
-    """rs_pc_create with an explicit path-filter table; returns the handle."""
-    from pyratslam_amd import _lib
-    from pyratslam_amd import filters as F
-    ge, gi, scale = F.separable_factors()
-    params = _lib.PcParams()
-    params.precision = _lib.RS_PREC_F32 if precision == 'float32' else _lib.RS_PREC_F64
-    params.global_inhibition = 0.2
-    params.ge[:] = list(ge)
-    params.gi[:] = list(gi)
-    params.k_scale = scale
-    params.nfilters = table.shape[0]
-    params.xy_filters = _lib.ptr(table, ctypes.c_double)
-    h = ctypes.c_void_p()
-    _lib.check(lib.rs_pc_create(*shape, ctypes.byref(params), 0, ctypes.byref(h)))
-    return h
+# rs_pc_create with an explicit path-filter table and the product's other parameters
+_create_with_table = _pc_asym.create
 
 
 @pytest.fixture(scope='module')
