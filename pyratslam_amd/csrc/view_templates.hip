@@ -370,9 +370,20 @@ __global__ __launch_bounds__(64) void vt_scan_generic_kernel(const uint4* __rest
 // ===========================================================================
 constexpr int PL_CG = 4;       // column groups of 8 bytes: W = 32
 
-// Per-wave stamp hook, empty in the library: tools/vt_probe.hip defines it (start
-// and end of every wave: realtime, shader clock, hw ids) before it includes this file.
+// Per-wave stamp hook, empty in the library: tools/vt_probe.hip defines it (realtime at
+// the phase ends of every wave of the plane scan, hw ids) before it includes this file.
+// VT_STAMP_BEGIN: kernel entry; VT_STAMP_KNOWN (slot 0): the list's length known and the
+// block stays; then slots 1 the first take returned, 2 first
+// batch staged (past the prologue's barrier), 3 this wave's template planes landed, 4 first
+// batch computed, 5 last batch computed, 6 end.  Every site has `ids` in scope (the probe
+// tells the launches apart by it).
 #ifndef VT_STAMP
+#define VT_STAMP_BEGIN() \
+    do {                 \
+    } while (0)
+#define VT_STAMP_KNOWN() \
+    do {                 \
+    } while (0)
 #define VT_STAMP(slot) \
     do {               \
     } while (0)
@@ -742,7 +753,7 @@ __shared__ uint4 vt_pl_qb[PlaneLds<H>::QP];   // odd batches
 __shared__ uint32_t vt_pl_part0[PL_NB][PL_NK][64];  // u16 pairs of partial counts, summed by ds_add
 __shared__ uint32_t vt_pl_part1[PL_NB][PL_NK][64];
 __shared__ int vt_pl_bidx[3];             // batches taken ahead (ring)
-__shared__ uint32_t vt_pl_ts[16][64];     // TS(o) of the block's 64 templates
+alignas(16) __shared__ uint32_t vt_pl_ts[16][64];  // TS(o) of the block's 64 templates (LDS-DMA, 16 bytes a lane)
 template <int H, int CUR>
 __device__ __forceinline__ uint4* pl_q() {
     if constexpr (CUR == 0) return vt_pl_qa<H>;
@@ -772,8 +783,9 @@ __device__ __forceinline__ void plane_load_units(const uint4* __restrict__ plane
 // planes and adds this batch's partial counts into LDS (ds_add; the per-half
 // sums stay < 2^16, so the packed pairs never carry); after it, wave w < nb
 // finishes query w of the batch and clears its partial slots for batch i+2.
-// Batches are taken one ahead by thread 0; a block stops taking after its first
-// failed take, so every block ends on exactly one failed take (counter rewind).
+// A block's first batch is its own (vt_plan::take_plan); the later ones are taken one
+// ahead by thread 0, and a block stops taking after its first failed take, so every
+// block that takes ends on exactly one failed take (counter rewind).
 // One batch of plane_wave: compute from qcur (staged by the previous batch or the
 // prologue) while this wave's share of the next batch goes global -> LDS into qnxt.
 // CUR is the parity of the iteration (it & 1), so the plane buffers and the
@@ -790,16 +802,55 @@ struct PlaneIds {
     int qc[PL_NB];  // query ids of the batch being computed (wave-uniform)
     int qnv;        // lane: query id of entry (lane & 3) of the batch staged next
 };
-template <int H, int HALF, bool MATRIX, int CUR, bool LIST>
+// One take from the group's counter (thread 0): the batch it stands for, tk.nbatch when the
+// block does not take; a failed take's value is kept for the rewind.
+__device__ __forceinline__ int plane_take(unsigned* __restrict__ ctr, const vt_plan::Take& tk, unsigned& failed) {
+    if (!tk.takes) return tk.nbatch;
+    const unsigned t = atomicAdd(ctr, 1u);
+    const int b = vt_plan::take_batch(tk, t);
+    if (b >= tk.nbatch) failed = t;   // (>= ndyn >= 1: never mistaken for "no failed take")
+    return b;
+}
+// Lanes' share of query batch `src` (ids qx[] with LIST, else consecutive from qn) -> LDS dst.
+template <int H, bool LIST>
+__device__ __forceinline__ void plane_stage(const uint4* __restrict__ qp4, int qn, int nbn, const int (&qx)[PL_NB],
+                                            uint4* dst, int wave, int lane) {
+    using LD = PlaneLds<H>;
+    constexpr int NT = 64 * LD::NW;
+    const int lim = nbn * LD::QW / 4;
+    const uint4* src = qp4 + (size_t)qn * (LD::QW / 4);
+#pragma unroll
+    for (int k = 0; k < (LD::QP + NT - 1) / NT; ++k) {
+        const int i0 = wave * 64 + k * NT;  // wave-uniform
+        if (i0 < lim) {
+            const uint4* from;
+            if constexpr (LIST) {   // a 1 KiB piece may straddle two entries: per-lane source
+                const int i = min(i0 + lane, lim - 1), e = i / (LD::QW / 4);
+                const int id = e == 0 ? qx[0] : e == 1 ? qx[1] : e == 2 ? qx[2] : qx[3];
+                from = qp4 + (size_t)id * (LD::QW / 4) + (i - e * (LD::QW / 4));
+            } else {
+                from = src + min(i0 + lane, lim - 1);
+            }
+            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)from,
+                                             (__attribute__((address_space(3))) void*)(dst + i0), 16, 0, 0);
+        }
+    }
+}
+// FIRST: the block's first batch.  The ids of the batch staged next were asked for only after
+// the prologue's barrier (they depend on the take), so a list block issues that DMA after its
+// first query's walk, when they have long arrived, not in front of the compute.
+template <int H, int HALF, bool MATRIX, int CUR, bool LIST, bool FIRST = false>
 __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HALF>::NUH][8], int it,
-                                            int& bi, int nbatch, int64_t slot, int64_t count,
+                                            int& bi, const vt_plan::Take& tk, int64_t slot, int64_t count,
                                             const uint4* __restrict__ qp4, const uint32_t* __restrict__ qsum,
                                             int nq, unsigned* __restrict__ ctr, int G, int g, ScanOut out,
                                             int rank, int nranks, int wave, int cg, int lane,
                                             unsigned& failed, const int* __restrict__ ids, PlaneIds& pid) {
     using R = PlaneRange<H, HALF>;
     using LD = PlaneLds<H>;
-    constexpr int NO = LD::NO, NK = LD::NK, NS = LD::NS, NT = 64 * LD::NW;
+    constexpr int NO = LD::NO, NK = LD::NK, NS = LD::NS;
+    constexpr bool DEFER = FIRST && LIST;
+    const int nbatch = tk.nbatch;
     if (bi >= nbatch) return false;  // block-uniform
     const uint4* qcur = pl_q<H, CUR>();
     uint4* qnxt = pl_q<H, CUR ^ 1>();
@@ -812,51 +863,40 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
     const int qb = (bi * G + g) * PL_NB, nb = min(PL_NB, nq - qb);
     // The take comes first (its result is waited for); with no next batch there is
     // no further take: this block's failed take was bn.
-    if (tid == 0) {  // the batch after next
-        const unsigned t = bn < nbatch ? atomicAdd(ctr, 1u) : (unsigned)nbatch;
-        vt_pl_bidx[r2] = (int)t;
-        if (bn < nbatch && (int)t >= nbatch) failed = t;
-    }
+    if (tid == 0)  // the batch after next
+        vt_pl_bidx[r2] = bn < nbatch ? plane_take(ctr, tk, failed) : nbatch;
     // the next batch's planes go global -> LDS directly (global_load_lds, 1 KiB per
     // wave-instruction, lane-linear), in flight through this batch's compute
     int qnx[PL_NB] = {0, 0, 0, 0};  // LIST: the next batch's query ids
-    if (bn < nbatch) {
-        const int qn = (bn * G + g) * PL_NB, nbn = min(PL_NB, nq - qn);
-        const int lim = nbn * LD::QW / 4;
-        const uint4* src = qp4 + (size_t)qn * (LD::QW / 4);
-        if constexpr (LIST) {
-            static_assert(PL_NB == 4, "four ids per batch");
+    auto stage_next = [&]() {
+        if (bn < nbatch) {
+            const int qn = (bn * G + g) * PL_NB, nbn = min(PL_NB, nq - qn);
+            if constexpr (LIST) {
+                static_assert(PL_NB == 4, "four ids per batch");
 #pragma unroll
-            for (int e = 0; e < PL_NB; ++e) qnx[e] = __builtin_amdgcn_readlane(pid.qnv, e);
-        }
-#pragma unroll
-        for (int k = 0; k < (LD::QP + NT - 1) / NT; ++k) {
-            const int i0 = wave * 64 + k * NT;  // wave-uniform
-            if (i0 < lim) {
-                const uint4* from;
-                if constexpr (LIST) {   // a 1 KiB piece may straddle two entries: per-lane source
-                    const int i = min(i0 + lane, lim - 1), e = i / (LD::QW / 4);
-                    const int id = e == 0 ? qnx[0] : e == 1 ? qnx[1] : e == 2 ? qnx[2] : qnx[3];
-                    from = qp4 + (size_t)id * (LD::QW / 4) + (i - e * (LD::QW / 4));
-                } else {
-                    from = src + min(i0 + lane, lim - 1);
-                }
-                __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)from,
-                                                 (__attribute__((address_space(3))) void*)(qnxt + i0), 16, 0, 0);
+                for (int e = 0; e < PL_NB; ++e) qnx[e] = __builtin_amdgcn_readlane(pid.qnv, e);
             }
+            plane_stage<H, LIST>(qp4, qn, nbn, qnx, qnxt, wave, lane);
         }
-    }
+    };
+    if constexpr (!DEFER) stage_next();
     const uint32_t* sq0 = reinterpret_cast<const uint32_t*>(qcur) + cg * NS * 8;
     QRow q = plane_read<H, HALF, PlaneWalk<H, HALF>::row(0)>(sq0);
-#pragma unroll 1
-    for (int b = 0; b < nb; ++b) {
+    auto walk = [&](int b) {
         uint32_t a[PL_NA];
 #pragma unroll
         for (int k = 0; k < PL_NA; ++k) a[k] = 0u;
         // (the last query of the batch reads its own first rows again)
         plane_walk<H, HALF, 0>(P, sq0 + b * (PL_CG * NS * 8), sq0 + min(b + 1, nb - 1) * (PL_CG * NS * 8), q, a,
                                part[b], lane);
+    };
+    if constexpr (DEFER) {
+        walk(0);
+        stage_next();
     }
+#pragma unroll 1
+    for (int b = DEFER ? 1 : 0; b < nb; ++b) walk(b);
+    if constexpr (FIRST) VT_STAMP(4);
     // every wave's DMA into qnxt has landed before any wave passes the barrier and
     // reads it (explicit: nothing else guarantees this wait stays in front of it)
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
@@ -885,27 +925,61 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
     return true;
 }
 
+// The block owns batch tk.sb of its group without asking (vt_plan::take_plan), so everything
+// the first batch needs is asked for at once, in one global round trip: the take of the
+// batch after it (thread 0, first: returns come back in order), the first batch's query
+// planes and TS by LDS-DMA, the template planes into P; the partial-count slots are zeroed
+// while they fly.  v0 (LIST): the lane's id of entry (lane & 3) of the static batch, read
+// by the kernel together with the list's length.
 template <int H, int HALF, bool MATRIX, bool LIST>
-__device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes,
+__device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes, const uint32_t* __restrict__ tsum,
                                            int tb, int64_t count, const uint4* __restrict__ qp4,
                                            const uint32_t* __restrict__ qsum, int nq,
                                            unsigned* __restrict__ ctr, int G, int g, ScanOut out,
                                            int rank, int nranks, int wave, int cg, int lane,
-                                           unsigned& failed, const int* __restrict__ ids) {
+                                           unsigned& failed, const int* __restrict__ ids,
+                                           const vt_plan::Take& tk, int v0) {
     using R = PlaneRange<H, HALF>;
-    uint32_t P[R::NUH][8];
-    plane_load_units<H, HALF>(planes, tb, cg, lane, P);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the template planes have landed before the loop
-    const int nbatch = ((nq + PL_NB - 1) / PL_NB - g + G - 1) / G;
-    const int64_t slot = (int64_t)tb * 64 + lane;
-    int bi = vt_pl_bidx[0];
+    const int nbatch = tk.nbatch, tid = wave * 64 + lane;
+    int bi = tk.sb, b1 = nbatch;
+    if (tid == 0) b1 = plane_take(ctr, tk, failed);
+    for (int i = tid; i < PL_NB * PL_NK * 64; i += 64 * PL_CG * PL_SPLIT) {
+        (&vt_pl_part0[0][0][0])[i] = 0u;
+        (&vt_pl_part1[0][0][0])[i] = 0u;
+    }
     PlaneIds pid{{0, 0, 0, 0}, 0};
-    if constexpr (LIST) {   // the ids of the first batch (staged by the prologue) and of the second
-        const int b1 = vt_pl_bidx[1];
-        const int v0 = ids[min((bi * G + g) * PL_NB + (lane & 3), nq - 1)];
-        pid.qnv = b1 < nbatch ? ids[min((b1 * G + g) * PL_NB + (lane & 3), nq - 1)] : 0;
+    if constexpr (LIST) {
 #pragma unroll
         for (int e = 0; e < PL_NB; ++e) pid.qc[e] = __builtin_amdgcn_readlane(v0, e);
+    }
+    {
+        const int qb = (bi * G + g) * PL_NB;
+        plane_stage<H, LIST>(qp4, qb, min(PL_NB, nq - qb), pid.qc, vt_pl_qa<H>, wave, lane);
+    }
+    uint32_t P[R::NUH][8];
+    plane_load_units<H, HALF>(planes, tb, cg, lane, P);
+    static_assert(sizeof(vt_pl_ts) == 4 * 64 * 16, "TS: one 1 KiB DMA piece from each of four waves");
+    if (wave < 4)
+        __builtin_amdgcn_global_load_lds(
+            (__attribute__((address_space(1))) const void*)(reinterpret_cast<const uint4*>(tsum) +
+                                                            (size_t)tb * 256 + wave * 64 + lane),
+            (__attribute__((address_space(3))) void*)(reinterpret_cast<uint4*>(&vt_pl_ts[0][0]) + wave * 64), 16, 0,
+            0);
+    if (tid == 0) {
+        vt_pl_bidx[0] = bi;
+        vt_pl_bidx[1] = b1;
+    }
+    VT_STAMP(1);
+    // every wave's share of the first batch and of TS has landed before any wave passes the
+    // barrier (and this wave's template planes with them: the walk needs them at once)
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    VT_STAMP(3);
+    __syncthreads();
+    VT_STAMP(2);
+    const int64_t slot = (int64_t)tb * 64 + lane;
+    if constexpr (LIST) {   // the ids of the second batch: used after the first query's walk
+        b1 = vt_pl_bidx[1];
+        pid.qnv = b1 < nbatch ? ids[min((b1 * G + g) * PL_NB + (lane & 3), nq - 1)] : 0;
     }
     // unrolled by two: even iterations compute from qa and stage into qb, odd ones
     // the other way round (the prologue staged the first batch into qa)
@@ -913,17 +987,17 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes,
     // LDS accesses after a DMA issued in the same loop iteration but not across the
     // loop header's merge, so the loop body starts with an odd batch, whose compute
     // follows its own DMA issue, not the header.
-    if (!plane_batch<H, HALF, MATRIX, 0, LIST>(P, 0, bi, nbatch, slot, count, qp4, qsum, nq, ctr, G, g, out, rank,
-                                               nranks, wave, cg, lane, failed, ids, pid))
-        return;
-    for (int it = 1;; it += 2) {
-        if (!plane_batch<H, HALF, MATRIX, 1, LIST>(P, it, bi, nbatch, slot, count, qp4, qsum, nq, ctr, G, g, out,
-                                                   rank, nranks, wave, cg, lane, failed, ids, pid))
-            break;
-        if (!plane_batch<H, HALF, MATRIX, 0, LIST>(P, it + 1, bi, nbatch, slot, count, qp4, qsum, nq, ctr, G, g,
-                                                   out, rank, nranks, wave, cg, lane, failed, ids, pid))
-            break;
-    }
+    if (plane_batch<H, HALF, MATRIX, 0, LIST, true>(P, 0, bi, tk, slot, count, qp4, qsum, nq, ctr, G, g, out, rank,
+                                                    nranks, wave, cg, lane, failed, ids, pid))
+        for (int it = 1;; it += 2) {
+            if (!plane_batch<H, HALF, MATRIX, 1, LIST>(P, it, bi, tk, slot, count, qp4, qsum, nq, ctr, G, g, out,
+                                                       rank, nranks, wave, cg, lane, failed, ids, pid))
+                break;
+            if (!plane_batch<H, HALF, MATRIX, 0, LIST>(P, it + 1, bi, tk, slot, count, qp4, qsum, nq, ctr, G, g,
+                                                       out, rank, nranks, wave, cg, lane, failed, ids, pid))
+                break;
+        }
+    VT_STAMP(5);
 }
 
 // nqc blocks serve each template block; they take query batches of PL_NB from
@@ -931,17 +1005,19 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes,
 // favours take more batches and no SIMD is left running a lone straggler.
 // LIST (pruned scan, passes B1 and B2): template block tb scans only the queries of
 // its list, pl.ids[tb * pl.ld ..] (pl.cnt[tb] entries, any order); nq is then the
-// list's length.  A block whose list is empty leaves at once, one whose group has
-// no batch after its one failed take (before it loads its template planes).
+// list's length.  A block whose list is empty, or whose static batch does not exist,
+// leaves at once: before it asks for its template planes, and without a take.
 // Batches per block of a list-driven pass (headline step, ms: 2 -> 0.525, 3 -> 0.515,
 // 4 -> 0.527, 6 -> 0.567).
 // Per launch (PlaneList::per): pass B1's lists hold only the queries the verification
 // left unsettled, about 64 per template block at the headline shape: one batch per
 // block there (VT_LIST_PER_B1; headline step, ms: 1 -> 0.467, 2 -> 0.473, 3 -> 0.493;
 // DESIGN section 19).
-#ifndef VT_LIST_PER
-#define VT_LIST_PER 3
-#endif
+// With the one-round-trip prologue (headline step, ms, per-process
+// medians: B2 1 -> 0.360, 2 -> 0.361, 3 -> 0.371, 4 -> 0.354; B1 2 -> 0.386 beside 0.371),
+// but 100,000 templates: 3 -> 6.59 ms per launch, 4 -> 7.51.  Pass B2 therefore takes
+// vt_plan::list_per(template blocks, resident thread blocks): 4 or 3.  VT_LIST_PER, when
+// defined (A/B builds), replaces the rule.
 #ifndef VT_LIST_PER_B1
 #define VT_LIST_PER_B1 1
 #endif
@@ -949,7 +1025,7 @@ struct PlaneList {
     const int* ids = nullptr;
     const unsigned* cnt = nullptr;
     int ld = 0;
-    int per = VT_LIST_PER;
+    int per = 1;
 };
 template <int H, bool MATRIX, bool LIST = false>
 __global__ __launch_bounds__(64 * PL_CG * PL_SPLIT) __attribute__((amdgpu_waves_per_eu(4, 4)))
@@ -965,73 +1041,50 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
     // several rounds.  XCD-aware: blocks b and b+8 share an XCD (and its L2); with
     // nqc >= 8 (a multiple of 8) the query batches are split into 8 groups by XCD, so
     // each L2 holds one group's planes
+    VT_STAMP_BEGIN();
     const int tb = (int)(blockIdx.x / (unsigned)nqc);
-    const int G = nqc >= 8 ? 8 : 1, g = nqc >= 8 ? (int)(blockIdx.x & 7) : 0;
+    const int l = (int)(blockIdx.x - (unsigned)tb * (unsigned)nqc);   // this block among its template block's
+    const int G = vt_plan::take_groups(nqc), g = vt_plan::take_group_of(l, nqc);
     unsigned* ctr = next_batch + (size_t)tb * 8 + g;
+    const int lane = threadIdx.x & 63;
     const int* ids = nullptr;
+    int v0 = 0;
     if constexpr (LIST) {
+        // One round trip: the list's length and, before it is known, the ids of the batch
+        // this block would own (the first `use` blocks own batches l >> 3 of group l & 7, or
+        // l).  The speculative read stays inside the slab (ld entries); its value is used
+        // only if the length says the entries exist.
+        ids = pl.ids + (size_t)tb * pl.ld;
+        v0 = ids[min(((G == 8 ? l >> 3 : l) * G + g) * PL_NB + (lane & 3), pl.ld - 1)];
         nq = (int)pl.cnt[tb];   // block-uniform
         if (nq == 0) return;
-        ids = pl.ids + (size_t)tb * pl.ld;
         // The grid is sized for a list of every query; a shorter list is served by
         // the first `use` of the template block's nqc blocks, about pl.per batches
         // each, so a block's fixed cost (its template planes, 128 KiB) is not paid per
-        // batch.  The others leave before they touch the batch counter.
-        int use = ((nq + PL_NB - 1) / PL_NB + pl.per - 1) / pl.per;
-        use = nqc >= 8 ? min(nqc, max(8, (use + 7) & ~7)) : min(nqc, max(1, use));
-        if ((int)(blockIdx.x - (unsigned)tb * (unsigned)nqc) >= use) return;
+        // batch.  The others leave before they ask for anything else.
+        const int use = vt_plan::list_use(nq, PL_NB, pl.per, nqc);
+        if (l >= use) return;
         nqc = use;
     }
-    VT_STAMP(0);
+    // Which batches are this block's: its static one, and the counter's (vt_plan.h).  The
+    // nqc / G blocks sharing a counter each end on exactly one failed take when the group
+    // has more batches than blocks, and on none otherwise.
+    const vt_plan::Take tk = vt_plan::take_plan(nq, PL_NB, l, nqc);
+    VT_STAMP_KNOWN();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63, cg = wave % PL_CG, half = wave / PL_CG;
-    const int nbatch = ((nq + PL_NB - 1) / PL_NB - g + G - 1) / G;
-    for (int i = threadIdx.x; i < 16 * 64; i += blockDim.x) vt_pl_ts[i >> 6][i & 63] = tsum[(size_t)tb * 1024 + i];
+    const int cg = wave % PL_CG, half = wave / PL_CG;
     unsigned failed = 0u;  // thread 0: the value of this block's one failed take
-    for (int i = threadIdx.x; i < PL_NB * PL_NK * 64; i += blockDim.x) {
-        (&vt_pl_part0[0][0][0])[i] = 0u;
-        (&vt_pl_part1[0][0][0])[i] = 0u;
-    }
-    if (threadIdx.x == 0) {  // the first batch and the one after it
-        const unsigned a = atomicAdd(ctr, 1u);
-        unsigned b = (unsigned)nbatch;
-        if ((int)a < nbatch) {
-            b = atomicAdd(ctr, 1u);
-            if ((int)b >= nbatch) failed = b;
-        } else {
-            failed = a;
-        }
-        vt_pl_bidx[0] = (int)a;
-        vt_pl_bidx[1] = (int)b;
-    }
-    __syncthreads();
-    if (vt_pl_bidx[0] < nbatch) {  // stage the first batch
-        constexpr int QW4 = PlaneLds<H>::QW / 4;
-        const int qb = (vt_pl_bidx[0] * G + g) * PL_NB, nb = min(PL_NB, nq - qb);
-        const uint4* qp4 = reinterpret_cast<const uint4*>(qp);
-        for (int i = threadIdx.x; i < nb * QW4; i += blockDim.x) {
-            if constexpr (LIST) {
-                const int e = i / QW4;
-                vt_pl_qa<H>[i] = qp4[(size_t)ids[qb + e] * QW4 + (i - e * QW4)];
-            } else {
-                vt_pl_qa<H>[i] = qp4[(size_t)qb * QW4 + i];
-            }
-        }
-    }
-    __syncthreads();
     const uint4* qp4 = reinterpret_cast<const uint4*>(qp);
-    if (LIST && vt_pl_bidx[0] >= nbatch) {   // (block-uniform) no batch for this block
+    if (tk.sb >= tk.nbatch) {   // (block-uniform) no batch for this block: it leaves the counter alone
     } else if (half == 0)
-        plane_wave<H, 0, MATRIX, LIST>(planes, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
-                                       wave, cg, lane, failed, ids);
+        plane_wave<H, 0, MATRIX, LIST>(planes, tsum, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
+                                       wave, cg, lane, failed, ids, tk, v0);
     else
-        plane_wave<H, 1, MATRIX, LIST>(planes, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
-                                       wave, cg, lane, failed, ids);
-    // Each of the nqc / G blocks sharing a counter ends on exactly one failed take, so
-    // the block whose failed take returned (group batches) + nqc / G - 1 is the
-    // counter's last user in this launch: it rewinds the counter for the next launch
-    // (no memset).
-    if (threadIdx.x == 0 && failed == (unsigned)(nbatch + nqc / G - 1)) *ctr = 0u;
+        plane_wave<H, 1, MATRIX, LIST>(planes, tsum, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
+                                       wave, cg, lane, failed, ids, tk, v0);
+    // The block whose failed take returned tk.last is the counter's last user in this
+    // launch: it rewinds the counter for the next launch (no memset).
+    if (threadIdx.x == 0 && tk.takes && failed == tk.last) *ctr = 0u;
     if constexpr (!MATRIX) {
         if (out.host) {   // (kernel argument: uniform)
             // The key export folded into the scan (small calls, vt_scan_local_impl): the
@@ -1064,7 +1117,7 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
             }
         }
     }
-    VT_STAMP(1);
+    VT_STAMP(6);
 }
 
 // --- Pruned plane scan (H = 64, keys): partial-distortion elimination.  Every term
@@ -2024,7 +2077,12 @@ int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
     vt_launch_plane_scan<64, false, true>(h, s, po, PlaneList{list1, cnt1, nq, VT_LIST_PER_B1});
     hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB.get(), nq,
                        h->dTbStar.get(), out.best, cnt2, list2, cnt1, verified, ntb, h->dPruneStat.get());
-    vt_launch_plane_scan<64, false, true>(h, s, po, PlaneList{list2, cnt2, nq, VT_LIST_PER});
+#ifdef VT_LIST_PER
+    const int per2 = VT_LIST_PER;
+#else
+    const int per2 = vt_plan::list_per(ntb, h->planeSlots);
+#endif
+    vt_launch_plane_scan<64, false, true>(h, s, po, PlaneList{list2, cnt2, nq, per2});
     if (out.host) vt_launch_keys_export(h, out.best, nq, out.host, vt_plan::VT_EXPORT_BLOCKS);
     RS_HIP(hipGetLastError());
     h->prunePairs = (int64_t)pairs;

@@ -37,6 +37,68 @@ inline int plane_split(int ntb, int nbatch, int slots, int nqc_override) {
     return nqc;
 }
 
+// --- How the thread blocks of one template block share its query batches (the plane scan's
+// kernel and tests/list_take_main.cpp run this one definition).
+// The blocks serving a template block are numbered l = 0 .. nblk-1.  With nblk >= 8 (a
+// multiple of 8) the batches are dealt to G = 8 groups (batch B belongs to group B % 8, one
+// group per XCD) and block l serves group l & 7; otherwise G = 1.  Each group has its own
+// counter.  Within a group, the k-th of its blocks (k = l >> 3, or l with G = 1) owns the
+// group's batch k statically: it needs no atomic to learn its first batch.  The group's
+// batches from nstat = nblk / G upwards are handed out by the counter: take t is batch
+// nstat + t.  A block keeps taking until its first failed take (a batch index >= nbatch).
+// Only blocks that own a static batch take, and only if the group has dynamic batches at
+// all, so with ndyn > 0 exactly nact = nstat blocks end on one failed take each, the failed
+// takes return ndyn .. ndyn + nact - 1, and the block that sees the largest is the
+// counter's last user in the launch: it stores zero for the next launch.
+#if defined(__HIPCC__)
+#define VT_PLAN_HD __host__ __device__
+#else
+#define VT_PLAN_HD
+#endif
+struct Take {
+    int nbatch;  // batches of this block's group
+    int nstat;   // blocks per counter = batches owned statically, at most
+    int sb;      // this block's static batch (it exists iff sb < nbatch)
+    int ndyn;    // batches the counter hands out
+    bool takes;  // this block touches the counter
+    unsigned last;  // the failed take's value that marks the counter's last user
+};
+VT_PLAN_HD inline int take_groups(int nblk) { return nblk >= 8 ? 8 : 1; }
+VT_PLAN_HD inline int take_group_of(int l, int nblk) { return nblk >= 8 ? (l & 7) : 0; }
+// Blocks that serve a list of nq entries in batches of nb, about `per` batches each, of the
+// nqc the grid holds per template block (a multiple of 8 when nqc >= 8).
+VT_PLAN_HD inline int list_use(int nq, int nb, int per, int nqc) {
+    const int use = ((nq + nb - 1) / nb + per - 1) / per;
+    if (nqc >= 8) {
+        const int u8 = (use + 7) & ~7;
+        return u8 < 8 ? 8 : (u8 > nqc ? nqc : u8);
+    }
+    return use < 1 ? 1 : (use > nqc ? nqc : use);
+}
+// Batches per block of list pass B2 (list_use's per).  A block's prologue is one round trip
+// for 128 KiB of template planes, paid per block, so fewer, longer blocks win while the
+// template blocks are few and their blocks run side by side: 1,000 templates (16 template
+// blocks; per 4 is 1,024 thread blocks there, two full rounds of the 512 resident) step in
+// 0.354 ms with 4 against 0.371 with 3.  With more template blocks than resident thread
+// blocks 3 measured faster (the cause is not established; the GPU is then full of other
+// template blocks' work either way): 100,000 templates (1,563 template blocks) 6.59 ms per launch with 3, 7.51
+// with 4; at 10,000 (157) the two are level.
+inline int list_per(int ntb, int resident_blocks) { return ntb < resident_blocks ? 4 : 3; }
+// Block l of the nblk that serve nq queries in batches of nb.
+VT_PLAN_HD inline Take take_plan(int nq, int nb, int l, int nblk) {
+    const int G = take_groups(nblk), g = take_group_of(l, nblk);
+    Take t;
+    t.nbatch = ((nq + nb - 1) / nb - g + G - 1) / G;
+    t.nstat = nblk / G;
+    t.sb = G == 8 ? (l >> 3) : l;
+    t.ndyn = t.nbatch > t.nstat ? t.nbatch - t.nstat : 0;
+    t.takes = t.ndyn > 0 && t.sb < t.nbatch;
+    t.last = (unsigned)(t.ndyn + (t.nstat < t.nbatch ? t.nstat : t.nbatch) - 1);
+    return t;
+}
+// The batch that take value t stands for (it exists iff it is < nbatch).
+VT_PLAN_HD inline int take_batch(const Take& t, unsigned take) { return t.nstat + (int)take; }
+
 // Frozen key scans of at least this many queries prune (RS_VT_PRUNE=1, the default).
 constexpr int VT_PRUNE_MIN_Q = 512;
 constexpr int64_t VT_PRUNE_MAX_TB = 65535;  // the list kernels' grid.y

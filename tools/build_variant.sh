@@ -11,5 +11,5 @@ $H --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Ipyratslam_amd/csrc -x 
    -mllvm -amdgpu-atomic-optimizer-strategy=None -mllvm -amdgpu-sched-strategy=max-ilp "$@" -c "$src" -o tools/ab/$name.vt.o
 $H --offload-arch=gfx950 -shared -fPIC -o tools/ab/$name.so pyratslam_amd/build/rs_common.o \
    pyratslam_amd/build/posecell.o pyratslam_amd/build/view_templates_float.o \
-   pyratslam_amd/build/visual_odometer.o tools/ab/$name.vt.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+   pyratslam_amd/build/visual_odometer.o pyratslam_amd/build/experience_map.o tools/ab/$name.vt.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 echo tools/ab/$name.so

@@ -30,6 +30,7 @@ def main():
     Q = a.queries
     for T in (int(t) for t in a.templates.split(',')):
         vts = ViewTemplates._from_shape((64, 32), 45000, device=0, capacity=T)
+        vts.set_timing(True)   # device_ms() is of HIP events around the scan
         for lo in range(0, T, 8192):
             vts.add(synthetic.library(min(8192, T - lo), seed=1, first=lo))
         qs, src = synthetic.queries(synthetic.library(min(T, 4096), seed=1), Q, seed=2)
