@@ -1174,6 +1174,129 @@ __device__ __forceinline__ uint32_t wave_min_u32_dpp(uint32_t v) {
                min((uint32_t)__builtin_amdgcn_readlane((int)v, 32), (uint32_t)__builtin_amdgcn_readlane((int)v, 48)));
 }
 
+// The walk adds TS once, after the minimum over the offsets: the staged sums are
+// PF_BIAS - QS_J (PF_BIAS above every QS_J, so every partial bound stays non-negative) and
+// a wave keeps tsb = sum_J TS_J - PF_NU * PF_BIAS per template.
+constexpr uint32_t PF_BIAS = PF_CGS * 32 * 256;
+static_assert(PF_NU * (PF_CGS * 32 * 256 + PF_BIAS) < (1u << 31), "the biased bounds do not wrap");
+
+// The first PF_CGS column groups of the PF_NU units of template blocks tb0 .. tb0 + PF_TPW - 1
+// (lane = template; a block past the library reads the last one and is not valid).
+__device__ __forceinline__ void pf_load(const uint4* __restrict__ planes, int ntb, int64_t count, int tb0, int lane,
+                                        uint32_t (&P)[PF_TPW][PF_NU][PF_CGS][8], uint32_t (&tsb)[PF_TPW],
+                                        bool (&valid)[PF_TPW]) {
+    constexpr int NU = 64 / 4;
+#pragma unroll
+    for (int t = 0; t < PF_TPW; ++t) {
+        const int tbc = min(tb0 + t, ntb - 1);
+        valid[t] = tb0 + t < ntb && (int64_t)(tb0 + t) * 64 + lane < count;
+        tsb[t] = 0u - PF_NU * PF_BIAS;
+#pragma unroll
+        for (int u = 0; u < PF_NU; ++u) {
+#pragma unroll
+            for (int cg = 0; cg < PF_CGS; ++cg) {
+                const uint4* src = planes + ((size_t)(tbc * PL_CG + cg) * NU + pf_unit(u)) * 128 + lane;
+                const uint4 a = src[0], b = src[64];
+                uint32_t(&p)[8] = P[t][u][cg];
+                p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w;
+                p[4] = b.x; p[5] = b.y; p[6] = b.z; p[7] = b.w;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) tsb[t] += (uint32_t)__builtin_popcount(p[k]) << k;
+            }
+        }
+    }
+}
+
+// Stage queries q0 .. q0 + nb - 1 for the walk (the whole thread block; barriers around it
+// are the caller's).
+__device__ __forceinline__ void pf_stage(const uint4* __restrict__ qc4, const uint32_t* __restrict__ qsj, int q0, int nb,
+                                         uint4 (&s_q)[PF_NB][PF_NU][PF_CGS][PL_NO][2],
+                                         uint32_t (&s_qs)[PF_NB][PF_NU][16]) {
+    constexpr int M = FAST_M, S0 = M - 3;
+    for (int i = threadIdx.x; i < nb * PF_QW4; i += blockDim.x) {
+        const int qq = i / PF_QW4, r = i - qq * PF_QW4;
+        const int u = r / (PF_CGS * PL_NO * 2), r2 = r - u * (PF_CGS * PL_NO * 2);
+        const int cg = r2 / (PL_NO * 2), w = r2 - cg * (PL_NO * 2);
+        // start rows 4J-(M-1) .. 4J+(M-1) of column group cg < PF_CGS, two uint4 each,
+        // shifted out of the two aligned units around each
+        (&s_q[0][0][0][0][0])[i] = qc_unit(qc4 + (size_t)(q0 + qq) * QC_Q4, cg,
+                                           4 * pf_unit(u) - (M - 1) - S0 + (w >> 1), w & 1);
+    }
+    if ((int)threadIdx.x < nb * PF_NU * 16)
+        (&s_qs[0][0][0])[threadIdx.x] = PF_BIAS - qsj[(size_t)q0 * PF_NU * 16 + threadIdx.x];
+}
+
+// One staged query against the wave's PF_TPW template blocks: v = (bound << 6) | lane of
+// the block's minimum (the lowest lane on ties), w = min2, the minimum over the block's
+// other valid templates (PF_NONE when it has no other).  Wave-uniform.
+__device__ __forceinline__ void pf_walk(const uint32_t (&P)[PF_TPW][PF_NU][PF_CGS][8], const uint32_t (&tsb)[PF_TPW],
+                                        const bool (&valid)[PF_TPW], const uint4 (&sq)[PF_NU][PF_CGS][PL_NO][2],
+                                        const uint32_t (&sqs)[PF_NU][16], int lane, uint32_t (&v)[PF_TPW],
+                                        uint32_t (&w)[PF_TPW]) {
+    uint32_t m[PF_TPW];
+#pragma unroll
+    for (int t = 0; t < PF_TPW; ++t) m[t] = 0xFFFFFFFFu;
+    // the planes of offset x, unit u, column groups cp .. cp + PF_CPS - 1
+    auto read_q = [&](int x, int u, int cp, uint32_t(&q)[PF_CPS][8]) {
+#pragma unroll
+        for (int i = 0; i < PF_CPS; ++i) {
+            const uint4 lo = sq[u][cp + i][PL_NO - 1 - x][0];
+            const uint4 hi = sq[u][cp + i][PL_NO - 1 - x][1];
+            q[i][0] = lo.x; q[i][1] = lo.y; q[i][2] = lo.z; q[i][3] = lo.w;
+            q[i][4] = hi.x; q[i][5] = hi.y; q[i][6] = hi.z; q[i][7] = hi.w;
+        }
+    };
+#pragma unroll
+    for (int x = 0; x < PL_NO; ++x) {   // offset o = x - (M-1): start row 4J - o
+        uint32_t lb[PF_TPW];
+#pragma unroll
+        for (int t = 0; t < PF_TPW; ++t) lb[t] = 0u;
+#pragma unroll
+        for (int u = 0; u < PF_NU; ++u) {
+            uint32_t c[PF_TPW];
+#pragma unroll
+            for (int t = 0; t < PF_TPW; ++t) c[t] = 0u;
+#pragma unroll
+            for (int cp = 0; cp < PF_CGS; cp += PF_CPS) {
+                uint32_t q[PF_CPS][8], b[PF_TPW][PF_CPS];
+                read_q(x, u, cp, q);
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+#pragma unroll
+                    for (int t = 0; t < PF_TPW; ++t)
+#pragma unroll
+                        for (int i = 0; i < PF_CPS; ++i)
+                            b[t][i] = __builtin_amdgcn_bitop3_b32(P[t][u][cp + i][k], q[i][k],
+                                                                  k ? b[t][i] : 0u, 0x8E);
+#pragma unroll
+                for (int t = 0; t < PF_TPW; ++t)
+#pragma unroll
+                    for (int i = 0; i < PF_CPS; ++i)
+                        asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(c[t]) : "v"(b[t][i]), "v"(c[t]));
+                // (the max-ILP scheduler would pull the reads of many offsets ahead and
+                // spill; the SIMD's other waves cover this wave's read latency)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            const uint32_t qsb = sqs[u][x];   // PF_BIAS - QS_J
+#pragma unroll
+            for (int t = 0; t < PF_TPW; ++t) lb[t] += (c[t] << 8) + qsb;
+        }
+#pragma unroll
+        for (int t = 0; t < PF_TPW; ++t) m[t] = min(m[t], lb[t]);
+    }
+    // All the reductions before the first store: behind a store's branch, a block's
+    // running minimum is used in a later basic block only, its updates sink there,
+    // and the 15 counts per block they wait for stay live (spills at four blocks).
+#pragma unroll
+    for (int t = 0; t < PF_TPW; ++t) {
+        // value and lane in one reduction (a bound is below 2^26; the lowest lane on
+        // ties), then the minimum over the valid templates other than that lane
+        const uint32_t lbt = m[t] + tsb[t];   // >= 0 in all; the parts wrap mod 2^32
+        v[t] = wave_min_u32_dpp(valid[t] ? (lbt << 6) | (uint32_t)lane : 0xFFFFFFFFu);
+        w[t] = wave_min_u32_dpp(valid[t] && lane != (int)(v[t] & 63u) ? lbt : PF_NONE);
+    }
+}
+
 // minlb[tb * nq + q], and second[tb * nq + q] = (min2 << 6) | lane: the lane that holds
 // the block's minimum (the lowest on ties) and min2, the minimum over the block's other
 // valid templates (PF_NONE when it has no other).  The pick verifies that one template
@@ -1188,7 +1311,6 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
                                                                     const uint32_t* __restrict__ qsj, int nq,
                                                                     uint32_t* __restrict__ minlb,
                                                                     uint32_t* __restrict__ second) {
-    constexpr int M = FAST_M, NU = 64 / 4, S0 = M - 3;
     static_assert(PF_CGS % PF_CPS == 0 && PF_CGS >= 1 && PF_CGS <= PL_CG, "whole steps of column groups, of the unit");
     static_assert(PF_NU * PF_CGS * 32 * 255 < (int)PF_NONE, "a bound and a lane fit one word");
     __shared__ uint4 s_q[PF_NB][PF_NU][PF_CGS][PL_NO][2];
@@ -1196,108 +1318,19 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int tb0 = (blockIdx.x * PF_WAVES + wave) * PF_TPW;
     const bool live = tb0 < ntb;   // wave-uniform; a wave past the library still stages
-    uint32_t P[PF_TPW][PF_NU][PF_CGS][8], ts[PF_TPW][PF_NU];
+    uint32_t P[PF_TPW][PF_NU][PF_CGS][8], tsb[PF_TPW];
     bool valid[PF_TPW];
-#pragma unroll
-    for (int t = 0; t < PF_TPW; ++t) {
-        const int tbc = min(tb0 + t, ntb - 1);
-        valid[t] = tb0 + t < ntb && (int64_t)(tb0 + t) * 64 + lane < count;
-#pragma unroll
-        for (int u = 0; u < PF_NU; ++u) {
-            ts[t][u] = 0u;
-#pragma unroll
-            for (int cg = 0; cg < PF_CGS; ++cg) {
-                const uint4* src = planes + ((size_t)(tbc * PL_CG + cg) * NU + pf_unit(u)) * 128 + lane;
-                const uint4 a = src[0], b = src[64];
-                uint32_t(&p)[8] = P[t][u][cg];
-                p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w;
-                p[4] = b.x; p[5] = b.y; p[6] = b.z; p[7] = b.w;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) ts[t][u] += (uint32_t)__builtin_popcount(p[k]) << k;
-            }
-        }
-    }
+    pf_load(planes, ntb, count, tb0, lane, P, tsb, valid);
     for (int q0 = blockIdx.y * PF_NB; q0 < nq; q0 += gridDim.y * PF_NB) {   // block-uniform
         const int nb = min(PF_NB, nq - q0);
         __syncthreads();   // the batch before has been read
-        for (int i = threadIdx.x; i < nb * PF_QW4; i += blockDim.x) {
-            const int qq = i / PF_QW4, r = i - qq * PF_QW4;
-            const int u = r / (PF_CGS * PL_NO * 2), r2 = r - u * (PF_CGS * PL_NO * 2);
-            const int cg = r2 / (PL_NO * 2), w = r2 - cg * (PL_NO * 2);
-            // start rows 4J-(M-1) .. 4J+(M-1) of column group cg < PF_CGS, two uint4 each,
-            // shifted out of the two aligned units around each
-            (&s_q[0][0][0][0][0])[i] = qc_unit(qc4 + (size_t)(q0 + qq) * QC_Q4, cg,
-                                               4 * pf_unit(u) - (M - 1) - S0 + (w >> 1), w & 1);
-        }
-        if ((int)threadIdx.x < nb * PF_NU * 16)
-            (&s_qs[0][0][0])[threadIdx.x] = qsj[(size_t)q0 * PF_NU * 16 + threadIdx.x];
+        pf_stage(qc4, qsj, q0, nb, s_q, s_qs);
         __syncthreads();
         if (!live) continue;
 #pragma unroll 1
         for (int qq = 0; qq < nb; ++qq) {
-            uint32_t m[PF_TPW];
-#pragma unroll
-            for (int t = 0; t < PF_TPW; ++t) m[t] = 0xFFFFFFFFu;
-            // the planes of offset x, unit u, column groups cp .. cp + PF_CPS - 1
-            auto read_q = [&](int x, int u, int cp, uint32_t(&q)[PF_CPS][8]) {
-#pragma unroll
-                for (int i = 0; i < PF_CPS; ++i) {
-                    const uint4 lo = s_q[qq][u][cp + i][PL_NO - 1 - x][0];
-                    const uint4 hi = s_q[qq][u][cp + i][PL_NO - 1 - x][1];
-                    q[i][0] = lo.x; q[i][1] = lo.y; q[i][2] = lo.z; q[i][3] = lo.w;
-                    q[i][4] = hi.x; q[i][5] = hi.y; q[i][6] = hi.z; q[i][7] = hi.w;
-                }
-            };
-#pragma unroll
-            for (int x = 0; x < PL_NO; ++x) {   // offset o = x - (M-1): start row 4J - o
-                uint32_t lb[PF_TPW];
-#pragma unroll
-                for (int t = 0; t < PF_TPW; ++t) lb[t] = 0u;
-#pragma unroll
-                for (int u = 0; u < PF_NU; ++u) {
-                    uint32_t c[PF_TPW];
-#pragma unroll
-                    for (int t = 0; t < PF_TPW; ++t) c[t] = 0u;
-#pragma unroll
-                    for (int cp = 0; cp < PF_CGS; cp += PF_CPS) {
-                        uint32_t q[PF_CPS][8], b[PF_TPW][PF_CPS];
-                        read_q(x, u, cp, q);
-#pragma unroll
-                        for (int k = 0; k < 8; ++k)
-#pragma unroll
-                            for (int t = 0; t < PF_TPW; ++t)
-#pragma unroll
-                                for (int i = 0; i < PF_CPS; ++i)
-                                    b[t][i] = __builtin_amdgcn_bitop3_b32(P[t][u][cp + i][k], q[i][k],
-                                                                          k ? b[t][i] : 0u, 0x8E);
-#pragma unroll
-                        for (int t = 0; t < PF_TPW; ++t)
-#pragma unroll
-                            for (int i = 0; i < PF_CPS; ++i)
-                                asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(c[t]) : "v"(b[t][i]), "v"(c[t]));
-                        // (the max-ILP scheduler would pull the reads of many offsets ahead and
-                        // spill; the SIMD's other waves cover this wave's read latency)
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    const uint32_t qs = s_qs[qq][u][x];
-#pragma unroll
-                    for (int t = 0; t < PF_TPW; ++t)
-                        lb[t] += (c[t] << 8) + (ts[t][u] - qs);   // >= 0 in all; the parts wrap mod 2^32
-                }
-#pragma unroll
-                for (int t = 0; t < PF_TPW; ++t) m[t] = min(m[t], lb[t]);
-            }
-            // All the reductions before the first store: behind a store's branch, a block's
-            // running minimum is used in a later basic block only, its updates sink there,
-            // and the 15 counts per block they wait for stay live (spills at four blocks).
             uint32_t v[PF_TPW], w[PF_TPW];
-#pragma unroll
-            for (int t = 0; t < PF_TPW; ++t) {
-                // value and lane in one reduction (a bound is below 2^26; the lowest lane on
-                // ties), then the minimum over the valid templates other than that lane
-                v[t] = wave_min_u32_dpp(valid[t] ? (m[t] << 6) | (uint32_t)lane : 0xFFFFFFFFu);
-                w[t] = wave_min_u32_dpp(valid[t] && lane != (int)(v[t] & 63u) ? m[t] : PF_NONE);
-            }
+            pf_walk(P, tsb, valid, s_q[qq], s_qs[qq], lane, v, w);
             if (lane == 0) {
 #pragma unroll
                 for (int t = 0; t < PF_TPW; ++t)
@@ -1357,23 +1390,28 @@ __device__ __forceinline__ void list_append(bool in, int q, unsigned* __restrict
 // (the rule of vt_prune_rest_kernel: list2).  Nothing else reads a query's full planes.
 constexpr int VT_VQ4 = PlaneLds<64>::QW / 4;   // uint4 of a query's planes
 constexpr int VT_VR = QC_NA + 7;               // staged unit rows: 3 never-counted, the units, the zero unit, 3 more
-__global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __restrict__ minlb,
-                                                             const uint32_t* __restrict__ second, int ntb, int nq,
-                                                             const uint4* __restrict__ planes,
-                                                             const uint32_t* __restrict__ tsum,
-                                                             const uint4* __restrict__ qc4,
-                                                             uint4* __restrict__ qp4,
-                                                             const uint32_t* __restrict__ qsum,
-                                                             unsigned long long* __restrict__ best, int rank,
-                                                             int nranks, int* __restrict__ tbstar) {
+// One wave's verification of query q (the body above, shared by vt_prune_verify_kernel and
+// the tail of vt_front_kernel, so the rule has one definition).  pick(pk, sec, m2) leaves
+// each lane's share of the pick: its least key (minLB << 32) | tb, that block's `second`,
+// and its lowest bound but one; the query's planes and QS are in flight through it.
+// s_q, s_t: the wave's own VT_VQS and VT_VTS uint4 of LDS.  `act` (wave-uniform) is false
+// for a wave that only keeps the thread block's barriers company: it writes nothing.
+// Every wave of the thread block must call this (one __syncthreads inside).
+constexpr int VT_VQS = PL_CG * VT_VR * 2, VT_VTS = PL_CG * (64 / 4) * 2;
+template <class Pick>
+__device__ __forceinline__ void vt_verify_query(int q, bool act, int lane, Pick&& pick, int nq,
+                                                const uint4* __restrict__ planes,
+                                                const uint32_t* __restrict__ tsum,
+                                                const uint4* __restrict__ qc4, uint4* __restrict__ qp4,
+                                                const uint32_t* __restrict__ qsum,
+                                                unsigned long long* __restrict__ best, int rank, int nranks,
+                                                int* __restrict__ tbstar, uint4* s_q, uint4* s_t) {
     constexpr int M = FAST_M, NU = 64 / 4, NS = PlaneLds<64>::NS, S0 = M - 3, S1 = 64 - M - 1;
     static_assert(PL_NO * PL_CG <= 64, "one lane per (offset, column group)");
     constexpr int QK = (QC_Q4 + 63) / 64;
-    // [cg][3 + aligned unit][2]: unit QC_NA is the zero unit; the rows before and after are
+    // s_q [cg][3 + aligned unit][2]: unit QC_NA is the zero unit; the rows before and after are
     // read (never counted) where a template unit meets no start row of the window
-    __shared__ uint4 s_q[PL_CG * VT_VR * 2];
-    __shared__ uint4 s_t[PL_CG * NU * 2];    // [cg][unit][2]
-    const int q = blockIdx.x, lane = threadIdx.x;
+    // s_t [cg][unit][2]
     const int x = lane >> 2, cg = lane & 3, o = x - (M - 1);
     // what does not wait for the pick, in flight through it: the query's planes and QS
     uint4 qv[QK];
@@ -1384,14 +1422,7 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
     // the lane's lowest bound but one (for the lowest bound of the blocks other than tb*)
     unsigned long long pk = ~0ull;
     uint32_t sec = 0u, m2 = 0xFFFFFFFFu;
-    for (int tb = lane; tb < ntb; tb += 64) {
-        const unsigned long long k = ((unsigned long long)minlb[(size_t)tb * nq + q] << 32) | (unsigned)tb;
-        const uint32_t s2 = second[(size_t)tb * nq + q];
-        const bool lt = k < pk;   // (selects: a branch would put the second read behind the first)
-        m2 = min(m2, (uint32_t)((lt ? pk : k) >> 32));
-        pk = lt ? k : pk;
-        sec = lt ? s2 : sec;
-    }
+    pick(pk, sec, m2);
     // (keeps the plane reads above in front of the reduction: left alone they sink to
     // their LDS stores, one memory round trip each)
 #pragma unroll
@@ -1452,7 +1483,7 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
     for (int off = 32; off > 0; off >>= 1) u0 = min(u0, (uint32_t)__shfl_xor(u0, off));
     u0 -= qs;
     const bool settled = (sec >> 6) > u0;
-    if (!settled || other <= u0) {   // (wave-uniform) a scan pass stages this query
+    if (act && (!settled || other <= u0)) {   // (wave-uniform) a scan pass stages this query
 #pragma unroll
         for (int k = 0; k < (VT_VQ4 + 63) / 64; ++k) {
             const int i = lane + 64 * k, g = i / (NS * 2), r = i - g * (NS * 2), si = r >> 1;
@@ -1462,12 +1493,118 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
             }
         }
     }
-    if (lane == 0) {
+    if (act && lane == 0) {
         if (settled) {
             const unsigned long long g = ((unsigned long long)tbs * 64 + tl) * nranks + rank;
             atomicMin(best + q, ((unsigned long long)u0 << 32) | g);
         }
         tbstar[q] = settled ? ~tbs : tbs;
+    }
+}
+
+__global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __restrict__ minlb,
+                                                             const uint32_t* __restrict__ second, int ntb, int nq,
+                                                             const uint4* __restrict__ planes,
+                                                             const uint32_t* __restrict__ tsum,
+                                                             const uint4* __restrict__ qc4,
+                                                             uint4* __restrict__ qp4,
+                                                             const uint32_t* __restrict__ qsum,
+                                                             unsigned long long* __restrict__ best, int rank,
+                                                             int nranks, int* __restrict__ tbstar) {
+    __shared__ uint4 s_q[VT_VQS];
+    __shared__ uint4 s_t[VT_VTS];
+    const int q = blockIdx.x, lane = threadIdx.x;
+    vt_verify_query(q, true, lane, [&](unsigned long long& pk, uint32_t& sec, uint32_t& m2) {
+        for (int tb = lane; tb < ntb; tb += 64) {
+            const unsigned long long k = ((unsigned long long)minlb[(size_t)tb * nq + q] << 32) | (unsigned)tb;
+            const uint32_t s2 = second[(size_t)tb * nq + q];
+            const bool lt = k < pk;   // (selects: a branch would put the second read behind the first)
+            m2 = min(m2, (uint32_t)((lt ? pk : k) >> 32));
+            pk = lt ? k : pk;
+            sec = lt ? s2 : sec;
+        }
+    }, nq, planes, tsum, qc4, qp4, qsum, best, rank, nranks, tbstar, s_q, s_t);
+}
+
+// The front of a pruned call in one launch (vt_plan::front_fused): a thread block owns
+// query groups of PF_NB queries (blockIdx.y, strided) and, for each, walks ALL template
+// blocks in chunks of PF_WAVES * PF_TPW (wave w: blocks c0 + w * PF_TPW ...), writes
+// minlb[] as the prefilter does (vt_prune_rest_kernel reads it) and leaves each
+// (bound, second) of the chunk in LDS; after the chunk's barrier wave w folds the chunk
+// into query w's pick, lane l the chunk's block l -- per lane the very update of the
+// verify kernel's pick loop, only with the blocks dealt 16 to a chunk instead of 64 to a
+// stride, and the wave-wide reductions that follow are associative.  Then wave w verifies
+// query w (vt_verify_query).  second[] is not written.
+// Barriers: every one is reached by all PF_WAVES waves -- the chunk loop's bounds are
+// block-uniform, a wave without a template block skips the walk only (no barrier inside),
+// and a wave without a query (w >= nb, the last group) verifies the group's last query
+// again with its writes off.  s_pick is double-buffered by chunk parity: with one barrier
+// per chunk a wave is at most one chunk ahead of a wave still folding.
+__global__ __launch_bounds__(64 * PF_WAVES) __attribute__((amdgpu_waves_per_eu(4)))
+void vt_front_kernel(const uint4* __restrict__ planes, int ntb, int64_t count, const uint4* __restrict__ qc4,
+                     const uint32_t* __restrict__ qsj, int nq, uint32_t* __restrict__ minlb,
+                     const uint32_t* __restrict__ tsum, uint4* __restrict__ qp4,
+                     const uint32_t* __restrict__ qsum, unsigned long long* __restrict__ best, int rank,
+                     int nranks, int* __restrict__ tbstar) {
+    constexpr int CH = PF_WAVES * PF_TPW;
+    static_assert(PF_WAVES == PF_NB, "one wave per query of the group in the tail");
+    static_assert(CH <= 64, "one lane per block of a chunk");
+    __shared__ uint4 s_q[PF_NB][PF_NU][PF_CGS][PL_NO][2];
+    __shared__ uint32_t s_qs[PF_NB][PF_NU][16];
+    __shared__ uint2 s_pick[2][PF_NB][CH];   // (minlb, second) of the chunk's blocks
+    __shared__ uint4 s_vq[PF_WAVES][VT_VQS];
+    __shared__ uint4 s_vt[PF_WAVES][VT_VTS];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    int par = 0;
+    for (int q0 = blockIdx.y * PF_NB; q0 < nq; q0 += gridDim.y * PF_NB) {   // block-uniform
+        const int nb = min(PF_NB, nq - q0);
+        const int qw = min(wave, nb - 1);   // the query this wave picks for and verifies
+        __syncthreads();   // the group before has been read
+        pf_stage(qc4, qsj, q0, nb, s_q, s_qs);
+        __syncthreads();
+        unsigned long long pk = ~0ull;
+        uint32_t sec = 0u, m2 = 0xFFFFFFFFu;
+        for (int c0 = 0; c0 < ntb; c0 += CH) {   // block-uniform
+            const int tb0 = c0 + wave * PF_TPW;
+            if (tb0 < ntb) {   // wave-uniform; no barrier inside
+                // (loaded per chunk and dead in the tail: the verification has the VGPRs)
+                uint32_t P[PF_TPW][PF_NU][PF_CGS][8], tsb[PF_TPW];
+                bool valid[PF_TPW];
+                pf_load(planes, ntb, count, tb0, lane, P, tsb, valid);
+#pragma unroll 1
+                for (int qq = 0; qq < nb; ++qq) {
+                    uint32_t v[PF_TPW], w[PF_TPW];
+                    pf_walk(P, tsb, valid, s_q[qq], s_qs[qq], lane, v, w);
+                    if (lane == 0) {
+#pragma unroll
+                        for (int t = 0; t < PF_TPW; ++t)
+                            if (tb0 + t < ntb) {
+                                minlb[(size_t)(tb0 + t) * nq + q0 + qq] = v[t] >> 6;
+                                s_pick[par][qq][wave * PF_TPW + t] = make_uint2(v[t] >> 6, (w[t] << 6) | (v[t] & 63u));
+                            }
+                    }
+                }
+            }
+            __syncthreads();
+            if (lane < CH && c0 + lane < ntb) {
+                const uint2 e = s_pick[par][qw][lane];
+                const unsigned long long k = ((unsigned long long)e.x << 32) | (unsigned)(c0 + lane);
+                const bool lt = k < pk;
+                m2 = min(m2, (uint32_t)((lt ? pk : k) >> 32));
+                pk = lt ? k : pk;
+                sec = lt ? e.y : sec;
+            }
+            par ^= 1;
+        }
+        // (the tail's lane arithmetic is loop-invariant: hoisted above the group loop it
+        // would stay live through the walk, in scratch)
+        int vl = lane;
+        asm volatile("" : "+v"(vl));
+        vt_verify_query(q0 + qw, wave < nb, vl, [&](unsigned long long& pk_, uint32_t& sec_, uint32_t& m2_) {
+            pk_ = pk;
+            sec_ = sec;
+            m2_ = m2;
+        }, nq, planes, tsum, qc4, qp4, qsum, best, rank, nranks, tbstar, s_vq[wave], s_vt[wave]);
     }
 }
 
@@ -1706,6 +1843,9 @@ struct rs_vt {
     // pruned plane scan (H = 64 frozen key scans; RS_VT_PRUNE): 0 dense everywhere, 1 above
     // VT_PRUNE_MIN_Q queries and one template block, 2 ("force") at any size
     int prune = 0;
+    // its front in one launch (vt_front_kernel; RS_VT_FRONT): 0 never, 1 where
+    // vt_plan::front_fused says so, 2 ("force") for any shape
+    int front = 1;
     rs::DevBuf<uint32_t> dQsj;        // QS_J of the queries in dQp
     rs::DevBuf<uint32_t> dQsjStream;  // ... of dQpStream
     // compact query planes (the aligned start rows).  A build ahead of a pruned scan fills
@@ -2059,13 +2199,21 @@ int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
     unsigned* verified = h->dListCnt.get() + 2 * (size_t)h->listCntCap;
     int* list1 = h->dList.get();
     int* list2 = h->dList.get() + pairs;
-    const vt_plan::Grid2 pf = vt_plan::prefilter_grid(ntb, nq, PF_WAVES * PF_TPW, PF_NB, VT_PF_GRID_CAP);
-    hipLaunchKernelGGL(vt_prefilter_kernel, dim3((unsigned)pf.x, (unsigned)pf.y), dim3(64 * PF_WAVES), 0, h->stream,
-                       s.planes, ntb, s.count, reinterpret_cast<const uint4*>(q.qc), q.qsj, nq, h->dMinLB.get(),
-                       h->dSecond.get());
-    hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, h->dMinLB.get(),
-                       h->dSecond.get(), ntb, nq, s.planes, s.ts, reinterpret_cast<const uint4*>(q.qc),
-                       reinterpret_cast<uint4*>(q.qp), q.qsum, out.best, s.rank, s.nranks, h->dTbStar.get());
+    if (h->front == 2 || (h->front == 1 && vt_plan::front_fused(ntb, PF_WAVES * PF_TPW))) {
+        const vt_plan::Grid2 fg = vt_plan::front_grid(nq, PF_NB, VT_PF_GRID_CAP);
+        hipLaunchKernelGGL(vt_front_kernel, dim3((unsigned)fg.x, (unsigned)fg.y), dim3(64 * PF_WAVES), 0, h->stream,
+                           s.planes, ntb, s.count, reinterpret_cast<const uint4*>(q.qc), q.qsj, nq, h->dMinLB.get(),
+                           s.ts, reinterpret_cast<uint4*>(q.qp), q.qsum, out.best, s.rank, s.nranks,
+                           h->dTbStar.get());
+    } else {
+        const vt_plan::Grid2 pf = vt_plan::prefilter_grid(ntb, nq, PF_WAVES * PF_TPW, PF_NB, VT_PF_GRID_CAP);
+        hipLaunchKernelGGL(vt_prefilter_kernel, dim3((unsigned)pf.x, (unsigned)pf.y), dim3(64 * PF_WAVES), 0,
+                           h->stream, s.planes, ntb, s.count, reinterpret_cast<const uint4*>(q.qc), q.qsj, nq,
+                           h->dMinLB.get(), h->dSecond.get());
+        hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, h->dMinLB.get(),
+                           h->dSecond.get(), ntb, nq, s.planes, s.ts, reinterpret_cast<const uint4*>(q.qc),
+                           reinterpret_cast<uint4*>(q.qp), q.qsum, out.best, s.rank, s.nranks, h->dTbStar.get());
+    }
     const dim3 lgrid((unsigned)((nq + VT_LIST_T - 1) / VT_LIST_T), (unsigned)ntb);
     hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar.get(), cnt1,
                        list1, verified, cnt2, ntb);
@@ -2559,6 +2707,17 @@ int rs_vt_create(int H, int W, int max_offset, uint64_t thr, int64_t capacity, i
         if (!e || e[0] == 0 || std::strcmp(e, "1") == 0) h->prune = 1;
         else if (std::strcmp(e, "force") == 0) h->prune = 2;
         else RS_CHECK(std::strcmp(e, "0") == 0, RS_ERR_ARG, "RS_VT_PRUNE='%s': expected 0, 1 or force", e);
+    }
+    if (h->planar && h->H == 64) {
+        // A/B switch: "0" keeps the prefilter and the verification two launches, "force"
+        // fuses them for any shape (tests), "1" (or unset) follows vt_plan::front_fused
+        const char* e = std::getenv("RS_VT_FRONT");
+        if (!e || e[0] == 0 || std::strcmp(e, "1") == 0) h->front = 1;
+        else if (std::strcmp(e, "force") == 0) h->front = 2;
+        else {
+            RS_CHECK(std::strcmp(e, "0") == 0, RS_ERR_ARG, "RS_VT_FRONT='%s': expected 0, 1 or force", e);
+            h->front = 0;
+        }
     }
     if (h->planar) {
         // resident blocks per CU: the occupancy API, capped by the kernel's own VGPR and

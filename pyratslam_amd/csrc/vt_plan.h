@@ -124,6 +124,22 @@ inline Grid2 prefilter_grid(int ntb, int nq, int tb_per_block, int q_per_batch, 
     return {pfx, std::min(nqb, std::max(1, cap / pfx))};
 }
 
+// Whether the prefilter and the verification run as one launch (vt_front_kernel: a thread
+// block walks every template block for its query groups, tb_per_block at a time, then picks
+// and verifies in its tail).  Yes when one thread block covers the library anyway: one
+// chunk, and the grid is the prefilter's own.  Otherwise the two launches, the prefilter's
+// grid with x > 1.  A wider rule, "or the query groups alone fill the resident thread
+// blocks", measured slower where it applied (10,000 templates x 5,120 queries, ten chunks
+// per group: 1.37 ms per step against 1.34): a thread block then loads
+// its template planes once per group and chunk, where the prefilter loads them once for
+// three groups.
+inline bool front_fused(int ntb, int tb_per_block) { return ntb <= tb_per_block; }
+// Its grid: x = 1, y the query groups within `cap` thread blocks; block y serves the groups
+// y, y + grid.y, ... (the kernel strides), so every group is served exactly once.
+inline Grid2 front_grid(int nq, int q_per_batch, int cap) {
+    return {1, std::max(1, std::min((nq + q_per_batch - 1) / q_per_batch, cap))};
+}
+
 // Thread blocks of 256 of a key export of n keys (the kernel strides): a batch's keys, and
 // the rows of rs_vt_match_stream.
 constexpr int VT_EXPORT_BLOCKS = 64, VT_EXPORT_BLOCKS_STREAM = 256;

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Per-pass median kernel times (us) of the pruned plane scan from a
-``rocprofv3 --kernel-trace --output-format csv`` folder: the prefilter's dispatches
-mark the pruned calls; of the list-driven scan's two dispatches per call the first
-is pass B1 and the second pass B2 (dispatch order).  Only calls of the most common
-prefilter grid (the headline shape in a plain bench) are counted.
+``rocprofv3 --kernel-trace --output-format csv`` folder: the prefilter's dispatches, or
+the fused front's (vt_front_kernel: prefilter, pick and verification in one launch), mark
+the pruned calls; of the list-driven scan's two dispatches per call the first is pass B1
+and the second pass B2 (dispatch order).  Only calls of the most common grid of that
+first kernel (the headline shape in a plain bench) are counted; a pass that a build
+does not launch is not reported.
 usage: python tools/prune_pass_medians.py TRACE_DIR [TRACE_DIR ...]   (one JSON object)"""
 import collections
 import csv
@@ -12,7 +14,7 @@ import json
 import os
 import sys
 
-NAMES = (('vt_qplane_kernel', 'qplane'), ('vt_prefilter_kernel', 'prefilter'), ('vt_prune_pick_kernel', 'pick'),
+NAMES = (('vt_qplane_kernel', 'qplane'), ('vt_prefilter_kernel', 'prefilter'), ('vt_front_kernel', 'front'), ('vt_prune_pick_kernel', 'pick'),
          ('vt_prune_verify_kernel', 'verify'), ('vt_prune_first_kernel', 'first'),
          ('vt_prune_rest_kernel', 'rest'), ('vt_prune_finish_kernel', 'finish'), ('vt_keys_export', 'export'),
          ('vt_scan_plane_kernel<64, false, true>', 'list_scan'))
@@ -30,8 +32,8 @@ def passes(d):
         if tag == 'qplane':
             pend = us
             continue
-        if tag == 'prefilter':
-            cur = {'grid': r.get('Grid_Size', r.get('Grid_Size_X', '')), 'qplane': pend, 'prefilter': us}
+        if tag in ('prefilter', 'front'):
+            cur = {'grid': r.get('Grid_Size', r.get('Grid_Size_X', '')), 'qplane': pend, tag: us}
             calls.append(cur)
         elif cur is not None:
             if tag == 'list_scan':
@@ -40,7 +42,7 @@ def passes(d):
     grid = collections.Counter(c['grid'] for c in calls).most_common(1)[0][0]
     calls = [c for c in calls if c['grid'] == grid]
     out = {'calls': len(calls)}
-    for k in ('qplane', 'prefilter', 'pick', 'verify', 'first', 'B1', 'rest', 'B2', 'finish', 'export'):
+    for k in ('qplane', 'prefilter', 'front', 'pick', 'verify', 'first', 'B1', 'rest', 'B2', 'finish', 'export'):
         v = sorted(c[k] for c in calls if k in c)
         if v:
             out[k] = round(v[len(v) // 2], 1)
