@@ -1,5 +1,5 @@
 // The pose-cell step's control records as kernel arguments and the host rules that form and
-// read them: pure functions of integers and small arrays, shared by posecell.hip and by
+// read them: pure functions of integers and small arrays, shared by posecell.hip (its host side; the kernels: pc_cols.h, pc_halo.h, pc_state.h) and by
 // tests/pc_ctl_main.cpp (built with the plain host compiler: no HIP runtime call here).
 // Everything sits in the unnamed namespace, as posecell.hip's kernels do: the control
 // structs are kernel parameter types, and the kernels' names carry their namespace.

@@ -1,5 +1,5 @@
 // The pose-cell packet's circular centroid: the six weighted sums of a
-// wrapped box round a cell, shared by pc_peak_kernel (posecell.hip), by rs_pc_peak_host and
+// wrapped box round a cell, shared by pc_peak_kernel (pc_state.h), by rs_pc_peak_host and
 // by tests/pc_peak_main.cpp.  All float64, every operation correctly rounded and
 // uncontracted (each function switches contraction off for itself: posecell.hip is not
 // built with -ffp-contract=off); no sin / cos is evaluated here, the weights are tables.

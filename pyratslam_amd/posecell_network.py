@@ -12,7 +12,9 @@ reference's ``get_pc_max`` is a placeholder: the packet's circular centroid (``p
 The pose-cell volume lives on the GPU; ``.posecells`` copies it to the host
 on access (and uploads on assignment).  The per-step control scalars are
 derived on the host exactly as the reference derives them (``filters``), the
-volume work runs in ``pc_excite`` + ``pc_path`` (``csrc/posecell.hip``).
+volume work runs in the step kernels of the handle's form: ``pc_excite_*`` + ``pc_path_*``, or
+``pc_step_halo`` (``csrc/pc_rows.h``, ``pc_stream.h``, ``pc_cols.h``, ``pc_halo.h``; one translation
+unit, ``csrc/posecell.hip``).
 """
 import ctypes
 import math

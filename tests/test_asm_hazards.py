@@ -1,7 +1,8 @@
 """Static regression guard for the class of bug behind round 1's illegal-address
 fault: no vector-memory load's destination register may be
 read or overwritten before an s_waitcnt retires the load.  Each HIP source is
-compiled to gfx950 device assembly and checked with tools/asm_load_hazards.py.
+compiled to gfx950 device assembly by the product's command (pyratslam_amd/_build.py,
+per-source flags included: the shipped kernels) and checked with tools/asm_load_hazards.py.
 CPU only (hipcc cross-compiles); skipped where hipcc is absent."""
 import os
 import shutil
@@ -11,8 +12,11 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
+sys.path.insert(0, ROOT)
+from pyratslam_amd import _build  # noqa: E402
+
+HIPCC = _build.HIPCC
 
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which('hipcc')), reason='hipcc absent')
@@ -20,11 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tools'))
 def test_no_load_register_hazards(tmp_path, src):
     import asm_load_hazards as H
     out = tmp_path / (src + '.s')
-    subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',
-                           '-I' + os.path.join(ROOT, 'include'),
-                           '-I' + os.path.join(ROOT, 'pyratslam_amd', 'csrc'), '-x', 'hip', '-S',
-                           '--cuda-device-only', os.path.join(ROOT, 'pyratslam_amd', 'csrc', src),
-                           '-o', str(out)], stderr=subprocess.DEVNULL)
+    subprocess.check_call(_build.compile_cmd(src, str(out), kind='asm'), stderr=subprocess.DEVNULL)
     lines = out.read_text().splitlines()
     bad = {}
     for name, body in H.kernels(lines):

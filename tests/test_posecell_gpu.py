@@ -319,13 +319,34 @@ def test_state_roundtrip_inject_and_argmax(pcn, monkeypatch, form, shape):
         assert net.posecells[-1, -1, -1] == pytest.approx(back[-1, -1, -1] + 1.0, rel=1e-6)
 
 
-def test_argmax_first_maximum_tie_break(pcn):
-    shape = (8, 8, 8)
-    net = pcn(shape, precision='float64')
-    v = np.zeros(shape)
-    v[5, 1, 2] = v[2, 7, 7] = v[2, 7, 1] = 1.0
+def _tie_break_states(shape):
+    """Stored states whose first maximum in C order is not the first in a layer-major
+    volume's memory order ((x, y, th) sits at (th * X + x) * Y + y there)."""
+    ties = np.zeros(shape)                      # (a) three equal maxima
+    ties[1, 0, 5] = ties[3, 0, 0] = ties[3, 0, 1] = 1.0
+    nans = np.zeros(shape)                      # (b) two NaNs behind a +inf: the first NaN wins
+    nans[0, 1, 3] = np.inf
+    nans[2, 3, 4] = nans[4, 0, 1] = np.nan
+    negz = np.zeros(shape)                      # (c) -0.0 is no maximum over +0.0
+    negz[1, 2, 3] = -0.0
+    return {'ties': (ties, (1, 0, 5)), 'nans': (nans, (2, 3, 4)), 'negzero': (negz, (0, 0, 0))}
+
+
+@pytest.mark.parametrize('state', ['ties', 'nans', 'negzero'])
+@pytest.mark.parametrize('form,shape', [('', (8, 8, 8)), ('cols', (16, 20, 10))], ids=['rows', 'cols'])
+@pytest.mark.parametrize('precision', ['float32', 'float64'])
+def test_argmax_first_maximum_tie_break(pcn, monkeypatch, precision, form, shape, state):
+    """get_pc_max on a stored state (pc_argmax_blocks, then pc_argmax_steps' fold): numpy's
+    argmax of the array read back, layer-major (rows) and theta-fastest (cols)."""
+    monkeypatch.setenv('RS_PC_FORM', form)
+    net = pcn(shape, precision=precision)
+    assert net.step_form() == (form or 'rows')
+    v, cell = _tie_break_states(shape)[state]
     net.posecells = v
-    assert net.get_pc_max() == (2, 7, 1)
+    back = net.posecells
+    want = tuple(int(c) for c in np.unravel_index(np.argmax(back), shape))
+    assert want == cell          # (the expectation itself: plain NumPy)
+    assert net.get_pc_max() == want
 
 
 def test_bad_inputs_raise(pcn):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel VGPR / SGPR / spill / LDS / occupancy table of a HIP source for gfx950
-(hipcc -Rpass-analysis=kernel-resource-usage, device-only compile, no GPU needed).
+(hipcc -Rpass-analysis=kernel-resource-usage on the product's compile command,
+pyratslam_amd/_build.py; device-only compile, no GPU needed).
 
 usage: tools/kernel_resources.py pyratslam_amd/csrc/posecell.hip [name-filter]
 """
@@ -10,15 +11,12 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from pyratslam_amd import _build  # noqa: E402  (the product's compile command, per-source flags included)
+
 src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ''
-extra = {'posecell.hip': ['-fno-slp-vectorize'],
-         'view_templates.hip': ['-mllvm', '-amdgpu-atomic-optimizer-strategy=None',
-                                '-mllvm', '-amdgpu-sched-strategy=max-ilp'],
-         'experience_map.hip': ['-ffp-contract=off']}
-cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-x', 'hip',
-       f'-I{ROOT}/include', f'-I{ROOT}/pyratslam_amd/csrc', '--cuda-device-only', '-c', src,
-       '-o', '/dev/null', '-Rpass-analysis=kernel-resource-usage', *extra.get(os.path.basename(src), [])]
+cmd = _build.compile_cmd(os.path.basename(src), '/dev/null', kind='remarks', path=os.path.abspath(src))
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
