@@ -222,6 +222,39 @@ int rs_pc_run_peaks(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const
                     const double* zf, int32_t* out_xyz, double* out_sums);
 int rs_pc_peak_host(int X, int Y, int TH, int r, const double* volume_xyth, const int32_t xyz[3],
                     const double* sc_x, const double* sc_y, const double* sc_th, double sums[6]);
+/* Injections inside a batched run: the view-template feedback without a host round trip
+ * per frame.  A run of n steps takes ni injections; injection i is (inj_step[i],
+ * inj_energy[i], inj_loc[3i .. 3i+2]) with 0 <= inj_step[i] <= n, the steps non-decreasing
+ * in i, and a location that is one of
+ *   (x, y, th)                  an explicit cell inside the grid;
+ *   (RS_PC_INJ_AT_PEAK, ., .)   the first maximum of the state as it stands when the
+ *                               injection is applied (what rs_pc_get_max would return there);
+ *   (RS_PC_INJ_SAME_AS, k, .)   k < i: the cell injection k of this call resolved to.
+ * The call is defined as this sequence on the same handle:
+ *   for s in 0 .. n-1:
+ *       for each injection i with inj_step[i] == s, in order:  rs_pc_inject(energy_i, cell_i)
+ *       rs_pc_update_odom(odom[s])
+ *   for each injection i with inj_step[i] == n, in order:      rs_pc_inject(energy_i, cell_i)
+ * and returns the same peaks (out_xyz[n*3]), every injection's resolved cell
+ * (out_inj_xyz[ni*3]) and leaves a stored volume equal to that sequence's bit for bit, in
+ * every step form and both precisions.  With out_sums (may be NULL; RS_ERR_STATE before
+ * rs_pc_set_peak_tables) step s's six sums are taken from the state before any injection
+ * with step s + 1.  One host sync: the call waits for the stream's completion.
+ * A LUT miss at step s (RS_ERR_LUT_KEY, *first_bad = s): the injections with
+ * inj_step[i] <= s have been applied, the later ones have not and their cells come back as
+ * (-1, -1, -1), and the state is the one the sequence leaves when its update fails.
+ * RS_ERR_ARG before any device work, the state untouched: steps out of order, a step
+ * outside [0, n], an explicit cell outside the grid, a same-as k >= i.  n == 0 with ni > 0
+ * applies the injections alone.  The energy is not restricted (a NaN makes a NaN state).
+ * rs_pc_run_inject: the same with the caller's control, as rs_pc_run is to rs_pc_run_odom. */
+#define RS_PC_INJ_AT_PEAK (-1)   /* inj_loc[3i] */
+#define RS_PC_INJ_SAME_AS (-2)   /* inj_loc[3i], inj_loc[3i+1] = k */
+int rs_pc_run_odom_inject(rs_pc* h, int n, const double* odom, int ni, const int32_t* inj_step,
+                          const double* inj_energy, const int32_t* inj_loc, int32_t* out_xyz,
+                          int32_t* out_inj_xyz, double* out_sums, int* first_bad);
+int rs_pc_run_inject(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
+                     const double* zf, int ni, const int32_t* inj_step, const double* inj_energy,
+                     const int32_t* inj_loc, int32_t* out_xyz, int32_t* out_inj_xyz, double* out_sums);
 /* whole volume as float64, C order (X, Y, TH) -- the reference's .posecells */
 int rs_pc_read(rs_pc* h, double* host_xyth);
 /* the same volume written by the GPU straight into pinned host memory from

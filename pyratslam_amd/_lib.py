@@ -28,6 +28,8 @@ RS_PC_DBG_POISON = 1
 RS_PC_DBG_SKIP_EXPORT = 2
 RS_PC_DBG_HALO_SETTLE = 3
 RS_PC_DBG_HALO_AMBIG = 4
+RS_PC_INJ_AT_PEAK = -1
+RS_PC_INJ_SAME_AS = -2
 RS_VT_FROZEN = 0
 RS_VT_SEQUENTIAL = 1
 RS_UNIQUE_ID_BYTES = 128
@@ -101,6 +103,10 @@ SIGNATURES = {
     'rs_pc_update_odom_peak': (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_double, _i32p, _f64p]),
     'rs_pc_run_odom_peaks': (ctypes.c_int, [_vp, ctypes.c_int, _f64p, _i32p, _f64p, _c_int_p]),
     'rs_pc_run_peaks': (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _i32p, _f64p, _i32p, _f64p]),
+    'rs_pc_run_odom_inject': (ctypes.c_int, [_vp, ctypes.c_int, _f64p, ctypes.c_int, _i32p, _f64p, _i32p, _i32p,
+                                             _i32p, _f64p, _c_int_p]),
+    'rs_pc_run_inject': (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _i32p, _f64p, ctypes.c_int, _i32p, _f64p,
+                                        _i32p, _i32p, _i32p, _f64p]),
     'rs_pc_peak_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p, _i32p,
                                        _f64p, _f64p, _f64p, _f64p]),
     'rs_pc_read': (ctypes.c_int, [_vp, _f64p]),

@@ -173,4 +173,29 @@ inline unsigned long long halo_key_from_records(const unsigned long long* rec, i
     return m;
 }
 
+// The rule of a run's injections (rs_pc_run_odom_inject): n steps, ni injections, step[ni]
+// and loc[3 ni].  The index of the first injection that breaks it with the reason in *why,
+// or -1: every step in [0, n] and not below the one before; a location that is a cell
+// inside the grid, (RS_PC_INJ_AT_PEAK, ., .), or (RS_PC_INJ_SAME_AS, k, .) with 0 <= k < i.
+// Reads step[0 .. ni) and loc[0 .. 3 ni) only.
+enum PcInjBad { PC_INJ_OK = 0, PC_INJ_BAD_STEP, PC_INJ_BAD_ORDER, PC_INJ_BAD_SAME, PC_INJ_BAD_CELL };
+inline int pc_inj_first_bad(int X, int Y, int TH, int n, int ni, const int32_t* step, const int32_t* loc,
+                            PcInjBad* why) {
+    for (int i = 0; i < ni; ++i) {
+        const int32_t* l = loc + 3 * (size_t)i;
+        PcInjBad bad = PC_INJ_OK;
+        if (step[i] < 0 || step[i] > n) bad = PC_INJ_BAD_STEP;
+        else if (i > 0 && step[i] < step[i - 1]) bad = PC_INJ_BAD_ORDER;
+        else if (l[0] == RS_PC_INJ_AT_PEAK) bad = PC_INJ_OK;
+        else if (l[0] == RS_PC_INJ_SAME_AS) bad = l[1] >= 0 && l[1] < i ? PC_INJ_OK : PC_INJ_BAD_SAME;
+        else if (!(l[0] >= 0 && l[0] < X && l[1] >= 0 && l[1] < Y && l[2] >= 0 && l[2] < TH)) bad = PC_INJ_BAD_CELL;
+        if (bad != PC_INJ_OK) {
+            *why = bad;
+            return i;
+        }
+    }
+    *why = PC_INJ_OK;
+    return -1;
+}
+
 }  // namespace

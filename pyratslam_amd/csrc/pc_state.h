@@ -153,6 +153,69 @@ __global__ void pc_inject_kernel(T* __restrict__ P, size_t idx, double energy) {
     if (threadIdx.x == 0) P[idx] = (T)((double)P[idx] + energy);
 }
 
+// An injection inside a batched run (rs_pc_run_odom_inject): one wave resolves the cell and
+// adds, with pc_inject_kernel's arithmetic.  The cell, as a C-order linear index, comes from
+//   PC_INJ_EXPLICIT  arg itself (the host checked it against the grid);
+//   PC_INJ_KEY       the key words pc_peak_kernel reads, reduced the same way: a float32
+//                    step's RES_SLOTS slot words (slot), else nb (value, index) block partials
+//                    (a float64 step's, or pc_argmax_blocks' of the stored state);
+//   PC_INJ_SAME      cells[arg], what an earlier injection of this call resolved to.
+// The resolved index goes to cells[i] for later launches of the call, ordered behind this one
+// on the stream, and to hcells[i] in pinned memory for the host (plain stores both: the host
+// reads them only once it has synchronised the stream, as it does a peaks call's sums).  No address outside P
+// is formed: a key no step wrote is clamped to cell 0 as pc_peak_kernel clamps it, and an
+// explicit or same-as index that is no cell (PC_INJ_NONE: an injection that never ran) adds
+// nothing and resolves to PC_INJ_NONE.
+enum { PC_INJ_EXPLICIT = 0, PC_INJ_KEY = 1, PC_INJ_SAME = 2 };
+constexpr unsigned PC_INJ_NONE = 0xFFFFFFFFu;
+
+template <typename T>
+__global__ __launch_bounds__(64) void pc_inject_run_kernel(T* __restrict__ P, int X, int Y, int TH, int thfast,
+                                                           int src, unsigned arg,
+                                                           const unsigned long long* __restrict__ slot,
+                                                           const T* __restrict__ bmax,
+                                                           const unsigned* __restrict__ bidx, int nb,
+                                                           unsigned* cells, unsigned* __restrict__ hcells, int i,
+                                                           double energy) {
+    const int lane = threadIdx.x;
+    const unsigned ncell = (unsigned)X * Y * TH;
+    unsigned lin;
+    if (src == PC_INJ_KEY) {   // (kernel arguments: uniform branches)
+        if (slot) {
+            lin = 0xFFFFFFFFu - (unsigned)(pc_slots_max(slot) & 0xFFFFFFFFull);
+        } else {
+            T bv = -std::numeric_limits<T>::infinity();
+            unsigned bl = 0xFFFFFFFFu;
+            for (int b = lane; b < nb; b += 64) {
+                const T v = bmax[b];
+                const unsigned l = bidx[b];
+                if (pc_better(v, l, bv, bl)) {
+                    bv = v;
+                    bl = l;
+                }
+            }
+            lin = pc_wave_best(bv, bl).l;
+        }
+        if (lin >= ncell) lin = 0u;
+    } else if (src == PC_INJ_SAME) {
+        lin = arg < (unsigned)i ? cells[arg] : PC_INJ_NONE;
+    } else {
+        lin = arg;
+    }
+    if (lane != 0) return;
+    if (lin >= ncell) {
+        cells[i] = PC_INJ_NONE;
+        hcells[i] = PC_INJ_NONE;
+        return;
+    }
+    const unsigned th = lin % (unsigned)TH, xy = lin / (unsigned)TH;
+    const unsigned y = xy % (unsigned)Y, x = xy / (unsigned)Y;
+    const size_t idx = thfast ? (size_t)lin : ((size_t)th * X + x) * Y + y;
+    P[idx] = (T)((double)P[idx] + energy);
+    cells[i] = lin;
+    hcells[i] = lin;
+}
+
 template <typename T>
 __global__ __launch_bounds__(NT) void pc_total_kernel(const T* __restrict__ P, size_t n,
                                                       double* __restrict__ out) {

@@ -141,6 +141,10 @@ struct rs_pc {
     int peakR = 0;
     rs::DevBuf<double> dPeakTab;
     rs::PinnedBuf<double> hPeak;
+    // injections inside a run (rs_pc_run_odom_inject): each one's resolved C-order cell, on the
+    // device for the call's same-as injections and in pinned memory for the host
+    rs::DevBuf<unsigned> dInj;
+    rs::PinnedBuf<unsigned> hInj;
 };
 
 namespace {
@@ -396,6 +400,87 @@ int pc_launch_peak(rs_pc* h, const void* P, const unsigned long long* slot, cons
     return RS_OK;
 }
 
+// The stored state's per-block argmax partials into dBmax / dBidx (*nb_out of them).
+int pc_launch_argmax_blocks(rs_pc* h, int* nb_out) {
+    const int nb = h->nBmaxCap < 1024 ? h->nBmaxCap : 1024;
+    *nb_out = nb;
+    pc_by_prec(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pc_argmax_blocks<T>), dim3(nb), dim3(NT), 0, h->stream, static_cast<const T*>(h->dP.get()),
+                           h->X, h->Y, h->TH, static_cast<T*>(h->dBmax.get()), h->dBidx.get(), (int)pc_thfast(h));
+    });
+    RS_HIP(hipGetLastError());
+    return RS_OK;
+}
+
+// A run's injections (rs_pc_run_odom_inject; checked by pc_check_inj): ni of them, in the
+// order of their steps.
+struct PcInj {
+    int ni = 0;
+    const int32_t* step = nullptr;
+    const double* energy = nullptr;
+    const int32_t* loc = nullptr;   // [3 ni]: (x, y, th) | (RS_PC_INJ_AT_PEAK, ., .) | (RS_PC_INJ_SAME_AS, k, .)
+};
+
+// Where the first maximum of the state in dP is keyed on the device, when it is: a float32
+// step's slot words, or nb block partials (pc_inject_run_kernel reads either).
+struct PcKeySrc {
+    const unsigned long long* slot = nullptr;
+    const void* bmax = nullptr;
+    const unsigned* bidx = nullptr;
+    int nb = 0;
+    bool valid() const { return slot || bmax; }
+};
+inline PcKeySrc step_key(const rs_pc* h, const StepOut& so) {
+    return h->prec == RS_PREC_F32 ? PcKeySrc{so.slot, nullptr, nullptr, 0} : PcKeySrc{nullptr, so.bmax, so.bidx, h->nPart};
+}
+
+int pc_grow_inj(rs_pc* h, int ni) {
+    if ((size_t)ni <= h->dInj.capacity()) return RS_OK;
+    // (every call with injections has synchronised the stream: nothing still uses the old blocks)
+    const size_t cap = rs::grown<size_t>(0, (size_t)ni, 64);
+    RS_TRY(h->hInj.reserve(cap, PC_FINE));
+    RS_TRY(h->dInj.reserve(cap));
+    RS_HIP(hipMemsetAsync(h->dInj.get(), 0xFF, sizeof(unsigned) * cap, h->stream));
+    return RS_OK;
+}
+
+// The injection point in front of step s (s == n: behind the last step): every injection
+// of the call with that step, in order, one pc_inject_run_kernel launch each, on the settled
+// state in dP.  key: where that state's first maximum is keyed, if a step of this call left
+// it; an at-peak injection without one -- before step 0, or behind another injection of this
+// point, which changed the state -- takes pc_argmax_blocks' partials of dP as it stands.
+int pc_inject_point(rs_pc* h, const PcInj& inj, int* cur, int s, PcKeySrc key) {
+    for (; *cur < inj.ni && inj.step[*cur] == s; ++*cur) {
+        const int i = *cur;
+        const int32_t* loc = inj.loc + 3 * (size_t)i;
+        int src = PC_INJ_EXPLICIT;
+        unsigned arg = 0u;
+        if (loc[0] == RS_PC_INJ_AT_PEAK) {
+            src = PC_INJ_KEY;
+            if (!key.valid()) {
+                int nb = 0;
+                RS_TRY(pc_launch_argmax_blocks(h, &nb));
+                key = PcKeySrc{nullptr, h->dBmax.get(), h->dBidx.get(), nb};
+            }
+        } else if (loc[0] == RS_PC_INJ_SAME_AS) {
+            src = PC_INJ_SAME;
+            arg = (unsigned)loc[1];
+        } else {
+            arg = ((unsigned)loc[0] * h->Y + loc[1]) * h->TH + loc[2];
+        }
+        pc_by_prec(h, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((pc_inject_run_kernel<T>), dim3(1), dim3(64), 0, h->stream, static_cast<T*>(h->dP.get()),
+                               h->X, h->Y, h->TH, (int)pc_thfast(h), src, arg, key.slot, static_cast<const T*>(key.bmax),
+                               key.bidx, key.nb, h->dInj.get(), h->hInj.dev(), i, inj.energy[i]);
+        });
+        RS_HIP(hipGetLastError());
+        key = PcKeySrc{};   // the state has changed
+    }
+    return RS_OK;
+}
+
 // The end of a call of n steps, either run path: no result word may still hold the
 // sentinel once the call has been waited for; the call's device time; the keys decoded.
 int pc_end_call(rs_pc* h, int n, int32_t* out_xyz) {
@@ -456,8 +541,12 @@ enum class HaloEnd { HostRecords, DevRecords, Finish };
 // HF_NEAR of the peak), pc_halo_finish normalises the state into dP, keys it and
 // exports.  One host sync (two for RES_AMBIG).  rs_pc_debug(RS_PC_DBG_HALO_SETTLE) makes
 // every later call finish.
+// With injections (inj): an injection point settles a pending state with one pc_halo_finish --
+// in front of step s > 0 it keys step s-1 in its slots from the normalised state, where an
+// at-peak injection and the step's peak launch find it -- and the step behind it starts from
+// the settled state in dP, as a call's first step does; the call always finishes.
 int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
-                const double* zf, int32_t* out_xyz, double* xp, double* sums) {
+                const double* zf, int32_t* out_xyz, double* xp, double* sums, const PcInj* inj) {
     RS_TRY(pc_grow_steps(h, n, false));   // (the control travels as kernel arguments)
     if (sums) RS_TRY(pc_grow_peaks(h, n));
     const bool pk = h->profiling && h->profKernels;
@@ -468,7 +557,7 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     const bool poll_env = halo_poll_env();
     // A peaks call (sums) finishes too: its last step is then keyed in last_slot from the
     // normalised state in dP, where the step's peak launch finds both (never RES_AMBIG)
-    const HaloEnd end = xp || sums || h->haloSettleAlways ? HaloEnd::Finish
+    const HaloEnd end = xp || sums || inj || h->haloSettleAlways ? HaloEnd::Finish
                         : n == 1 && h->hRec.get()     ? HaloEnd::HostRecords
                                                       : HaloEnd::DevRecords;
     const bool lazy = end != HaloEnd::Finish;
@@ -478,11 +567,21 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     // 1. the steps
     float* buf[2] = {static_cast<float*>(h->dP.get()), static_cast<float*>(h->dQ.get())};
     double* part[2] = {h->dPart.get(), h->dPart.get() + h->nPart};
-    const bool pend = h->haloPend;
-    const int c0 = pend ? h->haloCur : 0;          // the buffer step 0 reads
-    const int p0 = pend ? (h->haloPart ^ 1) : 0;   // the partials half step 0 writes
+    bool pend = h->haloPend;            // the state is U in buf[cb], its partials in part[ph]
+    int cb = pend ? h->haloCur : 0;     // the buffer the next step reads
+    int ph = pend ? h->haloPart : 1;    // the next step writes the other half (a settled state: half 0)
+    int icur = 0;                       // the next injection
     unsigned long long* const last_slot = h->dRes.get() + (size_t)(n - 1) * RES_SLOTS;
     for (int s = 0; s < n; ++s) {
+        unsigned long long* const prev = s > 0 ? h->dRes.get() + (size_t)(s - 1) * RES_SLOTS : nullptr;
+        // an injection point: step s-1 is keyed and its peak taken from the settled state here
+        const bool point = inj && icur < inj->ni && inj->step[icur] == s;
+        if (point) {
+            if (pend) RS_TRY(pc_launch_halo_finish(h, cb, ph, {prev}));
+            pend = false, cb = 0, ph = 1;
+            if (sums && s > 0) RS_TRY(pc_launch_peak(h, buf[0], prev, nullptr, nullptr, 0, s - 1));
+            RS_TRY(pc_inject_point(h, *inj, &icur, s, PcKeySrc{prev, nullptr, nullptr, 0}));
+        }
         PcCtlHalo c;
         make_ctl_halo(h->X, h->Y, h->TH, ox + (size_t)s * h->TH, oy + (size_t)s * h->TH, fidx + (size_t)s * h->TH,
                       zf + (size_t)s * FL, &c);
@@ -490,17 +589,16 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         unsigned long long* rec = nullptr;   // the last launch's records, where the ending reads them
         if (lazy && s == n - 1) rec = end == HaloEnd::HostRecords ? h->hRec.dev() : h->dRec.get();
         if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s], h->stream));
-        RS_TRY(pc_launch_halo_step<false>(h, buf[(c0 + s) & 1], buf[(c0 + s + 1) & 1],
-                                          part[s > 0 ? (p0 + s - 1) & 1 : pend ? h->haloPart : 0],
-                                          s > 0 || pend ? h->nPart : 0, part[(p0 + s) & 1],
-                                          s == 0 ? nullptr : slot - RES_SLOTS, slot, c, rec));
+        RS_TRY(pc_launch_halo_step<false>(h, buf[cb], buf[cb ^ 1], part[pend ? ph : 0], pend ? h->nPart : 0,
+                                          part[ph ^ 1], point ? nullptr : prev, slot, c, rec));
         if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s + 1], h->stream));
         // step s-1's key is complete now (this launch reduced it into slot - RES_SLOTS from the
         // state it loaded), and its U stays in the buffer this launch read until launch s+1
         // overwrites it: the peak launch of step s-1 goes between the two
-        if (sums && s > 0) RS_TRY(pc_launch_peak(h, buf[(c0 + s) & 1], slot - RES_SLOTS, nullptr, nullptr, 0, s - 1));
+        if (sums && s > 0 && !point) RS_TRY(pc_launch_peak(h, buf[cb], prev, nullptr, nullptr, 0, s - 1));
+        pend = true, cb ^= 1, ph ^= 1;
     }
-    const int cl = (c0 + n) & 1, pl = (p0 + n - 1) & 1;   // where the last U and its partials are
+    const int cl = cb, pl = ph;   // where the last U and its partials are
 
     // 2. the ending
     const int nb = hf_finish_blocks(h);
@@ -521,6 +619,8 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         RS_TRY(pc_launch_halo_finish(h, cl, pl, {last_slot, own_export ? n : 0, xp, flag_poll ? h->hFlag.dev() : nullptr, seq}));
         // the last step's peak: the normalised state in dP, its keys in last_slot
         if (sums) RS_TRY(pc_launch_peak(h, buf[0], last_slot, nullptr, nullptr, 0, n - 1));
+        // the injections behind the last step, on the state the pass has just settled and keyed
+        if (inj) RS_TRY(pc_inject_point(h, *inj, &icur, n, PcKeySrc{last_slot, nullptr, nullptr, 0}));
         if (!skipped && !own_export) {
             hipLaunchKernelGGL(pc_res_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes.get(), n,
                                h->hRes.dev());
@@ -561,7 +661,8 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     }
     // (A peaks call never polls: the early returns above are safe only because the host reads
     // nothing but the key words or flagged volume slices, and the sums are plain stores of the
-    // peak launches, visible to the host once the stream has synchronised.)
+    // peak launches, visible to the host once the stream has synchronised.  Nor does a call
+    // with injections: it finishes without xp, and its resolved cells are plain stores too.)
     if (!polled) RS_HIP(hipStreamSynchronize(h->stream));
     if (sums) std::memcpy(sums, h->hPeak.get(), sizeof(double) * 6 * (size_t)n);
 
@@ -697,10 +798,15 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
 }
 
 // n steps launched one by one on the handle's stream, then one export and a sync.
+// With injections (inj): each injection point is queued in front of its step, where the state
+// is in dP and the step before's key on the device (float32: its slot words; float64: its
+// block partials, which an at-peak injection's wave reduces itself).
 int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
-                  const double* zf, int32_t* out_xyz, double* xp, double* sums) {
+                  const double* zf, int32_t* out_xyz, double* xp, double* sums, const PcInj* inj = nullptr) {
     if (n == 0) return RS_OK;
-    if (h->form == PcForm::Halo) return pc_run_halo(h, n, ox, oy, fidx, zf, out_xyz, xp, sums);
+    // (the halo form's finishing pass exports in front of the injections behind the last step)
+    RS_CHECK(!(xp && inj), RS_ERR_STATE, "an eager readback takes no injections");
+    if (h->form == PcForm::Halo) return pc_run_halo(h, n, ox, oy, fidx, zf, out_xyz, xp, sums, inj);
     if (sums) RS_TRY(pc_grow_peaks(h, n));
     // Batches: the column form takes each step's control as kernel arguments too (its
     // path kernel then starts its window loads without a global round trip for the
@@ -716,9 +822,11 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     const bool pk = h->profiling && h->profKernels;
     if (pk) RS_TRY(pc_ensure_events(h, (size_t)4 * n));
     if (h->profiling) RS_HIP(hipEventRecord(h->ev0, h->stream));
+    int icur = 0;   // the next injection
     for (int s = 0; s < n; ++s) {
         const int pb = pk ? 4 * s : -1;
         const size_t b = (size_t)s * h->TH;
+        if (inj) RS_TRY(pc_inject_point(h, *inj, &icur, s, s > 0 ? step_key(h, step_out(h, s - 1)) : PcKeySrc{}));
         if (inline_ctl) {
             PcCtlInline c;
             make_ctl_inline(h->X, h->Y, h->TH, ox + b, oy + b, fidx + b, zf + (size_t)s * FL, &c);
@@ -736,6 +844,7 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
             RS_TRY(pc_launch_peak(h, h->dP.get(), f32 ? so.slot : nullptr, so.bmax, so.bidx, h->nPart, s));
         }
     }
+    if (inj) RS_TRY(pc_inject_point(h, *inj, &icur, n, step_key(h, step_out(h, n - 1))));
     if (h->prec == RS_PREC_F64) {
         hipLaunchKernelGGL((pc_argmax_steps<double>), dim3(n), dim3(NT), 0, h->stream,
                            static_cast<const double*>(h->dArgV.get()), h->dArgI.get(), h->nPart, h->dRes.get());
@@ -753,7 +862,8 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     // readback), its blocks' flags polled when the call may return early
     // (a peaks call synchronises the stream: the polled words' early return is safe only
     // because the host reads nothing else, and the sums are plain stores of other launches)
-    const bool may_poll = halo_poll_env() && !h->profiling && !skipped && n <= HF_POLL_MAX && !sums;
+    // (nor does a call with injections: their resolved cells are plain stores as well)
+    const bool may_poll = halo_poll_env() && !h->profiling && !skipped && n <= HF_POLL_MAX && !sums && !inj;
     int xnb = 0;
     unsigned seq = 0u;
     if (xp) RS_TRY(pc_launch_export(h, xp, may_poll, &xnb, &seq));
@@ -792,6 +902,56 @@ int pc_run_impl(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(pc_check_ctl(h, n, ox, oy, fidx, zf));
     return pc_run_direct(h, n, ox, oy, fidx, zf, out_xyz, xp, sums);
+}
+
+// A run's injections against the rule of rs_pc_run_odom_inject (pc_inj_first_bad, pc_ctl.h),
+// before any device work.
+int pc_check_inj(const rs_pc* h, int n, const PcInj& inj, const int32_t* out_inj_xyz) {
+    RS_CHECK(inj.ni >= 0, RS_ERR_ARG, "negative injection count");
+    if (inj.ni == 0) return RS_OK;
+    RS_CHECK(inj.step && inj.energy && inj.loc && out_inj_xyz, RS_ERR_ARG, "null injection array");
+    PcInjBad why = PC_INJ_OK;
+    const int i = pc_inj_first_bad(h->X, h->Y, h->TH, n, inj.ni, inj.step, inj.loc, &why);
+    if (i < 0) return RS_OK;
+    const int32_t* loc = inj.loc + 3 * (size_t)i;
+    RS_CHECK(why != PC_INJ_BAD_STEP, RS_ERR_ARG, "injection %d: step %d outside [0, %d]", i, inj.step[i], n);
+    RS_CHECK(why != PC_INJ_BAD_ORDER, RS_ERR_ARG, "injection %d: step %d after step %d", i, inj.step[i], inj.step[i - 1]);
+    RS_CHECK(why != PC_INJ_BAD_SAME, RS_ERR_ARG, "injection %d: same-as %d is no earlier injection", i, loc[1]);
+    RS_CHECK(false, RS_ERR_ARG, "injection %d: location (%d, %d, %d) outside grid (%d, %d, %d)", i, loc[0], loc[1], loc[2],
+             h->X, h->Y, h->TH);
+}
+
+// n steps with the injections of inj (checked) whose step is at most n: a caller that stops
+// at a LUT miss passes the steps before it, and the later injections never run.  Every
+// injection's resolved cell into out_inj_xyz, (-1, -1, -1) for one that did not run.
+int pc_run_inj(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx, const double* zf,
+               int32_t* out_xyz, double* sums, const PcInj& inj, int32_t* out_inj_xyz) {
+    RS_HIP(hipSetDevice(h->device));
+    if (n > 0) RS_TRY(pc_check_ctl(h, n, ox, oy, fidx, zf));
+    PcInj run = inj;
+    run.ni = 0;
+    while (run.ni < inj.ni && inj.step[run.ni] <= n) ++run.ni;
+    RS_TRY(pc_grow_inj(h, inj.ni));
+    for (int i = 0; i < inj.ni; ++i) h->hInj.get()[i] = PC_INJ_NONE;
+    if (n > 0) {
+        RS_TRY(pc_run_direct(h, n, ox, oy, fidx, zf, out_xyz, nullptr, sums, run.ni > 0 ? &run : nullptr));
+    } else if (run.ni > 0) {   // the injections alone, on the stored state
+        int cur = 0;
+        RS_TRY(pc_halo_settle(h));
+        RS_TRY(pc_inject_point(h, run, &cur, 0, PcKeySrc{}));
+        RS_HIP(hipStreamSynchronize(h->stream));
+    }
+    for (int i = 0; i < inj.ni; ++i) {
+        const unsigned lin = h->hInj.get()[i];
+        int32_t* o = out_inj_xyz + 3 * (size_t)i;
+        if (i < run.ni) {
+            RS_CHECK(lin < h->n, RS_ERR_HIP, "injection %d of %d: its cell did not reach the host", i, inj.ni);
+            decode_xyz(h, 0xFFFFFFFFull - lin, o);
+        } else {
+            o[0] = o[1] = o[2] = -1;
+        }
+    }
+    return RS_OK;
 }
 
 // path_integration's control for one step (posecell_network.py:252-308) in the
@@ -857,12 +1017,8 @@ int pc_odom_control(const OdoTables* h, double vtrans, double vrot, int32_t* ox,
 // key into dRes[0] and from there into hRes[0] once the stream has synchronised.
 template <typename T>
 int pc_argmax_queue(rs_pc* h, int* nb_out) {
-    const int nb = h->nBmaxCap < 1024 ? h->nBmaxCap : 1024;
-    *nb_out = nb;
-    hipLaunchKernelGGL((pc_argmax_blocks<T>), dim3(nb), dim3(NT), 0, h->stream,
-                       static_cast<const T*>(h->dP.get()), h->X, h->Y, h->TH, static_cast<T*>(h->dBmax.get()),
-                       h->dBidx.get(), (int)pc_thfast(h));
-    RS_HIP(hipGetLastError());
+    RS_TRY(pc_launch_argmax_blocks(h, nb_out));
+    const int nb = *nb_out;
     hipLaunchKernelGGL((pc_argmax_steps<T>), dim3(1), dim3(NT), 0, h->stream,
                        static_cast<const T*>(h->dBmax.get()), h->dBidx.get(), nb, h->dRes.get());
     RS_HIP(hipGetLastError());
@@ -1311,12 +1467,14 @@ int rs_pc_update_odom_read(rs_pc* h, double vtrans, double vrot, int32_t out_xyz
 }
 
 // A batch of steps from odometry samples; sums: six peak sums per step (pc_run_impl).
-static int pc_run_odom(rs_pc* h, int n, const double* odom, int32_t* out_xyz, int* first_bad, double* sums) {
+static int pc_run_odom(rs_pc* h, int n, const double* odom, int32_t* out_xyz, int* first_bad, double* sums,
+                       const PcInj* inj = nullptr, int32_t* out_inj_xyz = nullptr) {
     rs::clear_error();
     RS_CHECK(h, RS_ERR_STATE, "null pose-cell handle");
     RS_CHECK(h->odoReady, RS_ERR_STATE, "rs_pc_set_odometry_tables has not been called");
     RS_CHECK(!sums || h->peakR > 0, RS_ERR_STATE, "rs_pc_set_peak_tables has not been called");
     RS_CHECK(n >= 0 && (odom || n == 0), RS_ERR_ARG, "bad odometry batch");
+    if (inj) RS_TRY(pc_check_inj(h, n, *inj, out_inj_xyz));
     if (first_bad) *first_bad = -1;
     const size_t th = h->TH;
     h->cOx.resize(th * (n > 0 ? n : 1));
@@ -1368,8 +1526,12 @@ static int pc_run_odom(rs_pc* h, int n, const double* odom, int32_t* out_xyz, in
         if (fail_st == RS_ERR_LUT_KEY) todo = fail;
         else RS_CHECK(false, fail_st, "odometry of step %d outside the control tables", fail);
     }
-    RS_TRY(pc_run_impl(h, todo, h->cOx.data(), h->cOy.data(), h->cRows.data(), h->cZf.data(),
-                       out_xyz, nullptr, sums));
+    if (inj && inj->ni > 0)
+        RS_TRY(pc_run_inj(h, todo, h->cOx.data(), h->cOy.data(), h->cRows.data(), h->cZf.data(), out_xyz, sums, *inj,
+                          out_inj_xyz));
+    else
+        RS_TRY(pc_run_impl(h, todo, h->cOx.data(), h->cOy.data(), h->cRows.data(), h->cZf.data(),
+                           out_xyz, nullptr, sums));
     if (todo < n) {
         RS_TRY(rs_pc_excite(h));
         if (first_bad) *first_bad = todo;
@@ -1438,6 +1600,26 @@ int rs_pc_run_peaks(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const
     rs::clear_error();
     RS_CHECK(out_sums || n <= 0, RS_ERR_ARG, "null sums");
     return pc_run_impl(h, n, ox, oy, fidx, zf, out_xyz, nullptr, out_sums);
+}
+
+int rs_pc_run_odom_inject(rs_pc* h, int n, const double* odom, int ni, const int32_t* inj_step,
+                          const double* inj_energy, const int32_t* inj_loc, int32_t* out_xyz, int32_t* out_inj_xyz,
+                          double* out_sums, int* first_bad) {
+    const PcInj inj{ni, inj_step, inj_energy, inj_loc};
+    return pc_run_odom(h, n, odom, out_xyz, first_bad, out_sums, &inj, out_inj_xyz);
+}
+
+int rs_pc_run_inject(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx, const double* zf,
+                     int ni, const int32_t* inj_step, const double* inj_energy, const int32_t* inj_loc,
+                     int32_t* out_xyz, int32_t* out_inj_xyz, double* out_sums) {
+    rs::clear_error();
+    RS_CHECK(h, RS_ERR_STATE, "null pose-cell handle");
+    RS_CHECK(n >= 0, RS_ERR_ARG, "negative step count");
+    RS_CHECK(!out_sums || h->peakR > 0, RS_ERR_STATE, "rs_pc_set_peak_tables has not been called");
+    const PcInj inj{ni, inj_step, inj_energy, inj_loc};
+    RS_TRY(pc_check_inj(h, n, inj, out_inj_xyz));
+    if (ni == 0) return pc_run_impl(h, n, ox, oy, fidx, zf, out_xyz, nullptr, out_sums);
+    return pc_run_inj(h, n, ox, oy, fidx, zf, out_xyz, out_sums, inj, out_inj_xyz);
 }
 
 int rs_pc_peak_host(int X, int Y, int TH, int r, const double* volume, const int32_t xyz[3], const double* sc_x,

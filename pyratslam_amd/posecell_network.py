@@ -117,6 +117,8 @@ class PoseCellNetwork:
     Extra keyword arguments are accepted and ignored, like the reference (:24).
     """
 
+    AT_PEAK = 'peak'   # run(injections=...): the first maximum of the state at that point
+
     def __init__(self, shape, precision='float32', device=0, readback='lazy',
                  cells_to_avg=pc_peak.CELLS_TO_AVG, **kwargs):
         if readback not in ('lazy', 'eager'):
@@ -129,6 +131,7 @@ class PoseCellNetwork:
         # run(poses=True) that raised the reference's LUT KeyError at step s: the (s, 3) poses
         # of the steps before it (the call's return value is lost to the exception)
         self.last_poses = None
+        self.last_injection_cells = None   # run(injections=...): the cells of its last call
         self._fresh = None   # eager: the volume exported by the last update()
         if len(shape) != 3:
             raise TypeError('PoseCellNetwork shape must be (X, Y, TH), got %r' % (shape,))
@@ -381,16 +384,27 @@ class PoseCellNetwork:
 
     step = update
 
-    def run(self, odometry, poses=False):
+    def run(self, odometry, poses=False, injections=None):
         """``update`` for every row (vtrans, vrot) of ``odometry``; one host round trip.
 
         Returns an int32 array (n, 3) of max_pc per step; with ``poses=True``,
         ``(maxes, poses)``, poses a float64 (n, 3) array of each step's sub-cell pose.
         A LUT KeyError at step s leaves the state the reference would (steps < s done,
         then steps 1-4 of s).
+
+        ``injections``: a sequence of ``(step, energy, loc)``, steps non-decreasing in
+        ``0 .. n``; injection i is applied in front of step ``step`` (``n``: behind the last
+        one) exactly as ``inject(energy, cell)`` between two ``update`` calls would be.
+        ``loc`` is a tuple ``(x, y, th)`` (``inject``'s rules), ``PoseCellNetwork.AT_PEAK``
+        (what ``get_pc_max()`` would return at that point) or ``('same', k)`` with k < i (the
+        cell injection k resolved to).  The resolved cells come back as an ``(ni, 3)`` int32
+        array, last in the returned tuple; after a LUT KeyError they are in
+        ``last_injection_cells``, ``(-1, -1, -1)`` for the injections behind the failing step.
         """
         od = np.ascontiguousarray(np.asarray(odometry, dtype=np.float64).reshape(-1, 2))
         n = od.shape[0]
+        if injections is not None:
+            return self._run_inject(od, poses, injections)
         if poses:
             return self._run_poses(od)
         if n == 1 and not self._eager:
@@ -446,6 +460,83 @@ class PoseCellNetwork:
             F.step_control(od[bad.value, 0], od[bad.value, 1], self.shape[2], self.filter_table)
             raise KeyError('LUT miss at step %d' % bad.value)  # pragma: no cover
         return out, self._poses(out, sums)
+
+    def _injection_arrays(self, n, injections):
+        """``injections`` as rs_pc_run_odom_inject's arrays (ValueError / IndexError before
+        any device work, as the library itself refuses what is left)."""
+        inj = list(injections)
+        step = np.empty(len(inj), dtype=np.int32)
+        energy = np.empty(len(inj), dtype=np.float64)
+        loc = np.zeros((len(inj), 3), dtype=np.int32)
+        X, Y, TH = self.shape
+        for i, (st, e, where) in enumerate(inj):
+            if int(st) != st or not 0 <= st <= n:
+                raise ValueError('injection %d: step %r outside 0 .. %d' % (i, st, n))
+            if i and st < step[i - 1]:
+                raise ValueError('injection %d: step %d after step %d' % (i, st, step[i - 1]))
+            step[i], energy[i] = st, float(e)
+            if isinstance(where, str) and where == self.AT_PEAK:
+                loc[i, 0] = _lib.RS_PC_INJ_AT_PEAK
+            elif isinstance(where, tuple) and len(where) == 2 and where[0] == 'same':
+                k = where[1]
+                if int(k) != k or not 0 <= k < i:
+                    raise ValueError("injection %d: ('same', %r) is no earlier injection" % (i, k))
+                loc[i, :2] = _lib.RS_PC_INJ_SAME_AS, k
+            else:
+                if isinstance(where, list):
+                    raise TypeError('an injection location is a tuple (x, y, th)')
+                x, y, th = (int(v) for v in where)
+                x, y, th = x + X if x < 0 else x, y + Y if y < 0 else y, th + TH if th < 0 else th
+                if not (0 <= x < X and 0 <= y < Y and 0 <= th < TH):
+                    raise IndexError('injection %d: location %r outside grid %r' % (i, where, self.shape))
+                loc[i] = x, y, th
+        return step, energy, loc
+
+    def _run_inject(self, od, poses, injections):
+        """run(injections=...): rs_pc_run_odom_inject, with run()'s KeyError and host-control
+        paths (rs_pc_run_inject)."""
+        n = od.shape[0]
+        step, energy, loc = self._injection_arrays(n, injections)
+        ni = len(step)
+        out = np.empty((n, 3), dtype=np.int32)
+        cells = np.full((ni, 3), -1, dtype=np.int32)
+        sums = np.empty((n, 6), dtype=np.float64) if poses else None
+        inj_args = (ni, _lib.ptr(step, ctypes.c_int32), _lib.ptr(energy, ctypes.c_double),
+                    _lib.ptr(loc, ctypes.c_int32))
+        out_args = (_lib.ptr(out, ctypes.c_int32), _lib.ptr(cells, ctypes.c_int32),
+                    _lib.ptr(sums, ctypes.c_double) if poses else None)
+        bad = ctypes.c_int(-1)
+        self.last_injection_cells = cells
+        with self._mutex:
+            if poses:
+                self._peak_tables()
+            self._fresh = None
+            st = self._lib.rs_pc_run_odom_inject(self._h, n, _lib.ptr(od, ctypes.c_double), *inj_args, *out_args,
+                                                 ctypes.byref(bad))
+            first_bad = bad.value if st == _lib.RS_ERR_LUT_KEY else None
+            if st == _lib.RS_ERR_CTL_RANGE:
+                ox, oy, rows, zf, first_bad = F.batch_control(od, self.shape[2], self.filter_table)
+                todo = n if first_bad is None else first_bad
+                # (a LUT miss: the steps before it with the injections up to it, then steps 1-4)
+                keep = int(np.searchsorted(step, todo, side='right'))
+                _lib.check(self._lib.rs_pc_run_inject(
+                    self._h, todo, _lib.ptr(ox, ctypes.c_int32), _lib.ptr(oy, ctypes.c_int32),
+                    _lib.ptr(rows, ctypes.c_int32), _lib.ptr(zf, ctypes.c_double), keep, *inj_args[1:], *out_args))
+                if first_bad is not None:
+                    _lib.check(self._lib.rs_pc_excite(self._h))
+            elif st not in (_lib.RS_OK, _lib.RS_ERR_LUT_KEY):
+                _lib.check(st)
+            todo = n if first_bad is None else first_bad
+            if todo > 0:
+                self.max_pc = tuple(int(v) for v in out[todo - 1])
+            # (an injection behind the last step has changed the state since its peak was taken)
+            self._max_valid = first_bad is None and todo > 0 and not (ni and step[-1] == n)
+        if first_bad is not None:
+            if poses:
+                self.last_poses = self._poses(out[:todo], sums[:todo])
+            F.step_control(od[first_bad, 0], od[first_bad, 1], self.shape[2], self.filter_table)
+            raise KeyError('LUT miss at step %d' % first_bad)  # pragma: no cover
+        return (out, self._poses(out, sums), cells) if poses else (out, cells)
 
     def _run_host_control(self, od, poses=False):
         """run() with the control computed here (filters.batch_control) and handed to

@@ -39,7 +39,10 @@ same pipeline over an array of frames, batched on the GPU.
 experiences and relaxes the map on the GPU) in place of the dead-reckoned ``ExperienceMap``;
 ``--subcell-peak`` also records the sub-cell pose of every update (``pc_pose``: the activity
 packet's circular centroid, ``PoseCellNetwork.update_pose`` / ``run(poses=True)``), while the
-view templates, the feedback injection and both maps still receive the integer peak cell.
+view templates, the feedback injection and both maps still receive the integer peak cell;
+``--window K`` (``RatslamReplay(window=K)``) matches K frames with one ``match_batch`` and steps
+the twists between them with one ``run``, the feedback injections inside it
+(``run(injections=...)``), with the outputs of the frame-by-frame loop.
 """
 import argparse
 import json
@@ -66,6 +69,40 @@ ODOM_TOPIC = 'navbot/odom'
 IMAGE_TOPIC = 'navbot/camera/image'
 
 
+def window_boundaries(messages, odom_freq=ODOM_FREQ):
+    """The window scheduler's first half, a pure function of a window's messages --
+    ``('odom', twist)`` with ``twist.linear`` / ``twist.angular``, or ``('image', frame)`` --
+    to ``(steps, bounds)``: the (vtrans, vrot) of every twist the node would queue
+    (``odom_callback``'s 0.001 filter, ``drain``'s division), and for each frame its boundary,
+    the number of steps applied before the frame is matched."""
+    steps, bounds = [], []
+    for kind, msg in messages:
+        if kind == 'odom':
+            if abs(msg.linear[0]) > 0.001 or abs(msg.angular[2]) > 0.001:
+                steps.append((msg.linear[0] / odom_freq, msg.angular[2] / odom_freq))
+        else:
+            bounds.append(len(steps))
+    return steps, bounds
+
+
+def injection_kinds(template_index, known):
+    """... and its second half: the injection of each frame of a window (or batch) from the
+    frames' template indices and the number of templates ``known`` before it:
+    ``('stored', t)`` for a template that existed, ``('peak',)`` for the frame that creates
+    one (it is stored, and fed back, at the peak of that moment) and ``('same', j)`` for a
+    later frame that matches the template frame j of this window created."""
+    kinds, creator = [], {}
+    for j, t in enumerate(int(t) for t in template_index):
+        if t < known:
+            kinds.append(('stored', t))
+        elif t in creator:
+            kinds.append(('same', creator[t]))
+        else:
+            creator[t] = j
+            kinds.append(('peak',))
+    return kinds
+
+
 class RatslamReplay:
     """``RatslamRos`` driven by recorded messages.
 
@@ -78,7 +115,7 @@ class RatslamReplay:
                  x_step=X_STEP, y_step=Y_STEP, match_threshold=MATCH_THRESHOLD,
                  odom_freq=ODOM_FREQ, feedback_energy=None, pcn=None, vts=None, em=None,
                  device=0, precision='float32', batch=True, publish=False,
-                 use_visual_odometry=False, vo=None, subcell_peak=False):
+                 use_visual_odometry=False, vo=None, subcell_peak=False, window=1):
         # publish: the node's per-step work in full -- every update reads the whole
         # .posecells volume, as ros_simulate.py:140-145 does to publish it -- so steps
         # go one by one (no batched run()) and the network exports eagerly
@@ -98,6 +135,13 @@ class RatslamReplay:
         self.odom_freq = odom_freq
         self.feedback_energy = feedback_energy
         self.batch = batch and hasattr(pcn, 'run') and not publish
+        # run(injections=...): the feedback inside a batched run (the oracle has none)
+        self._run_injects = self.batch and _takes_injections(pcn)
+        # window: frames matched, and their twists stepped, per batched call of replay_events /
+        # replay_bag (1: the per-frame loop)
+        if int(window) != window or window < 1:
+            raise ValueError('window must be a positive integer, got %r' % (window,))
+        self.window = int(window)
         self.published = 0   # .posecells volumes read (publish=True)
         self.twist_data = deque()
         # USE_VISUAL_ODOMETRY (ros_simulate.py:81, 90): no odometry subscription, every
@@ -176,44 +220,104 @@ class RatslamReplay:
             for vt, vr in steps:
                 self.update_posecells(vt, vr)
 
-    def _run(self, odometry):
-        """``pcn.run``; with ``subcell_peak`` the poses come back with the peaks and are recorded."""
+    def _run(self, odometry, injections=None):
+        """``pcn.run``; with ``subcell_peak`` the poses come back with the peaks and are recorded.
+        With ``injections``: ``(maxes, cells)``."""
+        kw = {} if injections is None else {'injections': injections}
         if not self.subcell_peak:
-            return self.pcn.run(odometry)
-        maxes, poses = self.pcn.run(odometry, poses=True)
+            return self.pcn.run(odometry, **kw)
+        maxes, poses, *cells = self.pcn.run(odometry, poses=True, **kw)
         self.pc_pose.extend(tuple(float(v) for v in p) for p in poses)
-        return maxes
+        return maxes if injections is None else (maxes, cells[0])
+
+    def _feedback_injections(self, kinds, bounds):
+        """``injection_kinds`` as ``run(injections=...)``: frame j injects at its boundary."""
+        where = {'stored': lambda t: tuple(self.vts.templates[t].location()),
+                 'peak': lambda: self.pcn.AT_PEAK, 'same': lambda j: ('same', j)}
+        return [(b, self.feedback_energy, where[k[0]](*k[1:])) for k, b in zip(kinds, bounds)]
+
+    def _windowed(self):
+        """Whether replay_events / replay_bag go window by window (else the per-frame loop)."""
+        return (self.window > 1 and self._run_injects and not self.use_visual_odometry
+                and hasattr(self.vts, 'match_batch') and getattr(self.vts, 'nranks', 1) == 1)
+
+    def _replay_messages(self, messages):
+        """``('odom', twist)`` / ``('image', frame)`` messages in order: the per-frame loop, or
+        windows of up to ``window`` frames with the twists between them."""
+        if not self._windowed():
+            for kind, msg in messages:
+                if kind == 'odom':
+                    self.odom_callback(msg)
+                else:
+                    self.drain()
+                    self.vis_callback(msg)
+                    if self.use_visual_odometry:   # a visual delta is applied right after its frame
+                        self.drain()
+            self.drain()
+            return self
+        self.drain()
+        pending, frames = [], 0
+        for m in messages:
+            pending.append(m)
+            frames += m[0] != 'odom'
+            if frames == self.window:
+                self._replay_window(pending)
+                pending, frames = [], 0
+        self._replay_window(pending)
+        return self
+
+    def _replay_window(self, messages):
+        """One window: one ``match_batch`` of its frames with placeholder cells, one ``run`` of
+        all its steps (with feedback, the frames' injections at their boundaries), the new
+        templates' cells filled in, then the records in message order."""
+        steps, bounds = window_boundaries(messages, self.odom_freq)
+        images = [m[1] for m in messages if m[0] != 'odom']
+        if not steps and not images:
+            return
+        known = len(self.vts.templates)
+        matched = self.vts.match_batch(images, [(0, 0, 0)] * len(images)) if images else []
+        index = [int(t.get_index()) for t in matched]
+        kinds = injection_kinds(index, known)
+        od = np.array(steps, dtype=np.float64).reshape(-1, 2)
+        if self.feedback_energy and images:
+            maxes, cells = self._run(od, self._feedback_injections(kinds, bounds))
+        else:
+            # a template created in front of the window's first step is stored at the peak now
+            start = (self.pcn.get_pc_max() if any(k == ('peak',) and b == 0 for k, b in zip(kinds, bounds))
+                     else None)
+            maxes = self._run(od) if steps else []
+            cells = [start if b == 0 else maxes[b - 1] for b in bounds]
+        for t, k, cell in zip(matched, kinds, cells):
+            if k == ('peak',):
+                t.pc_x, t.pc_y, t.pc_th = (int(v) for v in cell)
+        frame = 0
+        for s in range(len(steps) + 1):
+            while frame < len(bounds) and bounds[frame] == s:
+                self.template_index.append(index[frame])
+                if self._em_links:
+                    self.em.on_template(index[frame])
+                frame += 1
+            if s < len(steps):
+                self._record(steps[s][0], steps[s][1], maxes[s])
 
     # -- drivers -----------------------------------------------------------------
     def replay_events(self, events):
         """``synthetic.ros_stream`` events (already decoded)."""
-        for ev in events:
-            if ev[0] == 'odom':
-                self.odom_callback(rosbag.Twist(ev[2], ev[3]))
-            else:
-                self.drain()
-                self.vis_callback(ev[2])
-                if self.use_visual_odometry:   # a visual delta is applied right after its frame
-                    self.drain()
-        self.drain()
-        return self
+        return self._replay_messages(('odom', rosbag.Twist(ev[2], ev[3])) if ev[0] == 'odom' else ('image', ev[2])
+                                     for ev in events)
 
     def replay_bag(self, path, odom_topic=ODOM_TOPIC, image_topic=IMAGE_TOPIC):
         """Messages of a bag in order; odometry from nav_msgs/Odometry (or a bare
         geometry_msgs/Twist), frames from sensor_msgs/Image."""
         o, i = odom_topic.lstrip('/'), image_topic.lstrip('/')
-        for m in rosbag.read_bag(path, topics={o, i}):
-            if m.topic.lstrip('/') == o:
-                tw = rosbag.decode_twist(m.data) if m.type == 'geometry_msgs/Twist' else \
-                    rosbag.decode_odometry_twist(m.data)
-                self.odom_callback(tw)
-            else:
-                self.drain()
-                self.vis_callback(rosbag.image_to_mono8(rosbag.decode_image(m.data)))
-                if self.use_visual_odometry:
-                    self.drain()
-        self.drain()
-        return self
+        def messages():
+            for m in rosbag.read_bag(path, topics={o, i}):
+                if m.topic.lstrip('/') == o:
+                    yield 'odom', (rosbag.decode_twist(m.data) if m.type == 'geometry_msgs/Twist' else
+                                   rosbag.decode_odometry_twist(m.data))
+                else:
+                    yield 'image', rosbag.image_to_mono8(rosbag.decode_image(m.data))
+        return self._replay_messages(messages())
 
     def replay_frames(self, frames, batch=64):
         """The camera-only pipeline (``use_visual_odometry=True``) over a uint8
@@ -222,9 +326,15 @@ class RatslamReplay:
         its peaks, and ``vts.match_frames`` matches frame i at the peak after deltas
         0..i-1 (the last peak carries over from the batch before).  Without feedback
         that is exactly the per-frame order -- match at the current peak, then the
-        frame's delta, then the step.  With ``feedback_energy`` (the match changes the
-        state the next step starts from), or with a drop-in ``vo`` / ``vts`` / ``pcn``
-        that has no batched form, the frames go one by one through ``vis_callback``."""
+        frame's delta, then the step.  With ``feedback_energy`` the match changes the
+        state the next step starts from, but not the other way round (a match depends on
+        the frames and the library only): the batch is matched with placeholder cells,
+        then stepped by one ``pcn.run(deltas, injections=...)`` with frame i's injection in
+        front of step i -- at the stored cell of a template that existed, at the peak of that
+        moment for the frame that creates one, at the same cell for a later frame of the batch
+        that matches it -- and the new templates take the cells their injections resolved to.
+        With a drop-in ``vo`` / ``vts`` / ``pcn`` that has no batched form, the frames go one
+        by one through ``vis_callback``."""
         if not self.use_visual_odometry:
             raise ValueError('replay_frames is the camera-only pipeline: construct with '
                              'use_visual_odometry=True')
@@ -234,7 +344,7 @@ class RatslamReplay:
         if f.ndim != 3:
             raise ValueError('frames must be (n, im_h, im_w), got shape %r' % (f.shape,))
         from .visual_odometer import SimpleVisualOdometer
-        batched = (not self.feedback_energy and self.batch and batch > 1
+        batched = ((not self.feedback_energy or self._run_injects) and self.batch and batch > 1
                    and isinstance(self.vo, SimpleVisualOdometer)
                    and hasattr(self.vts, 'match_frames') and getattr(self.vts, 'nranks', 1) == 1)
         if not batched:
@@ -258,10 +368,22 @@ class RatslamReplay:
                 n = chunk.shape[0]
                 buf.upload(chunk)
                 deltas = self.vo.run((n, buf))
-                peak = tuple(int(v) for v in self.pcn.get_pc_max())
-                maxes = self._run(deltas)
-                pcs = [peak] + [tuple(int(v) for v in m) for m in maxes[:-1]]
-                idx, _, _ = self.vts.match_frames((n, buf), pcs)
+                if self.feedback_energy:
+                    # the match does not depend on the pose cells: placeholder cells, then one
+                    # run with frame i's injection in front of step i, and the new templates'
+                    # cells from what their at-peak injections resolved to
+                    known = len(self.vts.templates)
+                    idx, _, new = self.vts.match_frames((n, buf), None)
+                    kinds = injection_kinds(idx, known)
+                    maxes, cells = self._run(deltas, self._feedback_injections(kinds, range(n)))
+                    for j in np.flatnonzero(new):
+                        t = self.vts.templates[int(idx[j])]
+                        t.pc_x, t.pc_y, t.pc_th = (int(v) for v in cells[j])
+                else:
+                    peak = tuple(int(v) for v in self.pcn.get_pc_max())
+                    maxes = self._run(deltas)
+                    pcs = [peak] + [tuple(int(v) for v in m) for m in maxes[:-1]]
+                    idx, _, _ = self.vts.match_frames((n, buf), pcs)
                 self.template_index.extend(int(j) for j in idx)
                 for (vt, vr), m, j in zip(deltas, maxes, idx):
                     if self._em_links:   # the frame's match, then its step: the per-frame order
@@ -279,6 +401,15 @@ class RatslamReplay:
                 'em_points': np.array(self.em_points, dtype=np.float64).reshape(-1, 2),
                 'template_index': np.array(self.template_index, dtype=np.int64),
                 'templates': len(self.vts.templates)}
+
+
+def _takes_injections(pcn):
+    """Whether ``pcn.run`` takes ``injections`` (PoseCellNetwork's; a drop-in may not)."""
+    import inspect
+    try:
+        return 'injections' in inspect.signature(pcn.run).parameters
+    except (TypeError, ValueError):
+        return False
 
 
 def sharded_templates(d, device, host_reduce=False, x_range=X_RANGE, y_range=Y_RANGE, x_step=X_STEP,
@@ -322,6 +453,9 @@ def main(argv=None):
     ap.add_argument('--subcell-peak', action='store_true',
                     help='record the sub-cell pose of every update (pc_pose): the activity '
                          'packet\'s circular centroid, computed on the GPU behind each step')
+    ap.add_argument('--window', type=int, default=1, metavar='K',
+                    help='match K frames and step the twists between them per batched call '
+                         '(odometry mode; 1: frame by frame)')
     ap.add_argument('--host-reduce', action='store_true',
                     help='combine the ranks\' keys on the host (several ranks on one GPU)')
     args = ap.parse_args(argv)
@@ -341,7 +475,8 @@ def main(argv=None):
         em = LinkedExperienceMap(exp_loops=EXP_LOOPS if args.exp_loops is None else args.exp_loops,
                                  device=dev)
     r = RatslamReplay(device=dev, precision=args.precision, feedback_energy=args.feedback, vts=vts,
-                      use_visual_odometry=args.visual_odometry, em=em, subcell_peak=args.subcell_peak)
+                      use_visual_odometry=args.visual_odometry, em=em, subcell_peak=args.subcell_peak,
+                      window=args.window)
     d.barrier()
     t0 = time.perf_counter()
     if args.bag:
