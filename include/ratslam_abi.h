@@ -313,6 +313,22 @@ typedef struct rs_vt rs_vt;
  * capacity = initial number of templates this rank can hold (grows by doubling). */
 int rs_vt_create(int H, int W, int max_offset, uint64_t match_threshold, int64_t capacity,
                  int device, rs_vt** out);
+/* The metric of a uint8 library, fixed at create.
+ *   RS_VT_METRIC_WRAPPED  sum of (T - Q) mod 256 per byte pair: numpy's own arithmetic on
+ *                         uint8 arrays (the reference on mono8 frames); a pixel where the
+ *                         query is one grey level above the template scores 255
+ *   RS_VT_METRIC_SAD      sum of |T - Q| on the bytes as integers: the reference's
+ *                         ViewTemplate.match on the same arrays cast to float
+ * Everything behind a score -- packed keys, first argmin, threshold, in-batch candidates,
+ * append, the min-reduction over ranks, rs_vt_match_stream / _frames / _scores -- is the
+ * same for both.  rs_vt_create is rs_vt_create_metric with RS_VT_METRIC_WRAPPED.  Another
+ * metric: RS_ERR_ARG before any device work, *out left NULL.  A SAD handle has no bit
+ * planes and never prunes: RS_VT_SCAN, RS_VT_PRUNE and RS_VT_FRONT are not read for it. */
+#define RS_VT_METRIC_WRAPPED 0
+#define RS_VT_METRIC_SAD     1
+int rs_vt_create_metric(int H, int W, int max_offset, uint64_t match_threshold, int64_t capacity,
+                        int device, int metric, rs_vt** out);
+int rs_vt_metric(const rs_vt* h, int* metric);
 int rs_vt_destroy(rs_vt* h);
 /* global number of stored templates (over all ranks) */
 int rs_vt_count(const rs_vt* h, int64_t* count);
@@ -381,7 +397,9 @@ int rs_vt_set_timing(rs_vt* h, int enable);
  * NULL for a null handle.  "carry" names the family, not the launch: a key scan of
  * little work (fewer than 2,048 template blocks x queries, at most 8 dword columns)
  * runs its column form, vt_scan_carry_col_kernel; score matrices and every other
- * key scan run vt_scan_carry_kernel */
+ * key scan run vt_scan_carry_kernel.  A RS_VT_METRIC_SAD handle: "sad" (max_offset 8,
+ * H in {32, 64}, any W: a template column's rows in registers, v_sad_u8 per dword pair
+ * and offset) or "sad-generic" (any other shape) */
 const char* rs_vt_scan_form(const rs_vt* h);
 /* "plane-pruned": a plane handle (H == 64) whose large frozen key scans prune template
  * blocks by an exact partial-score bound: a prefilter bounds every

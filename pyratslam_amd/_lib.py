@@ -32,6 +32,8 @@ RS_PC_INJ_AT_PEAK = -1
 RS_PC_INJ_SAME_AS = -2
 RS_VT_FROZEN = 0
 RS_VT_SEQUENTIAL = 1
+RS_VT_METRIC_WRAPPED = 0
+RS_VT_METRIC_SAD = 1
 RS_UNIQUE_ID_BYTES = 128
 RS_DT_F32 = 0
 RS_DT_F64 = 1
@@ -122,6 +124,9 @@ SIGNATURES = {
     'rs_pc_debug_value': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     'rs_vt_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
                                     ctypes.c_int64, ctypes.c_int, ctypes.POINTER(_vp)]),
+    'rs_vt_create_metric': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                           ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    'rs_vt_metric': (ctypes.c_int, [_vp, _c_int_p]),
     'rs_vt_destroy': (ctypes.c_int, [_vp]),
     'rs_vt_count': (ctypes.c_int, [_vp, _i64p]),
     'rs_vt_add': (ctypes.c_int, [_vp, ctypes.c_int, _u8p, _i64p]),
@@ -185,7 +190,7 @@ SIGNATURES = {
 
 # statistics calls an older build of the library lacks: tools/stream_ab.py loads such
 # builds by path for an A/B; calling one of these on them raises AttributeError
-NEWER_SYMBOLS = {'rs_vt_prune_stats', 'rs_vt_prune_verified'}
+NEWER_SYMBOLS = {'rs_vt_prune_stats', 'rs_vt_prune_verified', 'rs_vt_create_metric', 'rs_vt_metric'}
 
 _lib = None
 _lock = threading.Lock()

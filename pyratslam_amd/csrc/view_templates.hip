@@ -342,6 +342,10 @@ __global__ __launch_bounds__(64) void vt_scan_generic_kernel(const uint4* __rest
     emit_score<MATRIX>(out, (int64_t)tb * 64 + lane, count, qi, nq, best, rank, nranks, lane == 0);
 }
 
+static_assert(vt_plan::METRIC_WRAPPED == RS_VT_METRIC_WRAPPED && vt_plan::METRIC_SAD == RS_VT_METRIC_SAD,
+              "vt_plan.h restates the ABI's metric codes");
+#include "vt_sad.h"
+
 // ===========================================================================
 // Bit-plane scan (default for W = 32, H in {32, 64}, max_offset 8).
 //
@@ -1834,6 +1838,9 @@ struct rs_vt {
     // bit-plane scan (default when W == 32, H in {32, 64}, max_offset 8; RS_VT_SCAN=plane):
     // planes + TS of the library and candidate slots, query planes + raw sums
     bool planar = false;
+    // the metric, fixed at create (rs_vt_create_metric): RS_VT_METRIC_SAD handles are never
+    // planar and never prune; their query form (vt_qform_sad_kernel) lives in dQf
+    int metric = RS_VT_METRIC_WRAPPED;
     rs::DevBuf<uint32_t> dLibP, dLibTs, dCandP, dCandTs;
     rs::DevBuf<uint32_t> dQp, dQsumRaw;   // (with qCap, like dQsj and dQc)
     int planeSlots = 0;  // resident plane-scan blocks on the device (occupancy x CUs)
@@ -2057,7 +2064,10 @@ int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
 // Build the query forms of nq raw queries in device memory (default: dQraw) into the view q.
 // The plane scan reads only the planes; the byte-SWAR forms serve the other scans.
 int vt_build_forms(rs_vt* h, const QueryForms& q, int nq, const uint8_t* src) {
-    if (!h->planar)
+    if (h->metric == RS_VT_METRIC_SAD)
+        hipLaunchKernelGGL(vt_qform_sad_kernel, dim3(nq), dim3(256), 0, h->stream, src, h->H, h->W, h->WD,
+                           reinterpret_cast<uint32_t*>(h->dQf.get()));
+    else if (!h->planar)
         hipLaunchKernelGGL(vt_qform_kernel, dim3(nq), dim3(256), 0, h->stream, src, h->H, h->W,
                            h->WD, h->M, h->dQf.get(), h->dQsum.get());
     else {
@@ -2267,6 +2277,26 @@ int vt_launch_plane(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int
     return RS_OK;
 }
 
+// A scan under the true-SAD metric: the fast form or the generic one (vt_plan::sad_fast).
+template <bool MATRIX>
+int vt_launch_sad(rs_vt* h, const uint4* lib, int ntb, int64_t count, int nq, ScanOut out, int rank, int nranks) {
+    const uint32_t* qd = reinterpret_cast<const uint32_t*>(h->dQf.get());
+    if (vt_plan::sad_fast(h->H, h->M)) {
+        const int nqc = vt_plan::sad_split(ntb, (nq + SAD_NQ - 1) / SAD_NQ);
+        RS_CHECK((int64_t)ntb * nqc < (1ll << 31), RS_ERR_ARG, "scan grid too large (%d x %d)", ntb, nqc);
+        vt_by_h(h, [&](auto H) {
+            hipLaunchKernelGGL((vt_scan_sad_kernel<decltype(H)::value, MATRIX>), dim3((unsigned)(ntb * nqc)),
+                               dim3(64 * vt_plan::sad_waves(h->WD)), 0, h->stream, lib, ntb, count, h->WD, qd, nq,
+                               nqc, out, rank, nranks);
+        });
+    } else {
+        hipLaunchKernelGGL((vt_scan_sad_generic_kernel<MATRIX>), dim3((unsigned)(ntb * nq)), dim3(64), 0, h->stream,
+                           lib, ntb, count, h->H, h->M, h->WD, qd, nq, out, rank, nranks);
+    }
+    RS_HIP(hipGetLastError());
+    return RS_OK;
+}
+
 // Launch a scan of queries [0, nq) against `count` slots of the library (or of
 // the candidate buffer), starting at 64-slot block tb0 of it (q: the plane scan's forms).
 template <bool MATRIX>
@@ -2278,6 +2308,7 @@ int vt_launch_scan(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int 
     const int ntb = (int)((count + 63) / 64);
     const bool fast = h->M == FAST_M && (h->H == 64 || h->H == 32);
     RS_CHECK((int64_t)ntb * nq < (1ll << 31), RS_ERR_ARG, "scan grid too large (%d x %d)", ntb, nq);
+    if (h->metric == RS_VT_METRIC_SAD) return vt_launch_sad<MATRIX>(h, lib, ntb, count, nq, out, rank, nranks);
     if (fast && !MATRIX && (int64_t)ntb * nq < 2048 && h->WD <= 8) {
         // few waves of work: spread each template over 8 column lanes
         const dim3 grid((unsigned)((count + 7) / 8), nq);
@@ -2675,9 +2706,16 @@ extern "C" {
 
 int rs_vt_create(int H, int W, int max_offset, uint64_t thr, int64_t capacity, int device,
                  rs_vt** out) {
+    return rs_vt_create_metric(H, W, max_offset, thr, capacity, device, RS_VT_METRIC_WRAPPED, out);
+}
+
+int rs_vt_create_metric(int H, int W, int max_offset, uint64_t thr, int64_t capacity, int device,
+                        int metric, rs_vt** out) {
     rs::clear_error();
     RS_CHECK(out, RS_ERR_ARG, "null output handle pointer");
     *out = nullptr;
+    RS_CHECK(vt_plan::metric_known(metric), RS_ERR_ARG, "unknown metric %d: expected RS_VT_METRIC_WRAPPED or "
+             "RS_VT_METRIC_SAD", metric);
     RS_CHECK(H > 0 && W > 0 && H <= 4096 && W <= 4096, RS_ERR_ARG, "bad template shape (%d, %d)", H, W);
     RS_CHECK(max_offset >= 1 && max_offset <= 64, RS_ERR_ARG, "max_offset %d outside [1, 64]", max_offset);
     RS_CHECK(capacity >= 0, RS_ERR_ARG, "negative capacity");
@@ -2693,8 +2731,11 @@ int rs_vt_create(int H, int W, int max_offset, uint64_t thr, int64_t capacity, i
     h->H = H; h->W = W; h->M = max_offset; h->thr = (double)thr; h->device = device;
     h->WD = (W + 3) / 4;
     h->HQ = (H + 3) / 4;
-    h->planar = W == 8 * PL_CG && (H == 64 || H == 32) && max_offset == FAST_M;
-    if (const char* e = std::getenv("RS_VT_SCAN")) {
+    h->metric = metric;
+    // (a term is at most 255 under either metric: the bound above holds for both)
+    const bool wrapped = metric == RS_VT_METRIC_WRAPPED;   // RS_VT_SCAN / _PRUNE / _FRONT are its switches
+    h->planar = wrapped && W == 8 * PL_CG && (H == 64 || H == 32) && max_offset == FAST_M;
+    if (const char* e = wrapped ? std::getenv("RS_VT_SCAN") : nullptr) {
         // A/B switch: "carry" forces the byte-SWAR carry-count scan; "plane" (or
         // unset) keeps the default
         if (std::strcmp(e, "carry") == 0) h->planar = false;
@@ -2966,8 +3007,15 @@ int rs_vt_set_threshold(rs_vt* h, double threshold) {
     return RS_OK;
 }
 
+int rs_vt_metric(const rs_vt* h, int* metric) {
+    RS_CHECK(h && metric, RS_ERR_ARG, "null argument");
+    *metric = h->metric;
+    return RS_OK;
+}
+
 const char* rs_vt_scan_form(const rs_vt* h) {
     if (!h) return nullptr;
+    if (h->metric == RS_VT_METRIC_SAD) return vt_plan::sad_form(h->H, h->M);
     if (h->planar) return h->prune ? "plane-pruned" : "plane";
     if (h->M != FAST_M || (h->H != 64 && h->H != 32)) return "generic";
     return "carry";

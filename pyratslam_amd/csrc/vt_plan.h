@@ -211,4 +211,30 @@ inline HostGroups host_groups(int nb) {
     return {gb, nb >= 4 ? 1 : gb, nb};
 }
 
+// --- True-SAD metric (RS_VT_METRIC_SAD; csrc/vt_sad.h).
+constexpr int METRIC_WRAPPED = 0, METRIC_SAD = 1;   // RS_VT_METRIC_* of the ABI
+inline bool metric_known(int metric) { return metric == METRIC_WRAPPED || metric == METRIC_SAD; }
+// The fast form keeps a template column's H rows in registers and has an instance for the
+// two shipped heights at the reference's max_offset; every other shape is generic.
+inline bool sad_fast(int H, int max_offset) { return max_offset == 8 && (H == 64 || H == 32); }
+inline const char* sad_form(int H, int max_offset) { return sad_fast(H, max_offset) ? "sad" : "sad-generic"; }
+// Queries per group (accumulator sets per wave).  2: 107 VGPRs at H = 64, two 8-wave blocks
+// a CU, so one block's LDS phase and barrier run beside the other's v_sad_u8 stream;
+// 1,024 queries x 10,000 templates of 64 x 32 scan in 1.95 ms with 2 or 3, 2.16 with 4
+// (135 VGPRs, one block a CU) and 2.14 with 8 (tools/vt_sad_ab.py).
+constexpr int SAD_NQ = 2;
+constexpr int SAD_NW = 8;   // waves per block, at most: one dword column each per pass
+inline int sad_waves(int WD) { return std::min(WD, SAD_NW); }
+// Blocks per template block (nqc) of the fast form: block j of a template block walks the
+// query groups j, j + nqc, .. with its template columns resident.  The blocks are equal and
+// 512 are resident (two a CU), so the grid wants many rounds of them, or its last round
+// leaves CUs idle: enough blocks for about SAD_TARGET_BLOCKS in the grid.  But a block's
+// prologue (its columns, 128 KiB at W = 32, into registers) is paid per block: no block
+// walks fewer than SAD_MIN_GROUPS groups while the groups allow it.
+constexpr int SAD_TARGET_BLOCKS = 4096, SAD_MIN_GROUPS = 8;
+inline int sad_split(int ntb, int ngroups) {
+    const int want = (SAD_TARGET_BLOCKS + ntb - 1) / ntb;
+    return std::max(1, std::min(want, ngroups / SAD_MIN_GROUPS));
+}
+
 }  // namespace vt_plan

@@ -115,7 +115,7 @@ class RatslamReplay:
                  x_step=X_STEP, y_step=Y_STEP, match_threshold=MATCH_THRESHOLD,
                  odom_freq=ODOM_FREQ, feedback_energy=None, pcn=None, vts=None, em=None,
                  device=0, precision='float32', batch=True, publish=False,
-                 use_visual_odometry=False, vo=None, subcell_peak=False, window=1):
+                 use_visual_odometry=False, vo=None, subcell_peak=False, window=1, vt_metric='wrapped'):
         # publish: the node's per-step work in full -- every update reads the whole
         # .posecells volume, as ros_simulate.py:140-145 does to publish it -- so steps
         # go one by one (no batched run()) and the network exports eagerly
@@ -128,7 +128,14 @@ class RatslamReplay:
             from .view_templates import ViewTemplates
             vts = ViewTemplates(x_range=x_range, y_range=y_range, x_step=x_step, y_step=y_step,
                                 im_x=im_size[0], im_y=im_size[1], match_threshold=match_threshold,
-                                device=device)
+                                device=device, metric=vt_metric)
+        elif getattr(vts, 'metric', vt_metric) != vt_metric:
+            raise ValueError('vt_metric=%r, but the view templates passed in score by %r'
+                             % (vt_metric, vts.metric))
+        # the metric of the default uint8 library ('wrapped': the reference's numpy arithmetic on
+        # mono8 frames; 'sad': true |T - Q|, for two-sided camera noise -- with a threshold of
+        # its own, the shipped 45000 sits on the wrapped metric's noise floor)
+        self.vt_metric = vt_metric
         self.pcn, self.vts = pcn, vts
         self.em = em if em is not None else ExperienceMap()
         self._em_links = hasattr(self.em, 'on_template')   # (LinkedExperienceMap)
@@ -413,7 +420,7 @@ def _takes_injections(pcn):
 
 
 def sharded_templates(d, device, host_reduce=False, x_range=X_RANGE, y_range=Y_RANGE, x_step=X_STEP,
-                      y_step=Y_STEP, im_size=IM_SIZE, match_threshold=MATCH_THRESHOLD):
+                      y_step=Y_STEP, im_size=IM_SIZE, match_threshold=MATCH_THRESHOLD, metric='wrapped'):
     """The view-template library sharded over the ranks of ``d`` (a dist.Dist):
     template g on rank g % N, one RCCL allreduce(min) per match (or the host
     reducer of the control plane with ``host_reduce``, for several ranks on one
@@ -421,14 +428,16 @@ def sharded_templates(d, device, host_reduce=False, x_range=X_RANGE, y_range=Y_R
     from .view_templates import ShardedViewTemplates
     if host_reduce:
         return ShardedViewTemplates(x_range, y_range, x_step, y_step, im_size[0], im_size[1],
-                                    match_threshold, d.rank, d.world, reducer=d.min_keys, device=device)
+                                    match_threshold, d.rank, d.world, reducer=d.min_keys, device=device,
+                                    metric=metric)
     uid = d.bcast_bytes(ShardedViewTemplates.unique_id() if d.rank == 0 else None)
     return ShardedViewTemplates(x_range, y_range, x_step, y_step, im_size[0], im_size[1],
                                 match_threshold, d.rank, d.world, reducer='rccl', unique_id=uid,
-                                device=device)
+                                device=device, metric=metric)
 
 
-def main(argv=None):
+def build_parser():
+    """The command line of ``python -m pyratslam_amd.replay``."""
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument('--bag', help='ROS 1 bag with navbot/odom and navbot/camera/image')
@@ -458,6 +467,21 @@ def main(argv=None):
                          '(odometry mode; 1: frame by frame)')
     ap.add_argument('--host-reduce', action='store_true',
                     help='combine the ranks\' keys on the host (several ranks on one GPU)')
+    ap.add_argument('--vt-metric', choices=('wrapped', 'sad'), default='wrapped',
+                    help='score of the uint8 view templates: "wrapped" is the reference\'s numpy '
+                         'arithmetic on mono8 frames, sum((T - Q) mod 256), where a pixel one grey '
+                         'level above its template scores 255; "sad" is the true sum of |T - Q|, '
+                         'for cameras with two-sided noise.  Choose --match-threshold with it')
+    ap.add_argument('--match-threshold', type=float, default=MATCH_THRESHOLD, metavar='T',
+                    help='a frame whose best score exceeds T becomes a new template (default %d, '
+                         'the reference\'s, which sits on the wrapped metric\'s noise floor: under '
+                         '--vt-metric sad, 300 frames of the synthetic stream make a single '
+                         'template with it, and 61 with 2048, 4 per window pixel)' % MATCH_THRESHOLD)
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.exp_loops is not None and not args.loop_closure:
         ap.error('--exp-loops needs --loop-closure')
@@ -468,7 +492,8 @@ def main(argv=None):
     from .dist import Dist
     d = Dist(args.gpus)
     dev = d.local if args.device is None else args.device
-    vts = sharded_templates(d, dev, args.host_reduce) if d.world > 1 else None
+    vts = (sharded_templates(d, dev, args.host_reduce, match_threshold=args.match_threshold,
+                             metric=args.vt_metric) if d.world > 1 else None)
     em = None
     if args.loop_closure:
         from .linked_experience_map import EXP_LOOPS, LinkedExperienceMap
@@ -476,7 +501,7 @@ def main(argv=None):
                                  device=dev)
     r = RatslamReplay(device=dev, precision=args.precision, feedback_energy=args.feedback, vts=vts,
                       use_visual_odometry=args.visual_odometry, em=em, subcell_peak=args.subcell_peak,
-                      window=args.window)
+                      window=args.window, vt_metric=args.vt_metric, match_threshold=args.match_threshold)
     d.barrier()
     t0 = time.perf_counter()
     if args.bag:

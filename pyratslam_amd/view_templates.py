@@ -6,7 +6,8 @@ pc_x, pc_y, pc_th)`` -> ``ViewTemplate`` (``.get_index()``, ``.location()``,
 ``.template``, ``.match(other)``) and the ``.templates`` list.
 
 The library lives on the GPU (``csrc/view_templates.hip``); each match scans it
-with the wrapped-uint8 row-shift score and applies the reference's strict
+with the wrapped-uint8 row-shift score (``metric='wrapped'``, the default) or the true sum
+of absolute differences (``metric='sad'``: two-sided camera noise) and applies the reference's strict
 threshold / first-argmin / append-on-miss rule.  ``match_batch`` runs many
 matches with the exact sequential semantics in one call.
 ``ShardedViewTemplates`` spreads the library over ranks (one GPU each).
@@ -34,6 +35,9 @@ import numpy as np
 from . import _lib
 
 MAX_OFFSET = 8  # view_templates.py:14
+# metric of a uint8 library (rs_vt_create_metric): 'wrapped' is numpy's own uint8 arithmetic,
+# sum((T - Q) mod 256), the reference on mono8 frames; 'sad' the true sum of |T - Q|
+METRICS = {'wrapped': _lib.RS_VT_METRIC_WRAPPED, 'sad': _lib.RS_VT_METRIC_SAD}
 _FLOAT_CODES = {np.dtype(np.float32): _lib.RS_DT_F32, np.dtype(np.float64): _lib.RS_DT_F64}
 
 
@@ -59,11 +63,38 @@ def sad_scores(templates, queries, max_offset=MAX_OFFSET, device=0):
     return out
 
 
-def _wrapped_scores(templates, queries, device=0):
-    """uint8 pair scores through a temporary device library (float-mode libraries
-    that also hold uint8 templates)."""
+def numpy_sad_u8_scores(library, query, max_offset=MAX_OFFSET):
+    """The 'sad' metric restated in NumPy: uint64[T] scores of one (H, W) uint8 query against
+    a (T, H, W) uint8 library, min over the row offsets of sum |T - Q| on the bytes as
+    integers -- ``ViewTemplate.match`` (view_templates.py:16-28) on the arrays cast to float."""
+    lib = np.asarray(library)
+    q = np.asarray(query)
+    if lib.dtype != np.uint8 or q.dtype != np.uint8:
+        raise TypeError('numpy_sad_u8_scores takes uint8 arrays, got %s and %s' % (lib.dtype, q.dtype))
+    t, h, _ = lib.shape
+    if t == 0:
+        return np.zeros(0, dtype=np.uint64)
+    q = q[max_offset:h - max_offset][None]
+    best = None
+    for o in range(-max_offset + 1, max_offset):
+        a = lib[:, max_offset + o:h - max_offset + o, :]
+        # |a - q| = max - min: no byte wraps, summed as integers
+        d = (np.maximum(a, q) - np.minimum(a, q)).sum(axis=(1, 2), dtype=np.uint64)
+        best = d if best is None else np.minimum(best, d)
+    return best
+
+
+def _metric_code(metric):
+    if metric not in METRICS:
+        raise ValueError('unknown metric %r: expected one of %s' % (metric, sorted(METRICS)))
+    return METRICS[metric]
+
+
+def _u8_scores(templates, queries, device=0, metric='wrapped'):
+    """uint8 pair scores, by ``metric``, through a temporary device library (float-mode
+    libraries that also hold uint8 templates)."""
     t = np.ascontiguousarray(templates, dtype=np.uint8)
-    lib = ViewTemplates._from_shape(t.shape[1:], np.inf, device=device, capacity=len(t))
+    lib = ViewTemplates._from_shape(t.shape[1:], np.inf, device=device, capacity=len(t), metric=metric)
     try:
         lib.add(t)
         return lib.scores(queries)
@@ -97,7 +128,9 @@ class ViewTemplate:
     def match(self, new_template):
         """Row-shift score against ``new_template`` (view_templates.py:16-28), on the
         GPU: uint8 arrays wrap mod 256 (numpy uint8 arithmetic, a numpy.uint64
-        score); float arrays give numpy's true sum of |T - Q| in their dtype."""
+        score) -- or, for a template owned by a library of metric 'sad', give the true
+        sum of |T - Q| (also uint64); float arrays give numpy's true sum of |T - Q| in
+        their dtype."""
         if self.template is None:
             owner = self._owner
             raise ValueError('the bytes of template %d live on rank %d (template g is stored on '
@@ -113,7 +146,8 @@ class ViewTemplate:
             return owner.scores(q[None], self.index, 1)[0, 0]
         if self._solo is None:
             t = np.ascontiguousarray(t)
-            self._solo = ViewTemplates._from_shape(t.shape, np.inf, device=dev)
+            self._solo = ViewTemplates._from_shape(t.shape, np.inf, device=dev,
+                                                   metric=owner.metric if owner is not None else 'wrapped')
             self._solo.add(t[None])
         return self._solo.scores(q[None], 0, 1)[0, 0]
 
@@ -128,19 +162,21 @@ class ViewTemplates:
     """Library of view templates on one GPU (view_templates.py:40-75)."""
 
     def __init__(self, x_range, y_range, x_step, y_step, im_x, im_y, match_threshold,
-                 device=0, capacity=1024):
+                 device=0, capacity=1024, metric='wrapped'):
         self.mask, self.shape = py2_mask(x_range, y_range, x_step, y_step, im_x, im_y)
-        self._init_device(self.shape, match_threshold, device, capacity)
+        self._init_device(self.shape, match_threshold, device, capacity, metric)
 
     @classmethod
-    def _from_shape(cls, shape, match_threshold, device=0, capacity=64):
+    def _from_shape(cls, shape, match_threshold, device=0, capacity=64, metric='wrapped'):
         self = cls.__new__(cls)
         self.mask = None
         self.shape = tuple(int(s) for s in shape)
-        self._init_device(self.shape, match_threshold, device, capacity)
+        self._init_device(self.shape, match_threshold, device, capacity, metric)
         return self
 
-    def _init_device(self, shape, match_threshold, device, capacity):
+    def _init_device(self, shape, match_threshold, device, capacity, metric='wrapped'):
+        code = _metric_code(metric)      # (a ValueError before anything is created)
+        self.metric = metric
         self.shape = (int(shape[0]), int(shape[1]))
         self.match_threshold = match_threshold
         self.templates = []
@@ -155,8 +191,12 @@ class ViewTemplates:
         self._h = None
         self._lib = _lib.require_device()
         h = ctypes.c_void_p()
-        _lib.check(self._lib.rs_vt_create(self.shape[0], self.shape[1], MAX_OFFSET, 0,
-                                          int(capacity), self.device, ctypes.byref(h)))
+        if code == _lib.RS_VT_METRIC_WRAPPED:
+            _lib.check(self._lib.rs_vt_create(self.shape[0], self.shape[1], MAX_OFFSET, 0,
+                                              int(capacity), self.device, ctypes.byref(h)))
+        else:
+            _lib.check(self._lib.rs_vt_create_metric(self.shape[0], self.shape[1], MAX_OFFSET, 0,
+                                                     int(capacity), self.device, code, ctypes.byref(h)))
         self._h = h
         # `min(match_val) > match_threshold` (view_templates.py:67), compared in float64 as
         # numpy compares the uint64 score with a Python number (inf: never, < 0: always)
@@ -470,7 +510,7 @@ class ViewTemplates:
             for dt, ids in groups.items():
                 lib = np.stack([np.asarray(self.templates[i].template) for i in ids])
                 if dt == np.uint8 and template.dtype == np.uint8:
-                    sc = _wrapped_scores(lib, template[None], self.device)[0]
+                    sc = _u8_scores(lib, template[None], self.device, self.metric)[0]
                 else:
                     sc = sad_scores(lib, template[None], MAX_OFFSET, self.device)[0]
                 for i, v in zip(ids, sc):
@@ -604,17 +644,17 @@ class ShardedViewTemplates(ViewTemplates):
     _resident_ok = False
 
     def __init__(self, x_range, y_range, x_step, y_step, im_x, im_y, match_threshold,
-                 rank, nranks, reducer='rccl', unique_id=None, device=0, capacity=1024):
+                 rank, nranks, reducer='rccl', unique_id=None, device=0, capacity=1024, metric='wrapped'):
         self.mask, self.shape = py2_mask(x_range, y_range, x_step, y_step, im_x, im_y)
-        self._init_device(self.shape, match_threshold, device, capacity)
+        self._init_device(self.shape, match_threshold, device, capacity, metric)
         self._attach(rank, nranks, reducer, unique_id)
 
     @classmethod
     def from_shape(cls, shape, match_threshold, rank, nranks, reducer='rccl', unique_id=None,
-                   device=0, capacity=1024):
+                   device=0, capacity=1024, metric='wrapped'):
         self = cls.__new__(cls)
         self.mask = None
-        self._init_device(shape, match_threshold, device, capacity)
+        self._init_device(shape, match_threshold, device, capacity, metric)
         self._attach(rank, nranks, reducer, unique_id)
         return self
 
