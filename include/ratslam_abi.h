@@ -38,6 +38,8 @@
  *   rs_vt_match_stream  many frozen-library batches, one host synchronisation
  *   rs_vt_read      ViewTemplate.template         view_templates.py:11
  *   rs_vt_scores    ViewTemplate.match per pair   view_templates.py:16-28 (uint8, wrapping)
+ *   rs_vt_offset_profile  the per-offset sums of ViewTemplate.match and which offset won,
+ *                   view_templates.py:19-27 (the reference keeps only the minimum)
  *   rs_sad_scores   ViewTemplate.match per pair   view_templates.py:16-28 (float32/float64)
  *   rs_vtf_create   ViewTemplates.__init__ for float frames  view_templates.py:42-57
  *   rs_vtf_add / rs_vtf_append_staged  templates.append(...)  view_templates.py:68-70
@@ -372,6 +374,25 @@ int rs_vt_match_frames(rs_vt* h, int nf, const uint8_t* frames, int mode, uint64
  * nranks must be 1): scores[q*nt + t]  -- ViewTemplate.match per pair */
 int rs_vt_scores(rs_vt* h, int nq, const uint8_t* queries, int64_t t0, int64_t nt,
                  uint64_t* scores);
+/* The row offset of a match (what OpenRatSLAM calls vt_relative_rad, in template rows): for
+ * query i and template index[i], with M = max_offset,
+ *   profile[i*(2M-1) + k] = sum_{r=M..H-M-1, c} term(T[r + k-(M-1)][c], Q[r][c]),  k = 0 .. 2M-2
+ * (term by the handle's metric; min over k = the pair's score), and offset[i] = o of the
+ * first minimal entry, o = k - (M-1): ViewTemplate.match's strict `<` from -M+1 upwards
+ * (view_templates.py:19-27).  An empty window (H == 2M): zeros and offset -(M-1).
+ * index[i] == -1: a row of UINT32_MAX and offset 0.  queries: nq*H*W host bytes, or device
+ * memory read in place, or NULL for the batch the last rs_vt_match_batch / _frames / _match
+ * staged (nq must be its size: RS_ERR_STATE otherwise) -- after a sequential match, a query
+ * that matched a template appended earlier in its batch is profiled against that template.
+ * Explicit queries leave the staged batch as it is.  profile may be NULL.  Any other index:
+ * RS_ERR_ARG before any device work; a sharded handle: RS_ERR_STATE.  The call returns with
+ * the results in the caller's arrays; its buffers are allocated by the first call.
+ * rs_vt_offset_profile_host is the same rule for one raw H x W pair on the host alone (no
+ * handle, no device). */
+int rs_vt_offset_profile(rs_vt* h, int nq, const uint8_t* queries, const int64_t* index,
+                         uint32_t* profile, int32_t* offset);
+int rs_vt_offset_profile_host(int metric, int H, int W, int max_offset, const uint8_t* tpl,
+                              const uint8_t* query, uint32_t* profile, int32_t* offset);
 /* The two halves of rs_vt_match_batch, for callers that combine the per-rank
  * keys themselves (any min-reduction over ranks; key = score << 32 | index,
  * UINT64_MAX = no template):

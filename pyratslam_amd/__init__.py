@@ -9,7 +9,8 @@ with the reference's API (``/root/reference/ratslam/posecell_network.py``,
 from .linked_experience_map import LinkedExperienceMap, NumpyLinkedExperienceMap  # noqa: F401
 from .pc_peak import numpy_peak_sums, peak_tables, pose_from_sums  # noqa: F401
 from .posecell_network import PoseCellNetwork  # noqa: F401
-from .view_templates import ShardedViewTemplates, ViewTemplate, ViewTemplates, numpy_sad_u8_scores  # noqa: F401
+from .view_templates import (ShardedViewTemplates, ViewTemplate, ViewTemplates, numpy_offset_profile,  # noqa: F401
+                             numpy_sad_u8_scores, refine_offset)
 from .visual_odometer import NumpyVisualOdometer, SimpleVisualOdometer  # noqa: F401
 
 __version__ = '0.1.0'

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "rs_common.h"
+#include "vt_offset_rule.h"
 #include "vt_plan.h"
 
 namespace {
@@ -345,6 +346,9 @@ __global__ __launch_bounds__(64) void vt_scan_generic_kernel(const uint4* __rest
 static_assert(vt_plan::METRIC_WRAPPED == RS_VT_METRIC_WRAPPED && vt_plan::METRIC_SAD == RS_VT_METRIC_SAD,
               "vt_plan.h restates the ABI's metric codes");
 #include "vt_sad.h"
+static_assert(rs::VTO_METRIC_WRAPPED == RS_VT_METRIC_WRAPPED && rs::VTO_METRIC_SAD == RS_VT_METRIC_SAD,
+              "vt_offset_rule.h restates the ABI's metric codes");
+#include "vt_offset.h"
 
 // ===========================================================================
 // Bit-plane scan (default for W = 32, H in {32, 64}, max_offset 8).
@@ -1883,6 +1887,13 @@ struct rs_vt {
     rs::DevBuf<uint8_t> dFrames;
     rs::PinnedBuf<uint8_t> hFrames;  // staging for host frames
     int frameCap = 0;
+    // rs_vt_offset_profile (vt_offset.h), allocated by its first call: explicit host queries
+    // (the staged batch in dQraw stays), and fine-grained arrays the kernel reads the indices
+    // from and stores profile[nq][2M-1] and offset[nq] into in place
+    rs::DevBuf<uint8_t> dOffQ;
+    rs::PinnedBuf<int64_t> hOffIdx;
+    rs::PinnedBuf<uint32_t> hOffProfile;
+    rs::PinnedBuf<int32_t> hOffOffset;
 };
 
 namespace {
@@ -2997,6 +3008,67 @@ int rs_vt_scores(rs_vt* h, int nq, const uint8_t* queries, int64_t t0, int64_t n
     RS_HIP(hipStreamSynchronize(h->stream));
     RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
     for (size_t i = 0; i < (size_t)nq * nt; ++i) scores[i] = h->hMat.get()[i];
+    return RS_OK;
+}
+
+int rs_vt_offset_profile(rs_vt* h, int nq, const uint8_t* queries, const int64_t* index, uint32_t* profile,
+                         int32_t* offset) {
+    rs::clear_error();
+    RS_CHECK(h, RS_ERR_STATE, "null view-template handle");
+    RS_CHECK(h->nranks == 1, RS_ERR_STATE, "rs_vt_offset_profile needs an unsharded library");
+    RS_CHECK(nq >= 0, RS_ERR_ARG, "negative query count");
+    if (nq == 0) return RS_OK;
+    RS_CHECK(index && offset, RS_ERR_ARG, "null argument");
+    for (int i = 0; i < nq; ++i)
+        RS_CHECK(index[i] >= -1 && index[i] < h->count, RS_ERR_ARG,
+                 "template index %lld of query %d outside [-1, %lld)", (long long)index[i], i,
+                 (long long)h->count);
+    RS_CHECK(queries || nq == h->stagedQ, RS_ERR_STATE, "no staged batch of %d queries (have %d)", nq,
+             h->stagedQ);
+    RS_HIP(hipSetDevice(h->device));
+    const size_t n = (size_t)nq, no = (size_t)(2 * h->M - 1), qb = (size_t)h->H * h->W * n;
+    RS_TRY(h->hOffIdx.reserve(rs::grown<size_t>(h->hOffIdx.capacity(), n, 64), VT_FINE));
+    RS_TRY(h->hOffProfile.reserve(rs::grown<size_t>(h->hOffProfile.capacity(), n * no, 64 * no), VT_FINE));
+    RS_TRY(h->hOffOffset.reserve(rs::grown<size_t>(h->hOffOffset.capacity(), n, 64), VT_FINE));
+    const uint8_t* src = h->dQraw.get();
+    if (queries && rs::on_device(queries)) {
+        src = queries;   // read in place
+    } else if (queries) {
+        RS_TRY(h->dOffQ.reserve(rs::grown<size_t>(h->dOffQ.capacity(), qb, 64 * (size_t)h->H * h->W)));
+        RS_HIP(hipMemcpyAsync(h->dOffQ.get(), queries, qb, hipMemcpyHostToDevice, h->stream));
+        src = h->dOffQ.get();
+    }
+    std::memcpy(h->hOffIdx.get(), index, sizeof(int64_t) * n);
+    const bool sad = h->metric == RS_VT_METRIC_SAD, fast = h->M == FAST_M;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(nq), dim3(64), 0, h->stream, h->dLib.get(), h->count, h->H, h->W,
+                           h->WD, h->HQ, h->M, src, h->hOffIdx.dev(), h->hOffProfile.dev(),
+                           h->hOffOffset.dev());
+    };
+    if (sad && fast) launch(vt_offset_profile_kernel<rs::VTO_METRIC_SAD, true>);
+    else if (sad) launch(vt_offset_profile_kernel<rs::VTO_METRIC_SAD, false>);
+    else if (fast) launch(vt_offset_profile_kernel<rs::VTO_METRIC_WRAPPED, true>);
+    else launch(vt_offset_profile_kernel<rs::VTO_METRIC_WRAPPED, false>);
+    RS_HIP(hipGetLastError());
+    // the results are the kernel's own stores: the call waits for the stream, and with it
+    // for everything queued before (an append's staging copies, a reader of hQraw)
+    RS_HIP(hipStreamSynchronize(h->stream));
+    h->stagingBusy = false;
+    h->qrawBusy = false;
+    if (profile) std::memcpy(profile, h->hOffProfile.get(), sizeof(uint32_t) * n * no);
+    std::memcpy(offset, h->hOffOffset.get(), sizeof(int32_t) * n);
+    return RS_OK;
+}
+
+int rs_vt_offset_profile_host(int metric, int H, int W, int max_offset, const uint8_t* tpl, const uint8_t* query,
+                              uint32_t* profile, int32_t* offset) {
+    rs::clear_error();
+    RS_CHECK(vt_plan::metric_known(metric), RS_ERR_ARG, "unknown metric %d", metric);
+    RS_CHECK(H > 0 && W > 0 && max_offset >= 1 && H >= 2 * max_offset, RS_ERR_ARG,
+             "bad shape (%d, %d) for max_offset %d", H, W, max_offset);
+    RS_CHECK((uint64_t)H * W * 255u < 0xFFFFFFFFull, RS_ERR_ARG, "template too large");
+    RS_CHECK(tpl && query && profile && offset, RS_ERR_ARG, "null argument");
+    *offset = rs::vto_profile_host(metric, H, W, max_offset, tpl, query, profile);
     return RS_OK;
 }
 

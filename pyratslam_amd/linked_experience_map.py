@@ -25,6 +25,14 @@ rounded and uncontracted, so that NumPy, the host rule (``rs_em_relax_host``) an
   from ``cur``'s relaxed pose, and the link ``cur -> new``.  Seen template whose
   experience ``e != cur``: the link ``cur -> e`` unless it exists.  ``e == cur``: nothing.
   When ``cur`` changes, ``ax = ay = 0`` and ``thc = ath``.  Then ``iterate()``.
+* ``on_template(index, rel_rad)``: ``rel_rad`` is the robot's heading minus the heading at
+  which the matched template's experience was stored (the view matcher's row offset as an
+  angle).  A seen template whose experience ``e != cur`` is then faced
+  ``wrap(f - rel_rad)`` by the closure link ``cur -> e`` -- the stored experience's heading,
+  not the robot's -- and becomes current with ``thc = ath - rel_rad``: ``thc`` is the dead-
+  reckoned heading that corresponds to ``e``'s own heading, which ``get_current_point`` and
+  the next measurement turn by.  An unseen template ignores it (the template is the frame
+  itself), and ``rel_rad == 0.0`` takes exactly the arithmetic above, bit for bit.
 * ``iterate(loops)``: ``loops`` damped-Jacobi sweeps, each reading the previous iterate
   only.  Link ``l``: ``ex = x_b - (x_a + d cos(th_a + h))``, ``ey`` with ``sin``,
   ``df = wrap(th_b - (th_a + f))``.  Experience ``i`` sums, from +0.0 and in order, its
@@ -169,12 +177,16 @@ class _LinkedMapBase:
         f = wrap(self.accum_delta_th - self.theta_current)
         return float(d), float(h), float(f)
 
-    def on_template(self, index):
-        """The frame matched view template ``index``: create, link or do nothing (module
-        docstring), relax, and return the experience now current."""
+    def on_template(self, index, rel_rad=0.0):
+        """The frame matched view template ``index``, seen turned by ``rel_rad`` from the
+        heading it was stored at: create, link or do nothing (module docstring), relax, and
+        return the experience now current."""
         index = int(index)
         if index < 0:
             raise ValueError('template index %d < 0' % index)
+        rel = np.float64(rel_rad)
+        if not np.isfinite(rel):
+            raise ValueError('rel_rad %r is not finite' % (rel_rad,))
         cur = self.current_exp
         d, h, f = self.measurement()
         e = self.vt_exp.get(index)
@@ -185,13 +197,14 @@ class _LinkedMapBase:
                 e = self.add_experience(cur, d, h, f, vt=index)
             if cur is not None:
                 self._link(cur, e, d, h, f)
+            rel = np.float64(0.0)      # unseen: the template is the frame itself
         elif e != cur and (cur, e) not in self._pairs:
-            self._link(cur, e, d, h, f)
+            self._link(cur, e, d, h, f if rel == 0.0 else float(wrap(np.float64(f) - rel)))
         if e != cur:
             self.current_exp = e
             self.accum_delta_x = np.float64(0.0)
             self.accum_delta_y = np.float64(0.0)
-            self.theta_current = self.accum_delta_th
+            self.theta_current = self.accum_delta_th if rel == 0.0 else self.accum_delta_th - rel
         self.iterate()
         return e
 

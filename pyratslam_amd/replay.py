@@ -42,7 +42,10 @@ packet's circular centroid, ``PoseCellNetwork.update_pose`` / ``run(poses=True)`
 view templates, the feedback injection and both maps still receive the integer peak cell;
 ``--window K`` (``RatslamReplay(window=K)``) matches K frames with one ``match_batch`` and steps
 the twists between them with one ``run``, the feedback injections inside it
-(``run(injections=...)``), with the outputs of the frame-by-frame loop.
+(``run(injections=...)``), with the outputs of the frame-by-frame loop;
+``--view-shift [--view-fov RAD]`` (``RatslamReplay(view_shift=True, view_fov=RAD)``) stores the
+view templates column-major, records the row offset of every match (``view_offset``) and hands
+it to the linked map as the angle the place is seen turned by.
 """
 import argparse
 import json
@@ -115,7 +118,15 @@ class RatslamReplay:
                  x_step=X_STEP, y_step=Y_STEP, match_threshold=MATCH_THRESHOLD,
                  odom_freq=ODOM_FREQ, feedback_energy=None, pcn=None, vts=None, em=None,
                  device=0, precision='float32', batch=True, publish=False,
-                 use_visual_odometry=False, vo=None, subcell_peak=False, window=1, vt_metric='wrapped'):
+                 use_visual_odometry=False, vo=None, subcell_peak=False, window=1, vt_metric='wrapped',
+                 view_shift=False, view_fov=None):
+        """``view_shift``: the view templates are stored column-major (``shift_axis='cols'``) and
+        every match's row offset is recorded (``results()['view_offset']``) and passed to a
+        linked map as ``rel_rad = offset * x_step * view_fov / im_width``: one template row is
+        ``x_step`` image columns, and a frame of ``im_width`` columns spans ``view_fov``, the
+        camera's horizontal field of view in radians.  Its sign is the camera's handedness:
+        positive where a larger heading moves the view towards larger image columns, as in
+        ``synthetic.ros_stream`` (+pi/2: a larger heading gives a positive offset there)."""
         # publish: the node's per-step work in full -- every update reads the whole
         # .posecells volume, as ros_simulate.py:140-145 does to publish it -- so steps
         # go one by one (no batched run()) and the network exports eagerly
@@ -124,11 +135,18 @@ class RatslamReplay:
             from .posecell_network import PoseCellNetwork
             pcn = PoseCellNetwork(shape=pose_size, precision=precision, device=device,
                                   readback='eager' if publish else 'lazy')
+        self.view_shift = bool(view_shift)
+        if self.view_shift and view_fov is None:
+            raise ValueError('view_shift needs view_fov, the camera\'s horizontal field of view in radians')
         if vts is None:
             from .view_templates import ViewTemplates
+            shift = {'shift_axis': 'cols', 'offsets': True} if self.view_shift else {}
             vts = ViewTemplates(x_range=x_range, y_range=y_range, x_step=x_step, y_step=y_step,
                                 im_x=im_size[0], im_y=im_size[1], match_threshold=match_threshold,
-                                device=device, metric=vt_metric)
+                                device=device, metric=vt_metric, **shift)
+        elif self.view_shift and not (getattr(vts, 'offsets', False)
+                                      and getattr(vts, 'shift_axis', 'rows') == 'cols'):
+            raise ValueError("view_shift needs view templates built with shift_axis='cols', offsets=True")
         elif getattr(vts, 'metric', vt_metric) != vt_metric:
             raise ValueError('vt_metric=%r, but the view templates passed in score by %r'
                              % (vt_metric, vts.metric))
@@ -137,6 +155,9 @@ class RatslamReplay:
         # its own, the shipped 45000 sits on the wrapped metric's noise floor)
         self.vt_metric = vt_metric
         self.pcn, self.vts = pcn, vts
+        # radians per template row, and the offsets of the frames so far
+        self.rad_per_row = float(x_step) * float(view_fov) / float(im_size[1]) if self.view_shift else 0.0
+        self.view_offset = []
         self.em = em if em is not None else ExperienceMap()
         self._em_links = hasattr(self.em, 'on_template')   # (LinkedExperienceMap)
         self.odom_freq = odom_freq
@@ -180,14 +201,31 @@ class RatslamReplay:
         pc_max = self.pcn.get_pc_max()
         template_match = self.vts.match(input=im, pc_x=pc_max[0], pc_y=pc_max[1], pc_th=pc_max[2])
         self.template_index.append(int(template_match.get_index()))
+        rel = self._view_rel(1)
         if self._em_links:   # a linked map learns which place the frame was recognised as
-            self.em.on_template(self.template_index[-1])
+            self._on_template(self.template_index[-1], rel[0])
         if self.feedback_energy:
             self.pcn.inject(self.feedback_energy, tuple(template_match.location()))
         if self.use_visual_odometry:   # ros_simulate.py:119-122
             delta = self.vo.update(im)
             self.deltas.append((float(delta[0]), float(delta[1])))
             self.vis_odom_data.append(delta)
+
+    def _view_rel(self, n):
+        """``view_shift``: record the offsets of the ``n`` frames just matched
+        (``vts.last_offsets``) and return their ``rel_rad``; all zero when off."""
+        if not self.view_shift:
+            return [0.0] * n
+        off = [int(o) for o in self.vts.last_offsets]
+        assert len(off) == n, (len(off), n)
+        self.view_offset.extend(off)
+        return [o * self.rad_per_row for o in off]
+
+    def _on_template(self, index, rel):
+        if self.view_shift:
+            self.em.on_template(index, rel)
+        else:
+            self.em.on_template(index)
 
     def update_posecells(self, vtrans, vrot):
         """ros_simulate.py:134-146 (publishing reduced to recording; with publish=True
@@ -284,6 +322,7 @@ class RatslamReplay:
         known = len(self.vts.templates)
         matched = self.vts.match_batch(images, [(0, 0, 0)] * len(images)) if images else []
         index = [int(t.get_index()) for t in matched]
+        rel = self._view_rel(len(index)) if images else []
         kinds = injection_kinds(index, known)
         od = np.array(steps, dtype=np.float64).reshape(-1, 2)
         if self.feedback_energy and images:
@@ -302,7 +341,7 @@ class RatslamReplay:
             while frame < len(bounds) and bounds[frame] == s:
                 self.template_index.append(index[frame])
                 if self._em_links:
-                    self.em.on_template(index[frame])
+                    self._on_template(index[frame], rel[frame])
                 frame += 1
             if s < len(steps):
                 self._record(steps[s][0], steps[s][1], maxes[s])
@@ -392,9 +431,10 @@ class RatslamReplay:
                     pcs = [peak] + [tuple(int(v) for v in m) for m in maxes[:-1]]
                     idx, _, _ = self.vts.match_frames((n, buf), pcs)
                 self.template_index.extend(int(j) for j in idx)
-                for (vt, vr), m, j in zip(deltas, maxes, idx):
+                rel = self._view_rel(n)
+                for (vt, vr), m, j, rr in zip(deltas, maxes, idx, rel):
                     if self._em_links:   # the frame's match, then its step: the per-frame order
-                        self.em.on_template(int(j))
+                        self._on_template(int(j), rr)
                     self.deltas.append((float(vt), float(vr)))
                     self._record(float(vt), float(vr), m)
         finally:
@@ -407,6 +447,7 @@ class RatslamReplay:
                 'pc_max': np.array(self.pc_max, dtype=np.int64).reshape(-1, 3),
                 'em_points': np.array(self.em_points, dtype=np.float64).reshape(-1, 2),
                 'template_index': np.array(self.template_index, dtype=np.int64),
+                **({'view_offset': np.array(self.view_offset, dtype=np.int64)} if self.view_shift else {}),
                 'templates': len(self.vts.templates)}
 
 
@@ -465,6 +506,13 @@ def build_parser():
     ap.add_argument('--window', type=int, default=1, metavar='K',
                     help='match K frames and step the twists between them per batched call '
                          '(odometry mode; 1: frame by frame)')
+    ap.add_argument('--view-shift', action='store_true',
+                    help='store the view templates column-major and use the row offset of every '
+                         'match as the angle the place is seen turned by (view_offset; with '
+                         '--loop-closure it corrects the closure links); one GPU')
+    ap.add_argument('--view-fov', type=float, default=None, metavar='RAD',
+                    help='the camera\'s horizontal field of view in radians under --view-shift, '
+                         'signed by its handedness (default pi/2, synthetic.ros_stream\'s camera)')
     ap.add_argument('--host-reduce', action='store_true',
                     help='combine the ranks\' keys on the host (several ranks on one GPU)')
     ap.add_argument('--vt-metric', choices=('wrapped', 'sad'), default='wrapped',
@@ -485,6 +533,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.exp_loops is not None and not args.loop_closure:
         ap.error('--exp-loops needs --loop-closure')
+    if args.view_fov is not None and not args.view_shift:
+        ap.error('--view-fov needs --view-shift')
+    if args.view_shift and args.gpus > 1:
+        ap.error('--view-shift needs an unsharded template library (--gpus 1)')
     from . import launch
     if args.gpus > 1 and not launch.under_launcher():
         return launch.spawn(args.gpus, ['-m', 'pyratslam_amd.replay'] + list(
@@ -501,7 +553,9 @@ def main(argv=None):
                                  device=dev)
     r = RatslamReplay(device=dev, precision=args.precision, feedback_energy=args.feedback, vts=vts,
                       use_visual_odometry=args.visual_odometry, em=em, subcell_peak=args.subcell_peak,
-                      window=args.window, vt_metric=args.vt_metric, match_threshold=args.match_threshold)
+                      window=args.window, vt_metric=args.vt_metric, match_threshold=args.match_threshold,
+                      view_shift=args.view_shift,
+                      view_fov=(math.pi / 2 if args.view_fov is None else args.view_fov) if args.view_shift else None)
     d.barrier()
     t0 = time.perf_counter()
     if args.bag:
@@ -517,6 +571,7 @@ def main(argv=None):
                           'seconds': dt, 'pc_max': res['pc_max'].tolist(),
                           'template_index': res['template_index'].tolist(),
                           'em_points': res['em_points'].tolist(),
+                          **({'view_offset': res['view_offset'].tolist()} if args.view_shift else {}),
                           **({'pc_pose': res['pc_pose'].tolist()} if args.subcell_peak else {}),
                           **({'experiences': r.em.poses().tolist(),
                               'links': [list(map(float, l)) for l in r.em.links().tolist()]}

@@ -12,6 +12,13 @@ threshold / first-argmin / append-on-miss rule.  ``match_batch`` runs many
 matches with the exact sequential semantics in one call.
 ``ShardedViewTemplates`` spreads the library over ranks (one GPU each).
 
+The score is a minimum over 2 * max_offset - 1 row offsets; ``offset_profile`` gives the sum
+at every offset and the offset that won (OpenRatSLAM's ``vt_relative_rad``, in template
+rows), and ``ViewTemplates(..., offsets=True)`` records both after every uint8 match call
+(``last_offsets`` / ``last_profiles``).  The reference shifts along template rows; a turn of
+the robot moves the view along image columns, so ``shift_axis='cols'`` stores the templates
+column-major (transposed) and the offset then means a heading.
+
 Frames are ``uint8`` on the ROS path (``ros_simulate.py:100-101``): the library
 then lives on the GPU and a score wraps mod 256 like numpy's uint8 subtraction.
 float32 / float64 frames follow the reference's float semantics instead (a true
@@ -84,6 +91,41 @@ def numpy_sad_u8_scores(library, query, max_offset=MAX_OFFSET):
     return best
 
 
+def numpy_offset_profile(template, query, max_offset=MAX_OFFSET, metric='wrapped'):
+    """The offset rule restated in NumPy for one (H, W) uint8 pair: ``(offset, profile
+    uint32[2M-1])``, the explicit loop over the offsets o = -(M-1) .. M-1 on the bytes as
+    integers, the first minimal entry's offset (``ViewTemplate.match``'s strict ``<``)."""
+    t = np.asarray(template).astype(np.int64)
+    q = np.asarray(query).astype(np.int64)
+    h, m = t.shape[0], int(max_offset)
+    _metric_code(metric)
+    prof = np.zeros(2 * m - 1, dtype=np.uint32)
+    for k, o in enumerate(range(-m + 1, m)):
+        d = t[m + o:h - m + o] - q[m:h - m]
+        prof[k] = (np.abs(d) if metric == 'sad' else d % 256).sum()
+    return int(np.argmin(prof)) - (m - 1), prof
+
+
+def refine_offset(profile):
+    """The sub-row offset of a profile (or of each row of an (n, 2M-1) array): the vertex of
+    the parabola through the minimum and its two neighbours, ``o + 0.5 (p- - p+) / (p- - 2 p0
+    + p+)``; the integer offset when the minimum is the first or the last entry or the
+    denominator is not positive (a flat profile)."""
+    p = np.asarray(profile, dtype=np.float64)
+    if p.ndim == 2:
+        return np.array([refine_offset(row) for row in p], dtype=np.float64)
+    if p.ndim != 1 or p.size % 2 != 1:
+        raise ValueError('a profile has 2 * max_offset - 1 entries, got shape %r' % (p.shape,))
+    k = int(np.argmin(p))
+    o = float(k - (p.size - 1) // 2)
+    if k == 0 or k == p.size - 1:
+        return o
+    den = p[k - 1] - 2.0 * p[k] + p[k + 1]
+    if not den > 0.0:
+        return o
+    return o + 0.5 * (p[k - 1] - p[k + 1]) / den
+
+
 def _metric_code(metric):
     if metric not in METRICS:
         raise ValueError('unknown metric %r: expected one of %s' % (metric, sorted(METRICS)))
@@ -151,6 +193,8 @@ class ViewTemplate:
             self._solo.add(t[None])
         return self._solo.scores(q[None], 0, 1)[0, 0]
 
+    refine_offset = staticmethod(refine_offset)
+
     def location(self):
         return (self.pc_x, self.pc_y, self.pc_th)
 
@@ -162,21 +206,39 @@ class ViewTemplates:
     """Library of view templates on one GPU (view_templates.py:40-75)."""
 
     def __init__(self, x_range, y_range, x_step, y_step, im_x, im_y, match_threshold,
-                 device=0, capacity=1024, metric='wrapped'):
-        self.mask, self.shape = py2_mask(x_range, y_range, x_step, y_step, im_x, im_y)
-        self._init_device(self.shape, match_threshold, device, capacity, metric)
+                 device=0, capacity=1024, metric='wrapped', offsets=False, shift_axis='rows'):
+        """``offsets``: record the row offset and the profile of every uint8 match call
+        (``last_offsets``, ``last_profiles``).  ``shift_axis``: ``'rows'`` shifts along the
+        gathered template's rows as the reference does; ``'cols'`` stores every template
+        transposed, so that the offset runs along image columns (``x_step`` columns a row)."""
+        self._set_geometry(x_range, y_range, x_step, y_step, im_x, im_y, shift_axis)
+        self._init_device(self.shape, match_threshold, device, capacity, metric, offsets)
+
+    def _set_geometry(self, x_range, y_range, x_step, y_step, im_x, im_y, shift_axis='rows'):
+        """The mask and the stored template shape (host only; a ValueError before any device work)."""
+        if shift_axis not in ('rows', 'cols'):
+            raise ValueError("shift_axis %r: expected 'rows' or 'cols'" % (shift_axis,))
+        self.mask, shape = py2_mask(x_range, y_range, x_step, y_step, im_x, im_y)
+        self.shift_axis = shift_axis
+        self._gathered_shape = shape      # input[mask].reshape(...), before the transpose
+        self.shape = shape if shift_axis == 'rows' else shape[::-1]
+        return self
 
     @classmethod
-    def _from_shape(cls, shape, match_threshold, device=0, capacity=64, metric='wrapped'):
+    def _from_shape(cls, shape, match_threshold, device=0, capacity=64, metric='wrapped', offsets=False):
         self = cls.__new__(cls)
         self.mask = None
         self.shape = tuple(int(s) for s in shape)
-        self._init_device(self.shape, match_threshold, device, capacity, metric)
+        self._init_device(self.shape, match_threshold, device, capacity, metric, offsets)
         return self
 
-    def _init_device(self, shape, match_threshold, device, capacity, metric='wrapped'):
+    shift_axis = 'rows'
+
+    def _init_device(self, shape, match_threshold, device, capacity, metric='wrapped', offsets=False):
         code = _metric_code(metric)      # (a ValueError before anything is created)
         self.metric = metric
+        self.offsets = bool(offsets)
+        self.last_offsets = self.last_profiles = None
         self.shape = (int(shape[0]), int(shape[1]))
         self.match_threshold = match_threshold
         self.templates = []
@@ -239,7 +301,19 @@ class ViewTemplates:
         if cache is None or cache[0] is not self.mask:
             cache = (self.mask, np.flatnonzero(self.mask.ravel()))
             self._mask_take = cache
-        return im.reshape(-1).take(cache[1]).reshape(self.shape)
+        if self.shift_axis == 'rows':
+            return im.reshape(-1).take(cache[1]).reshape(self.shape)
+        return np.ascontiguousarray(im.reshape(-1).take(cache[1]).reshape(self._gathered_shape).T)
+
+    def gather_pixels(self):
+        """The pixel table of ``rs_vt_set_subsample``: the frame's flat offsets of a
+        template's bytes in stored order (``shift_axis='cols'``: the mask's, transposed)."""
+        if self.mask is None:
+            raise ValueError('no subsampling mask: construct with the frame geometry')
+        pix = np.flatnonzero(self.mask.ravel())
+        if self.shift_axis == 'cols':
+            pix = pix.reshape(self._gathered_shape).T
+        return np.ascontiguousarray(pix.reshape(-1), dtype=np.int32)
 
     def _check_templates(self, t):
         t = np.asarray(t)
@@ -355,6 +429,7 @@ class ViewTemplates:
 
     def add(self, templates, locations=None):
         """Append templates unconditionally (indices len .. len+n-1)."""
+        self._offsets_take(templates)
         if self._use_resident(templates):
             t = self._check_float(templates, 'add()')
             first = ctypes.c_int64()
@@ -398,6 +473,66 @@ class ViewTemplates:
                                               int(t0), int(nt), _lib.ptr(out, ctypes.c_uint64)))
         return out
 
+    # -- row offsets -----------------------------------------------------------------
+    def _offset_profile(self, index, qptr):
+        """rs_vt_offset_profile of ``index`` against the queries at ``qptr`` (None: the staged
+        batch); call with the mutex held."""
+        index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+        n = index.shape[0]
+        offset = np.zeros(n, dtype=np.int32)
+        profile = np.zeros((n, 2 * MAX_OFFSET - 1), dtype=np.uint32)
+        _lib.check(self._lib.rs_vt_offset_profile(self._h, n, qptr, _lib.ptr(index, ctypes.c_int64),
+                                                  _lib.ptr(profile, ctypes.c_uint32),
+                                                  _lib.ptr(offset, ctypes.c_int32)))
+        return offset, profile
+
+    def _refuse_offsets(self, what):
+        self._refuse_float(what)
+        if self.nranks > 1:
+            raise TypeError('%s is not supported by a sharded library: the template of a match '
+                            'lives on one rank' % what)
+
+    def offset_profile(self, index, queries=None):
+        """The row offset of each (query, template ``index[i]``) pair and the sums it is the
+        first argmin of (rs_vt_offset_profile): ``(offset int32[n], profile uint32[n, 2M-1])``,
+        ``profile[i, k]`` the sum at offset ``k - (M - 1)`` under the library's metric, so that
+        ``profile[i].min()`` is the pair's score.  ``queries``: uint8 (n, H, W), or ``(n,
+        _lib.DeviceBuffer)`` read in place, or None for the batch the last match call staged
+        (which explicit queries leave as it is).  An index of -1 gives offset 0 and a row of
+        UINT32_MAX."""
+        self._refuse_offsets('offset_profile()')
+        index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+        keep = None
+        if queries is None:
+            qptr = None
+        elif isinstance(queries, tuple):
+            n, keep = int(queries[0]), queries[1]
+            if n != index.shape[0]:
+                raise ValueError('%d queries for %d indices' % (n, index.shape[0]))
+            if n * self.shape[0] * self.shape[1] > keep.nbytes:
+                raise ValueError('%d queries exceed the %d-byte device buffer' % (n, keep.nbytes))
+            qptr = keep.ptr
+        else:
+            keep = self._check_templates(queries)
+            if keep.shape[0] != index.shape[0]:
+                raise ValueError('%d queries for %d indices' % (keep.shape[0], index.shape[0]))
+            qptr = ctypes.c_void_p(keep.ctypes.data)
+        with self._mutex:
+            out = self._offset_profile(index, qptr)
+        del keep
+        return out
+
+    def _record_offsets(self, idx, new):
+        """``offsets=True``: the profile launch on the batch a match call just staged, with
+        the indices it returned, after its appends (a query that matched a template created
+        earlier in the same sequential batch is profiled against that template; one that
+        became a template meets itself: offset 0).  Call with the mutex held."""
+        if not self.offsets:
+            return
+        off, prof = self._offset_profile(idx, None)
+        off[np.asarray(new, dtype=bool)] = 0
+        self.last_offsets, self.last_profiles = off, prof
+
     # -- matching ----------------------------------------------------------------
     def _record(self, q, pcs, idx, new):
         for i in range(q.shape[0]):
@@ -412,6 +547,7 @@ class ViewTemplates:
         """Match already-subsampled (nq, H, W) queries; returns (index, score, is_new).
         On a float-resident library the queries and scores have the library's dtype
         (+inf where the library was empty)."""
+        self._offsets_take(queries)
         if self._use_resident(queries):
             q = self._check_float(queries, 'match_templates()')
             n = q.shape[0]
@@ -436,6 +572,7 @@ class ViewTemplates:
                 _lib.ptr(idx, ctypes.c_int64), _lib.ptr(new, ctypes.c_uint8)))
             if mode == _lib.RS_VT_SEQUENTIAL:
                 self._record(q, pcs if pcs is not None else [(0, 0, 0)] * n, idx, new)
+            self._record_offsets(idx, new)
         return idx, score, new.astype(bool)
 
     def match_stream(self, queries, nq=None):
@@ -467,9 +604,17 @@ class ViewTemplates:
         del keep
         return idx, score
 
+    def _offsets_take(self, arrays):
+        # offsets=True: the offset rule is defined on bytes; a float frame would move the
+        # library off the uint8 device path (module doc)
+        if self.offsets and np.asarray(arrays).dtype != np.uint8:
+            raise TypeError('offsets=True records row offsets of uint8 frames only; got %s'
+                            % np.asarray(arrays).dtype)
+
     def match(self, input, pc_x, pc_y, pc_th):
         """Best template for a frame, or a new one (view_templates.py:63-75)."""
         t = self.subsample(input)
+        self._offsets_take(t)
         if self._resident_for(t.dtype):
             with self._mutex:
                 idx, _, _ = self._resident_match(np.ascontiguousarray(t)[None], [(pc_x, pc_y, pc_th)])
@@ -484,6 +629,8 @@ class ViewTemplates:
         q = [self.subsample(im) for im in images]
         if not q:
             return []
+        for x in q:
+            self._offsets_take(x)
         if all(x.dtype == q[0].dtype for x in q) and self._resident_for(q[0].dtype):
             with self._mutex:
                 idx, _, _ = self._resident_match(np.stack(q), pcs)
@@ -526,9 +673,7 @@ class ViewTemplates:
     def _ensure_gather(self):
         if getattr(self, '_gather_ready', False):
             return
-        if self.mask is None:
-            raise ValueError('no subsampling mask: construct with the frame geometry')
-        pix = np.ascontiguousarray(np.flatnonzero(self.mask.ravel()), dtype=np.int32)
+        pix = self.gather_pixels()
         assert pix.size == self.shape[0] * self.shape[1]
         _lib.check(self._lib.rs_vt_set_subsample(self._h, self.mask.size,
                                                  _lib.ptr(pix, ctypes.c_int32)))
@@ -581,11 +726,12 @@ class ViewTemplates:
                             else:
                                 t = None
                         else:
-                            t = f[i][self.mask].reshape(self.shape)
+                            t = self.subsample(f[i])
                         p = pcs[i]
                         assert idx[i] == len(self.templates), (idx[i], len(self.templates))
                         self.templates.append(ViewTemplate(p[0], p[1], p[2], int(idx[i]), t,
                                                            _owner=self))
+            self._record_offsets(idx, new)
         return idx, score, new.astype(bool)
 
     def device_ms(self):
@@ -644,19 +790,28 @@ class ShardedViewTemplates(ViewTemplates):
     _resident_ok = False
 
     def __init__(self, x_range, y_range, x_step, y_step, im_x, im_y, match_threshold,
-                 rank, nranks, reducer='rccl', unique_id=None, device=0, capacity=1024, metric='wrapped'):
+                 rank, nranks, reducer='rccl', unique_id=None, device=0, capacity=1024, metric='wrapped',
+                 offsets=False):
+        self._no_offsets(offsets)
         self.mask, self.shape = py2_mask(x_range, y_range, x_step, y_step, im_x, im_y)
         self._init_device(self.shape, match_threshold, device, capacity, metric)
         self._attach(rank, nranks, reducer, unique_id)
 
     @classmethod
     def from_shape(cls, shape, match_threshold, rank, nranks, reducer='rccl', unique_id=None,
-                   device=0, capacity=1024, metric='wrapped'):
+                   device=0, capacity=1024, metric='wrapped', offsets=False):
+        cls._no_offsets(offsets)
         self = cls.__new__(cls)
         self.mask = None
         self._init_device(shape, match_threshold, device, capacity, metric)
         self._attach(rank, nranks, reducer, unique_id)
         return self
+
+    @staticmethod
+    def _no_offsets(offsets):
+        if offsets:
+            raise TypeError('offsets=True is not supported by a sharded library: the template of '
+                            'a match lives on one rank')
 
     def _attach(self, rank, nranks, reducer, unique_id):
         self.rank, self.nranks = int(rank), int(nranks)
