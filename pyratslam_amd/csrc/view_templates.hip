@@ -806,6 +806,9 @@ __device__ __forceinline__ void plane_load_units(const uint4* __restrict__ plane
 // entry's query id, and the finish uses the id.  The ids of the batch being
 // computed (qc) and of the one staged next (qnv, entry lane & 3) are carried from
 // batch to batch: the ids of the batch after next are read right after the barrier.
+// A list's batch is W = 4, 2 or 1 consecutive entries (vt_plan::list_width, decided by the
+// block from the list's length); a batch of fewer than PL_NB fills the first W slots of the
+// LDS buffers, and entries of (lane & 3) >= W in qnv and qc are read and never used.
 struct PlaneIds {
     int qc[PL_NB];  // query ids of the batch being computed (wave-uniform)
     int qnv;        // lane: query id of entry (lane & 3) of the batch staged next
@@ -853,11 +856,13 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
                                             const uint4* __restrict__ qp4, const uint32_t* __restrict__ qsum,
                                             int nq, unsigned* __restrict__ ctr, int G, int g, ScanOut out,
                                             int rank, int nranks, int wave, int cg, int lane,
-                                            unsigned& failed, const int* __restrict__ ids, PlaneIds& pid) {
+                                            unsigned& failed, const int* __restrict__ ids, PlaneIds& pid,
+                                            int w) {
     using R = PlaneRange<H, HALF>;
     using LD = PlaneLds<H>;
     constexpr int NO = LD::NO, NK = LD::NK, NS = LD::NS;
     constexpr bool DEFER = FIRST && LIST;
+    const int W = LIST ? w : PL_NB;   // entries per batch (block-uniform; a list's own, PlaneList)
     const int nbatch = tk.nbatch;
     if (bi >= nbatch) return false;  // block-uniform
     const uint4* qcur = pl_q<H, CUR>();
@@ -868,7 +873,7 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
     // 0 writes the one after it into slot (it+2) % 3, last read two barriers ago
     const int r1 = (it + 1) % 3, r2 = (it + 2) % 3;
     const int bn = vt_pl_bidx[r1];
-    const int qb = (bi * G + g) * PL_NB, nb = min(PL_NB, nq - qb);
+    const int qb = (bi * G + g) * W, nb = min(W, nq - qb);
     // The take comes first (its result is waited for); with no next batch there is
     // no further take: this block's failed take was bn.
     if (tid == 0)  // the batch after next
@@ -878,7 +883,7 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
     int qnx[PL_NB] = {0, 0, 0, 0};  // LIST: the next batch's query ids
     auto stage_next = [&]() {
         if (bn < nbatch) {
-            const int qn = (bn * G + g) * PL_NB, nbn = min(PL_NB, nq - qn);
+            const int qn = (bn * G + g) * W, nbn = min(W, nq - qn);
             if constexpr (LIST) {
                 static_assert(PL_NB == 4, "four ids per batch");
 #pragma unroll
@@ -927,7 +932,7 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
 #pragma unroll
         for (int e = 0; e < PL_NB; ++e) pid.qc[e] = qnx[e];
         const int b2 = vt_pl_bidx[r2];   // thread 0 wrote it before the barrier
-        pid.qnv = b2 < nbatch ? ids[min((b2 * G + g) * PL_NB + (lane & 3), nq - 1)] : 0;
+        pid.qnv = b2 < nbatch ? ids[min((b2 * G + g) * W + (lane & 3), nq - 1)] : 0;
     }
     bi = bn;
     return true;
@@ -937,8 +942,8 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
 // the first batch needs is asked for at once, in one global round trip: the take of the
 // batch after it (thread 0, first: returns come back in order), the first batch's query
 // planes and TS by LDS-DMA, the template planes into P; the partial-count slots are zeroed
-// while they fly.  v0 (LIST): the lane's id of entry (lane & 3) of the static batch, read
-// by the kernel together with the list's length.
+// while they fly.  v0 (LIST): the lanes' candidates for the static batch's ids, read by the
+// kernel together with the list's length (vt_plan::spec_index); w: the list's entries per batch.
 template <int H, int HALF, bool MATRIX, bool LIST>
 __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes, const uint32_t* __restrict__ tsum,
                                            int tb, int64_t count, const uint4* __restrict__ qp4,
@@ -946,9 +951,10 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes, con
                                            unsigned* __restrict__ ctr, int G, int g, ScanOut out,
                                            int rank, int nranks, int wave, int cg, int lane,
                                            unsigned& failed, const int* __restrict__ ids,
-                                           const vt_plan::Take& tk, int v0) {
+                                           const vt_plan::Take& tk, int v0, int w) {
     using R = PlaneRange<H, HALF>;
     const int nbatch = tk.nbatch, tid = wave * 64 + lane;
+    const int W = LIST ? w : PL_NB;   // entries per batch (block-uniform)
     int bi = tk.sb, b1 = nbatch;
     if (tid == 0) b1 = plane_take(ctr, tk, failed);
     for (int i = tid; i < PL_NB * PL_NK * 64; i += 64 * PL_CG * PL_SPLIT) {
@@ -958,11 +964,11 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes, con
     PlaneIds pid{{0, 0, 0, 0}, 0};
     if constexpr (LIST) {
 #pragma unroll
-        for (int e = 0; e < PL_NB; ++e) pid.qc[e] = __builtin_amdgcn_readlane(v0, e);
+        for (int e = 0; e < PL_NB; ++e) pid.qc[e] = __builtin_amdgcn_readlane(v0, vt_plan::spec_lane(W) + e);
     }
     {
-        const int qb = (bi * G + g) * PL_NB;
-        plane_stage<H, LIST>(qp4, qb, min(PL_NB, nq - qb), pid.qc, vt_pl_qa<H>, wave, lane);
+        const int qb = (bi * G + g) * W;
+        plane_stage<H, LIST>(qp4, qb, min(W, nq - qb), pid.qc, vt_pl_qa<H>, wave, lane);
     }
     uint32_t P[R::NUH][8];
     plane_load_units<H, HALF>(planes, tb, cg, lane, P);
@@ -987,7 +993,7 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes, con
     const int64_t slot = (int64_t)tb * 64 + lane;
     if constexpr (LIST) {   // the ids of the second batch: used after the first query's walk
         b1 = vt_pl_bidx[1];
-        pid.qnv = b1 < nbatch ? ids[min((b1 * G + g) * PL_NB + (lane & 3), nq - 1)] : 0;
+        pid.qnv = b1 < nbatch ? ids[min((b1 * G + g) * W + (lane & 3), nq - 1)] : 0;
     }
     // unrolled by two: even iterations compute from qa and stage into qb, odd ones
     // the other way round (the prologue staged the first batch into qa)
@@ -996,13 +1002,13 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes, con
     // loop header's merge, so the loop body starts with an odd batch, whose compute
     // follows its own DMA issue, not the header.
     if (plane_batch<H, HALF, MATRIX, 0, LIST, true>(P, 0, bi, tk, slot, count, qp4, qsum, nq, ctr, G, g, out, rank,
-                                                    nranks, wave, cg, lane, failed, ids, pid))
+                                                    nranks, wave, cg, lane, failed, ids, pid, W))
         for (int it = 1;; it += 2) {
             if (!plane_batch<H, HALF, MATRIX, 1, LIST>(P, it, bi, tk, slot, count, qp4, qsum, nq, ctr, G, g, out,
-                                                       rank, nranks, wave, cg, lane, failed, ids, pid))
+                                                       rank, nranks, wave, cg, lane, failed, ids, pid, W))
                 break;
             if (!plane_batch<H, HALF, MATRIX, 0, LIST>(P, it + 1, bi, tk, slot, count, qp4, qsum, nq, ctr, G, g,
-                                                       out, rank, nranks, wave, cg, lane, failed, ids, pid))
+                                                       out, rank, nranks, wave, cg, lane, failed, ids, pid, W))
                 break;
         }
     VT_STAMP(5);
@@ -1029,12 +1035,38 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes, con
 #ifndef VT_LIST_PER_B1
 #define VT_LIST_PER_B1 1
 #endif
+// Entries per batch: each thread block takes vt_plan::list_width of its
+// list's length, of per and of fill = resident thread blocks / template blocks, so a short
+// list (pass B1: about 63 entries) is served by a full resident round of blocks in batches
+// of 2 where batches of 4 occupy half of the device, and by no more blocks than that round
+// (vt_plan::list_round); nb = 4, 2 or 1 replaces the rule (RS_VT_LIST_NB, or -DVT_LIST_NB=n
+// for an A/B build).
+// lfirst: the grid is sized for lists of every query, so of pass B1's 128 blocks per template
+// block about 32 work and 96 leave on the list's length.  Numbered template block by template
+// block, the leavers of one stand in the dispatch order ahead of the next one's workers, and
+// once the workers fill most of the device they pass through the few slots left: the last
+// template blocks' workers started late (pass B1 at 2 per batch: 26.6 us; with the blocks
+// numbered l-major, every template block's l-th block side by side, 20.7).  Pass B2's lists
+// fill their blocks, and its query planes are shared by the template blocks of an XCD group:
+// it keeps the template-block-major order.
+// per, nb and fill share the word that held per: the kernel's arguments, the hidden ones
+// behind them included, keep their places, and the dense instances their code.
 struct PlaneList {
     const int* ids = nullptr;
     const unsigned* cnt = nullptr;
     int ld = 0;
-    int per = 1;
+    uint32_t per : 8;
+    uint32_t nb : 7;       // 0: by the rule
+    uint32_t lfirst : 1;   // block ids run over the template blocks first (vt_plan::block_id): pass B1
+    uint32_t fill : 16;
 };
+static_assert(sizeof(PlaneList) == 24, "the plane scan's kernel arguments keep their layout");
+#ifdef VT_LIST_NB
+static_assert(VT_LIST_NB == 1 || VT_LIST_NB == 2 || VT_LIST_NB == 4, "entries per batch: 1, 2 or 4");
+#else
+#define VT_LIST_NB 0
+#endif
+
 template <int H, bool MATRIX, bool LIST = false>
 __global__ __launch_bounds__(64 * PL_CG * PL_SPLIT) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __restrict__ tsum,
@@ -1050,34 +1082,40 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
     // nqc >= 8 (a multiple of 8) the query batches are split into 8 groups by XCD, so
     // each L2 holds one group's planes
     VT_STAMP_BEGIN();
-    const int tb = (int)(blockIdx.x / (unsigned)nqc);
-    const int l = (int)(blockIdx.x - (unsigned)tb * (unsigned)nqc);   // this block among its template block's
+    // (pass B1 numbers its blocks the other way round, PlaneList::lfirst)
+    const vt_plan::BlockId bid = vt_plan::block_id(blockIdx.x, ntb, nqc, LIST && pl.lfirst);
+    const int tb = bid.tb;
+    const int l = bid.l;   // this block among its template block's
     const int G = vt_plan::take_groups(nqc), g = vt_plan::take_group_of(l, nqc);
     unsigned* ctr = next_batch + (size_t)tb * 8 + g;
     const int lane = threadIdx.x & 63;
     const int* ids = nullptr;
     int v0 = 0;
+    int W = PL_NB;   // entries per batch: a list's own (block-uniform), the dense launch's constant
     if constexpr (LIST) {
         // One round trip: the list's length and, before it is known, the ids of the batch
         // this block would own (the first `use` blocks own batches l >> 3 of group l & 7, or
-        // l).  The speculative read stays inside the slab (ld entries); its value is used
+        // l) at each width the length may choose, in distinct lanes (vt_plan::spec_index).
+        // The speculative read stays inside the slab (ld entries); its value is used
         // only if the length says the entries exist.
         ids = pl.ids + (size_t)tb * pl.ld;
-        v0 = ids[min(((G == 8 ? l >> 3 : l) * G + g) * PL_NB + (lane & 3), pl.ld - 1)];
+        v0 = ids[vt_plan::spec_index((G == 8 ? l >> 3 : l) * G + g, lane, pl.ld)];
         nq = (int)pl.cnt[tb];   // block-uniform
         if (nq == 0) return;
+        W = pl.nb ? (int)pl.nb : vt_plan::list_width(nq, pl.per, pl.fill, nqc);
         // The grid is sized for a list of every query; a shorter list is served by
         // the first `use` of the template block's nqc blocks, about pl.per batches
         // each, so a block's fixed cost (its template planes, 128 KiB) is not paid per
         // batch.  The others leave before they ask for anything else.
-        const int use = vt_plan::list_use(nq, PL_NB, pl.per, nqc);
+        int use = vt_plan::list_use(nq, W, pl.per, nqc);
+        if (!pl.nb && W < PL_NB) use = vt_plan::list_round(use, pl.fill, nqc);   // (the rule's own: vt_plan.h)
         if (l >= use) return;
         nqc = use;
     }
     // Which batches are this block's: its static one, and the counter's (vt_plan.h).  The
     // nqc / G blocks sharing a counter each end on exactly one failed take when the group
     // has more batches than blocks, and on none otherwise.
-    const vt_plan::Take tk = vt_plan::take_plan(nq, PL_NB, l, nqc);
+    const vt_plan::Take tk = vt_plan::take_plan(nq, W, l, nqc);
     VT_STAMP_KNOWN();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int cg = wave % PL_CG, half = wave / PL_CG;
@@ -1086,10 +1124,10 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
     if (tk.sb >= tk.nbatch) {   // (block-uniform) no batch for this block: it leaves the counter alone
     } else if (half == 0)
         plane_wave<H, 0, MATRIX, LIST>(planes, tsum, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
-                                       wave, cg, lane, failed, ids, tk, v0);
+                                       wave, cg, lane, failed, ids, tk, v0, W);
     else
         plane_wave<H, 1, MATRIX, LIST>(planes, tsum, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
-                                       wave, cg, lane, failed, ids, tk, v0);
+                                       wave, cg, lane, failed, ids, tk, v0, W);
     // The block whose failed take returned tk.last is the counter's last user in this
     // launch: it rewinds the counter for the next launch (no memset).
     if (threadIdx.x == 0 && tk.takes && failed == tk.last) *ctr = 0u;
@@ -1402,12 +1440,14 @@ constexpr int VT_VR = QC_NA + 7;               // staged unit rows: 3 never-coun
 // the tail of vt_front_kernel, so the rule has one definition).  pick(pk, sec, m2) leaves
 // each lane's share of the pick: its least key (minLB << 32) | tb, that block's `second`,
 // and its lowest bound but one; the query's planes and QS are in flight through it.
-// s_q, s_t: the wave's own VT_VQS and VT_VTS uint4 of LDS.  `act` (wave-uniform) is false
-// for a wave that only keeps the thread block's barriers company: it writes nothing.
-// Every wave of the thread block must call this (one __syncthreads inside).
+// s_q, s_t: the wave's own VT_VQS and VT_VTS uint4 of LDS.  Between the staging stores and
+// the reads of other lanes' entries: WAVE_LDS = false, a __syncthreads (every wave of the
+// thread block must then call this); true, where s_q and s_t are no other wave's, the wave's
+// own wait for its LDS writes, so a thread block's waves verify independently and a wave
+// without a query does not call at all.
 constexpr int VT_VQS = PL_CG * VT_VR * 2, VT_VTS = PL_CG * (64 / 4) * 2;
-template <class Pick>
-__device__ __forceinline__ void vt_verify_query(int q, bool act, int lane, Pick&& pick, int nq,
+template <bool WAVE_LDS, class Pick>
+__device__ __forceinline__ void vt_verify_query(int q, int lane, Pick&& pick, int nq,
                                                 const uint4* __restrict__ planes,
                                                 const uint32_t* __restrict__ tsum,
                                                 const uint4* __restrict__ qc4, uint4* __restrict__ qp4,
@@ -1454,7 +1494,14 @@ __device__ __forceinline__ void vt_verify_query(int q, bool act, int lane, Pick&
         if (c < QC_Q4) s_q[(g * VT_VR + 3) * 2 + (c - g * (QC_NA * 2))] = qv[k];
     }
     if (lane < 2 * PL_CG) s_q[((lane >> 1) * VT_VR + 3 + QC_NA) * 2 + (lane & 1)] = make_uint4(0u, 0u, 0u, 0u);
-    __syncthreads();
+    if constexpr (WAVE_LDS) {
+        // (the clobber keeps the compiler's LDS reads below behind the stores above; the
+        // wave's LDS instructions complete in order)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+    } else {
+        __syncthreads();
+    }
     uint32_t cnt = 0u;
     if (x < PL_NO) {
         // start row 4j - o = S0 + 4 (j + a) + r: the units a + j and a + j + 1, shifted by 8r
@@ -1491,7 +1538,7 @@ __device__ __forceinline__ void vt_verify_query(int q, bool act, int lane, Pick&
     for (int off = 32; off > 0; off >>= 1) u0 = min(u0, (uint32_t)__shfl_xor(u0, off));
     u0 -= qs;
     const bool settled = (sec >> 6) > u0;
-    if (act && (!settled || other <= u0)) {   // (wave-uniform) a scan pass stages this query
+    if (!settled || other <= u0) {   // (wave-uniform) a scan pass stages this query
 #pragma unroll
         for (int k = 0; k < (VT_VQ4 + 63) / 64; ++k) {
             const int i = lane + 64 * k, g = i / (NS * 2), r = i - g * (NS * 2), si = r >> 1;
@@ -1501,7 +1548,7 @@ __device__ __forceinline__ void vt_verify_query(int q, bool act, int lane, Pick&
             }
         }
     }
-    if (act && lane == 0) {
+    if (lane == 0) {
         if (settled) {
             const unsigned long long g = ((unsigned long long)tbs * 64 + tl) * nranks + rank;
             atomicMin(best + q, ((unsigned long long)u0 << 32) | g);
@@ -1522,7 +1569,7 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
     __shared__ uint4 s_q[VT_VQS];
     __shared__ uint4 s_t[VT_VTS];
     const int q = blockIdx.x, lane = threadIdx.x;
-    vt_verify_query(q, true, lane, [&](unsigned long long& pk, uint32_t& sec, uint32_t& m2) {
+    vt_verify_query<false>(q, lane, [&](unsigned long long& pk, uint32_t& sec, uint32_t& m2) {
         for (int tb = lane; tb < ntb; tb += 64) {
             const unsigned long long k = ((unsigned long long)minlb[(size_t)tb * nq + q] << 32) | (unsigned)tb;
             const uint32_t s2 = second[(size_t)tb * nq + q];
@@ -1542,11 +1589,12 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
 // into query w's pick, lane l the chunk's block l -- per lane the very update of the
 // verify kernel's pick loop, only with the blocks dealt 16 to a chunk instead of 64 to a
 // stride, and the wave-wide reductions that follow are associative.  Then wave w verifies
-// query w (vt_verify_query).  second[] is not written.
+// query w (vt_verify_query) on its own: s_vq[w] and s_vt[w] are no other wave's, so the tail
+// has no block barrier, no wave waits for the slowest one's template round trip, and a wave
+// without a query (w >= nb, the last group) skips it.  second[] is not written.
 // Barriers: every one is reached by all PF_WAVES waves -- the chunk loop's bounds are
-// block-uniform, a wave without a template block skips the walk only (no barrier inside),
-// and a wave without a query (w >= nb, the last group) verifies the group's last query
-// again with its writes off.  s_pick is double-buffered by chunk parity: with one barrier
+// block-uniform and a wave without a template block skips the walk only (no barrier
+// inside).  s_pick is double-buffered by chunk parity: with one barrier
 // per chunk a wave is at most one chunk ahead of a wave still folding.
 __global__ __launch_bounds__(64 * PF_WAVES) __attribute__((amdgpu_waves_per_eu(4)))
 void vt_front_kernel(const uint4* __restrict__ planes, int ntb, int64_t count, const uint4* __restrict__ qc4,
@@ -1566,7 +1614,7 @@ void vt_front_kernel(const uint4* __restrict__ planes, int ntb, int64_t count, c
     int par = 0;
     for (int q0 = blockIdx.y * PF_NB; q0 < nq; q0 += gridDim.y * PF_NB) {   // block-uniform
         const int nb = min(PF_NB, nq - q0);
-        const int qw = min(wave, nb - 1);   // the query this wave picks for and verifies
+        const int qw = min(wave, nb - 1);   // the query this wave picks for (and verifies, if wave < nb)
         __syncthreads();   // the group before has been read
         pf_stage(qc4, qsj, q0, nb, s_q, s_qs);
         __syncthreads();
@@ -1608,11 +1656,12 @@ void vt_front_kernel(const uint4* __restrict__ planes, int ntb, int64_t count, c
         // would stay live through the walk, in scratch)
         int vl = lane;
         asm volatile("" : "+v"(vl));
-        vt_verify_query(q0 + qw, wave < nb, vl, [&](unsigned long long& pk_, uint32_t& sec_, uint32_t& m2_) {
-            pk_ = pk;
-            sec_ = sec;
-            m2_ = m2;
-        }, nq, planes, tsum, qc4, qp4, qsum, best, rank, nranks, tbstar, s_vq[wave], s_vt[wave]);
+        if (wave < nb)   // (wave-uniform; no barrier inside)
+            vt_verify_query<true>(q0 + wave, vl, [&](unsigned long long& pk_, uint32_t& sec_, uint32_t& m2_) {
+                pk_ = pk;
+                sec_ = sec;
+                m2_ = m2;
+            }, nq, planes, tsum, qc4, qp4, qsum, best, rank, nranks, tbstar, s_vq[wave], s_vt[wave]);
     }
 }
 
@@ -1857,6 +1906,8 @@ struct rs_vt {
     // its front in one launch (vt_front_kernel; RS_VT_FRONT): 0 never, 1 where
     // vt_plan::front_fused says so, 2 ("force") for any shape
     int front = 1;
+    // entries per batch of its list passes (RS_VT_LIST_NB): 0 by vt_plan::list_width, or 1, 2, 4
+    int listNb = VT_LIST_NB;
     rs::DevBuf<uint32_t> dQsj;        // QS_J of the queries in dQp
     rs::DevBuf<uint32_t> dQsjStream;  // ... of dQpStream
     // compact query planes (the aligned start rows).  A build ahead of a pruned scan fills
@@ -2243,7 +2294,11 @@ int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
     ScanOut po = out;
     po.host = nullptr;
     po.done = nullptr;
-    vt_launch_plane_scan<64, false, true>(h, s, po, PlaneList{list1, cnt1, nq, VT_LIST_PER_B1});
+    // working blocks per template block that make one resident round (vt_plan::list_width)
+    const uint32_t fill = (uint32_t)std::min(65535, std::max(1, h->planeSlots / ntb));
+    const uint32_t lnb = (uint32_t)h->listNb;
+    vt_launch_plane_scan<64, false, true>(h, s, po,
+                                          PlaneList{list1, cnt1, nq, (uint32_t)VT_LIST_PER_B1, lnb, 1u, fill});
     hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB.get(), nq,
                        h->dTbStar.get(), out.best, cnt2, list2, cnt1, verified, ntb, h->dPruneStat.get());
 #ifdef VT_LIST_PER
@@ -2251,7 +2306,7 @@ int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
 #else
     const int per2 = vt_plan::list_per(ntb, h->planeSlots);
 #endif
-    vt_launch_plane_scan<64, false, true>(h, s, po, PlaneList{list2, cnt2, nq, per2});
+    vt_launch_plane_scan<64, false, true>(h, s, po, PlaneList{list2, cnt2, nq, (uint32_t)per2, lnb, 0u, fill});
     if (out.host) vt_launch_keys_export(h, out.best, nq, out.host, vt_plan::VT_EXPORT_BLOCKS);
     RS_HIP(hipGetLastError());
     h->prunePairs = (int64_t)pairs;
@@ -2769,6 +2824,13 @@ int rs_vt_create_metric(int H, int W, int max_offset, uint64_t thr, int64_t capa
         else {
             RS_CHECK(std::strcmp(e, "0") == 0, RS_ERR_ARG, "RS_VT_FRONT='%s': expected 0, 1 or force", e);
             h->front = 0;
+        }
+        // A/B switch and tests: "1", "2" or "4" entries per batch in both list passes; unset:
+        // each list's own width (vt_plan::list_width)
+        if (const char* nb = std::getenv("RS_VT_LIST_NB"); nb && nb[0]) {
+            RS_CHECK((nb[0] == '1' || nb[0] == '2' || nb[0] == '4') && nb[1] == 0, RS_ERR_ARG,
+                     "RS_VT_LIST_NB='%s': expected 1, 2 or 4", nb);
+            h->listNb = nb[0] - '0';
         }
     }
     if (h->planar) {

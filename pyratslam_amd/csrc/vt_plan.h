@@ -65,6 +65,22 @@ struct Take {
 };
 VT_PLAN_HD inline int take_groups(int nblk) { return nblk >= 8 ? 8 : 1; }
 VT_PLAN_HD inline int take_group_of(int l, int nblk) { return nblk >= 8 ? (l & 7) : 0; }
+// Which template block a thread block of the plane scan serves, and which of that template
+// block's nqc blocks it is.  Template-block-major (the dense launch, pass B2): the nqc blocks
+// of a template block are adjacent ids.  lfirst (pass B1): block l of every template block,
+// then block l + 1 of every one, so the blocks that work (the first `use` of each) stand in
+// front of the ones that leave at once.
+struct BlockId {
+    int tb, l;
+};
+VT_PLAN_HD inline BlockId block_id(unsigned bid, int ntb, int nqc, bool lfirst) {
+    if (lfirst) {
+        const unsigned l = bid / (unsigned)ntb;
+        return {(int)(bid - l * (unsigned)ntb), (int)l};
+    }
+    const unsigned tb = bid / (unsigned)nqc;
+    return {(int)tb, (int)(bid - tb * (unsigned)nqc)};
+}
 // Blocks that serve a list of nq entries in batches of nb, about `per` batches each, of the
 // nqc the grid holds per template block (a multiple of 8 when nqc >= 8).
 VT_PLAN_HD inline int list_use(int nq, int nb, int per, int nqc) {
@@ -75,6 +91,43 @@ VT_PLAN_HD inline int list_use(int nq, int nb, int per, int nqc) {
     }
     return use < 1 ? 1 : (use > nqc ? nqc : use);
 }
+// Entries per batch (W) of a list pass, decided by each thread block from its list's length.
+// A batch is walked by one thread block, its entries one after the other, so a short list in
+// batches of 4 leaves most of the device idle: 63 entries are 16 working blocks per template
+// block, 256 on a device that holds 512, each walking four queries in turn behind its
+// prologue.  `fill` is the resident thread blocks divided by the template blocks (at least
+// 1): the working blocks per template block that make one full resident round.  The widest W
+// of {4, 2, 1} whose list_use reaches fill; 1 if none does.  Lists long enough for fill at 4
+// (pass B2 at the headline, every all-miss list, any library with more template blocks than
+// resident thread blocks) keep 4.  
+VT_PLAN_HD inline int list_width(int entries, int per, int fill, int nqc) {
+    if (list_use(entries, 4, per, nqc) >= fill) return 4;
+    if (list_use(entries, 2, per, nqc) >= fill) return 2;
+    return 1;
+}
+// The working blocks of a list whose batch the rule narrowed: no more than one resident round
+// (fill, in whole groups of 8 like list_use).  list_use rounds up to eight blocks' worth, so
+// lists a little longer than fill * w entries would otherwise put a few blocks into a second
+// round, each behind a prologue of its own; the batches beyond the blocks go to the counters,
+// where the blocks that finish first take them.
+VT_PLAN_HD inline int list_round(int use, int fill, int nqc) {
+    int cap = fill < 1 ? 1 : fill;
+    if (nqc >= 8) cap = (cap + 7) & ~7;
+    return use < cap ? use : cap;
+}
+// The ids of a block's static batch are read in the same trip as the list's length, so before
+// W is known: every lane reads one candidate, lanes 0-3 the four entries of the batch of 4,
+// lanes 4-5 the two of the batch of 2, lane 6 the one of the batch of 1 (lane 7 reads lane
+// 6's again; every eight lanes alike).  spec_index: the entry lane reads for the block whose
+// static batch is `batch` (sb * G + g), clamped into the slab of ld entries; spec_lane: the
+// lane that holds entry 0 of width w's batch, entry e in lane spec_lane(w) + e.
+VT_PLAN_HD inline int spec_width(int lane) { return (lane & 7) < 4 ? 4 : (lane & 7) < 6 ? 2 : 1; }
+VT_PLAN_HD inline int spec_entry(int lane) { return (lane & 7) < 4 ? (lane & 7) : (lane & 7) < 6 ? (lane & 7) - 4 : 0; }
+VT_PLAN_HD inline int spec_index(int batch, int lane, int ld) {
+    const int i = batch * spec_width(lane) + spec_entry(lane);
+    return i < ld - 1 ? i : ld - 1;
+}
+VT_PLAN_HD inline int spec_lane(int w) { return w == 4 ? 0 : w == 2 ? 4 : 6; }
 // Batches per block of list pass B2 (list_use's per).  A block's prologue is one round trip
 // for 128 KiB of template planes, paid per block, so fewer, longer blocks win while the
 // template blocks are few and their blocks run side by side: 1,000 templates (16 template
