@@ -454,10 +454,16 @@ int rs_vt_set_threshold(rs_vt* h, double threshold);
 
 /* ViewTemplate.match on float arrays (view_templates.py:16-28 with float32 or
  * float64 data: no uint8 wrap, a true sum |T - Q| per row offset in the arrays'
- * precision, numpy's pairwise summation order, first strict minimum over the
- * 2*max_offset-1 offsets from +inf).  templates[nt*H*W], queries[nq*H*W] and
- * scores[nq*nt] (scores[q*nt + t]) are host arrays of dtype RS_DT_F32 / F64;
- * the scores are computed on `device`. */
+ * precision, first strict minimum over the 2*max_offset-1 offsets from +inf).
+ * The summation is np.sum's, bit for bit: numpy's pairwise order within each chunk of
+ * 8,192 elements (its reduction buffer), the chunks' sums added in sequence; it is the
+ * plan of the device-resident library below, which this call creates, fills and
+ * destroys.  templates[nt*H*W], queries[nq*H*W] and scores[nq*nt] (scores[q*nt + t])
+ * are host arrays of dtype RS_DT_F32 / F64 (another value: RS_ERR_TYPE); the scores are
+ * computed on `device`.  Accepted, as by that library: H > 2*max_offset, W >= 1,
+ * 1 <= max_offset <= 16, H*W <= 2^30, nt < 2^31, and a launch of at most 65,535 query
+ * chunks (it splits the queries into no more than about 1,024 / nt); otherwise RS_ERR_ARG.
+ * Zero nt or nq: RS_OK, nothing read or written. */
 #define RS_DT_F32 0
 #define RS_DT_F64 1
 int rs_sad_scores(int device, int dtype, int H, int W, int max_offset, int64_t nt,

@@ -15,8 +15,8 @@ CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(ROOT, 'include')
 LIB = os.path.join(HERE, 'libratslam_hip.so')
 OBJDIR = os.path.join(HERE, 'build')
-# the translation units (posecell.hip includes its pc_*.h parts: one object, so the
-# file-wide flags below reach every pose-cell kernel)
+# the translation units (posecell.hip includes its pc_*.h parts, view_templates.hip its
+# vt_*.h parts: one object each, so the file-wide flags below reach every kernel of either)
 SOURCES = ['rs_common.cpp', 'posecell.hip', 'view_templates.hip', 'view_templates_float.hip',
            'visual_odometer.hip', 'experience_map.hip']
 # per-source flags: the plane scan's batch takes are single-lane atomics; the

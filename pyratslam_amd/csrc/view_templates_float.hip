@@ -17,6 +17,9 @@
 // so every lane of the octet ends with exactly ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)):
 // the additions of the plan, in the plan's order, and nothing else.  plan_eval() below
 // is the host evaluator of the same plan, lane for lane (rs_sad_plan_sum).
+// rs_sad_scores, the score matrix of host arrays, is such a library for one call: every
+// float score of the package is this plan's.
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -304,7 +307,7 @@ constexpr size_t LDS_BUDGET = 64 * 1024;
 // Host side
 // ===========================================================================
 // The buffers are rs::DevBuf members (rs_common.h; untyped ones count bytes, the element
-// being es wide).  Group capacity: qCap (dQ, dIn, dBest, dBidx).
+// being es wide).  Group capacities: qCap (dQ), scanCap (dIn, dBest, dBidx).
 struct rs_vtf {
     int H = 0, W = 0, M = 0, dtype = 0, device = 0;
     size_t es = 0;            // element size
@@ -317,11 +320,11 @@ struct rs_vtf {
     bool staged = false;      // template and query tiles fit the LDS budget
     int tsize = 0;            // elements of the padded template tile (tile_at)
     // staged queries and results
-    int qCap = 0, nqStaged = 0;
+    int qCap = 0, nqStaged = 0, scanCap = 0;
     rs::DevBuf<void> dQ;
-    rs::DevBuf<void> dIn;        // [qCap][qCap] in-batch scores
-    rs::DevBuf<void> dBest;      // [qCap]
-    rs::DevBuf<int64_t> dBidx;   // [qCap]
+    rs::DevBuf<void> dIn;        // [scanCap][scanCap] in-batch scores
+    rs::DevBuf<void> dBest;      // [scanCap]
+    rs::DevBuf<int64_t> dBidx;   // [scanCap]
     rs::DevBuf<void> dScores;    // (its capacity in bytes)
     bool timing = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -372,10 +375,21 @@ int ensure_queries(rs_vtf* h, int nq) {
     h->qCap = 0;
     h->nqStaged = 0;
     RS_TRY(h->dQ.reserve((size_t)cap * h->H * h->W * h->es));
+    h->qCap = cap;
+    return RS_OK;
+}
+
+// what rs_vtf_scan alone writes: a handle that only scores (rs_sad_scores' is one) never
+// allocates them
+int ensure_scan_results(rs_vtf* h, int nq) {
+    if (nq <= h->scanCap) return RS_OK;
+    RS_HIP(hipStreamSynchronize(h->stream));
+    const int cap = rs::grown(h->scanCap, nq, 1);
+    h->scanCap = 0;
     RS_TRY(h->dIn.reserve((size_t)cap * cap * h->es));
     RS_TRY(h->dBest.reserve((size_t)cap * h->es));
     RS_TRY(h->dBidx.reserve((size_t)cap));
-    h->qCap = cap;
+    h->scanCap = cap;
     return RS_OK;
 }
 
@@ -445,6 +459,15 @@ int launch_argmin(rs_vtf* h, int nq, int64_t nt) {
     return RS_OK;
 }
 
+// what a library (rs_vtf_create) and a one-off score matrix (rs_sad_scores) accept
+int check_geometry(int dtype, int H, int W, int max_offset) {
+    RS_CHECK(dtype == RS_DT_F32 || dtype == RS_DT_F64, RS_ERR_TYPE, "dtype %d is not F32/F64", dtype);
+    RS_CHECK(H > 0 && W > 0 && max_offset >= 1 && max_offset <= 16 && H > 2 * max_offset,
+             RS_ERR_ARG, "bad shape (%d, %d) for max_offset %d", H, W, max_offset);
+    RS_CHECK((int64_t)H * W <= (1ll << 30), RS_ERR_ARG, "template too large");
+    return RS_OK;
+}
+
 void fill_inf(int dtype, void* p, size_t n) {
     if (dtype == RS_DT_F32)
         for (size_t i = 0; i < n; ++i) static_cast<float*>(p)[i] = std::numeric_limits<float>::infinity();
@@ -461,10 +484,7 @@ int rs_vtf_create(int H, int W, int max_offset, int dtype, int64_t capacity, int
     rs::clear_error();
     RS_CHECK(out != nullptr, RS_ERR_ARG, "null output handle");
     *out = nullptr;
-    RS_CHECK(dtype == RS_DT_F32 || dtype == RS_DT_F64, RS_ERR_TYPE, "dtype %d is not F32/F64", dtype);
-    RS_CHECK(H > 0 && W > 0 && max_offset >= 1 && max_offset <= 16 && H > 2 * max_offset,
-             RS_ERR_ARG, "bad shape (%d, %d) for max_offset %d", H, W, max_offset);
-    RS_CHECK((int64_t)H * W <= (1ll << 30), RS_ERR_ARG, "template too large");
+    RS_TRY(check_geometry(dtype, H, W, max_offset));
     RS_CHECK(capacity >= 0, RS_ERR_ARG, "negative capacity");
     int ndev = 0;
     RS_HIP(hipGetDeviceCount(&ndev));
@@ -574,6 +594,7 @@ int rs_vtf_scan(rs_vtf* h, int nq, const void* queries, int want_inbatch, void* 
     RS_CHECK(!want_inbatch || inbatch, RS_ERR_ARG, "null in-batch matrix");
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(stage_queries(h, nq, queries));
+    RS_TRY(ensure_scan_results(h, nq));
     const int64_t nt = h->count;
     if (nt > 0) {
         RS_TRY(ensure_scores(h, (size_t)nq * nt));
@@ -642,6 +663,24 @@ int rs_vtf_last_ms(rs_vtf* h, double* ms) {
     RS_CHECK(h && ms, RS_ERR_ARG, "null argument");
     *ms = h->lastMs;
     return RS_OK;
+}
+
+// The score matrix of host arrays: a library for the duration of the call, so the one plan
+// and the one kernel of the resident path (out[q * nt + t], as rs_vtf_scores lays it out).
+int rs_sad_scores(int device, int dtype, int H, int W, int max_offset, int64_t nt,
+                  const void* templates, int nq, const void* queries, void* scores) {
+    rs::clear_error();
+    RS_TRY(check_geometry(dtype, H, W, max_offset));
+    RS_CHECK(nt >= 0 && nq >= 0, RS_ERR_ARG, "negative count");
+    if (nt == 0 || nq == 0) return RS_OK;
+    RS_CHECK(templates && queries && scores, RS_ERR_ARG, "null argument");
+    RS_CHECK(nt <= INT_MAX, RS_ERR_ARG, "too many templates");
+    rs_vtf* h = nullptr;
+    RS_TRY(rs_vtf_create(H, W, max_offset, dtype, nt, device, &h));
+    int rc = rs_vtf_add(h, (int)nt, templates, nullptr);
+    if (rc == RS_OK) rc = rs_vtf_scores(h, nq, queries, 0, nt, scores);
+    const int freed = free_handle(h);   // (not rs_vtf_destroy: a failure's message stays)
+    return rc != RS_OK ? rc : freed;
 }
 
 int rs_sad_plan_sum(int dtype, int64_t n, const void* values, void* out) {

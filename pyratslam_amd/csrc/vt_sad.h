@@ -1,5 +1,5 @@
 // True-SAD metric of the uint8 view-template matcher (RS_VT_METRIC_SAD), included by
-// view_templates.hip behind ScanOut / emit_score.
+// view_templates.hip behind vt_device.h (ScanOut / emit_score).
 //
 //   score(T, Q) = min_{o=-(M-1)..M-1} sum_{r=M..H-M-1, c} |T[r+o][c] - Q[r][c]|
 // on the bytes as integers: ViewTemplate.match (view_templates.py:16-28) on the same

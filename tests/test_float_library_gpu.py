@@ -75,6 +75,35 @@ def test_shapes_vs_oracle(vtmod, shape, dt):
     assert same_bits(lib.scores(b), ref_matrix(a, b))
 
 
+@pytest.mark.parametrize('dt', DTYPES)
+def test_window_longer_than_numpys_reduction_buffer(vtmod, dt):
+    """(18, 4200) at max_offset 8: a window of 2 x 4,200 = 8,400 elements, above the 8,192
+    that np.sum hands its pairwise loop at a time, so numpy's sum is the first 8,192
+    elements' pairwise sum plus the remaining 208's.  The template does not fit the scan's
+    LDS tile: the general instance.  Both the pair-wise call and the resident library
+    follow the one chunked plan.  Before rs_sad_scores took that plan its own unchunked
+    pairwise order failed the first assertion (a CPU emulation of both orders on these
+    inputs: a different minimum from np.sum's in 3 of 4 pairs, in float32 and in float64);
+    the second assertion held then too.  The resident library is an rs_vtf handle through
+    the ABI: a ViewTemplates also holds a uint8 handle, which takes no width above 4,096."""
+    from pyratslam_amd import _lib
+    rng = np.random.default_rng(0)
+    a = (rng.random((2, 18, 4200)) * 255).astype(dt)
+    b = (rng.random((2, 18, 4200)) * 255).astype(dt)
+    ref = ref_matrix(a, b)
+    assert same_bits(vtmod.sad_scores(a, b), ref)
+    lib, h = _lib.require_device(), ctypes.c_void_p()
+    code = _lib.RS_DT_F32 if dt is np.float32 else _lib.RS_DT_F64
+    _lib.check(lib.rs_vtf_create(18, 4200, vtmod.MAX_OFFSET, code, 2, 0, ctypes.byref(h)))
+    try:
+        _lib.check(lib.rs_vtf_add(h, 2, ctypes.c_void_p(a.ctypes.data), None))
+        sc = np.empty((2, 2), dtype=dt)
+        _lib.check(lib.rs_vtf_scores(h, 2, ctypes.c_void_p(b.ctypes.data), 0, 2, ctypes.c_void_p(sc.ctypes.data)))
+    finally:
+        _lib.check(lib.rs_vtf_destroy(h))
+    assert same_bits(sc, ref)
+
+
 # -- library sizes x batch sizes ---------------------------------------------------
 @pytest.fixture(scope='module', params=DTYPES, ids=['f32', 'f64'])
 def scan_case(request):

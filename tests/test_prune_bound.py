@@ -15,7 +15,7 @@ from oracle import view_templates as V
 
 M = V.MAX_OFFSET
 H, W = 64, 32
-# the prefilter's template units (pf_unit() of pyratslam_amd/csrc/view_templates.hip)
+# the prefilter's template units (pf_unit() of pyratslam_amd/csrc/vt_planes.h)
 PF_UNITS = (7,)
 
 

@@ -19,7 +19,7 @@ from test_prune_verify_rule import min_bounds, score_matrix, small_cases, verify
 M = V.MAX_OFFSET
 H, W = 64, 32
 # the columns of a unit the prefilter's bound covers (8 * VT_PF_CGS of
-# pyratslam_amd/csrc/view_templates.hip)
+# pyratslam_amd/csrc/vt_planes.h)
 PF_COLS = 16
 J = PF_UNITS[0]
 COLS = [8, 16, 32]      # 1, 2 and 4 column groups
