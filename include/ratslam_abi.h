@@ -393,6 +393,25 @@ int rs_vt_offset_profile(rs_vt* h, int nq, const uint8_t* queries, const int64_t
                          uint32_t* profile, int32_t* offset);
 int rs_vt_offset_profile_host(int metric, int H, int W, int max_offset, const uint8_t* tpl,
                               const uint8_t* query, uint32_t* profile, int32_t* offset);
+/* Patch normalisation (against a change of exposure between visits): with radius R > 0 every
+ * raw image that enters the handle -- template, query, gathered frame, stream batch, explicit
+ * offset-profile query -- is replaced on the device by its normalised bytes before anything
+ * else reads it, so the library, every scan, rs_vt_read and rs_vt_offset_profile work on
+ * normalised bytes.  At pixel (r, c), over the window of rows r-R..r+R and columns c-R..c+R
+ * clamped to the image (n pixels, sum S, square sum S2):
+ *   D = n*S2 - S*S,  N = n*p - S,  s = floor(sqrt(D)),
+ *   out = 128 if s == 0, else clamp(128 + sign(N) * ((gain*|N| + s/2) / s), 0, 255)
+ * in integers throughout (gain grey levels per local standard deviation around 128).
+ * radius 0 turns it off (the default; gain is then ignored); a radius outside [0, 7] or a gain
+ * outside [1, 127]: RS_ERR_ARG.  Allowed only while the handle holds no template and no staged
+ * batch (RS_ERR_STATE otherwise), so a library never mixes raw and normalised bytes.  Device
+ * and pinned inputs are read, never written.  Every rank of a sharded library sets the same.
+ * rs_vt_normalise reads the setting back (0, 0 when off; either pointer may be NULL).
+ * rs_vt_normalise_host is the same rule for one H x W image on the host alone (no handle, no
+ * device): src and dst are distinct arrays of H*W bytes, radius in [1, 7]. */
+int rs_vt_set_normalise(rs_vt* h, int radius, int gain);
+int rs_vt_normalise(const rs_vt* h, int* radius, int* gain);
+int rs_vt_normalise_host(int H, int W, int radius, int gain, const uint8_t* src, uint8_t* dst);
 /* The two halves of rs_vt_match_batch, for callers that combine the per-rank
  * keys themselves (any min-reduction over ranks; key = score << 32 | index,
  * UINT64_MAX = no template):

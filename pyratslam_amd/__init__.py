@@ -10,7 +10,7 @@ from .linked_experience_map import LinkedExperienceMap, NumpyLinkedExperienceMap
 from .pc_peak import numpy_peak_sums, peak_tables, pose_from_sums  # noqa: F401
 from .posecell_network import PoseCellNetwork  # noqa: F401
 from .view_templates import (ShardedViewTemplates, ViewTemplate, ViewTemplates, numpy_offset_profile,  # noqa: F401
-                             numpy_sad_u8_scores, refine_offset)
+                             normalise_u8, numpy_sad_u8_scores, refine_offset)
 from .visual_odometer import NumpyVisualOdometer, SimpleVisualOdometer  # noqa: F401
 
 __version__ = '0.1.0'

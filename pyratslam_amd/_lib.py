@@ -138,6 +138,9 @@ SIGNATURES = {
     'rs_vt_offset_profile': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _i64p, _u32p, _i32p]),
     'rs_vt_offset_profile_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _u8p, _u8p,
                                                  _u32p, _i32p]),
+    'rs_vt_set_normalise': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    'rs_vt_normalise': (ctypes.c_int, [_vp, _c_int_p, _c_int_p]),
+    'rs_vt_normalise_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _u8p, _u8p]),
     'rs_vt_set_subsample': (ctypes.c_int, [_vp, ctypes.c_int64, _i32p]),
     'rs_vt_match_frames': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _u64p, _i64p, _u8p]),
     'rs_vt_scan_local': (ctypes.c_int, [_vp, ctypes.c_int, _u8p, _u64p]),
@@ -194,7 +197,8 @@ SIGNATURES = {
 # statistics calls an older build of the library lacks: tools/stream_ab.py loads such
 # builds by path for an A/B; calling one of these on them raises AttributeError
 NEWER_SYMBOLS = {'rs_vt_prune_stats', 'rs_vt_prune_verified', 'rs_vt_create_metric', 'rs_vt_metric',
-                 'rs_vt_offset_profile', 'rs_vt_offset_profile_host'}
+                 'rs_vt_offset_profile', 'rs_vt_offset_profile_host', 'rs_vt_set_normalise',
+                 'rs_vt_normalise', 'rs_vt_normalise_host'}
 
 _lib = None
 _lock = threading.Lock()

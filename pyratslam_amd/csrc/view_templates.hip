@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "rs_common.h"
+#include "vt_norm_rule.h"
 #include "vt_offset_rule.h"
 #include "vt_plan.h"
 
@@ -53,6 +54,7 @@ static_assert(vt_plan::METRIC_WRAPPED == RS_VT_METRIC_WRAPPED && vt_plan::METRIC
 static_assert(rs::VTO_METRIC_WRAPPED == RS_VT_METRIC_WRAPPED && rs::VTO_METRIC_SAD == RS_VT_METRIC_SAD,
               "vt_offset_rule.h restates the ABI's metric codes");
 #include "vt_offset.h"
+#include "vt_norm.h"
 
 #include "vt_planes.h"
 #include "vt_plane_scan.h"
@@ -187,6 +189,14 @@ struct rs_vt {
     rs::PinnedBuf<int64_t> hOffIdx;
     rs::PinnedBuf<uint32_t> hOffProfile;
     rs::PinnedBuf<int32_t> hOffOffset;
+    // patch normalisation (rs_vt_set_normalise, vt_norm.h): radius 0 is off.  On a normalising
+    // handle every raw image is normalised on its way in, so dQraw, the library and dOffQ
+    // hold normalised bytes only; these buffers take the raw bytes first and are reserved
+    // on such a handle alone
+    int radius = 0, gain = 0;
+    rs::DevBuf<uint8_t> dNormRaw;     // (with qCap) raw uploads and gathers, normalised into dQraw
+    rs::DevBuf<uint8_t> dNormStream;  // rs_vt_match_stream: a call's normalised queries (fused, host groups)
+    rs::DevBuf<uint8_t> dOffRaw;      // rs_vt_offset_profile: raw host queries, normalised into dOffQ
 };
 
 namespace {
@@ -260,6 +270,7 @@ int vt_grow_queries(rs_vt* h, int nq) {
         if (h->prune) RS_TRY(h->dQc.reserve((size_t)QC_Q4 * 4 * n));
     }
     RS_TRY(h->dQraw.reserve(qb * n));
+    if (h->radius > 0) RS_TRY(h->dNormRaw.reserve(qb * n));
     RS_TRY(h->hQraw.reserve(qb * n, VT_FINE));
     RS_TRY(h->dQf.reserve((size_t)h->WD * h->H * n));
     RS_TRY(h->dQsum.reserve(n));
@@ -338,6 +349,17 @@ uint32_t* vt_compact_for(rs_vt* h, const QueryForms& q, int nq) {
     return compact ? q.qc : nullptr;
 }
 
+// Normalise n raw images at src (device memory, or pinned memory by its device address) into
+// dst on the handle's stream: the only launch of vt_normalise_kernel, for handles with
+// radius > 0.
+int vt_normalise(rs_vt* h, const uint8_t* src, uint8_t* dst, size_t n) {
+    const int tx = (h->W + VTN_T - 1) / VTN_T, ty = (h->H + VTN_T - 1) / VTN_T;
+    hipLaunchKernelGGL(vt_normalise_kernel, dim3((unsigned)(tx * ty), (unsigned)std::min<size_t>(n, 65535)),
+                       dim3(VTN_THREADS), 0, h->stream, src, dst, (int)n, h->H, h->W, h->radius, h->gain, tx);
+    RS_HIP(hipGetLastError());
+    return RS_OK;
+}
+
 // RS_VT_ZC=0: no batch is read in place from the pinned staging array (vt_plan::stages_in_place).
 bool vt_zc_env() { static const bool on = rs::env_on("RS_VT_ZC"); return on; }
 
@@ -347,6 +369,11 @@ int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
     RS_TRY(vt_qraw_idle(h));
     const QueryForms q = vt_batch_view(h);
     const size_t qb = (size_t)h->H * h->W * nq;
+    if (h->radius > 0) {   // raw bytes into the handle's own buffer, normalised into dQraw
+        RS_HIP(hipMemcpyAsync(h->dNormRaw.get(), queries, qb, hipMemcpyHostToDevice, h->stream));
+        RS_TRY(vt_normalise(h, h->dNormRaw.get(), h->dQraw.get(), (size_t)nq));
+        return vt_build_forms(h, q, nq);
+    }
     // larger batches: HIP's own upload of the caller's (pageable) array, which returns
     // once the bytes are staged (per-batch PCIe-inclusive rate 4.04-4.12 against 3.44-3.54
     // G compares/s through our memcpy into pinned staging, round 5).  The call waits for
@@ -407,8 +434,10 @@ int vt_stage_frames(rs_vt* h, int nf, const uint8_t* frames) {
         src = h->dFrames.get();
     }
     hipLaunchKernelGGL(vt_gather_kernel, dim3(nf), dim3(256), 0, h->stream, src,
-                       (size_t)h->frameBytes, h->dPix.get(), h->H * h->W, h->dQraw.get());
+                       (size_t)h->frameBytes, h->dPix.get(), h->H * h->W,
+                       h->radius > 0 ? h->dNormRaw.get() : h->dQraw.get());
     RS_HIP(hipGetLastError());
+    if (h->radius > 0) RS_TRY(vt_normalise(h, h->dNormRaw.get(), h->dQraw.get(), (size_t)nf));
     return vt_build_forms(h, vt_batch_view(h), nf);
 }
 
@@ -883,6 +912,11 @@ int vt_grow_stream_forms(rs_vt* h, size_t total) {
 int vt_stream_fused(rs_vt* h, size_t total, const uint8_t* queries, int64_t lc) {
     RS_TRY(vt_grow_stream_forms(h, total));
     const QueryForms q = vt_stream_view(h, 0);
+    if (h->radius > 0) {   // the caller's batches stay as they are
+        RS_TRY(h->dNormStream.reserve((size_t)h->H * h->W * total));
+        RS_TRY(vt_normalise(h, queries, h->dNormStream.get(), total));
+        queries = h->dNormStream.get();
+    }
     RS_TRY(vt_build_forms(h, q, (int)total, queries));
     const ScanOut out{h->dStream.get(), nullptr, 0};
     RS_TRY(vt_timed_scan(h, h->timing, [&] {
@@ -899,6 +933,7 @@ int vt_stream_host_groups(rs_vt* h, int nb, int nq, const uint8_t* queries, int6
     const size_t total = (size_t)nb * nq, qb = (size_t)h->H * h->W * nq;
     RS_TRY(vt_grow_stream_forms(h, total));
     const vt_plan::HostGroups plan = vt_plan::host_groups(nb);
+    if (h->radius > 0) RS_TRY(h->dNormStream.reserve(qb * nb));
     if (!h->ustream) {
         RS_HIP(hipStreamCreateWithFlags(&h->ustream, hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) {
@@ -921,7 +956,13 @@ int vt_stream_host_groups(rs_vt* h, int nb, int nq, const uint8_t* queries, int6
         RS_HIP(hipEventRecord(h->evUp[bi], h->ustream));
         RS_HIP(hipStreamWaitEvent(h->stream, h->evUp[bi], 0));
         const QueryForms q = vt_stream_view(h, (size_t)grp.b0 * nq);
-        RS_TRY(vt_build_forms(h, q, grp.n * nq, h->dUp[bi].get()));
+        const uint8_t* src = h->dUp[bi].get();
+        if (h->radius > 0) {   // each group into its own part of dNormStream
+            uint8_t* const dn = h->dNormStream.get() + qb * grp.b0;
+            RS_TRY(vt_normalise(h, src, dn, (size_t)grp.n * nq));
+            src = dn;
+        }
+        RS_TRY(vt_build_forms(h, q, grp.n * nq, src));
         RS_HIP(hipEventRecord(h->evUsed[bi], h->stream));
         const ScanOut out{h->dStream.get() + (size_t)grp.b0 * nq, nullptr, 0};
         RS_TRY(vt_launch_scan<false>(h, q, false, lc, grp.n * nq, out, h->rank, h->nranks));
@@ -941,7 +982,12 @@ int vt_stream_per_batch(rs_vt* h, int nb, int nq, const uint8_t* queries, bool o
         const ScanOut out{keys, nullptr, 0};
         const uint8_t* src = queries + qb * b;
         if (!on_device) {
-            RS_HIP(hipMemcpyAsync(h->dQraw.get(), src, qb, hipMemcpyHostToDevice, h->stream));
+            uint8_t* const up = h->radius > 0 ? h->dNormRaw.get() : h->dQraw.get();
+            RS_HIP(hipMemcpyAsync(up, src, qb, hipMemcpyHostToDevice, h->stream));
+            src = up;
+        }
+        if (h->radius > 0) {   // (a device batch is read where it is and left as it is)
+            RS_TRY(vt_normalise(h, src, h->dQraw.get(), (size_t)nq));
             src = h->dQraw.get();
         }
         RS_TRY(vt_build_forms(h, vt_batch_view(h), nq, src));
@@ -1159,15 +1205,16 @@ int rs_vt_add(rs_vt* h, int n, const uint8_t* templates, int64_t* first_index) {
                             (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeDevice ||
                              attr.type == hipMemoryTypeManaged);
     (void)hipGetLastError();  // a pageable pointer is not an error
-    RS_HIP(hipMemcpyAsync(h->dQraw.get(), templates, qb,
+    RS_HIP(hipMemcpyAsync(h->radius > 0 ? h->dNormRaw.get() : h->dQraw.get(), templates, qb,
                           attr.type == hipMemoryTypeDevice && direct_dma ? hipMemcpyDeviceToDevice
                                                                          : hipMemcpyHostToDevice,
                           h->stream));
+    int s = h->radius > 0 ? vt_normalise(h, h->dNormRaw.get(), h->dQraw.get(), (size_t)n) : RS_OK;
     h->stagedQ = 0;  // the staging buffer now holds templates, not a query batch
     std::vector<std::pair<int, int64_t>> news;
     news.reserve(n);
     for (int i = 0; i < n; ++i) news.emplace_back(i, h->count + i);
-    const int s = vt_append_staged(h, news);   // (its copies guarded by vt_staging_idle, not a sync)
+    if (s == RS_OK) s = vt_append_staged(h, news);   // (its copies guarded by vt_staging_idle, not a sync)
     // (on the error path as well: the upload above is queued either way)
     if (direct_dma) {
         const hipError_t e = hipStreamSynchronize(h->stream);
@@ -1281,6 +1328,48 @@ int rs_vt_set_shard(rs_vt* h, int rank, int nranks) {
     return RS_OK;
 }
 
+int rs_vt_set_normalise(rs_vt* h, int radius, int gain) {
+    rs::clear_error();
+    RS_CHECK(h, RS_ERR_STATE, "null view-template handle");
+    RS_CHECK(radius >= 0 && radius <= rs::VTN_MAX_RADIUS, RS_ERR_ARG, "radius %d outside [0, %d]", radius,
+             rs::VTN_MAX_RADIUS);
+    RS_CHECK(radius == 0 || (gain >= 1 && gain <= rs::VTN_MAX_GAIN), RS_ERR_ARG, "gain %d outside [1, %d]", gain,
+             rs::VTN_MAX_GAIN);
+    // a library or a staged batch of the other kind of bytes must not meet the new setting
+    RS_CHECK(h->count == 0 && h->stagedQ == 0, RS_ERR_STATE,
+             "set the normalisation before adding templates or staging a batch");
+    RS_HIP(hipSetDevice(h->device));
+    if (radius > 0) {
+        RS_TRY(h->dNormRaw.reserve((size_t)h->H * h->W * h->qCap));
+    } else {
+        RS_HIP(hipStreamSynchronize(h->stream));   // (queued work may still read them)
+        h->dNormRaw.reset();
+        h->dNormStream.reset();
+        h->dOffRaw.reset();
+    }
+    h->radius = radius;
+    h->gain = radius > 0 ? gain : 0;
+    return RS_OK;
+}
+
+int rs_vt_normalise(const rs_vt* h, int* radius, int* gain) {
+    RS_CHECK(h, RS_ERR_STATE, "null view-template handle");
+    if (radius) *radius = h->radius;
+    if (gain) *gain = h->gain;
+    return RS_OK;
+}
+
+int rs_vt_normalise_host(int H, int W, int radius, int gain, const uint8_t* src, uint8_t* dst) {
+    rs::clear_error();
+    RS_CHECK(H > 0 && W > 0 && H <= 4096 && W <= 4096, RS_ERR_ARG, "bad image shape (%d, %d)", H, W);
+    RS_CHECK(radius >= 1 && radius <= rs::VTN_MAX_RADIUS, RS_ERR_ARG, "radius %d outside [1, %d]", radius,
+             rs::VTN_MAX_RADIUS);
+    RS_CHECK(gain >= 1 && gain <= rs::VTN_MAX_GAIN, RS_ERR_ARG, "gain %d outside [1, %d]", gain, rs::VTN_MAX_GAIN);
+    RS_CHECK(src && dst && src != dst, RS_ERR_ARG, "null or aliased image");
+    rs::vtn_normalise_host(H, W, radius, gain, src, dst);
+    return RS_OK;
+}
+
 int rs_vt_rank(const rs_vt* h, int* rank, int* nranks) {
     RS_CHECK(h, RS_ERR_STATE, "null view-template handle");
     if (rank) *rank = h->rank;
@@ -1337,10 +1426,21 @@ int rs_vt_offset_profile(rs_vt* h, int nq, const uint8_t* queries, const int64_t
     RS_TRY(h->hOffProfile.reserve(rs::grown<size_t>(h->hOffProfile.capacity(), n * no, 64 * no), VT_FINE));
     RS_TRY(h->hOffOffset.reserve(rs::grown<size_t>(h->hOffOffset.capacity(), n, 64), VT_FINE));
     const uint8_t* src = h->dQraw.get();
-    if (queries && rs::on_device(queries)) {
+    const size_t offq = rs::grown<size_t>(h->dOffQ.capacity(), qb, 64 * (size_t)h->H * h->W);
+    if (queries && h->radius > 0) {   // raw queries, host or device, normalised into dOffQ
+        RS_TRY(h->dOffQ.reserve(offq));
+        const uint8_t* raw = queries;
+        if (!rs::on_device(queries)) {
+            RS_TRY(h->dOffRaw.reserve(h->dOffQ.capacity()));
+            RS_HIP(hipMemcpyAsync(h->dOffRaw.get(), queries, qb, hipMemcpyHostToDevice, h->stream));
+            raw = h->dOffRaw.get();
+        }
+        RS_TRY(vt_normalise(h, raw, h->dOffQ.get(), n));
+        src = h->dOffQ.get();
+    } else if (queries && rs::on_device(queries)) {
         src = queries;   // read in place
     } else if (queries) {
-        RS_TRY(h->dOffQ.reserve(rs::grown<size_t>(h->dOffQ.capacity(), qb, 64 * (size_t)h->H * h->W)));
+        RS_TRY(h->dOffQ.reserve(offq));
         RS_HIP(hipMemcpyAsync(h->dOffQ.get(), queries, qb, hipMemcpyHostToDevice, h->stream));
         src = h->dOffQ.get();
     }

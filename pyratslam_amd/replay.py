@@ -119,14 +119,18 @@ class RatslamReplay:
                  odom_freq=ODOM_FREQ, feedback_energy=None, pcn=None, vts=None, em=None,
                  device=0, precision='float32', batch=True, publish=False,
                  use_visual_odometry=False, vo=None, subcell_peak=False, window=1, vt_metric='wrapped',
-                 view_shift=False, view_fov=None):
-        """``view_shift``: the view templates are stored column-major (``shift_axis='cols'``) and
+                 view_shift=False, view_fov=None, vt_normalise=None):
+        """``vt_normalise``: None, or ``(radius, gain)``: the view templates are patch-normalised
+        on the GPU (``ViewTemplates(normalise=...)``), against a change of exposure between visits.
+        ``view_shift``: the view templates are stored column-major (``shift_axis='cols'``) and
         every match's row offset is recorded (``results()['view_offset']``) and passed to a
         linked map as ``rel_rad = offset * x_step * view_fov / im_width``: one template row is
         ``x_step`` image columns, and a frame of ``im_width`` columns spans ``view_fov``, the
         camera's horizontal field of view in radians.  Its sign is the camera's handedness:
         positive where a larger heading moves the view towards larger image columns, as in
         ``synthetic.ros_stream`` (+pi/2: a larger heading gives a positive offset there)."""
+        from .view_templates import _normalise_arg
+        vt_normalise = _normalise_arg(vt_normalise)     # (a ValueError before anything is created)
         # publish: the node's per-step work in full -- every update reads the whole
         # .posecells volume, as ros_simulate.py:140-145 does to publish it -- so steps
         # go one by one (no batched run()) and the network exports eagerly
@@ -143,17 +147,21 @@ class RatslamReplay:
             shift = {'shift_axis': 'cols', 'offsets': True} if self.view_shift else {}
             vts = ViewTemplates(x_range=x_range, y_range=y_range, x_step=x_step, y_step=y_step,
                                 im_x=im_size[0], im_y=im_size[1], match_threshold=match_threshold,
-                                device=device, metric=vt_metric, **shift)
+                                device=device, metric=vt_metric, normalise=vt_normalise, **shift)
         elif self.view_shift and not (getattr(vts, 'offsets', False)
                                       and getattr(vts, 'shift_axis', 'rows') == 'cols'):
             raise ValueError("view_shift needs view templates built with shift_axis='cols', offsets=True")
         elif getattr(vts, 'metric', vt_metric) != vt_metric:
             raise ValueError('vt_metric=%r, but the view templates passed in score by %r'
                              % (vt_metric, vts.metric))
+        elif getattr(vts, 'normalise', vt_normalise) != vt_normalise:
+            raise ValueError('vt_normalise=%r, but the view templates passed in normalise by %r'
+                             % (vt_normalise, vts.normalise))
         # the metric of the default uint8 library ('wrapped': the reference's numpy arithmetic on
         # mono8 frames; 'sad': true |T - Q|, for two-sided camera noise -- with a threshold of
         # its own, the shipped 45000 sits on the wrapped metric's noise floor)
         self.vt_metric = vt_metric
+        self.vt_normalise = vt_normalise
         self.pcn, self.vts = pcn, vts
         # radians per template row, and the offsets of the frames so far
         self.rad_per_row = float(x_step) * float(view_fov) / float(im_size[1]) if self.view_shift else 0.0
@@ -461,7 +469,8 @@ def _takes_injections(pcn):
 
 
 def sharded_templates(d, device, host_reduce=False, x_range=X_RANGE, y_range=Y_RANGE, x_step=X_STEP,
-                      y_step=Y_STEP, im_size=IM_SIZE, match_threshold=MATCH_THRESHOLD, metric='wrapped'):
+                      y_step=Y_STEP, im_size=IM_SIZE, match_threshold=MATCH_THRESHOLD, metric='wrapped',
+                      normalise=None):
     """The view-template library sharded over the ranks of ``d`` (a dist.Dist):
     template g on rank g % N, one RCCL allreduce(min) per match (or the host
     reducer of the control plane with ``host_reduce``, for several ranks on one
@@ -470,11 +479,27 @@ def sharded_templates(d, device, host_reduce=False, x_range=X_RANGE, y_range=Y_R
     if host_reduce:
         return ShardedViewTemplates(x_range, y_range, x_step, y_step, im_size[0], im_size[1],
                                     match_threshold, d.rank, d.world, reducer=d.min_keys, device=device,
-                                    metric=metric)
+                                    metric=metric, normalise=normalise)
     uid = d.bcast_bytes(ShardedViewTemplates.unique_id() if d.rank == 0 else None)
     return ShardedViewTemplates(x_range, y_range, x_step, y_step, im_size[0], im_size[1],
                                 match_threshold, d.rank, d.world, reducer='rccl', unique_id=uid,
-                                device=device, metric=metric)
+                                device=device, metric=metric, normalise=normalise)
+
+
+VT_NORMALISE_GAIN = 32   # --vt-normalise R: the gain when only the radius is given
+
+
+def parse_vt_normalise(text):
+    """``R`` or ``R,G`` of ``--vt-normalise`` -> ``(radius, gain)``."""
+    from .view_templates import _normalise_arg
+    parts = text.split(',')
+    try:
+        if len(parts) not in (1, 2):
+            raise ValueError(text)
+        value = (int(parts[0]), int(parts[1]) if len(parts) == 2 else VT_NORMALISE_GAIN)
+        return _normalise_arg(value)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError('expected R or R,G with R in 1..7 and G in 1..127 (%s)' % e)
 
 
 def build_parser():
@@ -520,6 +545,12 @@ def build_parser():
                          'arithmetic on mono8 frames, sum((T - Q) mod 256), where a pixel one grey '
                          'level above its template scores 255; "sad" is the true sum of |T - Q|, '
                          'for cameras with two-sided noise.  Choose --match-threshold with it')
+    ap.add_argument('--vt-normalise', type=parse_vt_normalise, default=None, metavar='R[,G]',
+                    help='patch-normalise the uint8 view templates on the GPU, against a change of '
+                         'exposure between visits: every pixel in units of the standard deviation '
+                         'of its (2R+1)^2 neighbourhood, G grey levels per unit around 128 (R in '
+                         '1..7, G in 1..127, default %d).  Choose --match-threshold with it'
+                         % VT_NORMALISE_GAIN)
     ap.add_argument('--match-threshold', type=float, default=MATCH_THRESHOLD, metavar='T',
                     help='a frame whose best score exceeds T becomes a new template (default %d, '
                          'the reference\'s, which sits on the wrapped metric\'s noise floor: under '
@@ -545,7 +576,7 @@ def main(argv=None):
     d = Dist(args.gpus)
     dev = d.local if args.device is None else args.device
     vts = (sharded_templates(d, dev, args.host_reduce, match_threshold=args.match_threshold,
-                             metric=args.vt_metric) if d.world > 1 else None)
+                             metric=args.vt_metric, normalise=args.vt_normalise) if d.world > 1 else None)
     em = None
     if args.loop_closure:
         from .linked_experience_map import EXP_LOOPS, LinkedExperienceMap
@@ -553,7 +584,8 @@ def main(argv=None):
                                  device=dev)
     r = RatslamReplay(device=dev, precision=args.precision, feedback_energy=args.feedback, vts=vts,
                       use_visual_odometry=args.visual_odometry, em=em, subcell_peak=args.subcell_peak,
-                      window=args.window, vt_metric=args.vt_metric, match_threshold=args.match_threshold,
+                      window=args.window, vt_metric=args.vt_metric, vt_normalise=args.vt_normalise,
+                      match_threshold=args.match_threshold,
                       view_shift=args.view_shift,
                       view_fov=(math.pi / 2 if args.view_fov is None else args.view_fov) if args.view_shift else None)
     d.barrier()

@@ -19,6 +19,12 @@ rows), and ``ViewTemplates(..., offsets=True)`` records both after every uint8 m
 the robot moves the view along image columns, so ``shift_axis='cols'`` stores the templates
 column-major (transposed) and the offset then means a heading.
 
+``ViewTemplates(..., normalise=(radius, gain))`` patch-normalises every uint8 template and query
+on the GPU on its way into the library (``rs_vt_set_normalise``): each pixel
+in units of its neighbourhood's standard deviation, so that a place seen again under another
+exposure still matches.  The library, ``ViewTemplate.template`` and every score then are of
+normalised bytes (``normalise_u8`` is the rule in NumPy); float frames are a ``TypeError``.
+
 Frames are ``uint8`` on the ROS path (``ros_simulate.py:100-101``): the library
 then lives on the GPU and a score wraps mod 256 like numpy's uint8 subtraction.
 float32 / float64 frames follow the reference's float semantics instead (a true
@@ -126,6 +132,76 @@ def refine_offset(profile):
     return o + 0.5 * (p[k - 1] - p[k + 1]) / den
 
 
+MAX_NORM_RADIUS, MAX_NORM_GAIN = 7, 127   # rs_vt_set_normalise's ranges (csrc/vt_norm_rule.h)
+
+
+def _normalise_arg(normalise):
+    """``normalise=None`` or ``(radius, gain)`` -> None or a tuple of two checked ints (a
+    ValueError before anything is created)."""
+    if normalise is None:
+        return None
+    try:
+        radius, gain = normalise
+        ok = int(radius) == radius and int(gain) == gain
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not 1 <= radius <= MAX_NORM_RADIUS or not 1 <= gain <= MAX_NORM_GAIN:
+        raise ValueError('normalise=%r: expected None or (radius in [1, %d], gain in [1, %d])'
+                         % (normalise, MAX_NORM_RADIUS, MAX_NORM_GAIN))
+    return int(radius), int(gain)
+
+
+def _u8_images(images, what):
+    a = np.asarray(images)
+    if a.dtype != np.uint8:
+        raise TypeError('%s takes uint8 images, got %s' % (what, a.dtype))
+    if a.ndim not in (2, 3):
+        raise ValueError('%s takes (H, W) or (n, H, W) images, got shape %r' % (what, a.shape))
+    return a
+
+
+def normalise_u8(images, radius, gain):
+    """Patch normalisation restated in NumPy (the rule of csrc/vt_norm_rule.h, DESIGN section
+    33) for (H, W) or (n, H, W) uint8 images: each pixel in units of the standard deviation of
+    its (2 radius + 1)^2 window, clamped to the image, ``gain`` grey levels per unit around
+    128.  Summed-area window sums, integer arithmetic throughout, the square root brought to
+    the exact floor by an integer step either way."""
+    R, G = _normalise_arg((radius, gain))
+    a = _u8_images(images, 'normalise_u8')
+    p = a.reshape((-1,) + a.shape[-2:]).astype(np.int64)
+    n_img, h, w = p.shape
+    r0, r1 = np.maximum(np.arange(h) - R, 0)[:, None], (np.minimum(np.arange(h) + R, h - 1) + 1)[:, None]
+    c0, c1 = np.maximum(np.arange(w) - R, 0)[None, :], (np.minimum(np.arange(w) + R, w - 1) + 1)[None, :]
+
+    def window_sum(x):
+        sat = np.zeros((n_img, h + 1, w + 1), dtype=np.int64)
+        sat[:, 1:, 1:] = x.cumsum(axis=1).cumsum(axis=2)
+        return sat[:, r1, c1] - sat[:, r0, c1] - sat[:, r1, c0] + sat[:, r0, c0]
+
+    n = (r1 - r0) * (c1 - c0)
+    S, S2 = window_sum(p), window_sum(p * p)
+    D, N = n * S2 - S * S, n * p - S
+    s = np.sqrt(D.astype(np.float64)).astype(np.int64)
+    s -= s * s > D                     # the float estimate, then s^2 <= D < (s + 1)^2
+    s += (s + 1) * (s + 1) <= D
+    q = (G * np.abs(N) + s // 2) // np.maximum(s, 1)
+    out = np.where(s == 0, 128, np.clip(128 + np.sign(N) * q, 0, 255))
+    return out.astype(np.uint8).reshape(a.shape)
+
+
+def normalise_host(images, radius, gain):
+    """The same rule by the library's own host code (rs_vt_normalise_host: no device)."""
+    R, G = _normalise_arg((radius, gain))
+    a = np.ascontiguousarray(_u8_images(images, 'normalise_host'))
+    out = np.empty_like(a)
+    lib = _lib.load()
+    src, dst = a.reshape((-1,) + a.shape[-2:]), out.reshape((-1,) + a.shape[-2:])
+    for i in range(src.shape[0]):
+        _lib.check(lib.rs_vt_normalise_host(a.shape[-2], a.shape[-1], R, G, _lib.ptr(src[i], ctypes.c_uint8),
+                                            _lib.ptr(dst[i], ctypes.c_uint8)))
+    return out
+
+
 def _metric_code(metric):
     if metric not in METRICS:
         raise ValueError('unknown metric %r: expected one of %s' % (metric, sorted(METRICS)))
@@ -181,11 +257,18 @@ class ViewTemplate:
         q = np.ascontiguousarray(new_template)
         t = np.asarray(self.template)
         dev = self._owner.device if self._owner is not None else 0
+        norm = self._owner.normalise if self._owner is not None else None
+        if norm is not None:
+            self._owner._normalise_take(q)
         if t.dtype != np.uint8 or q.dtype != np.uint8:
             return sad_scores(t[None], q[None], self.max_offset, dev)[0, 0]
         owner = self._owner
         if owner is not None and owner.nranks == 1 and not owner._float:
-            return owner.scores(q[None], self.index, 1)[0, 0]
+            return owner.scores(q[None], self.index, 1)[0, 0]   # (a normalising owner normalises q)
+        if norm is not None:
+            # self.template holds normalised bytes already, and the helper library below is a
+            # plain one: q is normalised here, once
+            q = normalise_host(q, *norm)
         if self._solo is None:
             t = np.ascontiguousarray(t)
             self._solo = ViewTemplates._from_shape(t.shape, np.inf, device=dev,
@@ -206,13 +289,17 @@ class ViewTemplates:
     """Library of view templates on one GPU (view_templates.py:40-75)."""
 
     def __init__(self, x_range, y_range, x_step, y_step, im_x, im_y, match_threshold,
-                 device=0, capacity=1024, metric='wrapped', offsets=False, shift_axis='rows'):
+                 device=0, capacity=1024, metric='wrapped', offsets=False, shift_axis='rows', normalise=None):
         """``offsets``: record the row offset and the profile of every uint8 match call
         (``last_offsets``, ``last_profiles``).  ``shift_axis``: ``'rows'`` shifts along the
         gathered template's rows as the reference does; ``'cols'`` stores every template
-        transposed, so that the offset runs along image columns (``x_step`` columns a row)."""
+        transposed, so that the offset runs along image columns (``x_step`` columns a row).
+        ``normalise``: None, or ``(radius, gain)`` for patch normalisation on the GPU
+        (``normalise_u8``): every uint8 template and query is normalised on its way in, the
+        library compares normalised bytes, and float frames are a TypeError."""
+        normalise = _normalise_arg(normalise)
         self._set_geometry(x_range, y_range, x_step, y_step, im_x, im_y, shift_axis)
-        self._init_device(self.shape, match_threshold, device, capacity, metric, offsets)
+        self._init_device(self.shape, match_threshold, device, capacity, metric, offsets, normalise)
 
     def _set_geometry(self, x_range, y_range, x_step, y_step, im_x, im_y, shift_axis='rows'):
         """The mask and the stored template shape (host only; a ValueError before any device work)."""
@@ -225,17 +312,22 @@ class ViewTemplates:
         return self
 
     @classmethod
-    def _from_shape(cls, shape, match_threshold, device=0, capacity=64, metric='wrapped', offsets=False):
+    def _from_shape(cls, shape, match_threshold, device=0, capacity=64, metric='wrapped', offsets=False,
+                    normalise=None):
         self = cls.__new__(cls)
         self.mask = None
         self.shape = tuple(int(s) for s in shape)
-        self._init_device(self.shape, match_threshold, device, capacity, metric, offsets)
+        self._init_device(self.shape, match_threshold, device, capacity, metric, offsets, normalise)
         return self
 
     shift_axis = 'rows'
 
-    def _init_device(self, shape, match_threshold, device, capacity, metric='wrapped', offsets=False):
+    normalise = None
+
+    def _init_device(self, shape, match_threshold, device, capacity, metric='wrapped', offsets=False,
+                     normalise=None):
         code = _metric_code(metric)      # (a ValueError before anything is created)
+        normalise = _normalise_arg(normalise)
         self.metric = metric
         self.offsets = bool(offsets)
         self.last_offsets = self.last_profiles = None
@@ -263,6 +355,9 @@ class ViewTemplates:
         # `min(match_val) > match_threshold` (view_templates.py:67), compared in float64 as
         # numpy compares the uint64 score with a Python number (inf: never, < 0: always)
         _lib.check(self._lib.rs_vt_set_threshold(h, float(match_threshold)))
+        if normalise is not None:
+            _lib.check(self._lib.rs_vt_set_normalise(h, normalise[0], normalise[1]))
+        self.normalise = normalise
 
     # -- lifetime ---------------------------------------------------------------
     def close(self):
@@ -330,6 +425,17 @@ class ViewTemplates:
         else:
             _lib.check(self._lib.rs_vt_count(self._h, ctypes.byref(c)))
         return c.value
+
+    def _normalise_take(self, arrays):
+        # a normalising library compares normalised bytes: a float frame would leave the
+        # uint8 device path (module doc), so it is refused before that path is chosen
+        if self.normalise is not None and np.asarray(arrays).dtype != np.uint8:
+            raise TypeError('normalise=%r normalises uint8 frames only; got %s'
+                            % (self.normalise, np.asarray(arrays).dtype))
+
+    def _stored(self, t):
+        """The bytes the library keeps of raw uint8 template(s) ``t``: ``ViewTemplate.template``."""
+        return t if self.normalise is None else normalise_host(t, *self.normalise)
 
     def _refuse_float(self, what):
         # after a float frame the Python template list holds templates the uint8 device
@@ -430,6 +536,7 @@ class ViewTemplates:
     def add(self, templates, locations=None):
         """Append templates unconditionally (indices len .. len+n-1)."""
         self._offsets_take(templates)
+        self._normalise_take(templates)
         if self._use_resident(templates):
             t = self._check_float(templates, 'add()')
             first = ctypes.c_int64()
@@ -447,6 +554,7 @@ class ViewTemplates:
         with self._mutex:
             _lib.check(self._lib.rs_vt_add(self._h, t.shape[0], _lib.ptr(t, ctypes.c_uint8),
                                            ctypes.byref(first)))
+            t = self._stored(t)
             for i in range(t.shape[0]):
                 loc = locations[i] if locations is not None else (0, 0, 0)
                 self.templates.append(ViewTemplate(loc[0], loc[1], loc[2], first.value + i, t[i],
@@ -456,6 +564,7 @@ class ViewTemplates:
     def scores(self, queries, t0=0, nt=None):
         """(nq, nt) scores of queries vs templates [t0, t0+nt) -- ViewTemplate.match:
         uint64 on a uint8 library, the library's dtype on a float-resident one."""
+        self._normalise_take(queries)
         if self._use_resident(queries):
             q = self._check_float(queries, 'scores()')
             nt = self.count() - t0 if nt is None else nt
@@ -539,7 +648,7 @@ class ViewTemplates:
             if new[i]:
                 assert idx[i] == len(self.templates), (idx[i], len(self.templates))
                 p = pcs[i]
-                self.templates.append(ViewTemplate(p[0], p[1], p[2], int(idx[i]), q[i].copy(),
+                self.templates.append(ViewTemplate(p[0], p[1], p[2], int(idx[i]), self._stored(q[i]).copy(),
                                                    _owner=self))
         return [self.templates[int(j)] for j in idx]
 
@@ -548,6 +657,7 @@ class ViewTemplates:
         On a float-resident library the queries and scores have the library's dtype
         (+inf where the library was empty)."""
         self._offsets_take(queries)
+        self._normalise_take(queries)
         if self._use_resident(queries):
             q = self._check_float(queries, 'match_templates()')
             n = q.shape[0]
@@ -615,6 +725,7 @@ class ViewTemplates:
         """Best template for a frame, or a new one (view_templates.py:63-75)."""
         t = self.subsample(input)
         self._offsets_take(t)
+        self._normalise_take(t)
         if self._resident_for(t.dtype):
             with self._mutex:
                 idx, _, _ = self._resident_match(np.ascontiguousarray(t)[None], [(pc_x, pc_y, pc_th)])
@@ -631,6 +742,7 @@ class ViewTemplates:
             return []
         for x in q:
             self._offsets_take(x)
+            self._normalise_take(x)
         if all(x.dtype == q[0].dtype for x in q) and self._resident_for(q[0].dtype):
             with self._mutex:
                 idx, _, _ = self._resident_match(np.stack(q), pcs)
@@ -726,7 +838,7 @@ class ViewTemplates:
                             else:
                                 t = None
                         else:
-                            t = self.subsample(f[i])
+                            t = self._stored(self.subsample(f[i]))
                         p = pcs[i]
                         assert idx[i] == len(self.templates), (idx[i], len(self.templates))
                         self.templates.append(ViewTemplate(p[0], p[1], p[2], int(idx[i]), t,
@@ -791,19 +903,21 @@ class ShardedViewTemplates(ViewTemplates):
 
     def __init__(self, x_range, y_range, x_step, y_step, im_x, im_y, match_threshold,
                  rank, nranks, reducer='rccl', unique_id=None, device=0, capacity=1024, metric='wrapped',
-                 offsets=False):
+                 offsets=False, normalise=None):
         self._no_offsets(offsets)
+        normalise = _normalise_arg(normalise)
         self.mask, self.shape = py2_mask(x_range, y_range, x_step, y_step, im_x, im_y)
-        self._init_device(self.shape, match_threshold, device, capacity, metric)
+        self._init_device(self.shape, match_threshold, device, capacity, metric, normalise=normalise)
         self._attach(rank, nranks, reducer, unique_id)
 
     @classmethod
     def from_shape(cls, shape, match_threshold, rank, nranks, reducer='rccl', unique_id=None,
-                   device=0, capacity=1024, metric='wrapped', offsets=False):
+                   device=0, capacity=1024, metric='wrapped', offsets=False, normalise=None):
         cls._no_offsets(offsets)
+        normalise = _normalise_arg(normalise)
         self = cls.__new__(cls)
         self.mask = None
-        self._init_device(shape, match_threshold, device, capacity, metric)
+        self._init_device(shape, match_threshold, device, capacity, metric, normalise=normalise)
         self._attach(rank, nranks, reducer, unique_id)
         return self
 
@@ -839,6 +953,7 @@ class ShardedViewTemplates(ViewTemplates):
     def match_templates(self, queries, pcs=None, mode=_lib.RS_VT_SEQUENTIAL):
         if self.reducer == 'rccl':
             return super().match_templates(queries, pcs, mode)
+        self._normalise_take(queries)
         q = self._check_templates(queries)
         n = q.shape[0]
         local = np.empty(n, dtype=np.uint64)
