@@ -98,22 +98,52 @@ void ro_conv_z(const double* P, const double* zf, double* out, int X, int Y, int
         }
 }
 
+/* numpy.sum of a contiguous float64 array, in numpy's order: up to 128 elements go into
+ * eight accumulators that are added as a tree, more are halved (the first half a multiple
+ * of eight) ... */
+static double np_pairwise(const double* a, size_t n) {
+    if (n < 8) {
+        double res = 0.0;
+        for (size_t i = 0; i < n; ++i) res += a[i];
+        return res;
+    }
+    if (n <= 128) {
+        double r[8];
+        size_t i;
+        for (int j = 0; j < 8; ++j) r[j] = a[j];
+        for (i = 8; i < n - (n % 8); i += 8)
+            for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) res += a[i];
+        return res;
+    }
+    size_t n2 = n / 2;
+    n2 -= n2 % 8;
+    return np_pairwise(a, n2) + np_pairwise(a + n2, n - n2);
+}
+
+/* ... and the array is taken in blocks of numpy's default buffer size, 8192 elements, whose
+ * sums are added up in turn. */
+static double np_sum(const double* a, size_t n) {
+    double total = 0.0;
+    for (size_t i = 0; i < n; i += 8192) total += np_pairwise(a + i, n - i < 8192 ? n - i : 8192);
+    return total;
+}
+
 /* One update (posecell_network.py:326-353).  P is updated in place; tmp has X*Y*TH
- * doubles.  The normalisation total is a plain sequential sum (numpy uses a
- * pairwise sum: results agree to rounding).  Returns the argmax in out_xyz. */
+ * doubles.  The normalisation total is summed in numpy.sum's order (np_sum), so a step is
+ * the NumPy oracle's bit for bit, whatever the thread count.  Returns the argmax in out_xyz. */
 void ro_update(double* P, double* tmp, const double* K, double inhib, const int* ox,
                const int* oy, const double* F, const double* zf, int X, int Y, int TH,
                int* out_xyz) {
     const size_t n = (size_t)X * Y * TH;
     ro_conv3d(P, K, tmp, X, Y, TH);
-    double total = 0;
-#pragma omp parallel for reduction(+ : total) schedule(static)
+#pragma omp parallel for schedule(static)
     for (size_t e = 0; e < n; ++e) {
-        double v = tmp[e];
-        v = v < inhib ? 0.0 : v - inhib;
-        tmp[e] = v;
-        total += v;
+        const double v = tmp[e];
+        tmp[e] = v < inhib ? 0.0 : v - inhib;
     }
+    const double total = np_sum(tmp, n);
     if (total != 0) {
 #pragma omp parallel for schedule(static)
         for (size_t e = 0; e < n; ++e) tmp[e] /= total;

@@ -201,15 +201,16 @@ def mistake_cell(shape):
     return (shape[0] // 3, (2 * shape[1]) // 3, shape[2] // 2)
 
 
-def step(p, k3, inhibition, filters, ox, oy, zf, mistake=None):
+def step(p, k3, inhibition, filters, ox, oy, zf, mistake=None, cell=None):
     """One update in p's precision.  ``filters`` is (7, 7, TH), a filter per layer.  Returns
-    the new state and the total the excited state was divided by."""
+    the new state and the total the excited state was divided by.  ``cell``: where a
+    mistake that has a place is planted (mistake_cell otherwise)."""
     dt = p.dtype.type
     shape = p.shape
     X, Y, TH = shape
     h = P.HALF
     k3, filters, zf = k3.astype(dt), filters.astype(dt), zf.astype(dt)
-    c = mistake_cell(shape)
+    c = mistake_cell(shape) if cell is None else tuple(cell)
     tx, ty = min(TILE, X), min(TILE, Y)
     # excitation
     pp = np.pad(p, h, mode='wrap')

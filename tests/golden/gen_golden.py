@@ -22,7 +22,9 @@ Shims (each is the smallest change that restores the Python-2 meaning):
     ``pyopencl`` whose ``Program.build`` compiles the kernel text with gcc and
     runs each NDRange as a host triple loop.
 
-Usage: python tests/golden/gen_golden.py [--out tests/golden]
+Usage: python tests/golden/gen_golden.py [--out tests/golden] [--only NAME]
+``--only long`` writes the long pose-cell trajectories ``pc_long_*.npz``; it takes about a
+quarter of an hour (see gen_long) and is left out of a run without ``--only``.
 """
 import argparse
 import builtins
@@ -552,11 +554,68 @@ def gen_nonfinite(pn, out):
         builtins.math = saved
 
 
+def gen_long(pn, out, names=None):
+    """Long trajectories (tests/_pc_long.py): the reference itself over 1,000 to 2,000 steps of
+    the benched odometry stream with centre injection, its peak and top-two gap at every step
+    and its state at every 10th; then, from those states, the errors of the project's
+    emulations that the bounds of test_pc_long_gpu.py are made of (e32w, e32f, e64n).
+
+    The reference takes 10 to 70 ms per step.  The emulations run through the NumPy oracle,
+    0.1 to 0.2 s per step at 64x64x36: about eight minutes for that trajectory (3,000
+    emulated steps) and a quarter of an hour for all four one after another (--trajectory
+    makes one, so four processes can share the work).  That is offline work; the tests
+    recompute only a sample."""
+    import time
+    tests = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [os.path.dirname(tests), tests]
+    import _pc_long as L
+    for name in names or L.NAMES:
+        shape, n = L.TRAJECTORIES[name]
+        odom = L.odometry(name)
+        t0 = time.time()
+        net = pn.PoseCellNetwork(shape)
+        loc = tuple(int(math.floor(s / 2)) for s in shape)
+        net.inject(1, loc)
+        states, maxes, gaps = [np.array(net.posecells, dtype=np.float64)], [], []
+        for s, v in enumerate(odom):
+            net.update((float(v[0]), float(v[1])))
+            maxes.append(net.max_pc)
+            gaps.append(L.top_two_gap(net.posecells))
+            if (s + 1) % L.WINDOW == 0:
+                states.append(np.array(net.posecells, dtype=np.float64))
+        cx, cy, cth = L.face_crossings(maxes, shape)
+        print('%s: reference %d steps in %.0f s; face crossings x %d, y %d, theta %d; gaps <= %g: %d'
+              % (name, n, time.time() - t0, cx, cy, cth, L.GAP_MIN, int((np.array(gaps) <= L.GAP_MIN).sum())), flush=True)
+        assert cx >= L.MIN_XY_CROSSINGS and cy >= L.MIN_XY_CROSSINGS, (name, cx, cy)
+        if name.endswith('_turn'):
+            assert cth >= L.MIN_TH_CROSSINGS_TURN, (name, cth)
+        t0 = time.time()
+        e32w = np.array([L.window_e32(states[w], odom[w * L.WINDOW:(w + 1) * L.WINDOW], states[w + 1])
+                         for w in range(n // L.WINDOW)])
+        e32f = L.free_errors(states[0], odom, states.__getitem__, 'e32f')
+        e64n = L.free_errors(states[0], odom, states.__getitem__, 'e64n')
+        print('%s: emulations in %.0f s; e32w max %.2e median %.2e, e32f max %.2e, e64n max %.2e'
+              % (name, time.time() - t0, e32w.max(), np.median(e32w), e32f.max(), e64n.max()), flush=True)
+        parts = [coo(p) for p in states]
+        np.savez_compressed(
+            os.path.join(out, 'pc_long_%s.npz' % name),
+            shape=np.array(shape, dtype=np.int64), inject=np.array(loc, dtype=np.int64), odom=odom,
+            max_pc=np.array(maxes, dtype=np.int32), gap=np.array(gaps),
+            nnz=np.array([len(i) for i, _ in parts], dtype=np.int32),
+            coo_idx=np.concatenate([i for i, _ in parts]).astype(np.int32),
+            coo_val=np.concatenate([x for _, x in parts]),
+            e32w=e32w, e32f=e32f, e64n=e64n)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.dirname(os.path.abspath(__file__)))
     ap.add_argument('--only', choices=['kernels', 'posecell', 'templates', 'float_pairs',
-                                       'ros_replay', 'death', 'nonfinite'])
+                                       'ros_replay', 'death', 'nonfinite', 'long'],
+                    help="'long' (the pc_long_* trajectories) takes about a quarter of an hour, most of it the "
+                         'NumPy emulations at 64x64x36, and runs only when asked for')
+    ap.add_argument('--trajectory', action='append',
+                    help='with --only long: this trajectory only (repeatable; default: all four)')
     args = ap.parse_args()
     pn, vt = load_reference()
     if args.only in (None, 'kernels'):
@@ -573,6 +632,8 @@ def main():
         gen_death(pn, args.out)
     if args.only in (None, 'nonfinite'):
         gen_nonfinite(pn, args.out)
+    if args.only == 'long':
+        gen_long(pn, args.out, args.trajectory)
     print('golden vectors written to', args.out)
 
 
