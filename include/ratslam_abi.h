@@ -457,8 +457,17 @@ const char* rs_vt_scan_form(const rs_vt* h);
  * settled in their candidate block, by verifying one template or by scanning the block
  * (= queries), out[1] = (block, query) pairs of pass B2, out[2] = template blocks x
  * queries, out[3] = scan passes launched; all 0 before the first pruned scan.  Reads the
- * device counters on demand (synchronises the handle's stream); the match calls do not. */
+ * device counters on demand (synchronises the handle's stream); the match calls do not.
+ * RS_VT_PASSES (read at create): "1" (default) the verification writes one list per template
+ * block on its verified score U0 >= U(q), a superset of the two passes' lists, and ONE list
+ * pass scans it; "2" passes B1 and B2.  The statistics are the two-pass
+ * rule's counts in either mode (out[3] == 2): with one pass a counting kernel takes them
+ * on demand from what the call left. */
 int rs_vt_prune_stats(rs_vt* h, int64_t out[4]);
+/* *out = the (block, query) pairs the last pruned scan launch actually scanned: the entries
+ * of its lists (with one pass the lists on U0: at least the two-pass rule's pairs plus the
+ * unsettled queries); 0 before the first pruned scan.  Reads on demand like rs_vt_prune_stats. */
+int rs_vt_prune_scanned(rs_vt* h, int64_t* out);
 /* *out = the queries the last pruned scan launch settled by verification alone (they
  * took no block scan in pass B1); 0 before the first pruned scan.  Reads on demand like
  * rs_vt_prune_stats. */

@@ -150,6 +150,7 @@ SIGNATURES = {
     'rs_vt_scan_form': (ctypes.c_char_p, [_vp]),
     'rs_vt_prune_stats': (ctypes.c_int, [_vp, _i64p]),
     'rs_vt_prune_verified': (ctypes.c_int, [_vp, _i64p]),
+    'rs_vt_prune_scanned': (ctypes.c_int, [_vp, _i64p]),
     'rs_vt_set_threshold': (ctypes.c_int, [_vp, ctypes.c_double]),
     'rs_sad_scores': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp]),
@@ -196,7 +197,7 @@ SIGNATURES = {
 
 # statistics calls an older build of the library lacks: tools/stream_ab.py loads such
 # builds by path for an A/B; calling one of these on them raises AttributeError
-NEWER_SYMBOLS = {'rs_vt_prune_stats', 'rs_vt_prune_verified', 'rs_vt_create_metric', 'rs_vt_metric',
+NEWER_SYMBOLS = {'rs_vt_prune_stats', 'rs_vt_prune_verified', 'rs_vt_prune_scanned', 'rs_vt_create_metric', 'rs_vt_metric',
                  'rs_vt_offset_profile', 'rs_vt_offset_profile_host', 'rs_vt_set_normalise',
                  'rs_vt_normalise', 'rs_vt_normalise_host'}
 

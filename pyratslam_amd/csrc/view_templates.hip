@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "rs_common.h"
@@ -176,6 +177,15 @@ struct rs_vt {
     int64_t prunePairs = 0;          // its ntb * nq
     int prunePasses = 0;             // its scan passes (0: no pruned launch yet)
     int pruneNtb = 0;                // its template blocks (the entries of list2's counters)
+    // the single list pass (RS_VT_PASSES): 1 (default) the front writes the
+    // lists on U0 and one pass scans them, 2 the chain first, B1, rest, B2
+    int passes = 1;
+    int pruneMode = 0;               // the passes the last pruned launch ran with (the statistics' source)
+    int pruneNq = 0;                 // its queries
+    rs::DevBuf<uint32_t> dUblk;      // [nq] U(q): U0 of a settled query, else its candidate block's minimum
+    rs::DevBuf<unsigned> dCntPar;    // [2][cntPar.cap] the single pass's list counters, by call parity
+    vt_plan::ParityCounters cntPar;
+    rs::DevBuf<unsigned long long> dCountAcc;  // rs_vt_prune_stats: the counting kernel's two sums
     // on-device subsampling of camera frames (rs_vt_set_subsample / rs_vt_match_frames)
     rs::DevBuf<int32_t> dPix;  // H*W byte offsets of the kept pixels in a frame
     int64_t frameBytes = 0;
@@ -505,7 +515,7 @@ struct PlaneScan {
     int nq, nqc, rank, nranks;
 };
 template <int H, bool MATRIX, bool LIST>
-void vt_launch_plane_scan(rs_vt* h, const PlaneScan& s, const ScanOut& out, const PlaneList& list) {
+void vt_launch_plane_scan(rs_vt* h, const PlaneScan& s, const ScanOut& out, const PlaneListArg<LIST>& list) {
     hipLaunchKernelGGL((vt_scan_plane_kernel<H, MATRIX, LIST>), s.grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream,
                        s.planes, s.ts, s.ntb, s.count, s.q.qp, s.q.qsum, s.nq, s.nqc, h->dCtr.get(), out, s.rank,
                        s.nranks, list);
@@ -523,6 +533,16 @@ int vt_ensure_prune_buffers(rs_vt* h, int ntb, int nq) {
         h->pruneCap = cap;
     }
     RS_TRY(h->dTbStar.reserve((size_t)nq));  // (exact)
+    RS_TRY(h->dUblk.reserve((size_t)nq));
+    if (vt_plan::parity_grows(h->cntPar, ntb)) {   // zero at first; every call zeroes the other parity's
+        vt_plan::ParityCounters grown = h->cntPar;
+        vt_plan::parity_grown(grown, ntb);
+        h->cntPar = vt_plan::ParityCounters{};
+        RS_TRY(h->dCntPar.reserve(2 * (size_t)grown.cap));
+        RS_HIP(hipMemsetAsync(h->dCntPar.get(), 0, sizeof(unsigned) * 2 * (size_t)grown.cap, h->stream));
+        grown.par = 0;
+        h->cntPar = grown;
+    }
     if (ntb > h->listCntCap) {  // zero at first; the list kernels zero what they are about to fill
         const int cap = std::max(ntb, 2 * h->listCntCap);
         h->listCntCap = 0;
@@ -537,9 +557,10 @@ int vt_ensure_prune_buffers(rs_vt* h, int ntb, int nq) {
     return RS_OK;
 }
 
-// Pruned scan of the frozen library (vt_prunes): prefilter, verification, then the scan of
-// each query's candidate block (list 1, pass B1) and of the blocks its bound leaves (list 2,
-// pass B2).
+// Pruned scan of the frozen library (vt_prunes): prefilter and verification (one launch where
+// vt_plan::front_fused), then one list pass over the lists the verification wrote on U0, or,
+// with two passes (RS_VT_PASSES=2), the scan of each query's candidate block (list 1, pass B1)
+// and of the blocks its bound leaves (list 2, pass B2).
 int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
     const QueryForms& q = s.q;
     const int ntb = s.ntb, nq = s.nq;
@@ -555,24 +576,27 @@ int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
     unsigned* verified = h->dListCnt.get() + 2 * (size_t)h->listCntCap;
     int* list1 = h->dList.get();
     int* list2 = h->dList.get() + pairs;
+    const bool single = vt_plan::prune_passes(h->passes, ntb, nq) == 1;
+    FrontLists fl{};
+    if (single) {
+        const vt_plan::ParityCall pc = vt_plan::parity_begin(h->cntPar, ntb);
+        fl = FrontLists{h->dCntPar.get() + pc.mine, list1, h->dUblk.get(), h->dCntPar.get() + pc.other, pc.nzero};
+    }
     if (h->front == 2 || (h->front == 1 && vt_plan::front_fused(ntb, PF_WAVES * PF_TPW))) {
         const vt_plan::Grid2 fg = vt_plan::front_grid(nq, PF_NB, VT_PF_GRID_CAP);
         hipLaunchKernelGGL(vt_front_kernel, dim3((unsigned)fg.x, (unsigned)fg.y), dim3(64 * PF_WAVES), 0, h->stream,
                            s.planes, ntb, s.count, reinterpret_cast<const uint4*>(q.qc), q.qsj, nq, h->dMinLB.get(),
                            s.ts, reinterpret_cast<uint4*>(q.qp), q.qsum, out.best, s.rank, s.nranks,
-                           h->dTbStar.get());
+                           h->dTbStar.get(), fl);
     } else {
         const vt_plan::Grid2 pf = vt_plan::prefilter_grid(ntb, nq, PF_WAVES * PF_TPW, PF_NB, VT_PF_GRID_CAP);
         hipLaunchKernelGGL(vt_prefilter_kernel, dim3((unsigned)pf.x, (unsigned)pf.y), dim3(64 * PF_WAVES), 0,
                            h->stream, s.planes, ntb, s.count, reinterpret_cast<const uint4*>(q.qc), q.qsj, nq,
-                           h->dMinLB.get(), h->dSecond.get());
+                           h->dMinLB.get(), h->dSecond.get(), fl);
         hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, h->dMinLB.get(),
                            h->dSecond.get(), ntb, nq, s.planes, s.ts, reinterpret_cast<const uint4*>(q.qc),
-                           reinterpret_cast<uint4*>(q.qp), q.qsum, out.best, s.rank, s.nranks, h->dTbStar.get());
+                           reinterpret_cast<uint4*>(q.qp), q.qsum, out.best, s.rank, s.nranks, h->dTbStar.get(), fl);
     }
-    const dim3 lgrid((unsigned)((nq + VT_LIST_T - 1) / VT_LIST_T), (unsigned)ntb);
-    hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar.get(), cnt1,
-                       list1, verified, cnt2, ntb);
     // the passes min into the same keys; the folded export (out.host) needs one
     // launch to be the last, so a pruned call exports with vt_keys_export
     ScanOut po = out;
@@ -581,21 +605,35 @@ int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
     // working blocks per template block that make one resident round (vt_plan::list_width)
     const uint32_t fill = (uint32_t)std::min(65535, std::max(1, h->planeSlots / ntb));
     const uint32_t lnb = (uint32_t)h->listNb;
-    vt_launch_plane_scan<64, false, true>(h, s, po,
-                                          PlaneList{list1, cnt1, nq, (uint32_t)VT_LIST_PER_B1, lnb, 1u, fill});
-    hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB.get(), nq,
-                       h->dTbStar.get(), out.best, cnt2, list2, cnt1, verified, ntb, h->dPruneStat.get());
 #ifdef VT_LIST_PER
     const int per2 = VT_LIST_PER;
 #else
     const int per2 = vt_plan::list_per(ntb, h->planeSlots);
 #endif
-    vt_launch_plane_scan<64, false, true>(h, s, po, PlaneList{list2, cnt2, nq, (uint32_t)per2, lnb, 0u, fill});
+    h->prunePairs = (int64_t)pairs;
+    h->prunePasses = 2;   // (the statistics are the two-pass rule's in either mode)
+    h->pruneNtb = ntb;
+    h->pruneNq = nq;
+    h->pruneMode = single ? 1 : 2;
+    if (single) {   // pass B2's settings over the one list, but its width chosen for four resident
+        // rounds of blocks (vt_plan::single_pass_fill); the candidate block's wave stores U(q)
+        const uint32_t fill1 = (uint32_t)vt_plan::single_pass_fill((int)fill);
+        vt_launch_plane_scan<64, false, true>(
+            h, s, po, PlaneListU{{list1, fl.cnt, nq, (uint32_t)per2, lnb, 0u, fill1}, h->dTbStar.get(), h->dUblk.get()});
+        if (out.host) vt_launch_keys_export(h, out.best, nq, out.host, vt_plan::VT_EXPORT_BLOCKS);
+        RS_HIP(hipGetLastError());
+        return RS_OK;
+    }
+    const dim3 lgrid((unsigned)((nq + VT_LIST_T - 1) / VT_LIST_T), (unsigned)ntb);
+    hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar.get(), cnt1,
+                       list1, verified, cnt2, ntb);
+    vt_launch_plane_scan<64, false, true>(h, s, po,
+                                          PlaneListU{{list1, cnt1, nq, (uint32_t)VT_LIST_PER_B1, lnb, 1u, fill}});
+    hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB.get(), nq,
+                       h->dTbStar.get(), out.best, cnt2, list2, cnt1, verified, ntb, h->dPruneStat.get());
+    vt_launch_plane_scan<64, false, true>(h, s, po, PlaneListU{{list2, cnt2, nq, (uint32_t)per2, lnb, 0u, fill}});
     if (out.host) vt_launch_keys_export(h, out.best, nq, out.host, vt_plan::VT_EXPORT_BLOCKS);
     RS_HIP(hipGetLastError());
-    h->prunePairs = (int64_t)pairs;
-    h->prunePasses = 2;
-    h->pruneNtb = ntb;
     return RS_OK;
 }
 
@@ -1115,6 +1153,11 @@ int rs_vt_create_metric(int H, int W, int max_offset, uint64_t thr, int64_t capa
         // A/B switch: "0" keeps the prefilter and the verification two launches, "force"
         // fuses them for any shape (tests), "1" (or unset) follows vt_plan::front_fused
         RS_TRY(vt_env_switch("RS_VT_FRONT", &h->front));
+        // A/B switch: "1" (or unset) one list pass on the verified score, "2" the two-pass chain
+        if (const char* ps = std::getenv("RS_VT_PASSES"); ps && ps[0]) {
+            RS_CHECK((ps[0] == '1' || ps[0] == '2') && ps[1] == 0, RS_ERR_ARG, "RS_VT_PASSES='%s': expected 1 or 2", ps);
+            h->passes = ps[0] - '0';
+        }
         // A/B switch and tests: "1", "2" or "4" entries per batch in both list passes; unset:
         // each list's own width (vt_plan::list_width)
         if (const char* nb = std::getenv("RS_VT_LIST_NB"); nb && nb[0]) {
@@ -1499,12 +1542,37 @@ const char* rs_vt_scan_form(const rs_vt* h) {
     return "carry";
 }
 
+namespace {
+// The two-pass rule's counts of the last (single-pass) pruned call, from the buffers it left:
+// acc[0] the pairs of the rule's second list, acc[1] the settled queries (vt_prune_count_kernel).
+int vt_prune_count(rs_vt* h, unsigned long long acc[2]) {
+    if (!h->dCountAcc.get()) RS_TRY(h->dCountAcc.reserve(2));
+    RS_HIP(hipMemsetAsync(h->dCountAcc.get(), 0, 2 * sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(vt_prune_count_kernel, dim3((unsigned)((h->pruneNq + 255) / 256)), dim3(256), 0, h->stream,
+                       h->dMinLB.get(), h->pruneNq, h->pruneNtb, h->dTbStar.get(), h->dUblk.get(),
+                       h->dCountAcc.get());
+    RS_HIP(hipGetLastError());
+    RS_HIP(hipMemcpyAsync(acc, h->dCountAcc.get(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream));
+    return RS_OK;
+}
+}  // namespace
+
 int rs_vt_prune_stats(rs_vt* h, int64_t out[4]) {
     rs::clear_error();
     RS_CHECK(h && out, RS_ERR_ARG, "null argument");
     out[0] = out[1] = out[2] = out[3] = 0;
     if (h->prunePasses == 0) return RS_OK;
     RS_HIP(hipSetDevice(h->device));
+    out[2] = h->prunePairs;
+    out[3] = h->prunePasses;
+    if (h->pruneMode == 1) {   // a single list pass: the rule's counts, counted on demand
+        unsigned long long acc[2] = {0ull, 0ull};
+        RS_TRY(vt_prune_count(h, acc));
+        out[0] = h->pruneNq;
+        out[1] = (int64_t)acc[0];
+        return RS_OK;
+    }
     // the pairs of B2: list2's counters, which stay until the next pruned launch's lists
     unsigned long long s0 = 0ull;
     std::vector<unsigned> c2((size_t)h->pruneNtb);
@@ -1514,8 +1582,30 @@ int rs_vt_prune_stats(rs_vt* h, int64_t out[4]) {
     RS_HIP(hipStreamSynchronize(h->stream));
     out[0] = (int64_t)s0;
     for (const unsigned c : c2) out[1] += (int64_t)c;
-    out[2] = h->prunePairs;
-    out[3] = h->prunePasses;
+    return RS_OK;
+}
+
+int rs_vt_prune_scanned(rs_vt* h, int64_t* out) {
+    rs::clear_error();
+    RS_CHECK(h && out, RS_ERR_ARG, "null argument");
+    *out = 0;
+    if (h->prunePasses == 0) return RS_OK;
+    RS_HIP(hipSetDevice(h->device));
+    if (h->pruneMode == 1) {   // the one list's entries: the last call's parity of the counters
+        std::vector<unsigned> c((size_t)h->pruneNtb);
+        RS_HIP(hipMemcpyAsync(c.data(), h->dCntPar.get() + vt_plan::parity_last_offset(h->cntPar),
+                              sizeof(unsigned) * c.size(), hipMemcpyDeviceToHost, h->stream));
+        RS_HIP(hipStreamSynchronize(h->stream));
+        for (const unsigned n : c) *out += (int64_t)n;
+        return RS_OK;
+    }
+    // two passes: list 1 holds the unsettled queries, list 2 the rule's pairs
+    int64_t st[4];
+    unsigned long long v = 0ull;
+    RS_TRY(rs_vt_prune_stats(h, st));
+    RS_HIP(hipMemcpyAsync(&v, h->dPruneStat.get() + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream));
+    *out = st[0] - (int64_t)v + st[1];
     return RS_OK;
 }
 
@@ -1525,6 +1615,12 @@ int rs_vt_prune_verified(rs_vt* h, int64_t* out) {
     *out = 0;
     if (h->prunePasses == 0) return RS_OK;
     RS_HIP(hipSetDevice(h->device));
+    if (h->pruneMode == 1) {
+        unsigned long long acc[2] = {0ull, 0ull};
+        RS_TRY(vt_prune_count(h, acc));
+        *out = (int64_t)acc[1];
+        return RS_OK;
+    }
     unsigned long long v = 0ull;
     RS_HIP(hipMemcpyAsync(&v, h->dPruneStat.get() + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream));
     RS_HIP(hipStreamSynchronize(h->stream));

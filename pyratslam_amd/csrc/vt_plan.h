@@ -166,6 +166,55 @@ inline bool prunes(int H, bool cand, int64_t tb0, bool forms, int64_t ntb, int p
            (prune == 2 || (prune == 1 && nq >= VT_PRUNE_MIN_Q && ntb >= 2));
 }
 
+// --- The single list pass (RS_VT_PASSES).  passes: 1, the front kernel
+// writes one list per template block on its verified score U0 and one list pass scans it;
+// 2, the candidate block's pass (B1), then the lists on U(q) (B2).  No shape keeps two
+// passes by rule today: the place for one is here.
+inline int prune_passes(int passes_switch, int /*ntb*/, int /*nq*/) { return passes_switch == 2 ? 2 : 1; }
+// The `fill` its list pass hands vt_plan::list_width: four resident rounds' worth of working
+// blocks per template block, where passes B1 and B2 ask for one.  Measured at the headline
+// (sixteen lists of about 1,005 entries, fill 32): in batches of 4 the pass is 64 working blocks
+// per template block and takes 207 us, in batches of 2 (128 blocks) 171, of 1 181; lists that
+// reach four rounds at 4 entries (every all-miss list) keep 4.  
+#ifndef VT_SINGLE_ROUNDS
+#define VT_SINGLE_ROUNDS 4
+#endif
+inline int single_pass_fill(int fill) { return std::min(65535, VT_SINGLE_ROUNDS * std::max(1, fill)); }
+// Its list counters need no closing launch: they are doubled by call parity.  A pruned call
+// appends to its own parity's counters, which the call before left at zero, and its first
+// thread block zeroes the other parity's, the call before's, which nobody appends to during
+// this call; the next call starts behind this one on the stream.  So the last call's counts
+// stay readable until the next pruned call begins.  `used` is how many counters of a parity
+// may be nonzero: what the next call has to zero.  A growth reallocates zeroed.
+struct ParityCounters {
+    int cap = 0;             // counters per parity
+    int par = 0;             // the next pruned call's parity
+    int used[2] = {0, 0};    // counters of each parity that may be nonzero
+    int last = -1;           // the last pruned call's parity (-1: none yet)
+};
+struct ParityCall {
+    size_t mine, other;      // offsets of this call's counters and of the ones it zeroes
+    int nzero;               // how many of the others it zeroes
+};
+// Whether ntb counters per parity need a larger (zeroed) buffer, and its new capacity.
+inline bool parity_grows(const ParityCounters& s, int ntb) { return ntb > s.cap; }
+inline void parity_grown(ParityCounters& s, int ntb) {
+    s.cap = std::max(ntb, 2 * s.cap);
+    s.used[0] = s.used[1] = 0;
+    s.last = -1;
+}
+inline ParityCall parity_begin(ParityCounters& s, int ntb) {
+    const int p = s.par;
+    const ParityCall c{(size_t)p * (size_t)s.cap, (size_t)(p ^ 1) * (size_t)s.cap, s.used[p ^ 1]};
+    s.used[p ^ 1] = 0;
+    s.used[p] = ntb;
+    s.last = p;
+    s.par = p ^ 1;
+    return c;
+}
+// Where the last pruned call's counts are (valid while s.last >= 0).
+inline size_t parity_last_offset(const ParityCounters& s) { return (size_t)s.last * (size_t)s.cap; }
+
 // The prefilter's grid: x covers the template blocks, tb_per_block to a thread block; y the
 // batches of q_per_batch queries, as many as keep the grid within `cap` thread blocks (at
 // least one: the kernel strides over the rest).

@@ -213,9 +213,15 @@ __device__ __forceinline__ void plane_load_units(const uint4* __restrict__ plane
 // A list's batch is W = 4, 2 or 1 consecutive entries (vt_plan::list_width, decided by the
 // block from the list's length); a batch of fewer than PL_NB fills the first W slots of the
 // LDS buffers, and entries of (lane & 3) >= W in qnv and qc are read and never used.
+// Single list pass (tbstar != nullptr): the finishing wave of entry (tb, q) with tbstar[q] == tb,
+// the candidate block of an unsettled query, stores the block's minimum score, U(q), into
+// ublk[q] (rs_vt_prune_stats counts the two-pass rule from it).
 struct PlaneIds {
     int qc[PL_NB];  // query ids of the batch being computed (wave-uniform)
     int qnv;        // lane: query id of entry (lane & 3) of the batch staged next
+    const int* tbstar = nullptr;
+    uint32_t* ublk = nullptr;
+    int tb = 0;     // the thread block's template block
 };
 // One take from the group's counter (thread 0): the batch it stands for, tk.nbatch when the
 // block does not take; a failed take's value is kept for the rewind.
@@ -330,7 +336,19 @@ __device__ __forceinline__ bool plane_batch(const uint32_t (&P)[PlaneRange<H, HA
 #pragma unroll
         for (int x = 0; x < NO; ++x)   // each count with its own TS(o)
             best = min(best, vt_pl_ts[x][lane] + 256u * (pl_half(x) ? t[pl_slot(x)] >> 16 : t[pl_slot(x)] & 0xFFFFu));
-        emit_score<MATRIX>(out, slot, count, qi, LIST ? qi + 1 : nq, best - qsum[qi], rank, nranks, lane == 0);
+        if constexpr (LIST) {
+            // emit_score's key, with the reduced one at hand for ublk
+            const unsigned long long g = (unsigned long long)slot * nranks + rank;
+            const unsigned long long key =
+                wave_min_u64(slot < count ? (((unsigned long long)(best - qsum[qi]) << 32) | g) : NO_KEY);
+            if (lane == 0) {
+                atomicMin(out.best + qi, key);
+                // (read behind the reduction: ahead of it the value costs the walk a VGPR)
+                if (pid.tbstar && pid.tbstar[qi] == pid.tb) pid.ublk[qi] = (uint32_t)(key >> 32);
+            }
+        } else {
+            emit_score<MATRIX>(out, slot, count, qi, nq, best - qsum[qi], rank, nranks, lane == 0);
+        }
     }
     if constexpr (LIST) {
 #pragma unroll
@@ -355,7 +373,8 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes, con
                                            unsigned* __restrict__ ctr, int G, int g, ScanOut out,
                                            int rank, int nranks, int wave, int cg, int lane,
                                            unsigned& failed, const int* __restrict__ ids,
-                                           const vt_plan::Take& tk, int v0, int w) {
+                                           const vt_plan::Take& tk, int v0, int w, const int* tbstar,
+                                           uint32_t* ublk) {
     using R = PlaneRange<H, HALF>;
     const int nbatch = tk.nbatch, tid = wave * 64 + lane;
     const int W = LIST ? w : PL_NB;   // entries per batch (block-uniform)
@@ -365,7 +384,7 @@ __device__ __forceinline__ void plane_wave(const uint4* __restrict__ planes, con
         (&vt_pl_part0[0][0][0])[i] = 0u;
         (&vt_pl_part1[0][0][0])[i] = 0u;
     }
-    PlaneIds pid{{0, 0, 0, 0}, 0};
+    PlaneIds pid{{0, 0, 0, 0}, 0, tbstar, ublk, tb};
     if constexpr (LIST) {
 #pragma unroll
         for (int e = 0; e < PL_NB; ++e) pid.qc[e] = __builtin_amdgcn_readlane(v0, vt_plan::spec_lane(W) + e);
@@ -465,6 +484,14 @@ struct PlaneList {
     uint32_t fill : 16;
 };
 static_assert(sizeof(PlaneList) == 24, "the plane scan's kernel arguments keep their layout");
+// The list instance's own argument: the single list pass's two buffers behind the dense
+// instances' words (they keep PlaneList, and with it their arguments' places).
+struct PlaneListU : PlaneList {
+    const int* tbstar = nullptr;   // nullptr: passes B1 and B2
+    uint32_t* ublk = nullptr;
+};
+template <bool LIST>
+using PlaneListArg = std::conditional_t<LIST, PlaneListU, PlaneList>;
 #ifdef VT_LIST_NB
 static_assert(VT_LIST_NB == 1 || VT_LIST_NB == 2 || VT_LIST_NB == 4, "entries per batch: 1, 2 or 4");
 #else
@@ -477,7 +504,7 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
                           int ntb, int64_t count, const uint32_t* __restrict__ qp,
                           const uint32_t* __restrict__ qsum, int nq, int nqc,
                           unsigned* __restrict__ next_batch, ScanOut out, int rank, int nranks,
-                          PlaneList pl) {
+                          PlaneListArg<LIST> pl) {
     static_assert(PL_SPLIT == 2, "two row ranges");
     static_assert(!(LIST && MATRIX), "lists feed the key scan only");
     // The nqc blocks of a template block are adjacent block ids, so they are dispatched
@@ -525,13 +552,19 @@ void vt_scan_plane_kernel(const uint4* __restrict__ planes, const uint32_t* __re
     const int cg = wave % PL_CG, half = wave / PL_CG;
     unsigned failed = 0u;  // thread 0: the value of this block's one failed take
     const uint4* qp4 = reinterpret_cast<const uint4*>(qp);
+    const int* tbstar = nullptr;
+    uint32_t* ublk = nullptr;
+    if constexpr (LIST) {
+        tbstar = pl.tbstar;
+        ublk = pl.ublk;
+    }
     if (tk.sb >= tk.nbatch) {   // (block-uniform) no batch for this block: it leaves the counter alone
     } else if (half == 0)
         plane_wave<H, 0, MATRIX, LIST>(planes, tsum, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
-                                       wave, cg, lane, failed, ids, tk, v0, W);
+                                       wave, cg, lane, failed, ids, tk, v0, W, tbstar, ublk);
     else
         plane_wave<H, 1, MATRIX, LIST>(planes, tsum, tb, count, qp4, qsum, nq, ctr, G, g, out, rank, nranks,
-                                       wave, cg, lane, failed, ids, tk, v0, W);
+                                       wave, cg, lane, failed, ids, tk, v0, W, tbstar, ublk);
     // The block whose failed take returned tk.last is the counter's last user in this
     // launch: it rewinds the counter for the next launch (no memset).
     if (threadIdx.x == 0 && tk.takes && failed == tk.last) *ctr = 0u;

@@ -17,6 +17,9 @@
 // best[]; pass B2 scans it against every other block with minLB <= U(q) -- "<=": a
 // block that may hold an equal score at a lower index is scanned too.  A block left
 // out has minLB > U(q) >= the minimum, so none of its scores is the minimum.
+// With a single list pass (the default, RS_VT_PASSES) the verification
+// lists on its own score U0 >= U(q) instead, tb* for an unsettled query and every other block
+// with minLB <= U0: a superset of the two lists, scanned once, the same keys.
 constexpr int PF_WAVES = 4;   // waves per thread block
 // Template blocks per wave: every staged query plane is read once (an LDS broadcast)
 // for all of them, which divides the LDS reads per VALU instruction: at one block per
@@ -169,6 +172,23 @@ __device__ __forceinline__ void pf_walk(const uint32_t (&P)[PF_TPW][PF_NU][PF_CG
     }
 }
 
+// The single list pass: where the verification writes the lists itself.
+// cnt == nullptr: two passes, the list kernels below write them.  cnt[tb] counts list[tb * nq ..],
+// this call's parity of the counters; the call's first thread block zeroes the nzero counters
+// of the other parity (vt_plan::parity_begin).  ublk[q] = U0 of a settled query (the list pass
+// stores U(q) of the others): with minlb and tbstar, what rs_vt_prune_stats counts from.
+struct FrontLists {
+    unsigned* cnt = nullptr;
+    int* list = nullptr;
+    uint32_t* ublk = nullptr;
+    unsigned* zero = nullptr;
+    int nzero = 0;
+};
+__device__ __forceinline__ void front_zero(const FrontLists& fl) {
+    if (blockIdx.x == 0 && blockIdx.y == 0)   // (block-uniform)
+        for (int b = threadIdx.x; b < fl.nzero; b += blockDim.x) fl.zero[b] = 0u;
+}
+
 // minlb[tb * nq + q], and second[tb * nq + q] = (min2 << 6) | lane: the lane that holds
 // the block's minimum (the lowest on ties) and min2, the minimum over the block's other
 // valid templates (PF_NONE when it has no other).  The pick verifies that one template
@@ -182,7 +202,8 @@ void vt_prefilter_kernel(const uint4* __restrict__ planes, int ntb,
                                                                     const uint4* __restrict__ qc4,
                                                                     const uint32_t* __restrict__ qsj, int nq,
                                                                     uint32_t* __restrict__ minlb,
-                                                                    uint32_t* __restrict__ second) {
+                                                                    uint32_t* __restrict__ second, FrontLists fl) {
+    front_zero(fl);
     static_assert(PF_CGS % PF_CPS == 0 && PF_CGS >= 1 && PF_CGS <= PL_CG, "whole steps of column groups, of the unit");
     static_assert(PF_NU * PF_CGS * 32 * 255 < (int)PF_NONE, "a bound and a lane fit one word");
     __shared__ uint4 s_q[PF_NB][PF_NU][PF_CGS][PL_NO][2];
@@ -279,7 +300,8 @@ __device__ __forceinline__ void vt_verify_query(int q, int lane, Pick&& pick, in
                                                 const uint4* __restrict__ qc4, uint4* __restrict__ qp4,
                                                 const uint32_t* __restrict__ qsum,
                                                 unsigned long long* __restrict__ best, int rank, int nranks,
-                                                int* __restrict__ tbstar, uint4* s_q, uint4* s_t) {
+                                                int* __restrict__ tbstar, uint4* s_q, uint4* s_t,
+                                                const uint32_t* minlb, int ntb, const FrontLists& fl) {
     constexpr int M = FAST_M, NU = 64 / 4, NS = PlaneLds<64>::NS, S0 = M - 3, S1 = 64 - M - 1;
     static_assert(PL_NO * PL_CG <= 64, "one lane per (offset, column group)");
     constexpr int QK = (QC_Q4 + 63) / 64;
@@ -364,6 +386,10 @@ __device__ __forceinline__ void vt_verify_query(int q, int lane, Pick&& pick, in
     for (int off = 32; off > 0; off >>= 1) u0 = min(u0, (uint32_t)__shfl_xor(u0, off));
     u0 -= qs;
     const bool settled = (sec >> 6) > u0;
+    // single list pass: the bounds of the first 64 blocks, in flight through the expansion below
+    const bool lists = fl.cnt && (!settled || other <= u0);   // (wave-uniform)
+    uint32_t mlb0 = 0u;
+    if (lists && lane < ntb) mlb0 = minlb[(size_t)lane * nq + q];
     if (!settled || other <= u0) {   // (wave-uniform) a scan pass stages this query
 #pragma unroll
         for (int k = 0; k < (VT_VQ4 + 63) / 64; ++k) {
@@ -374,10 +400,26 @@ __device__ __forceinline__ void vt_verify_query(int q, int lane, Pick&& pick, in
             }
         }
     }
+    if (lists) {   // single list pass: the lists, written here
+        asm volatile("" : "+v"(mlb0));   // (mlb0 is needed here: its read does not sink into the loop)
+        // tb* if the query is unsettled, and every other block whose bound does not exceed U0
+        // (>= U(q): a superset of the two passes' lists, and keys meet by atomicMin).  Lane =
+        // template block; the bounds are re-read (this wave's lanes hold no complete copy of
+        // them past one chunk): the thread block's own stores, behind the chunk loop's last
+        // barrier, or the prefilter launch's.  One atomic per listed (tb, q), none elsewhere.
+        for (int tb = lane; tb < ntb; tb += 64) {
+            const bool in = tb == tbs ? !settled : (tb < 64 ? mlb0 : minlb[(size_t)tb * nq + q]) <= u0;
+            if (in) {
+                const unsigned p = atomicAdd(fl.cnt + tb, 1u);
+                if (p < (unsigned)nq) fl.list[(size_t)tb * nq + p] = q;   // (always: a query joins a list once)
+            }
+        }
+    }
     if (lane == 0) {
         if (settled) {
             const unsigned long long g = ((unsigned long long)tbs * 64 + tl) * nranks + rank;
             atomicMin(best + q, ((unsigned long long)u0 << 32) | g);
+            if (fl.cnt) fl.ublk[q] = u0;
         }
         tbstar[q] = settled ? ~tbs : tbs;
     }
@@ -391,7 +433,8 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
                                                              uint4* __restrict__ qp4,
                                                              const uint32_t* __restrict__ qsum,
                                                              unsigned long long* __restrict__ best, int rank,
-                                                             int nranks, int* __restrict__ tbstar) {
+                                                             int nranks, int* __restrict__ tbstar,
+                                                             FrontLists fl) {
     __shared__ uint4 s_q[VT_VQS];
     __shared__ uint4 s_t[VT_VTS];
     const int q = blockIdx.x, lane = threadIdx.x;
@@ -404,7 +447,7 @@ __global__ __launch_bounds__(64) void vt_prune_verify_kernel(const uint32_t* __r
             pk = lt ? k : pk;
             sec = lt ? s2 : sec;
         }
-    }, nq, planes, tsum, qc4, qp4, qsum, best, rank, nranks, tbstar, s_q, s_t);
+    }, nq, planes, tsum, qc4, qp4, qsum, best, rank, nranks, tbstar, s_q, s_t, minlb, ntb, fl);
 }
 
 // The front of a pruned call in one launch (vt_plan::front_fused): a thread block owns
@@ -427,7 +470,8 @@ void vt_front_kernel(const uint4* __restrict__ planes, int ntb, int64_t count, c
                      const uint32_t* __restrict__ qsj, int nq, uint32_t* __restrict__ minlb,
                      const uint32_t* __restrict__ tsum, uint4* __restrict__ qp4,
                      const uint32_t* __restrict__ qsum, unsigned long long* __restrict__ best, int rank,
-                     int nranks, int* __restrict__ tbstar) {
+                     int nranks, int* __restrict__ tbstar, FrontLists fl) {
+    front_zero(fl);
     constexpr int CH = PF_WAVES * PF_TPW;
     static_assert(PF_WAVES == PF_NB, "one wave per query of the group in the tail");
     static_assert(CH <= 64, "one lane per block of a chunk");
@@ -487,7 +531,7 @@ void vt_front_kernel(const uint4* __restrict__ planes, int ntb, int64_t count, c
                 pk_ = pk;
                 sec_ = sec;
                 m2_ = m2;
-            }, nq, planes, tsum, qc4, qp4, qsum, best, rank, nranks, tbstar, s_vq[wave], s_vt[wave]);
+            }, nq, planes, tsum, qc4, qp4, qsum, best, rank, nranks, tbstar, s_vq[wave], s_vt[wave], minlb, ntb, fl);
     }
 }
 
@@ -547,6 +591,30 @@ __global__ __launch_bounds__(VT_LIST_T) void vt_prune_rest_kernel(const uint32_t
             stat[2] = v;
         }
     }
+}
+
+// rs_vt_prune_stats after a single list pass: the two-pass rule's counts, from what the
+// call left.  vt_prune_rest_kernel's predicate, counted instead of listed: acc[0] += the
+// pairs (tb, q) with tb != tb* and minlb[tb][q] <= ublk[q] (ublk[q] = U(q): U0 of a settled
+// query, the candidate block's minimum of the others), acc[1] += the settled marks in tbstar.
+__global__ __launch_bounds__(256) void vt_prune_count_kernel(const uint32_t* __restrict__ minlb, int nq, int ntb,
+                                                             const int* __restrict__ tbstar,
+                                                             const uint32_t* __restrict__ ublk,
+                                                             unsigned long long* __restrict__ acc) {
+    __shared__ unsigned s_acc[2];
+    if (threadIdx.x < 2) s_acc[threadIdx.x] = 0u;
+    __syncthreads();
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q < nq) {
+        const int ts = tbstar[q], tbs = ts < 0 ? ~ts : ts;
+        const uint32_t u = ublk[q];
+        unsigned n = 0u;
+        for (int tb = 0; tb < ntb; ++tb) n += tb != tbs && minlb[(size_t)tb * nq + q] <= u;
+        if (n) atomicAdd(&s_acc[0], n);
+        if (ts < 0) atomicAdd(&s_acc[1], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && s_acc[threadIdx.x]) atomicAdd(acc + threadIdx.x, (unsigned long long)s_acc[threadIdx.x]);
 }
 
 // The batch's first-argmin keys -> the pinned host buffer (system-scope stores),

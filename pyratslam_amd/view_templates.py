@@ -871,19 +871,29 @@ class ViewTemplates:
         return self._lib.rs_vt_scan_form(self._h).decode()
 
     def prune_stats(self):
-        """Of the last pruned scan launch ('plane-pruned' handles): (block, query) pairs
-        scanned by pass B1, by pass B2, template blocks x queries, passes launched;
-        zeros before the first pruned scan (rs_vt_prune_stats)."""
+        """Of the last pruned scan launch ('plane-pruned' handles), the two-pass rule's counts:
+        (block, query) pairs of pass B1, of pass B2, template blocks x queries, the rule's
+        passes; zeros before the first pruned scan (rs_vt_prune_stats).  With a single list
+        pass (RS_VT_PASSES=1, the default) they are counted on demand, the same numbers;
+        prune_scanned() tells the pairs actually scanned."""
         out = (ctypes.c_int64 * 4)()
         _lib.check(self._lib.rs_vt_prune_stats(self._h, out))
         return tuple(int(v) for v in out)
 
     def prune_verified(self):
-        """Of the last pruned scan launch: the queries settled by verifying the one
-        template the prefilter singled out, without a block scan in pass B1; 0 before
-        the first pruned scan (rs_vt_prune_verified)."""
+        """Of the last pruned scan launch, the two-pass rule's counts: the queries settled by
+        verifying the one template the prefilter singled out, without a block scan in pass
+        B1; 0 before the first pruned scan (rs_vt_prune_verified)."""
         out = ctypes.c_int64(0)
         _lib.check(self._lib.rs_vt_prune_verified(self._h, ctypes.byref(out)))
+        return int(out.value)
+
+    def prune_scanned(self):
+        """Of the last pruned scan launch: the (block, query) pairs its list passes actually
+        scanned (with a single list pass, the lists on the verified score: at least the
+        rule's pairs); 0 before the first pruned scan (rs_vt_prune_scanned)."""
+        out = ctypes.c_int64(0)
+        _lib.check(self._lib.rs_vt_prune_scanned(self._h, ctypes.byref(out)))
         return int(out.value)
 
 

@@ -3,7 +3,8 @@
 ``rocprofv3 --kernel-trace --output-format csv`` folder: the prefilter's dispatches, or
 the fused front's (vt_front_kernel: prefilter, pick and verification in one launch), mark
 the pruned calls; of the list-driven scan's two dispatches per call the first is pass B1
-and the second pass B2 (dispatch order).  Only calls of the most common grid of that
+and the second pass B2 (dispatch order), behind vt_prune_first_kernel; a call without that
+kernel is the four-kernel chain (qplane, front, the one list pass, export) and its scan `list`.  Only calls of the most common grid of that
 first kernel (the headline shape in a plain bench) are counted; a pass that a build
 does not launch is not reported.
 usage: python tools/prune_pass_medians.py TRACE_DIR [TRACE_DIR ...]   (one JSON object)"""
@@ -37,12 +38,12 @@ def passes(d):
             calls.append(cur)
         elif cur is not None:
             if tag == 'list_scan':
-                tag = 'B2' if 'B1' in cur else 'B1'
+                tag = ('B2' if 'B1' in cur else 'B1') if 'first' in cur else 'list'
             cur.setdefault(tag, us)
     grid = collections.Counter(c['grid'] for c in calls).most_common(1)[0][0]
     calls = [c for c in calls if c['grid'] == grid]
     out = {'calls': len(calls)}
-    for k in ('qplane', 'prefilter', 'front', 'pick', 'verify', 'first', 'B1', 'rest', 'B2', 'finish', 'export'):
+    for k in ('qplane', 'prefilter', 'front', 'pick', 'verify', 'first', 'B1', 'rest', 'B2', 'list', 'finish', 'export'):
         v = sorted(c[k] for c in calls if k in c)
         if v:
             out[k] = round(v[len(v) // 2], 1)

@@ -8,7 +8,7 @@
            hit_frac = 0, 0.5 and 0.9, RS_VT_PRUNE=0 against 1, with prune_stats; under
            ``rocprofv3 --kernel-trace`` the trace holds the passes' own times
 
-usage: python tools/prune_probe.py [sweep] [allmiss] [--reps 20] [--lib OTHER.so] [--noise N]
+usage: python tools/prune_probe.py [sweep] [allmiss] [--reps 20] [--lib OTHER.so] [--noise N] [--hits 0,0.5,0.9]
 (--lib: another build of the library, e.g. the parent commit's, for a before/after;
 --noise: a hit is its template lowered by 0..N per pixel, 3 as the bench's: the larger, the
 closer a hit's score comes to the other blocks' bounds and the less the prefilter prunes)"""
@@ -47,6 +47,7 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--lib', default=None)
     ap.add_argument('--noise', type=int, default=3)
+    ap.add_argument('--hits', default='0,0.5,0.9', help="hit fractions of the 'allmiss' part")
     a = ap.parse_args()
     from pyratslam_amd import _lib, synthetic
     if a.lib:
@@ -54,6 +55,9 @@ def main():
 
     def stats(h):   # with the verified count where the build has it
         return list(h.prune_stats()) + ([h.prune_verified()] if hasattr(_lib.load(), 'rs_vt_prune_verified') else [])
+
+    def scanned(h):   # the pairs actually scanned, beside the rule's (prune_stats()[1]); None: an older build
+        return h.prune_scanned() if hasattr(_lib.load(), 'rs_vt_prune_scanned') else None
     lib = synthetic.library(1000, seed=1)
     hs = {p: handle(p) for p in ('0', '1', 'force')}
     for h in hs.values():
@@ -76,10 +80,11 @@ def main():
             rec['same_keys'] = bool(np.array_equal(outs['0'][0], outs['force'][0]) and
                                     np.array_equal(outs['0'][1], outs['force'][1]))
             rec['prune_stats'] = stats(hs['force'])
+            rec['pairs_scanned'] = scanned(hs['force'])
             print(json.dumps(rec), flush=True)
             buf.close()
     if 'allmiss' in a.what:
-        for hit in (0.0, 0.5, 0.9):
+        for hit in (float(x) for x in a.hits.split(',')):
             qs = np.stack([synthetic.queries_fast(lib, 1024, seed=2 + 1000 * b, hit_frac=hit, noise=a.noise)[0] for b in range(10)])
             buf = _lib.DeviceBuffer(qs.nbytes).upload(qs)
             rec = {'probe': 'allmiss', 'lib': a.lib or 'tree', 'noise': a.noise, 'hit_frac': hit, 'templates': 1000, 'queries': 10240}
@@ -91,6 +96,7 @@ def main():
             rec['same_keys'] = bool(np.array_equal(outs['0'][0], outs['1'][0]) and
                                     np.array_equal(outs['0'][1], outs['1'][1]))
             rec['prune_stats'] = stats(hs['1'])
+            rec['pairs_scanned'] = scanned(hs['1'])
             print(json.dumps(rec), flush=True)
             buf.close()
     for h in hs.values():
