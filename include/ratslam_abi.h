@@ -659,6 +659,45 @@ int rs_em_relax_host(int nexp, int nlinks, const int32_t* from, const int32_t* t
                      const double* heading, const double* facing, double* xyth, int loops,
                      double correction);
 
+/* ------------------------------------------------------------------------ */
+/* Pose-cell ensemble                                                        */
+/* ------------------------------------------------------------------------ */
+/* B independent float32 pose-cell networks of one shape, each stepped by one workgroup out
+ * of a compute unit's LDS.  A member's result depends on its own state
+ * and control only: not on B, on its index, or on how a run is cut into launches.
+ *   rs_pce_fit      host only: *lds_bytes (may be NULL) = the LDS a member's workgroup needs;
+ *                   RS_ERR_ARG when a dimension is below 7 or the plan exceeds 160 KiB
+ *   rs_pce_create   params as for rs_pc_create (precision must be RS_PREC_F32, at most 16
+ *                   filters); global_inhibition[B], or NULL for params' value in every
+ *                   member.  Volumes start all zero.  Argument errors (RS_ERR_ARG, *out NULL)
+ *                   come before any device call.  RS_PCE_CHUNK=K in the environment forces
+ *                   K steps per launch (default: what keeps a launch's control in 32 MiB).
+ *   rs_pce_run      n steps of every member, one host synchronisation; member-major arrays
+ *                   ox, oy, fidx [(m * n + s) * TH + k], zf [(m * n + s) * 7 + t] and
+ *                   out_xyz [(m * n + s) * 3]: each step's first maximum in C order.  A null
+ *                   array or a fidx outside the table: RS_ERR_ARG, nothing run.
+ *   rs_pce_inject   posecells[member][x][y][th] += energy, member -1: every member; queued
+ *   rs_pce_get_max  out_xyz[B * 3]: each member's first maximum in C order
+ *   rs_pce_read, rs_pce_write   members [first, first + count) as float64, C order
+ *                   (member, X, Y, TH); a value that is not a finite float32 is refused
+ *                   (RS_ERR_ARG, nothing written)
+ *   rs_pce_set_timing, rs_pce_last_ms   HIP events around the launches of every later
+ *                   rs_pce_run; the last run's device time in ms, -1 when it ran untimed */
+typedef struct rs_pce rs_pce;
+int rs_pce_fit(int X, int Y, int TH, size_t* lds_bytes);
+int rs_pce_create(int B, int X, int Y, int TH, const rs_pc_params* params,
+                  const double* global_inhibition, int device, rs_pce** out);
+int rs_pce_destroy(rs_pce* h);
+int rs_pce_shape(const rs_pce* h, int* B, int* X, int* Y, int* TH);
+int rs_pce_run(rs_pce* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
+               const double* zf, int32_t* out_xyz);
+int rs_pce_inject(rs_pce* h, int member, double energy, int x, int y, int th);
+int rs_pce_get_max(rs_pce* h, int32_t* out_xyz);
+int rs_pce_read(rs_pce* h, int first, int count, double* volumes);
+int rs_pce_write(rs_pce* h, int first, int count, const double* volumes);
+int rs_pce_set_timing(rs_pce* h, int enable);
+int rs_pce_last_ms(rs_pce* h, double* ms);
+
 /* Multi-GPU: one process per GPU, library sharded round-robin (template g lives
  * on rank g % nranks at slot g / nranks); per query the local first-argmin keys
  * (score << 32 | g) are combined with one RCCL allreduce(min, uint64).        */

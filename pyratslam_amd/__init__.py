@@ -8,6 +8,7 @@ with the reference's API (``/root/reference/ratslam/posecell_network.py``,
 """
 from .linked_experience_map import LinkedExperienceMap, NumpyLinkedExperienceMap  # noqa: F401
 from .pc_peak import numpy_peak_sums, peak_tables, pose_from_sums  # noqa: F401
+from .pose_ensemble import PoseCellEnsemble  # noqa: F401
 from .posecell_network import PoseCellNetwork  # noqa: F401
 from .view_templates import (ShardedViewTemplates, ViewTemplate, ViewTemplates, numpy_offset_profile,  # noqa: F401
                              normalise_u8, numpy_sad_u8_scores, refine_offset)

@@ -18,7 +18,7 @@ OBJDIR = os.path.join(HERE, 'build')
 # the translation units (posecell.hip includes its pc_*.h parts, view_templates.hip its
 # vt_*.h parts: one object each, so the file-wide flags below reach every kernel of either)
 SOURCES = ['rs_common.cpp', 'posecell.hip', 'view_templates.hip', 'view_templates_float.hip',
-           'visual_odometer.hip', 'experience_map.hip']
+           'visual_odometer.hip', 'experience_map.hip', 'pose_ensemble.hip']
 # per-source flags: the plane scan's batch takes are single-lane atomics; the
 # wave-aggregating atomic optimizer only adds a readfirstlane round trip to them.
 # The pose-cell stencils keep scalar FMAs: SLP packing into v_pk_fma_f32 pairs the
@@ -31,6 +31,8 @@ EXTRA = {'view_templates.hip': ['-mllvm', '-amdgpu-atomic-optimizer-strategy=Non
          # pc_step_halo's first 9 arguments (the union image's addresses, the partial sums) preloaded
          # into scalar registers (pc_halo.h, before pc_step_halo)
          'posecell.hip': ['-fno-slp-vectorize', '-mllvm', '-amdgpu-kernarg-preload-count=9'],
+         # the ensemble's stencils keep scalar FMAs for the same reason (pce_run_kernel 86 -> 66 VGPRs)
+         'pose_ensemble.hip': ['-fno-slp-vectorize'],
          # the linked map's float64 rule is defined operation by operation (em_rule.h): a
          # fused multiply-add would round x + w * sx once where NumPy rounds twice
          'experience_map.hip': ['-ffp-contract=off']}

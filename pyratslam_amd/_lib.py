@@ -189,6 +189,18 @@ SIGNATURES = {
     'rs_em_form': (ctypes.c_char_p, [_vp]),
     'rs_em_relax_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _i32p, _i32p, _f64p, _f64p, _f64p,
                                         _f64p, ctypes.c_int, ctypes.c_double]),
+    'rs_pce_fit': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'rs_pce_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.POINTER(PcParams), _f64p, ctypes.c_int, ctypes.POINTER(_vp)]),
+    'rs_pce_destroy': (ctypes.c_int, [_vp]),
+    'rs_pce_shape': (ctypes.c_int, [_vp, _c_int_p, _c_int_p, _c_int_p, _c_int_p]),
+    'rs_pce_run': (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _i32p, _f64p, _i32p]),
+    'rs_pce_inject': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'rs_pce_get_max': (ctypes.c_int, [_vp, _i32p]),
+    'rs_pce_read': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _f64p]),
+    'rs_pce_write': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _f64p]),
+    'rs_pce_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'rs_pce_last_ms': (ctypes.c_int, [_vp, _f64p]),
     'rs_comm_unique_id': (ctypes.c_int, [_u8p]),
     'rs_vt_attach_comm': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _u8p]),
     'rs_vt_set_shard': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
@@ -199,7 +211,8 @@ SIGNATURES = {
 # builds by path for an A/B; calling one of these on them raises AttributeError
 NEWER_SYMBOLS = {'rs_vt_prune_stats', 'rs_vt_prune_verified', 'rs_vt_prune_scanned', 'rs_vt_create_metric', 'rs_vt_metric',
                  'rs_vt_offset_profile', 'rs_vt_offset_profile_host', 'rs_vt_set_normalise',
-                 'rs_vt_normalise', 'rs_vt_normalise_host'}
+                 'rs_vt_normalise', 'rs_vt_normalise_host'} | {
+                     name for name in SIGNATURES if name.startswith('rs_pce_')}
 
 _lib = None
 _lock = threading.Lock()
