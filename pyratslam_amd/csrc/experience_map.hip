@@ -84,14 +84,12 @@ int em_check_link(int n, int from, int to) {
 }  // namespace
 
 // The buffers are rs::DevBuf / rs::PinnedBuf members (rs_common.h).  Group capacities: cap
-// experiences (dPose[2], dOff, hOff), lcap links (dLinks, dAdj, hLinks, hAdj).
+// experiences (dPose[2], dOff, hOff), lcap links (dLinks, dAdj, hLinks, hAdj).  The stream
+// and the events are rs::Stream / rs::Event owners.
 struct rs_em {
     int device = 0;
     double c = 0.5;
     int forced = EM_AUTO;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};   // around the relax launches (timing)
-    hipEvent_t evUp = nullptr;               // after the last read of the pinned staging
     int n = 0, cap = 0, lcap = 0, canon = 0;
     std::vector<EmLink> links;               // the list itself (host)
     size_t uploaded = 0;                     // link records already in dLinks
@@ -103,6 +101,10 @@ struct rs_em {
     rs::PinnedBuf<int32_t> hOff, hAdj;
     rs::PinnedBuf<double> hPose;             // staging of rs_em_read / rs_em_write
     bool timing = false, timed = false;
+    // the owners come after the buffers: members go in reverse order, streams and events first
+    rs::Stream stream;
+    rs::Event ev[2];   // around the relax launches (timing)
+    rs::Event evUp;    // after the last read of the pinned staging
 };
 
 namespace {
@@ -116,14 +118,14 @@ int em_form_for(const rs_em* h, int n) {
 int em_grow_pose(rs_em* h, int n) {
     if (n <= h->cap) return RS_OK;
     const int cap = rs::grown(h->cap, n, 1);
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     rs::DevBuf<double> a, b;
     RS_TRY(a.reserve(3 * (size_t)cap, "experience poses"));
     RS_TRY(b.reserve(3 * (size_t)cap, "experience poses"));
     if (h->n > 0) {
         RS_HIP(hipMemcpyAsync(a.get(), h->dPose[h->canon].get(), sizeof(double) * 3 * h->n,
-                              hipMemcpyDeviceToDevice, h->stream));
-        RS_HIP(hipStreamSynchronize(h->stream));
+                              hipMemcpyDeviceToDevice, h->stream.get()));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
     }
     h->dPose[0] = std::move(a);
     h->dPose[1] = std::move(b);
@@ -136,9 +138,9 @@ int em_grow_pose(rs_em* h, int n) {
 int em_upload_topology(rs_em* h) {
     const size_t L = h->links.size();
     const size_t noff = 2 * (size_t)h->cap + 1;
-    RS_HIP(hipEventSynchronize(h->evUp));   // the last upload has read the pinned staging
+    RS_HIP(hipEventSynchronize(h->evUp.get()));   // the last upload has read the pinned staging
     if (noff > h->dOff.capacity() || (int64_t)L > h->lcap)
-        RS_HIP(hipStreamSynchronize(h->stream));   // queued kernels read the blocks about to go
+        RS_HIP(hipStreamSynchronize(h->stream.get()));   // queued kernels read the blocks about to go
     RS_TRY(h->dOff.reserve(noff, "incidence offsets"));
     RS_TRY(h->hOff.reserve(noff, hipHostMallocDefault, "incidence offsets"));
     if ((int64_t)L > h->lcap) {
@@ -153,19 +155,19 @@ int em_upload_topology(rs_em* h) {
     }
     rs::em_build_incidence(h->n, (int)L, h->links.data(), h->hOff.get(), h->hAdj.get());
     RS_HIP(hipMemcpyAsync(h->dOff.get(), h->hOff.get(), sizeof(int32_t) * (2 * (size_t)h->n + 1),
-                          hipMemcpyHostToDevice, h->stream));
+                          hipMemcpyHostToDevice, h->stream.get()));
     if (L > 0) {
         RS_HIP(hipMemcpyAsync(h->dAdj.get(), h->hAdj.get(), sizeof(int32_t) * 2 * L, hipMemcpyHostToDevice,
-                              h->stream));
+                              h->stream.get()));
         const size_t u = h->uploaded;
         if (L > u) {
             std::memcpy(h->hLinks.get() + u, h->links.data() + u, sizeof(EmLink) * (L - u));
             RS_HIP(hipMemcpyAsync(h->dLinks.get() + u, h->hLinks.get() + u, sizeof(EmLink) * (L - u),
-                                  hipMemcpyHostToDevice, h->stream));
+                                  hipMemcpyHostToDevice, h->stream.get()));
             h->uploaded = L;
         }
     }
-    RS_HIP(hipEventRecord(h->evUp, h->stream));
+    RS_HIP(hipEventRecord(h->evUp.get(), h->stream.get()));
     h->topoDirty = false;
     return RS_OK;
 }
@@ -211,30 +213,20 @@ int rs_em_create(int capacity, double correction, int device, rs_em** out) {
         else if (!std::strcmp(e, "sweep")) forced = EM_SWEEP;
         else RS_CHECK(!*e, RS_ERR_ARG, "RS_EM_FORM=%s: expected lds or sweep", e);
     }
-    int ndev = 0;
-    RS_HIP(hipGetDeviceCount(&ndev));
-    RS_CHECK(device >= 0 && device < ndev, RS_ERR_ARG, "device %d not in [0, %d)", device, ndev);
-    RS_HIP(hipSetDevice(device));
-    rs_em* h = new rs_em();
+    RS_TRY(rs::use_device(device));
+    // one failure exit: rs_em_destroy takes a handle at any stage
+    std::unique_ptr<rs_em, int (*)(rs_em*)> owner(new rs_em(), rs_em_destroy);
+    rs_em* const h = owner.get();
     h->device = device;
     h->c = correction;
     h->forced = forced;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evUp, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(h->evUp, h->stream);
-    if (e != hipSuccess) {
-        rs::set_error("experience-map stream/event creation failed: %s", hipGetErrorString(e));
-        rs_em_destroy(h);
-        return RS_ERR_HIP;
-    }
-    int s = em_grow_pose(h, capacity);
-    if (s == RS_OK) s = h->hPose.reserve(3, hipHostMallocDefault, "pose staging");
-    if (s != RS_OK) {
-        rs_em_destroy(h);
-        return s;
-    }
-    *out = h;
+    RS_TRY(h->stream.create());
+    for (rs::Event& e : h->ev) RS_TRY(e.create());
+    RS_TRY(h->evUp.create(hipEventDisableTiming));
+    RS_HIP(hipEventRecord(h->evUp.get(), h->stream.get()));
+    RS_TRY(em_grow_pose(h, capacity));
+    RS_TRY(h->hPose.reserve(3, hipHostMallocDefault, "pose staging"));
+    *out = owner.release();
     return RS_OK;
 }
 
@@ -242,12 +234,8 @@ int rs_em_destroy(rs_em* h) {
     if (!h) return RS_OK;
     (void)hipSetDevice(h->device);
     // queued work that failed after a call returned is reported here, not dropped
-    const hipError_t se = h->stream ? hipStreamSynchronize(h->stream) : hipSuccess;
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->evUp) (void)hipEventDestroy(h->evUp);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;  // (the buffers go with their members)
+    const hipError_t se = rs::sync_streams({h->stream.get()});
+    delete h;  // (the streams and events, then the buffers, go with their members)
     RS_CHECK(se == hipSuccess, RS_ERR_HIP, "work queued before rs_em_destroy failed: %s", hipGetErrorString(se));
     return RS_OK;
 }
@@ -267,7 +255,7 @@ int rs_em_add_experience(rs_em* h, int from, double d, double heading, double fa
     RS_CHECK(h->n < INT32_MAX / 8, RS_ERR_ARG, "too many experiences");
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(em_grow_pose(h, h->n + 1));
-    hipLaunchKernelGGL(em_place_kernel, dim3(1), dim3(64), 0, h->stream, h->dPose[h->canon].get(), from,
+    hipLaunchKernelGGL(em_place_kernel, dim3(1), dim3(64), 0, h->stream.get(), h->dPose[h->canon].get(), from,
                        h->n, d, heading, facing);
     RS_HIP(hipGetLastError());
     if (id) *id = h->n;
@@ -299,16 +287,16 @@ int rs_em_relax(rs_em* h, int loops) {
     RS_HIP(hipSetDevice(h->device));
     if (h->topoDirty) RS_TRY(em_upload_topology(h));
     const bool timed = h->timing;
-    if (timed) RS_HIP(hipEventRecord(h->ev[0], h->stream));
+    if (timed) RS_HIP(hipEventRecord(h->ev[0].get(), h->stream.get()));
     if (form == EM_LDS) {
-        hipLaunchKernelGGL(em_relax_lds_kernel, dim3(1), dim3(EM_LDS_THREADS), 0, h->stream,
+        hipLaunchKernelGGL(em_relax_lds_kernel, dim3(1), dim3(EM_LDS_THREADS), 0, h->stream.get(),
                            h->dPose[h->canon].get(), h->n, h->dOff.get(), h->dAdj.get(), h->dLinks.get(),
                            loops, h->c);
         RS_HIP(hipGetLastError());
     } else {
         const int blocks = (h->n + EM_SWEEP_THREADS - 1) / EM_SWEEP_THREADS;
         for (int it = 0; it < loops; ++it) {
-            hipLaunchKernelGGL(em_relax_sweep_kernel, dim3(blocks), dim3(EM_SWEEP_THREADS), 0, h->stream,
+            hipLaunchKernelGGL(em_relax_sweep_kernel, dim3(blocks), dim3(EM_SWEEP_THREADS), 0, h->stream.get(),
                                h->dPose[h->canon].get(), h->dPose[h->canon ^ 1].get(), h->n, h->dOff.get(),
                                h->dAdj.get(), h->dLinks.get(), h->c);
             RS_HIP(hipGetLastError());
@@ -316,7 +304,7 @@ int rs_em_relax(rs_em* h, int loops) {
         }
     }
     if (timed) {
-        RS_HIP(hipEventRecord(h->ev[1], h->stream));
+        RS_HIP(hipEventRecord(h->ev[1].get(), h->stream.get()));
         h->timed = true;
     }
     return RS_OK;
@@ -332,8 +320,8 @@ int rs_em_read(rs_em* h, int first, int n, double* xyth) {
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(h->hPose.reserve(3 * (size_t)n, hipHostMallocDefault, "pose staging"));
     RS_HIP(hipMemcpyAsync(h->hPose.get(), h->dPose[h->canon].get() + 3 * (size_t)first, sizeof(double) * 3 * n,
-                          hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+                          hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     std::memcpy(xyth, h->hPose.get(), sizeof(double) * 3 * n);
     return RS_OK;
 }
@@ -349,8 +337,8 @@ int rs_em_write(rs_em* h, int first, int n, const double* xyth) {
     RS_TRY(h->hPose.reserve(3 * (size_t)n, hipHostMallocDefault, "pose staging"));
     std::memcpy(h->hPose.get(), xyth, sizeof(double) * 3 * n);
     RS_HIP(hipMemcpyAsync(h->dPose[h->canon].get() + 3 * (size_t)first, h->hPose.get(), sizeof(double) * 3 * n,
-                          hipMemcpyHostToDevice, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));   // the staging is free again
+                          hipMemcpyHostToDevice, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));   // the staging is free again
     return RS_OK;
 }
 
@@ -367,8 +355,8 @@ int rs_em_last_ms(rs_em* h, double* ms) {
     *ms = -1.0;
     if (!h->timed) return RS_OK;
     float t = 0.f;
-    RS_HIP(hipEventSynchronize(h->ev[1]));
-    RS_HIP(hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
+    RS_HIP(hipEventSynchronize(h->ev[1].get()));
+    RS_HIP(hipEventElapsedTime(&t, h->ev[0].get(), h->ev[1].get()));
     *ms = t;
     return RS_OK;
 }

@@ -299,6 +299,8 @@ __global__ void pce_inject_kernel(float* state, int B, int N, int member, int li
 
 }  // namespace
 
+// The buffers are rs::DevBuf / rs::PinnedBuf members, the stream and the events rs::Stream /
+// rs::Event owners (rs_common.h).
 struct rs_pce {
     int device = 0;
     int B = 0, X = 0, Y = 0, TH = 0;
@@ -307,8 +309,6 @@ struct rs_pce {
     PceArgs args{};
     int nfilters = 0;
     int forced_chunk = 0;                  // RS_PCE_CHUNK, read at create
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
     rs::DevBuf<float> dState, dInhib, dFilt;
     rs::DevBuf<unsigned char> dCtl[2];     // a launch's records, two slots in turn
     rs::DevBuf<int32_t> dOut;
@@ -316,6 +316,9 @@ struct rs_pce {
     rs::PinnedBuf<int32_t> hOut;
     rs::PinnedBuf<float> hState;           // staging of rs_pce_read / rs_pce_write
     bool timing = false, timed = false;
+    // the owners come after the buffers: members go in reverse order, streams and events first
+    rs::Stream stream;
+    rs::Event ev[2];
 };
 
 extern "C" {
@@ -356,11 +359,10 @@ int rs_pce_create(int B, int X, int Y, int TH, const rs_pc_params* p, const doub
             forced = (int)v;
         }
     }
-    int ndev = 0;
-    RS_HIP(hipGetDeviceCount(&ndev));
-    RS_CHECK(device >= 0 && device < ndev, RS_ERR_ARG, "device %d not in [0, %d)", device, ndev);
-    RS_HIP(hipSetDevice(device));
-    rs_pce* h = new rs_pce();
+    RS_TRY(rs::use_device(device));
+    // one failure exit: rs_pce_destroy takes a handle at any stage
+    std::unique_ptr<rs_pce, int (*)(rs_pce*)> owner(new rs_pce(), rs_pce_destroy);
+    rs_pce* const h = owner.get();
     h->device = device;
     h->B = B, h->X = X, h->Y = Y, h->TH = TH, h->N = N;
     h->fit = fit;
@@ -375,40 +377,26 @@ int rs_pce_create(int B, int X, int Y, int TH, const rs_pc_params* p, const doub
     for (int t = 0; t < PCE_TAPS; ++t) a.ge[t] = (float)p->ge[t], a.gi[t] = (float)p->gi[t];
     a.ks = (float)p->k_scale;
 
-    auto fail = [&](int s) {
-        rs_pce_destroy(h);
-        return s;
-    };
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(pce_run_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)fit.total);
-    if (e != hipSuccess) {
-        rs::set_error("ensemble stream/event/kernel setup failed: %s", hipGetErrorString(e));
-        return fail(RS_ERR_HIP);
-    }
+    RS_TRY(h->stream.create());
+    for (rs::Event& e : h->ev) RS_TRY(e.create());
+    RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pce_run_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)fit.total));
     const size_t nft = (size_t)p->nfilters * PCE_TAPS * PCE_TAPS;
-    int s = h->dState.reserve((size_t)B * N, "ensemble volumes");
-    if (s == RS_OK) s = h->dInhib.reserve(B, "ensemble inhibitions");
-    if (s == RS_OK) s = h->dFilt.reserve(nft, "path filters");
-    if (s == RS_OK) s = h->dOut.reserve(3 * (size_t)B, "ensemble peaks");
-    if (s == RS_OK) s = h->hOut.reserve(3 * (size_t)B, hipHostMallocDefault, "ensemble peaks");
-    if (s == RS_OK) s = h->hState.reserve(std::max((size_t)B, nft), hipHostMallocDefault, "ensemble staging");
-    if (s != RS_OK) return fail(s);
+    RS_TRY(h->dState.reserve((size_t)B * N, "ensemble volumes"));
+    RS_TRY(h->dInhib.reserve(B, "ensemble inhibitions"));
+    RS_TRY(h->dFilt.reserve(nft, "path filters"));
+    RS_TRY(h->dOut.reserve(3 * (size_t)B, "ensemble peaks"));
+    RS_TRY(h->hOut.reserve(3 * (size_t)B, hipHostMallocDefault, "ensemble peaks"));
+    RS_TRY(h->hState.reserve(std::max((size_t)B, nft), hipHostMallocDefault, "ensemble staging"));
     float* st = h->hState.get();
     for (size_t i = 0; i < nft; ++i) st[i] = (float)p->xy_filters[i];
-    e = hipMemcpyAsync(h->dFilt.get(), st, sizeof(float) * nft, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    RS_HIP(hipMemcpyAsync(h->dFilt.get(), st, sizeof(float) * nft, hipMemcpyHostToDevice, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));   // the staging is free again
     for (int m = 0; m < B; ++m) st[m] = (float)(global_inhibition ? global_inhibition[m] : p->global_inhibition);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->dInhib.get(), st, sizeof(float) * B, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->dState.get(), 0, sizeof(float) * (size_t)B * N, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        rs::set_error("ensemble upload failed: %s", hipGetErrorString(e));
-        return fail(RS_ERR_HIP);
-    }
-    *out = h;
+    RS_HIP(hipMemcpyAsync(h->dInhib.get(), st, sizeof(float) * B, hipMemcpyHostToDevice, h->stream.get()));
+    RS_HIP(hipMemsetAsync(h->dState.get(), 0, sizeof(float) * (size_t)B * N, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
+    *out = owner.release();
     return RS_OK;
 }
 
@@ -416,11 +404,8 @@ int rs_pce_destroy(rs_pce* h) {
     if (!h) return RS_OK;
     (void)hipSetDevice(h->device);
     // queued work that failed after a call returned is reported here, not dropped
-    const hipError_t se = h->stream ? hipStreamSynchronize(h->stream) : hipSuccess;
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;  // (the buffers go with their members)
+    const hipError_t se = rs::sync_streams({h->stream.get()});
+    delete h;  // (the streams and events, then the buffers, go with their members)
     RS_CHECK(se == hipSuccess, RS_ERR_HIP, "work queued before rs_pce_destroy failed: %s", hipGetErrorString(se));
     return RS_OK;
 }
@@ -458,7 +443,7 @@ int rs_pce_run(rs_pce* h, int n, const int32_t* ox, const int32_t* oy, const int
     const int nchunks = rs::pce_chunk_count(n, K);
     // (queued launches of an earlier call may still read the blocks a growth would free)
     if (steps * rb > h->hCtl.capacity() || (size_t)B * K * rb > h->dCtl[0].capacity() || 3 * steps > h->dOut.capacity())
-        RS_HIP(hipStreamSynchronize(h->stream));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
     RS_TRY(h->hCtl.reserve(steps * rb, hipHostMallocDefault, "ensemble control"));
     for (auto& d : h->dCtl) RS_TRY(d.reserve((size_t)B * K * rb, "ensemble control"));
     RS_TRY(h->dOut.reserve(3 * steps, "ensemble peaks"));
@@ -475,25 +460,25 @@ int rs_pce_run(rs_pce* h, int n, const int32_t* ox, const int32_t* oy, const int
             }
     }
     const bool timed = h->timing;
-    if (timed) RS_HIP(hipEventRecord(h->ev[0], h->stream));
+    if (timed) RS_HIP(hipEventRecord(h->ev[0].get(), h->stream.get()));
     size_t off = 0;
     for (int c = 0; c < nchunks; ++c) {
         int first, count;
         rs::pce_chunk(n, K, c, &first, &count);
         const size_t bytes = (size_t)B * count * rb;
         unsigned char* d = h->dCtl[c & 1].get();
-        RS_HIP(hipMemcpyAsync(d, h->hCtl.get() + off, bytes, hipMemcpyHostToDevice, h->stream));
+        RS_HIP(hipMemcpyAsync(d, h->hCtl.get() + off, bytes, hipMemcpyHostToDevice, h->stream.get()));
         off += bytes;
-        hipLaunchKernelGGL(pce_run_kernel, dim3(B), dim3(PCE_THREADS), h->fit.total, h->stream, h->args,
+        hipLaunchKernelGGL(pce_run_kernel, dim3(B), dim3(PCE_THREADS), h->fit.total, h->stream.get(), h->args,
                            h->dState.get(), h->dInhib.get(), h->dFilt.get(), d, count, n, first, h->dOut.get());
         RS_HIP(hipGetLastError());
     }
     if (timed) {
-        RS_HIP(hipEventRecord(h->ev[1], h->stream));
+        RS_HIP(hipEventRecord(h->ev[1].get(), h->stream.get()));
         h->timed = true;
     }
-    RS_HIP(hipMemcpyAsync(h->hOut.get(), h->dOut.get(), sizeof(int32_t) * 3 * steps, hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipMemcpyAsync(h->hOut.get(), h->dOut.get(), sizeof(int32_t) * 3 * steps, hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     std::memcpy(out_xyz, h->hOut.get(), sizeof(int32_t) * 3 * steps);
     return RS_OK;
 }
@@ -505,7 +490,7 @@ int rs_pce_inject(rs_pce* h, int member, double energy, int x, int y, int th) {
     RS_CHECK(x >= 0 && x < h->X && y >= 0 && y < h->Y && th >= 0 && th < h->TH, RS_ERR_ARG,
              "cell (%d, %d, %d) outside grid (%d, %d, %d)", x, y, th, h->X, h->Y, h->TH);
     RS_HIP(hipSetDevice(h->device));
-    hipLaunchKernelGGL(pce_inject_kernel, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, h->dState.get(), h->B,
+    hipLaunchKernelGGL(pce_inject_kernel, dim3((h->B + 255) / 256), dim3(256), 0, h->stream.get(), h->dState.get(), h->B,
                        (int)h->N, member, (x * h->Y + y) * h->TH + th, (float)energy);
     RS_HIP(hipGetLastError());
     return RS_OK;
@@ -516,11 +501,11 @@ int rs_pce_get_max(rs_pce* h, int32_t* out_xyz) {
     RS_CHECK(h, RS_ERR_STATE, "null ensemble handle");
     RS_CHECK(out_xyz, RS_ERR_ARG, "null argument");
     RS_HIP(hipSetDevice(h->device));
-    hipLaunchKernelGGL(pce_argmax_kernel, dim3(h->B), dim3(PCE_ARGMAX_THREADS), 0, h->stream, h->dState.get(),
+    hipLaunchKernelGGL(pce_argmax_kernel, dim3(h->B), dim3(PCE_ARGMAX_THREADS), 0, h->stream.get(), h->dState.get(),
                        (int)h->N, h->Y, h->TH, h->dOut.get());
     RS_HIP(hipGetLastError());
-    RS_HIP(hipMemcpyAsync(h->hOut.get(), h->dOut.get(), sizeof(int32_t) * 3 * h->B, hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipMemcpyAsync(h->hOut.get(), h->dOut.get(), sizeof(int32_t) * 3 * h->B, hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     std::memcpy(out_xyz, h->hOut.get(), sizeof(int32_t) * 3 * h->B);
     return RS_OK;
 }
@@ -534,11 +519,11 @@ int rs_pce_read(rs_pce* h, int first, int count, double* volumes) {
     RS_CHECK(volumes, RS_ERR_ARG, "null argument");
     RS_HIP(hipSetDevice(h->device));
     const size_t cells = (size_t)count * h->N;
-    if (cells > h->hState.capacity()) RS_HIP(hipStreamSynchronize(h->stream));
+    if (cells > h->hState.capacity()) RS_HIP(hipStreamSynchronize(h->stream.get()));
     RS_TRY(h->hState.reserve(cells, hipHostMallocDefault, "ensemble staging"));
     RS_HIP(hipMemcpyAsync(h->hState.get(), h->dState.get() + (size_t)first * h->N, sizeof(float) * cells,
-                          hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+                          hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     const float* st = h->hState.get();
     for (size_t i = 0; i < cells; ++i) volumes[i] = (double)st[i];
     return RS_OK;
@@ -558,13 +543,13 @@ int rs_pce_write(rs_pce* h, int first, int count, const double* volumes) {
             return RS_ERR_ARG;
         }
     RS_HIP(hipSetDevice(h->device));
-    RS_HIP(hipStreamSynchronize(h->stream));   // the staging is free, a growth frees nothing in use
+    RS_HIP(hipStreamSynchronize(h->stream.get()));   // the staging is free, a growth frees nothing in use
     RS_TRY(h->hState.reserve(cells, hipHostMallocDefault, "ensemble staging"));
     float* st = h->hState.get();
     for (size_t i = 0; i < cells; ++i) st[i] = (float)volumes[i];
     RS_HIP(hipMemcpyAsync(h->dState.get() + (size_t)first * h->N, st, sizeof(float) * cells, hipMemcpyHostToDevice,
-                          h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+                          h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     return RS_OK;
 }
 
@@ -581,8 +566,8 @@ int rs_pce_last_ms(rs_pce* h, double* ms) {
     *ms = -1.0;
     if (!h->timed) return RS_OK;
     float t = 0.f;
-    RS_HIP(hipEventSynchronize(h->ev[1]));
-    RS_HIP(hipEventElapsedTime(&t, h->ev[0], h->ev[1]));
+    RS_HIP(hipEventSynchronize(h->ev[1].get()));
+    RS_HIP(hipEventElapsedTime(&t, h->ev[0].get(), h->ev[1].get()));
     *ms = t;
     return RS_OK;
 }

@@ -82,10 +82,10 @@ enum class PcForm { Rows, Stream, Cols, Halo };
 
 // The buffers are rs::DevBuf / rs::PinnedBuf members (rs_common.h; untyped ones count bytes,
 // the element being esz wide).  Group capacities: resCap (dRes, hRes, dArgV, dArgI), ctlCap.
+// The stream and the events are rs::Stream / rs::Event owners.
 struct rs_pc {
     int X = 0, Y = 0, TH = 0, prec = RS_PREC_F32, device = 0;
     size_t n = 0, esz = 4;
-    hipStream_t stream = nullptr;
     rs::DevBuf<void> dP;
     rs::DevBuf<void> dQ;
     rs::DevBuf<void> dFilt;
@@ -108,11 +108,9 @@ struct rs_pc {
     rs::DevBuf<double> dScalar;
     SepKernel<float> kf{};
     SepKernel<double> kd{};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float lastMs = 0.f;
     bool profiling = false;  // HIP events around the whole call (device_ms)
     bool profKernels = false;  // ... and around every launch (kernel_ms; the events add gaps)
-    std::vector<hipEvent_t> evPool;
     double kernelMs[2] = {0.0, 0.0};
     PcForm form = PcForm::Rows;  // the step-kernel family (pc_choose_form); its geometry below
     int rowsYP = 0;         // rows: the kernels' YP instance, 64 (Y <= 64) or 128 (Y <= 128)
@@ -145,6 +143,10 @@ struct rs_pc {
     // device for the call's same-as injections and in pinned memory for the host
     rs::DevBuf<unsigned> dInj;
     rs::PinnedBuf<unsigned> hInj;
+    // the owners come after the buffers: members go in reverse order, streams and events first
+    rs::Stream stream;
+    rs::Event ev0, ev1;             // around the whole call (profiling)
+    std::vector<rs::Event> evPool;  // around every launch (profKernels; pc_ensure_events)
 };
 
 namespace {
@@ -175,7 +177,7 @@ int pc_grow_steps(rs_pc* h, int n, bool ctl = true) {
         RS_TRY(h->dRes.reserve((size_t)RES_SLOTS * cap));
         // every slot starts zeroed (the excitation's block 0 zeroes a step's slots again
         // before its path kernel max-reduces into them; no step ever reads freed data)
-        RS_HIP(hipMemsetAsync(h->dRes.get(), 0, sizeof(unsigned long long) * RES_SLOTS * cap, h->stream));
+        RS_HIP(hipMemsetAsync(h->dRes.get(), 0, sizeof(unsigned long long) * RES_SLOTS * cap, h->stream.get()));
         // the export kernel stores each step's key here with a system-scope store:
         // fine-grained (coherent) host memory, so the store is visible once the stream
         // has synchronised; pc_run_impl also checks a sentinel per step (RES_NONE)
@@ -197,12 +199,12 @@ int pc_grow_steps(rs_pc* h, int n, bool ctl = true) {
     return RS_OK;
 }
 
+// A pool of `need` events at least.  The missing ones are created whole or not at all: a
+// refused creation leaves the pool at its old size.
 int pc_ensure_events(rs_pc* h, size_t need) {
-    while (h->evPool.size() < need) {
-        hipEvent_t e;
-        RS_HIP(hipEventCreate(&e));
-        h->evPool.push_back(e);
-    }
+    std::vector<rs::Event> fresh(need > h->evPool.size() ? need - h->evPool.size() : 0);
+    for (rs::Event& e : fresh) RS_TRY(e.create());
+    for (rs::Event& e : fresh) h->evPool.push_back(std::move(e));
     return RS_OK;
 }
 
@@ -333,7 +335,7 @@ int pc_launch_halo_finish(rs_pc* h, int src_buf, int part_half, const HaloFinish
     float* buf[2] = {static_cast<float*>(h->dP.get()), static_cast<float*>(h->dQ.get())};
     const int n4 = (int)(h->n / 4), nb = hf_finish_blocks(h);
     if (o.nexp > 0) std::memset(h->hKey.get(), 0, sizeof(unsigned long long) * nb);
-    hipLaunchKernelGGL(pc_halo_finish, dim3(nb), dim3(256), 0, h->stream, buf[src_buf], buf[0], n4,
+    hipLaunchKernelGGL(pc_halo_finish, dim3(nb), dim3(256), 0, h->stream.get(), buf[src_buf], buf[0], n4,
                        h->dPart.get() + (size_t)part_half * h->nPart, h->nPart, o.slot, h->dRes.get(), o.nexp,
                        h->hRes.dev(), o.nexp > 0 ? h->hKey.dev() : nullptr, o.xp, (int)(h->n * sizeof(float)),
                        o.flag, o.seq);
@@ -351,7 +353,7 @@ int pc_launch_halo_step(rs_pc* h, const float* src, float* dst, const double* pa
                         double* part_out, unsigned long long* prev_slot, unsigned long long* slot,
                         const PcCtlHalo& c, unsigned long long* rec) {
     const int nblk = h->cgx * h->cgy;
-    hf_launch<EXC>(h->TH, dim3(nblk), h->stream, src, hf_pack(h->X, h->Y), hf_pack(h->cgx, nblk),
+    hf_launch<EXC>(h->TH, dim3(nblk), h->stream.get(), src, hf_pack(h->X, h->Y), hf_pack(h->cgx, nblk),
                    hf_pack(c.ux, c.uy), hf_pack(c.uw, c.uh), hf_magic(h->cgx), hf_magic(c.uh), part_in, npart_in, dst,
                    part_out, prev_slot, slot, static_cast<const float*>(h->dFilt.get()), h->nf, c, h->kf, rec);
     RS_HIP(hipGetLastError());
@@ -372,7 +374,7 @@ int pc_launch_export(rs_pc* h, double* dst, bool may_poll, int* nb, unsigned* se
     *seq = fl ? pc_next_seq(h) : 0u;
     pc_by_prec(h, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((pc_export2_kernel<T>), dim3(xnb), dim3(NT), 0, h->stream,
+        hipLaunchKernelGGL((pc_export2_kernel<T>), dim3(xnb), dim3(NT), 0, h->stream.get(),
                            static_cast<const T*>(h->dP.get()), dst, h->X, h->Y, h->TH, (int)pc_thfast(h),
                            fl ? h->hFlag.dev() : nullptr, *seq);
     });
@@ -392,7 +394,7 @@ int pc_launch_peak(rs_pc* h, const void* P, const unsigned long long* slot, cons
                    const unsigned* bidx, int nb, int s) {
     pc_by_prec(h, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((pc_peak_kernel<T>), dim3(1), dim3(64), 0, h->stream, static_cast<const T*>(P), h->X,
+        hipLaunchKernelGGL((pc_peak_kernel<T>), dim3(1), dim3(64), 0, h->stream.get(), static_cast<const T*>(P), h->X,
                            h->Y, h->TH, (int)pc_thfast(h), h->peakR, slot, static_cast<const T*>(bmax), bidx, nb,
                            h->dPeakTab.get(), h->hPeak.dev() + 6 * (size_t)s);
     });
@@ -406,7 +408,7 @@ int pc_launch_argmax_blocks(rs_pc* h, int* nb_out) {
     *nb_out = nb;
     pc_by_prec(h, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((pc_argmax_blocks<T>), dim3(nb), dim3(NT), 0, h->stream, static_cast<const T*>(h->dP.get()),
+        hipLaunchKernelGGL((pc_argmax_blocks<T>), dim3(nb), dim3(NT), 0, h->stream.get(), static_cast<const T*>(h->dP.get()),
                            h->X, h->Y, h->TH, static_cast<T*>(h->dBmax.get()), h->dBidx.get(), (int)pc_thfast(h));
     });
     RS_HIP(hipGetLastError());
@@ -441,7 +443,7 @@ int pc_grow_inj(rs_pc* h, int ni) {
     const size_t cap = rs::grown<size_t>(0, (size_t)ni, 64);
     RS_TRY(h->hInj.reserve(cap, PC_FINE));
     RS_TRY(h->dInj.reserve(cap));
-    RS_HIP(hipMemsetAsync(h->dInj.get(), 0xFF, sizeof(unsigned) * cap, h->stream));
+    RS_HIP(hipMemsetAsync(h->dInj.get(), 0xFF, sizeof(unsigned) * cap, h->stream.get()));
     return RS_OK;
 }
 
@@ -471,7 +473,7 @@ int pc_inject_point(rs_pc* h, const PcInj& inj, int* cur, int s, PcKeySrc key) {
         }
         pc_by_prec(h, [&](auto t) {
             using T = decltype(t);
-            hipLaunchKernelGGL((pc_inject_run_kernel<T>), dim3(1), dim3(64), 0, h->stream, static_cast<T*>(h->dP.get()),
+            hipLaunchKernelGGL((pc_inject_run_kernel<T>), dim3(1), dim3(64), 0, h->stream.get(), static_cast<T*>(h->dP.get()),
                                h->X, h->Y, h->TH, (int)pc_thfast(h), src, arg, key.slot, static_cast<const T*>(key.bmax),
                                key.bidx, key.nb, h->dInj.get(), h->hInj.dev(), i, inj.energy[i]);
         });
@@ -488,7 +490,7 @@ int pc_end_call(rs_pc* h, int n, int32_t* out_xyz) {
         RS_CHECK(h->hRes.get()[s] != RES_NONE, RS_ERR_HIP,
                  "step %d of %d: its argmax key did not reach the host result buffer after the "
                  "stream synchronised", s, n);
-    if (h->profiling) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
+    if (h->profiling) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0.get(), h->ev1.get()));
     else h->lastMs = 0.f;  // the call-bracketing events are recorded only while profiling
     if (out_xyz)
         for (int s = 0; s < n; ++s) decode_xyz(h, h->hRes.get()[s], out_xyz + 3 * (size_t)s);
@@ -519,7 +521,7 @@ int pc_halo_settle_read(rs_pc* h, double* xp_dev, bool* done) {
     const bool fl = pc_flags_ok(h, nb);
     const unsigned seq = fl ? pc_next_seq(h) : 0u;
     RS_TRY(pc_launch_halo_finish(h, h->haloCur, h->haloPart, {nullptr, 0, xp_dev, fl ? h->hFlag.dev() : nullptr, seq}));
-    if (!(fl && pc_poll_flags(h, nb, seq))) RS_HIP(hipStreamSynchronize(h->stream));
+    if (!(fl && pc_poll_flags(h, nb, seq))) RS_HIP(hipStreamSynchronize(h->stream.get()));
     *done = true;
     return RS_OK;
 }
@@ -562,7 +564,7 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
                                                       : HaloEnd::DevRecords;
     const bool lazy = end != HaloEnd::Finish;
     if (end == HaloEnd::HostRecords) std::memset(h->hRec.get(), 0, sizeof(unsigned long long) * 2 * h->nPart);
-    if (h->profiling) RS_HIP(hipEventRecord(h->ev0, h->stream));
+    if (h->profiling) RS_HIP(hipEventRecord(h->ev0.get(), h->stream.get()));
 
     // 1. the steps
     float* buf[2] = {static_cast<float*>(h->dP.get()), static_cast<float*>(h->dQ.get())};
@@ -588,10 +590,10 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         unsigned long long* const slot = h->dRes.get() + (size_t)s * RES_SLOTS;
         unsigned long long* rec = nullptr;   // the last launch's records, where the ending reads them
         if (lazy && s == n - 1) rec = end == HaloEnd::HostRecords ? h->hRec.dev() : h->dRec.get();
-        if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s], h->stream));
+        if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s].get(), h->stream.get()));
         RS_TRY(pc_launch_halo_step<false>(h, buf[cb], buf[cb ^ 1], part[pend ? ph : 0], pend ? h->nPart : 0,
                                           part[ph ^ 1], point ? nullptr : prev, slot, c, rec));
-        if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s + 1], h->stream));
+        if (pk) RS_HIP(hipEventRecord(h->evPool[2 * s + 1].get(), h->stream.get()));
         // step s-1's key is complete now (this launch reduced it into slot - RES_SLOTS from the
         // state it loaded), and its U stays in the buffer this launch read until launch s+1
         // overwrites it: the peak launch of step s-1 goes between the two
@@ -609,9 +611,9 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     // own export: pc_halo_finish stores the words of steps 0 .. n-2 itself, and every block
     // its key of step n-1 into hKey, reduced below once the launch has been waited for
     const bool own_export = end == HaloEnd::Finish && !skipped && n <= HF_EXP_MAX;
-    if (pk) RS_HIP(hipEventRecord(h->evPool[2 * n], h->stream));
+    if (pk) RS_HIP(hipEventRecord(h->evPool[2 * n].get(), h->stream.get()));
     if (end == HaloEnd::DevRecords && !skipped) {
-        hipLaunchKernelGGL(pc_halo_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes.get(), n,
+        hipLaunchKernelGGL(pc_halo_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream.get(), h->dRes.get(), n,
                            h->dRec.get(), h->nPart, h->hRes.dev());
         RS_HIP(hipGetLastError());
     }
@@ -622,7 +624,7 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         // the injections behind the last step, on the state the pass has just settled and keyed
         if (inj) RS_TRY(pc_inject_point(h, *inj, &icur, n, PcKeySrc{last_slot, nullptr, nullptr, 0}));
         if (!skipped && !own_export) {
-            hipLaunchKernelGGL(pc_res_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream, h->dRes.get(), n,
+            hipLaunchKernelGGL(pc_res_export, dim3(n < 1024 ? n : 1024), dim3(64), 0, h->stream.get(), h->dRes.get(), n,
                                h->hRes.dev());
             RS_HIP(hipGetLastError());
         }
@@ -633,8 +635,8 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         h->haloPart = pl;
     }
     h->dbgSkipExport = false;
-    if (pk) RS_HIP(hipEventRecord(h->evPool[2 * n + 1], h->stream));
-    if (h->profiling) RS_HIP(hipEventRecord(h->ev1, h->stream));
+    if (pk) RS_HIP(hipEventRecord(h->evPool[2 * n + 1].get(), h->stream.get()));
+    if (h->profiling) RS_HIP(hipEventRecord(h->ev1.get(), h->stream.get()));
 
     // 3. the wait
     // A one-step call returns as soon as every block's record has reached the pinned host
@@ -663,7 +665,7 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
     // nothing but the key words or flagged volume slices, and the sums are plain stores of the
     // peak launches, visible to the host once the stream has synchronised.  Nor does a call
     // with injections: it finishes without xp, and its resolved cells are plain stores too.)
-    if (!polled) RS_HIP(hipStreamSynchronize(h->stream));
+    if (!polled) RS_HIP(hipStreamSynchronize(h->stream.get()));
     if (sums) std::memcpy(sums, h->hPeak.get(), sizeof(double) * 6 * (size_t)n);
 
     // 4. the last step's key
@@ -683,9 +685,9 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         // (its slots were zeroed by the last launch and nothing has reduced into them)
         last = RES_NONE;
         RS_TRY(pc_launch_halo_finish(h, cl, pl, {last_slot}));
-        hipLaunchKernelGGL(pc_res_export, dim3(1), dim3(64), 0, h->stream, last_slot, 1, h->hRes.dev() + (n - 1));
+        hipLaunchKernelGGL(pc_res_export, dim3(1), dim3(64), 0, h->stream.get(), last_slot, 1, h->hRes.dev() + (n - 1));
         RS_HIP(hipGetLastError());
-        if (!(poll_env && pc_poll_words(h, n - 1, n))) RS_HIP(hipStreamSynchronize(h->stream));
+        if (!(poll_env && pc_poll_words(h, n - 1, n))) RS_HIP(hipStreamSynchronize(h->stream.get()));
         ++h->haloAmbig;
     }
     RS_TRY(pc_end_call(h, n, out_xyz));
@@ -693,11 +695,11 @@ int pc_run_halo(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int
         h->kernelMs[0] = h->kernelMs[1] = 0.0;
         for (int s = 0; s < n; ++s) {
             float a = 0.f;
-            RS_HIP(hipEventElapsedTime(&a, h->evPool[2 * s], h->evPool[2 * s + 1]));
+            RS_HIP(hipEventElapsedTime(&a, h->evPool[2 * s].get(), h->evPool[2 * s + 1].get()));
             h->kernelMs[0] += a;
         }
         float b = 0.f;
-        RS_HIP(hipEventElapsedTime(&b, h->evPool[2 * n], h->evPool[2 * n + 1]));
+        RS_HIP(hipEventElapsedTime(&b, h->evPool[2 * n].get(), h->evPool[2 * n + 1].get()));
         h->kernelMs[1] = b;
     }
     return RS_OK;
@@ -733,15 +735,15 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
     // excitation, then path integration, each between its profiling events; without a
     // control the excitation alone (rs_pc_excite() normalises with pc_scale_kernel)
     auto two = [&](auto&& excite, auto&& path) -> int {
-        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base], h->stream));
+        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base].get(), h->stream.get()));
         excite();
         RS_HIP(hipGetLastError());
-        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 1], h->stream));
+        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 1].get(), h->stream.get()));
         if (!ctl) return RS_OK;
-        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 2], h->stream));
+        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 2].get(), h->stream.get()));
         path();
         RS_HIP(hipGetLastError());
-        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 3], h->stream));
+        if (prof_base >= 0) RS_HIP(hipEventRecord(h->evPool[prof_base + 3].get(), h->stream.get()));
         return RS_OK;
     };
     switch (h->form) {
@@ -757,10 +759,10 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
             constexpr bool DMA = FIX != 0 && std::is_same<CTL, PcCtlInline>::value;
             constexpr int PTHM = FIX != 0 && !DMA ? co_thmax<T>() : THM;
             return two([&] { hipLaunchKernelGGL((pc_excite_cols<T, CO_TX, CO_TY, NW, THM, CHUNK, FIX>), g, dim3(64 * NW), 0,
-                                                h->stream, P, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x, Q, part, slot,
+                                                h->stream.get(), P, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x, Q, part, slot,
                                                 h->coKC, k); },
                        [&] { hipLaunchKernelGGL((pc_path_cols<T, CO_TX, CO_TY, NW, PTHM, CHUNK, CTL, DMA ? FIX : 0>), g,
-                                                dim3(64 * NW), 0, h->stream, Q, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x,
+                                                dim3(64 * NW), 0, h->stream.get(), Q, h->X, h->Y, h->TH, h->cgx, h->cgy, (int)g.x,
                                                 Pn, part, h->nPart, filt, h->nf, *ctl, slot, bmax, bidx, h->coKC); });
         };
         const bool whole = h->coKC >= h->TH;
@@ -775,9 +777,9 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
         const dim3 grid(G.gx * G.gy * G.gz), block(64 * h->swr * h->swc);
         return with_stream_variant(h->sbx, h->swr, h->swc, [&](auto bx, auto wr, auto wc) -> int {
             constexpr int BX = decltype(bx)::value, WR = decltype(wr)::value, WC = decltype(wc)::value;
-            return two([&] { hipLaunchKernelGGL((pc_excite_stream<T, BX, WR, WC>), grid, block, 0, h->stream, P, Q, part,
+            return two([&] { hipLaunchKernelGGL((pc_excite_stream<T, BX, WR, WC>), grid, block, 0, h->stream.get(), P, Q, part,
                                                 slot, h->X, h->Y, h->TH, G, k); },
-                       [&] { hipLaunchKernelGGL((pc_path_stream<T, BX, WR, WC, CTL>), grid, block, 0, h->stream, Q, Pn, part,
+                       [&] { hipLaunchKernelGGL((pc_path_stream<T, BX, WR, WC, CTL>), grid, block, 0, h->stream.get(), Q, Pn, part,
                                                 h->nPart, filt, h->nf, *ctl, slot, bmax, bidx, h->X, h->Y, h->TH, G); });
         });
     }
@@ -785,9 +787,9 @@ int pc_launch_step(rs_pc* h, const StepOut& so, const CTL* ctl, int prof_base) {
         const dim3 g((h->X + RT_BX - 1) / RT_BX, (h->TH + RT_BK - 1) / RT_BK);
         auto rows = [&](auto yp) -> int {
             constexpr int YP = decltype(yp)::value;
-            return two([&] { hipLaunchKernelGGL((pc_excite_rows<T, YP>), g, dim3(RT_NT), 0, h->stream, P, Q, part, slot,
+            return two([&] { hipLaunchKernelGGL((pc_excite_rows<T, YP>), g, dim3(RT_NT), 0, h->stream.get(), P, Q, part, slot,
                                                 h->X, h->Y, h->TH, k); },
-                       [&] { hipLaunchKernelGGL((pc_path_rows<T, YP, CTL>), g, dim3(RT_NT), 0, h->stream, Q, Pn, part,
+                       [&] { hipLaunchKernelGGL((pc_path_rows<T, YP, CTL>), g, dim3(RT_NT), 0, h->stream.get(), Q, Pn, part,
                                                 h->nPart, filt, h->nf, *ctl, slot, bmax, bidx, h->X, h->Y, h->TH); });
         };
         return h->rowsYP == 64 ? rows(Int<64>{}) : rows(Int<128>{});
@@ -817,11 +819,11 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     if (!inline_ctl) {
         RS_TRY(pc_pack_ctl(h, n, ox, oy, fidx, zf));
         RS_HIP(hipMemcpyAsync(h->dCtl.get(), h->hCtl.get(), h->ctlStride * n, hipMemcpyHostToDevice,
-                              h->stream));
+                              h->stream.get()));
     }
     const bool pk = h->profiling && h->profKernels;
     if (pk) RS_TRY(pc_ensure_events(h, (size_t)4 * n));
-    if (h->profiling) RS_HIP(hipEventRecord(h->ev0, h->stream));
+    if (h->profiling) RS_HIP(hipEventRecord(h->ev0.get(), h->stream.get()));
     int icur = 0;   // the next injection
     for (int s = 0; s < n; ++s) {
         const int pb = pk ? 4 * s : -1;
@@ -846,7 +848,7 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     }
     if (inj) RS_TRY(pc_inject_point(h, *inj, &icur, n, step_key(h, step_out(h, n - 1))));
     if (h->prec == RS_PREC_F64) {
-        hipLaunchKernelGGL((pc_argmax_steps<double>), dim3(n), dim3(NT), 0, h->stream,
+        hipLaunchKernelGGL((pc_argmax_steps<double>), dim3(n), dim3(NT), 0, h->stream.get(),
                            static_cast<const double*>(h->dArgV.get()), h->dArgI.get(), h->nPart, h->dRes.get());
         RS_HIP(hipGetLastError());
     }
@@ -854,7 +856,7 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     const bool skipped = h->dbgSkipExport;
     if (!h->dbgSkipExport) {
         hipLaunchKernelGGL(pc_res_export, dim3(n < 1024 ? n : 1024), dim3(64), 0,
-                           h->stream, h->dRes.get(), n, h->hRes.dev());
+                           h->stream.get(), h->dRes.get(), n, h->hRes.dev());
         RS_HIP(hipGetLastError());
     }
     h->dbgSkipExport = false;
@@ -867,22 +869,22 @@ int pc_run_direct(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const i
     int xnb = 0;
     unsigned seq = 0u;
     if (xp) RS_TRY(pc_launch_export(h, xp, may_poll, &xnb, &seq));
-    if (h->profiling) RS_HIP(hipEventRecord(h->ev1, h->stream));
+    if (h->profiling) RS_HIP(hipEventRecord(h->ev1.get(), h->stream.get()));
     // the result words polled (pc_poll_words), and with an eager readback the volume's
     // flags first (each block's stores released at system scope before its flag), unless
     // the call is profiled, long or its export was withheld (RS_PC_HALO_POLL=0: always the
     // stream synchronisation; RS_PC_HALO_FLAGS=0: for an eager readback)
     const bool polled = may_poll && (xp ? seq != 0u && pc_poll_flags(h, xnb, seq) : true) &&
                         pc_poll_words(h, 0, n);
-    if (!polled) RS_HIP(hipStreamSynchronize(h->stream));
+    if (!polled) RS_HIP(hipStreamSynchronize(h->stream.get()));
     if (sums) std::memcpy(sums, h->hPeak.get(), sizeof(double) * 6 * (size_t)n);
     RS_TRY(pc_end_call(h, n, out_xyz));
     if (pk) {
         h->kernelMs[0] = h->kernelMs[1] = 0.0;
         for (int s = 0; s < n; ++s) {
             float a = 0.f, b = 0.f;
-            RS_HIP(hipEventElapsedTime(&a, h->evPool[4 * s], h->evPool[4 * s + 1]));
-            RS_HIP(hipEventElapsedTime(&b, h->evPool[4 * s + 2], h->evPool[4 * s + 3]));
+            RS_HIP(hipEventElapsedTime(&a, h->evPool[4 * s].get(), h->evPool[4 * s + 1].get()));
+            RS_HIP(hipEventElapsedTime(&b, h->evPool[4 * s + 2].get(), h->evPool[4 * s + 3].get()));
             h->kernelMs[0] += a;
             h->kernelMs[1] += b;
         }
@@ -939,7 +941,7 @@ int pc_run_inj(rs_pc* h, int n, const int32_t* ox, const int32_t* oy, const int3
         int cur = 0;
         RS_TRY(pc_halo_settle(h));
         RS_TRY(pc_inject_point(h, run, &cur, 0, PcKeySrc{}));
-        RS_HIP(hipStreamSynchronize(h->stream));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
     }
     for (int i = 0; i < inj.ni; ++i) {
         const unsigned lin = h->hInj.get()[i];
@@ -1019,11 +1021,11 @@ template <typename T>
 int pc_argmax_queue(rs_pc* h, int* nb_out) {
     RS_TRY(pc_launch_argmax_blocks(h, nb_out));
     const int nb = *nb_out;
-    hipLaunchKernelGGL((pc_argmax_steps<T>), dim3(1), dim3(NT), 0, h->stream,
+    hipLaunchKernelGGL((pc_argmax_steps<T>), dim3(1), dim3(NT), 0, h->stream.get(),
                        static_cast<const T*>(h->dBmax.get()), h->dBidx.get(), nb, h->dRes.get());
     RS_HIP(hipGetLastError());
     RS_HIP(hipMemcpyAsync(h->hRes.get(), h->dRes.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                          h->stream));
+                          h->stream.get()));
     return RS_OK;
 }
 
@@ -1031,7 +1033,7 @@ template <typename T>
 int pc_argmax_impl(rs_pc* h, int32_t* out) {
     int nb = 0;
     RS_TRY(pc_argmax_queue<T>(h, &nb));
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     decode_xyz(h, h->hRes.get()[0], out);
     return RS_OK;
 }
@@ -1258,12 +1260,11 @@ int rs_pc_create(int X, int Y, int TH, const rs_pc_params* p, int device, rs_pc*
     RS_CHECK(p->precision == RS_PREC_F32 || p->precision == RS_PREC_F64, RS_ERR_ARG,
              "precision must be RS_PREC_F32 or RS_PREC_F64");
     RS_CHECK(p->nfilters >= 1 && p->xy_filters, RS_ERR_ARG, "empty path-integration filter table");
-    int ndev = 0;
-    RS_HIP(hipGetDeviceCount(&ndev));
-    RS_CHECK(device >= 0 && device < ndev, RS_ERR_ARG, "device %d not in [0, %d)", device, ndev);
-    RS_HIP(hipSetDevice(device));
+    RS_TRY(rs::use_device(device));
 
-    rs_pc* h = new rs_pc();
+    // one failure exit: rs_pc_destroy takes a handle at any stage
+    std::unique_ptr<rs_pc, int (*)(rs_pc*)> owner(new rs_pc(), rs_pc_destroy);
+    rs_pc* const h = owner.get();
     h->X = X; h->Y = Y; h->TH = TH; h->prec = p->precision; h->device = device;
     h->n = (size_t)X * Y * TH;
     h->esz = p->precision == RS_PREC_F32 ? 4 : 8;
@@ -1271,57 +1272,47 @@ int rs_pc_create(int X, int Y, int TH, const rs_pc_params* p, int device, rs_pc*
     fill_sep(h->kf, p);
     fill_sep(h->kd, p);
     h->ctlStride = rs::round_up(ctl_off_zf(h) + sizeof(double) * 8, 16);
-    if (int st = pc_choose_form(h); st != RS_OK) {
-        delete h;
-        return st;
-    }
+    RS_TRY(pc_choose_form(h));
     h->nBmaxCap = h->nPart > 1024 ? h->nPart : 1024;
 
-    // everything the handle allocates; what a failure leaves behind goes with rs_pc_destroy
-    auto init = [&]() -> int {
-        RS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        RS_TRY(h->dP.reserve(h->n * h->esz));
-        RS_TRY(h->dQ.reserve(h->n * h->esz));
-        RS_HIP(hipMemsetAsync(h->dP.get(), 0, h->n * h->esz, h->stream));  // zeros(shape), :27
-        // Q and the partials are rewritten in full by every excitation before a path
-        // kernel reads them; zeroed anyway so that no launch can see a freed handle's data
-        // (rs_pc_debug(RS_PC_DBG_POISON) + tests/test_posecell_gpu.py check the former)
-        RS_HIP(hipMemsetAsync(h->dQ.get(), 0, h->n * h->esz, h->stream));
-        // (the halo form keeps two steps' partial sums: the one it reads, the one it writes)
-        RS_TRY(h->dPart.reserve((size_t)h->nPart * 2));
-        RS_HIP(hipMemsetAsync(h->dPart.get(), 0, sizeof(double) * h->nPart * 2, h->stream));
-        RS_TRY(h->dRec.reserve(2 * (size_t)h->nPart));
-        // the volume-writing kernels' per-block flags (pc_halo_finish, pc_export2_kernel)
-        RS_TRY(h->hFlag.reserve(HF_FLAGS, PC_FINE));
-        std::memset(h->hFlag.get(), 0, sizeof(unsigned) * HF_FLAGS);
-        if (h->form == PcForm::Halo) {
-            RS_TRY(h->hRec.reserve(2 * (size_t)h->nPart, PC_FINE));
-            RS_TRY(h->hKey.reserve(HF_FLAGS, PC_FINE));
-        }
-        RS_TRY(h->dBmax.reserve(h->esz * h->nBmaxCap));
-        RS_TRY(h->dBidx.reserve((size_t)h->nBmaxCap));
-        RS_TRY(h->dTmp.reserve(h->n));
-        RS_TRY(h->dScalar.reserve(1));
-        RS_TRY(h->dFilt.reserve(h->esz * FT * h->nf));
-        if (h->prec == RS_PREC_F32) {
-            std::vector<float> f(FT * (size_t)h->nf);
-            for (size_t i = 0; i < f.size(); ++i) f[i] = (float)p->xy_filters[i];
-            RS_HIP(hipMemcpy(h->dFilt.get(), f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
-        } else {
-            RS_HIP(hipMemcpy(h->dFilt.get(), p->xy_filters, FT * (size_t)h->nf * sizeof(double),
-                             hipMemcpyHostToDevice));
-        }
-        RS_HIP(hipEventCreate(&h->ev0));
-        RS_HIP(hipEventCreate(&h->ev1));
-        RS_TRY(pc_grow_steps(h, 16));
-        RS_HIP(hipStreamSynchronize(h->stream));
-        return RS_OK;
-    };
-    if (const int st = init(); st != RS_OK) {
-        rs_pc_destroy(h);
-        return st;
+    // everything the handle allocates
+    RS_TRY(h->stream.create());
+    RS_TRY(h->dP.reserve(h->n * h->esz));
+    RS_TRY(h->dQ.reserve(h->n * h->esz));
+    RS_HIP(hipMemsetAsync(h->dP.get(), 0, h->n * h->esz, h->stream.get()));  // zeros(shape), :27
+    // Q and the partials are rewritten in full by every excitation before a path
+    // kernel reads them; zeroed anyway so that no launch can see a freed handle's data
+    // (rs_pc_debug(RS_PC_DBG_POISON) + tests/test_posecell_gpu.py check the former)
+    RS_HIP(hipMemsetAsync(h->dQ.get(), 0, h->n * h->esz, h->stream.get()));
+    // (the halo form keeps two steps' partial sums: the one it reads, the one it writes)
+    RS_TRY(h->dPart.reserve((size_t)h->nPart * 2));
+    RS_HIP(hipMemsetAsync(h->dPart.get(), 0, sizeof(double) * h->nPart * 2, h->stream.get()));
+    RS_TRY(h->dRec.reserve(2 * (size_t)h->nPart));
+    // the volume-writing kernels' per-block flags (pc_halo_finish, pc_export2_kernel)
+    RS_TRY(h->hFlag.reserve(HF_FLAGS, PC_FINE));
+    std::memset(h->hFlag.get(), 0, sizeof(unsigned) * HF_FLAGS);
+    if (h->form == PcForm::Halo) {
+        RS_TRY(h->hRec.reserve(2 * (size_t)h->nPart, PC_FINE));
+        RS_TRY(h->hKey.reserve(HF_FLAGS, PC_FINE));
     }
-    *out = h;
+    RS_TRY(h->dBmax.reserve(h->esz * h->nBmaxCap));
+    RS_TRY(h->dBidx.reserve((size_t)h->nBmaxCap));
+    RS_TRY(h->dTmp.reserve(h->n));
+    RS_TRY(h->dScalar.reserve(1));
+    RS_TRY(h->dFilt.reserve(h->esz * FT * h->nf));
+    if (h->prec == RS_PREC_F32) {
+        std::vector<float> f(FT * (size_t)h->nf);
+        for (size_t i = 0; i < f.size(); ++i) f[i] = (float)p->xy_filters[i];
+        RS_HIP(hipMemcpy(h->dFilt.get(), f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice));
+    } else {
+        RS_HIP(hipMemcpy(h->dFilt.get(), p->xy_filters, FT * (size_t)h->nf * sizeof(double),
+                         hipMemcpyHostToDevice));
+    }
+    RS_TRY(h->ev0.create());
+    RS_TRY(h->ev1.create());
+    RS_TRY(pc_grow_steps(h, 16));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
+    *out = owner.release();
     return RS_OK;
 }
 
@@ -1330,12 +1321,8 @@ int rs_pc_destroy(rs_pc* h) {
     (void)hipSetDevice(h->device);
     // the handle's last queued work: a fault or launch error the early-returning calls
     // left on the stream is reported here instead of being dropped
-    const hipError_t se = h->stream ? hipStreamSynchronize(h->stream) : hipSuccess;
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    for (hipEvent_t e : h->evPool) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;  // (the buffers go with their members)
+    const hipError_t se = rs::sync_streams({h->stream.get()});
+    delete h;  // (the streams and events, then the buffers, go with their members)
     RS_CHECK(se == hipSuccess, RS_ERR_HIP, "work queued before rs_pc_destroy failed: %s", hipGetErrorString(se));
     return RS_OK;
 }
@@ -1379,13 +1366,13 @@ int rs_pc_excite(rs_pc* h) {
     }
     pc_by_prec(h, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((pc_scale_kernel<T>), dim3(64), dim3(NT), 0, h->stream, static_cast<T*>(h->dQ.get()),
+        hipLaunchKernelGGL((pc_scale_kernel<T>), dim3(64), dim3(NT), 0, h->stream.get(), static_cast<T*>(h->dQ.get()),
                            h->n, h->dPart.get(), h->nPart);
     });
     RS_HIP(hipGetLastError());
     // Q has P's layout in every form (the column form: both theta-fastest)
-    RS_HIP(hipMemcpyAsync(h->dP.get(), h->dQ.get(), h->n * h->esz, hipMemcpyDeviceToDevice, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipMemcpyAsync(h->dP.get(), h->dQ.get(), h->n * h->esz, hipMemcpyDeviceToDevice, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     return RS_OK;
 }
 
@@ -1560,8 +1547,8 @@ int rs_pc_set_peak_tables(rs_pc* h, int r, const double* sc_x, const double* sc_
     h->peakR = 0;
     RS_TRY(h->dPeakTab.reserve(tab.size()));
     // (ordered behind any peak launch still queued on the handle's stream)
-    RS_HIP(hipMemcpyAsync(h->dPeakTab.get(), tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipMemcpyAsync(h->dPeakTab.get(), tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     h->peakR = r;
     return RS_OK;
 }
@@ -1577,7 +1564,7 @@ int rs_pc_get_peak(rs_pc* h, int32_t xyz[3], double sums[6]) {
     RS_TRY(pc_by_prec(h, [&](auto t) { return pc_argmax_queue<decltype(t)>(h, &nb); }));
     RS_TRY(pc_launch_peak(h, h->dP.get(), nullptr, h->dBmax.get(), h->dBidx.get(), nb, 0));
     // the stream's completion, not a polled word: the sums are plain stores (pc_run_direct)
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     decode_xyz(h, h->hRes.get()[0], xyz);
     std::memcpy(sums, h->hPeak.get(), sizeof(double) * 6);
     return RS_OK;
@@ -1646,7 +1633,7 @@ int rs_pc_inject(rs_pc* h, double energy, int x, int y, int th) {
     const size_t idx = pc_thfast(h) ? ((size_t)x * h->Y + y) * h->TH + th : ((size_t)th * h->X + x) * h->Y + y;
     pc_by_prec(h, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((pc_inject_kernel<T>), dim3(1), dim3(64), 0, h->stream, static_cast<T*>(h->dP.get()), idx,
+        hipLaunchKernelGGL((pc_inject_kernel<T>), dim3(1), dim3(64), 0, h->stream.get(), static_cast<T*>(h->dP.get()), idx,
                            energy);
     });
     RS_HIP(hipGetLastError());
@@ -1674,7 +1661,7 @@ int pc_read_volume(rs_pc* h, double* dst) {
     int nb = 0;
     unsigned seq = 0u;
     RS_TRY(pc_launch_export(h, dst, true, &nb, &seq));
-    if (!(seq != 0u && pc_poll_flags(h, nb, seq))) RS_HIP(hipStreamSynchronize(h->stream));
+    if (!(seq != 0u && pc_poll_flags(h, nb, seq))) RS_HIP(hipStreamSynchronize(h->stream.get()));
     return RS_OK;
 }
 
@@ -1707,14 +1694,14 @@ int rs_pc_write(rs_pc* h, const double* host) {
     RS_HIP(hipSetDevice(h->device));
     h->haloPend = false;  // (halo: the whole state is replaced)
     h->haloCur = 0;
-    RS_HIP(hipMemcpyAsync(h->dTmp.get(), host, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
+    RS_HIP(hipMemcpyAsync(h->dTmp.get(), host, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream.get()));
     pc_by_prec(h, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((pc_import_kernel<T>), dim3(256), dim3(NT), 0, h->stream, h->dTmp.get(),
+        hipLaunchKernelGGL((pc_import_kernel<T>), dim3(256), dim3(NT), 0, h->stream.get(), h->dTmp.get(),
                            static_cast<T*>(h->dP.get()), h->X, h->Y, h->TH, (int)pc_thfast(h));
     });
     RS_HIP(hipGetLastError());
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     return RS_OK;
 }
 
@@ -1725,12 +1712,12 @@ int rs_pc_total(rs_pc* h, double* total) {
     RS_TRY(pc_halo_settle(h));  // (halo: a state a call left unnormalised)
     pc_by_prec(h, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((pc_total_kernel<T>), dim3(1), dim3(NT), 0, h->stream, static_cast<const T*>(h->dP.get()),
+        hipLaunchKernelGGL((pc_total_kernel<T>), dim3(1), dim3(NT), 0, h->stream.get(), static_cast<const T*>(h->dP.get()),
                            h->n, h->dScalar.get());
     });
     RS_HIP(hipGetLastError());
-    RS_HIP(hipMemcpyAsync(total, h->dScalar.get(), sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipMemcpyAsync(total, h->dScalar.get(), sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     return RS_OK;
 }
 
@@ -1774,16 +1761,16 @@ int rs_pc_debug(rs_pc* h, int op) {
     if (op == RS_PC_DBG_POISON) {
         // every buffer a step writes before it reads: all bits set (NaN volumes, the
         // largest possible argmax key in every slot of every step)
-        RS_HIP(hipMemsetAsync(h->dQ.get(), 0xFF, h->n * h->esz, h->stream));
-        RS_HIP(hipMemsetAsync(h->dPart.get(), 0xFF, sizeof(double) * h->nPart * 2, h->stream));
-        RS_HIP(hipMemsetAsync(h->dRes.get(), 0xFF, sizeof(unsigned long long) * RES_SLOTS * h->resCap, h->stream));
-        RS_HIP(hipMemsetAsync(h->dBmax.get(), 0xFF, h->esz * h->nBmaxCap, h->stream));
-        RS_HIP(hipMemsetAsync(h->dBidx.get(), 0xFF, sizeof(unsigned) * h->nBmaxCap, h->stream));
-        if (h->dArgV.get()) RS_HIP(hipMemsetAsync(h->dArgV.get(), 0xFF, h->esz * (size_t)h->resCap * h->nPart, h->stream));
+        RS_HIP(hipMemsetAsync(h->dQ.get(), 0xFF, h->n * h->esz, h->stream.get()));
+        RS_HIP(hipMemsetAsync(h->dPart.get(), 0xFF, sizeof(double) * h->nPart * 2, h->stream.get()));
+        RS_HIP(hipMemsetAsync(h->dRes.get(), 0xFF, sizeof(unsigned long long) * RES_SLOTS * h->resCap, h->stream.get()));
+        RS_HIP(hipMemsetAsync(h->dBmax.get(), 0xFF, h->esz * h->nBmaxCap, h->stream.get()));
+        RS_HIP(hipMemsetAsync(h->dBidx.get(), 0xFF, sizeof(unsigned) * h->nBmaxCap, h->stream.get()));
+        if (h->dArgV.get()) RS_HIP(hipMemsetAsync(h->dArgV.get(), 0xFF, h->esz * (size_t)h->resCap * h->nPart, h->stream.get()));
         if (h->dArgI.get())
-            RS_HIP(hipMemsetAsync(h->dArgI.get(), 0xFF, sizeof(unsigned) * (size_t)h->resCap * h->nPart, h->stream));
+            RS_HIP(hipMemsetAsync(h->dArgI.get(), 0xFF, sizeof(unsigned) * (size_t)h->resCap * h->nPart, h->stream.get()));
         for (int s = 0; s < h->resCap; ++s) h->hRes.get()[s] = ~0ull;
-        RS_HIP(hipStreamSynchronize(h->stream));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
         return RS_OK;
     }
     if (op == RS_PC_DBG_SKIP_EXPORT) {

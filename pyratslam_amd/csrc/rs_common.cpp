@@ -37,6 +37,31 @@ hipError_t pinned_alloc(void** ptr, void** dev, size_t bytes, unsigned flags) {
 
 hipError_t pinned_free(void* ptr) { return forget(hipHostFree(ptr)); }
 
+hipError_t stream_create(hipStream_t* s) { return forget(hipStreamCreateWithFlags(s, hipStreamNonBlocking)); }
+
+hipError_t stream_destroy(hipStream_t s) { return forget(hipStreamDestroy(s)); }
+
+hipError_t event_create(hipEvent_t* e, unsigned flags) { return forget(hipEventCreateWithFlags(e, flags)); }
+
+hipError_t event_destroy(hipEvent_t e) { return forget(hipEventDestroy(e)); }
+
+int use_device(int device) {
+    int ndev = 0;
+    RS_HIP(hipGetDeviceCount(&ndev));
+    RS_CHECK(device >= 0 && device < ndev, RS_ERR_ARG, "device %d not in [0, %d)", device, ndev);
+    RS_HIP(hipSetDevice(device));
+    return RS_OK;
+}
+
+hipError_t sync_streams(std::initializer_list<hipStream_t> streams) {
+    hipError_t first = hipSuccess;
+    for (hipStream_t s : streams) {
+        const hipError_t e = s ? hipStreamSynchronize(s) : hipSuccess;
+        if (first == hipSuccess) first = e;
+    }
+    return first;
+}
+
 }  // namespace rs
 
 extern "C" {

@@ -1,5 +1,6 @@
-// Shared helpers of libratslam_hip: error state, HIP call checking and the two owning
-// buffer types (rs::DevBuf, rs::PinnedBuf) that hold every handle's device and pinned memory.
+// Shared helpers of libratslam_hip: error state, HIP call checking, the two owning buffer
+// types (rs::DevBuf, rs::PinnedBuf) that hold every handle's device and pinned memory, and
+// the two owners (rs::Stream, rs::Event) of its streams and events.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -202,5 +205,70 @@ private:
     T *p_ = nullptr, *d_ = nullptr;
     size_t n_ = 0;
 };
+
+// The library's only calls that create or destroy a stream (always hipStreamNonBlocking) or
+// an event (with the caller's flags), in rs_common.cpp.  A refused call leaves no error
+// behind either.
+hipError_t stream_create(hipStream_t* s);
+hipError_t stream_destroy(hipStream_t s);
+hipError_t event_create(hipEvent_t* e, unsigned flags);
+hipError_t event_destroy(hipEvent_t e);
+
+// Owning, move-only stream (rs::Stream) or event (rs::Event); get() is the raw object a
+// launch, record or wait takes.  create() on an owner that holds an object does nothing, as
+// reserve() within the capacity; a refused create() leaves it empty, get() == nullptr.  A
+// handle declares its owners after its buffers, so that they are destroyed first.  Objects
+// a call creates lazily as a group (a stream and the events recorded on it) are created
+// into locals and move-assigned into the handle once every one exists: the group is whole or
+// absent, and a call after a refused creation creates it again.
+template <class T, hipError_t (*Destroy)(T)>
+class Owned {
+public:
+    Owned() = default;
+    Owned(Owned&& o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+    Owned& operator=(Owned&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = std::exchange(o.p_, nullptr);
+        }
+        return *this;
+    }
+    ~Owned() { reset(); }
+
+    T get() const { return p_; }
+    void reset() {
+        if (p_) (void)Destroy(p_);
+        p_ = nullptr;
+    }
+
+protected:
+    int created(hipError_t e, const char* what) {
+        if (e == hipSuccess) return RS_OK;
+        p_ = nullptr;
+        set_error("creating %s failed: %s", what, hipGetErrorString(e));
+        return RS_ERR_HIP;
+    }
+    T p_ = nullptr;
+};
+
+class Stream : public Owned<hipStream_t, stream_destroy> {
+public:
+    int create(const char* what = "a stream") { return p_ ? RS_OK : created(stream_create(&p_), what); }
+};
+
+class Event : public Owned<hipEvent_t, event_destroy> {
+public:
+    int create(unsigned flags = hipEventDefault, const char* what = "an event") {
+        return p_ ? RS_OK : created(event_create(&p_, flags), what);
+    }
+};
+
+// What every rs_*_create does after its argument checks: `device` within the device count,
+// and current.
+int use_device(int device);
+
+// What every rs_*_destroy does first: synchronise each stream the handle owns (null: not yet
+// created) and return the first error, so that queued work that failed is reported, not dropped.
+hipError_t sync_streams(std::initializer_list<hipStream_t> streams);
 
 }  // namespace rs

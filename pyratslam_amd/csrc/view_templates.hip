@@ -77,7 +77,9 @@ struct QueryForms {
 // group capacities qCap, idxCap, matCap, candCap, frameCap, pruneCap, listCntCap,
 // qpStreamCap, streamCap and upCap keep).  The library (localCap: dLib, dLibP, dLibTs) is
 // copied when it grows, each buffer into a new block before its old one goes, so localCap
-// simply stays until all three have grown.
+// simply stays until all three have grown.  The streams and events are rs::Stream /
+// rs::Event owners; rs_vt_match_stream creates its two groups (the collective stream's, the
+// upload stream's) on first use, each whole or not at all.
 struct rs_vt {
     int H = 0, W = 0, M = 0, WD = 0, HQ = 0;
     // ViewTemplates.match's threshold (view_templates.py:67): a score (< 2^32, exact in
@@ -90,7 +92,6 @@ struct rs_vt {
     int64_t count = 0;     // global number of templates
     int64_t localCap = 0;  // local slots allocated (multiple of 64): dLib, dLibP, dLibTs
     rs::DevBuf<uint4> dLib;
-    hipStream_t stream = nullptr;
     // query staging
     int qCap = 0;
     rs::DevBuf<uint8_t> dQraw;
@@ -101,11 +102,7 @@ struct rs_vt {
     rs::DevBuf<unsigned long long> dBest;
     rs::PinnedBuf<unsigned long long> hBest;  // fine-grained: vt_fetch_keys polls the words the export kernel stores
     bool stagingBusy = false;  // copies from hSrc / hDst queued and not yet known to have run
-    hipStream_t cstream = nullptr;           // rs_vt_match_stream's collective stream
-    hipEvent_t evScan = nullptr, evComm = nullptr;
-    hipStream_t ustream = nullptr;           // rs_vt_match_stream: host batches' upload stream
-    hipEvent_t evUp[2] = {nullptr, nullptr}, evUsed[2] = {nullptr, nullptr};
-    rs::DevBuf<uint8_t> dUp[2];              // ... and its two raw-query group buffers
+    rs::DevBuf<uint8_t> dUp[2];              // rs_vt_match_stream: the upload stream's two raw-query group buffers
     size_t upCap = 0;                        // bytes per group buffer
     rs::DevBuf<uint32_t> dQpStream;          // rs_vt_match_stream: every batch's query planes
     rs::DevBuf<uint32_t> dQsumStream;
@@ -128,7 +125,6 @@ struct rs_vt {
     size_t matCap = 0;
     rs::DevBuf<uint32_t> dMat;
     rs::PinnedBuf<uint32_t> hMat;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timing = false;  // HIP events around every scan (rs_vt_set_timing; off: the keys are polled)
     bool timedScan = false;  // the last scan recorded ev0/ev1
     float lastMs = 0.f;
@@ -207,6 +203,13 @@ struct rs_vt {
     rs::DevBuf<uint8_t> dNormRaw;     // (with qCap) raw uploads and gathers, normalised into dQraw
     rs::DevBuf<uint8_t> dNormStream;  // rs_vt_match_stream: a call's normalised queries (fused, host groups)
     rs::DevBuf<uint8_t> dOffRaw;      // rs_vt_offset_profile: raw host queries, normalised into dOffQ
+    // the owners come after the buffers: members go in reverse order, streams and events first
+    rs::Stream stream;
+    rs::Event ev0, ev1;                      // around a timed scan
+    rs::Stream cstream;                      // rs_vt_match_stream's collective stream (vt_ensure_comm_stream)
+    rs::Event evScan, evComm;
+    rs::Stream ustream;                      // rs_vt_match_stream: host batches' upload stream (vt_ensure_upload_stream)
+    rs::Event evUp[2], evUsed[2];
 };
 
 namespace {
@@ -225,11 +228,11 @@ int vt_realloc_blocks(rs_vt* h, rs::DevBuf<T>& buf, int64_t keep, int64_t blocks
     rs::DevBuf<T> nb;
     const size_t bytes = (size_t)blocks * bb;
     RS_TRY(nb.reserve(bytes / sizeof(T), what));
-    RS_HIP(hipMemsetAsync(nb.get(), 0, bytes, h->stream));
+    RS_HIP(hipMemsetAsync(nb.get(), 0, bytes, h->stream.get()));
     if (buf.get()) {
         if (keep > 0)
-            RS_HIP(hipMemcpyAsync(nb.get(), buf.get(), (size_t)keep * bb, hipMemcpyDeviceToDevice, h->stream));
-        RS_HIP(hipStreamSynchronize(h->stream));
+            RS_HIP(hipMemcpyAsync(nb.get(), buf.get(), (size_t)keep * bb, hipMemcpyDeviceToDevice, h->stream.get()));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
     }
     buf = std::move(nb);
     return RS_OK;
@@ -258,7 +261,7 @@ int vt_grow_lib(rs_vt* h, int64_t need_slots) {
 // stream is synchronised here.  (rs_vt_add uploads the caller's array directly.)
 int vt_qraw_idle(rs_vt* h) {
     if (h->qrawBusy) {
-        RS_HIP(hipStreamSynchronize(h->stream));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
         h->qrawBusy = false;
     }
     return RS_OK;
@@ -365,7 +368,7 @@ uint32_t* vt_compact_for(rs_vt* h, const QueryForms& q, int nq) {
 int vt_normalise(rs_vt* h, const uint8_t* src, uint8_t* dst, size_t n) {
     const int tx = (h->W + VTN_T - 1) / VTN_T, ty = (h->H + VTN_T - 1) / VTN_T;
     hipLaunchKernelGGL(vt_normalise_kernel, dim3((unsigned)(tx * ty), (unsigned)std::min<size_t>(n, 65535)),
-                       dim3(VTN_THREADS), 0, h->stream, src, dst, (int)n, h->H, h->W, h->radius, h->gain, tx);
+                       dim3(VTN_THREADS), 0, h->stream.get(), src, dst, (int)n, h->H, h->W, h->radius, h->gain, tx);
     RS_HIP(hipGetLastError());
     return RS_OK;
 }
@@ -380,7 +383,7 @@ int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
     const QueryForms q = vt_batch_view(h);
     const size_t qb = (size_t)h->H * h->W * nq;
     if (h->radius > 0) {   // raw bytes into the handle's own buffer, normalised into dQraw
-        RS_HIP(hipMemcpyAsync(h->dNormRaw.get(), queries, qb, hipMemcpyHostToDevice, h->stream));
+        RS_HIP(hipMemcpyAsync(h->dNormRaw.get(), queries, qb, hipMemcpyHostToDevice, h->stream.get()));
         RS_TRY(vt_normalise(h, h->dNormRaw.get(), h->dQraw.get(), (size_t)nq));
         return vt_build_forms(h, q, nq);
     }
@@ -393,12 +396,12 @@ int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
         std::memcpy(h->hQraw.get(), queries, qb);
         h->qrawBusy = true;
         uint32_t* const qc = vt_compact_for(h, q, nq);
-        hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(qc ? VT_QC_THREADS : 256), 0, h->stream, h->hQraw.dev(), h->H,
+        hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(qc ? VT_QC_THREADS : 256), 0, h->stream.get(), h->hQraw.dev(), h->H,
                            h->M, q.qp, q.qsum, h->dQraw.get(), q.qsj, qc);
         RS_HIP(hipGetLastError());
         return RS_OK;
     }
-    RS_HIP(hipMemcpyAsync(h->dQraw.get(), queries, qb, hipMemcpyHostToDevice, h->stream));
+    RS_HIP(hipMemcpyAsync(h->dQraw.get(), queries, qb, hipMemcpyHostToDevice, h->stream.get()));
     return vt_build_forms(h, q, nq);
 }
 
@@ -406,14 +409,14 @@ int vt_stage_queries(rs_vt* h, int nq, const uint8_t* queries) {
 // The plane scan reads only the planes; the byte-SWAR forms serve the other scans.
 int vt_build_forms(rs_vt* h, const QueryForms& q, int nq, const uint8_t* src) {
     if (h->metric == RS_VT_METRIC_SAD)
-        hipLaunchKernelGGL(vt_qform_sad_kernel, dim3(nq), dim3(256), 0, h->stream, src, h->H, h->W, h->WD,
+        hipLaunchKernelGGL(vt_qform_sad_kernel, dim3(nq), dim3(256), 0, h->stream.get(), src, h->H, h->W, h->WD,
                            reinterpret_cast<uint32_t*>(h->dQf.get()));
     else if (!h->planar)
-        hipLaunchKernelGGL(vt_qform_kernel, dim3(nq), dim3(256), 0, h->stream, src, h->H, h->W,
+        hipLaunchKernelGGL(vt_qform_kernel, dim3(nq), dim3(256), 0, h->stream.get(), src, h->H, h->W,
                            h->WD, h->M, h->dQf.get(), h->dQsum.get());
     else {
         uint32_t* const qc = vt_compact_for(h, q, nq);
-        hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(qc ? VT_QC_THREADS : 256), 0, h->stream, src, h->H,
+        hipLaunchKernelGGL(vt_qplane_kernel, dim3(nq), dim3(qc ? VT_QC_THREADS : 256), 0, h->stream.get(), src, h->H,
                            h->M, q.qp, q.qsum, nullptr, q.qsj, qc);
     }
     RS_HIP(hipGetLastError());
@@ -440,10 +443,10 @@ int vt_stage_frames(rs_vt* h, int nf, const uint8_t* frames) {
         }
         const size_t fb = (size_t)h->frameBytes * nf;
         std::memcpy(h->hFrames.get(), frames, fb);
-        RS_HIP(hipMemcpyAsync(h->dFrames.get(), h->hFrames.get(), fb, hipMemcpyHostToDevice, h->stream));
+        RS_HIP(hipMemcpyAsync(h->dFrames.get(), h->hFrames.get(), fb, hipMemcpyHostToDevice, h->stream.get()));
         src = h->dFrames.get();
     }
-    hipLaunchKernelGGL(vt_gather_kernel, dim3(nf), dim3(256), 0, h->stream, src,
+    hipLaunchKernelGGL(vt_gather_kernel, dim3(nf), dim3(256), 0, h->stream.get(), src,
                        (size_t)h->frameBytes, h->dPix.get(), h->H * h->W,
                        h->radius > 0 ? h->dNormRaw.get() : h->dQraw.get());
     RS_HIP(hipGetLastError());
@@ -456,15 +459,15 @@ int vt_stage_frames(rs_vt* h, int nf, const uint8_t* frames) {
 int vt_store(rs_vt* h, bool cand, const uint8_t* d_raw, int n) {
     if (n == 0) return RS_OK;
     uint4* lib = cand ? h->dCand.get() : h->dLib.get();
-    RS_HIP(hipMemcpyAsync(h->dSrc.get(), h->hSrc.get(), sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream));
-    RS_HIP(hipMemcpyAsync(h->dDst.get(), h->hDst.get(), sizeof(int64_t) * n, hipMemcpyHostToDevice, h->stream));
+    RS_HIP(hipMemcpyAsync(h->dSrc.get(), h->hSrc.get(), sizeof(int32_t) * n, hipMemcpyHostToDevice, h->stream.get()));
+    RS_HIP(hipMemcpyAsync(h->dDst.get(), h->hDst.get(), sizeof(int64_t) * n, hipMemcpyHostToDevice, h->stream.get()));
     h->stagingBusy = true;
     const int64_t total = (int64_t)n * h->WD * h->HQ;
     const int grid = (int)std::min<int64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(vt_store_kernel, dim3(grid), dim3(256), 0, h->stream, d_raw, h->dSrc.get(),
+    hipLaunchKernelGGL(vt_store_kernel, dim3(grid), dim3(256), 0, h->stream.get(), d_raw, h->dSrc.get(),
                        h->dDst.get(), n, lib, h->H, h->W, h->WD, h->HQ);
     if (h->planar)
-        hipLaunchKernelGGL(vt_plane_store_kernel, dim3(n), dim3(256), 0, h->stream, d_raw, h->dSrc.get(),
+        hipLaunchKernelGGL(vt_plane_store_kernel, dim3(n), dim3(256), 0, h->stream.get(), d_raw, h->dSrc.get(),
                            h->dDst.get(), h->H, h->M, cand ? h->dCandP.get() : h->dLibP.get(),
                            cand ? h->dCandTs.get() : h->dLibTs.get());
     RS_HIP(hipGetLastError());
@@ -500,7 +503,7 @@ int vt_env_switch(const char* name, int* out) {
 
 // The only launch of vt_keys_export: n keys -> host (pinned, device address), reset behind it.
 void vt_launch_keys_export(rs_vt* h, unsigned long long* keys, int n, unsigned long long* host, int max_blocks) {
-    hipLaunchKernelGGL(vt_keys_export, dim3((unsigned)vt_plan::export_grid(n, max_blocks)), dim3(256), 0, h->stream,
+    hipLaunchKernelGGL(vt_keys_export, dim3((unsigned)vt_plan::export_grid(n, max_blocks)), dim3(256), 0, h->stream.get(),
                        keys, n, host);
 }
 
@@ -516,7 +519,7 @@ struct PlaneScan {
 };
 template <int H, bool MATRIX, bool LIST>
 void vt_launch_plane_scan(rs_vt* h, const PlaneScan& s, const ScanOut& out, const PlaneListArg<LIST>& list) {
-    hipLaunchKernelGGL((vt_scan_plane_kernel<H, MATRIX, LIST>), s.grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream,
+    hipLaunchKernelGGL((vt_scan_plane_kernel<H, MATRIX, LIST>), s.grid, dim3(64 * PL_CG * PL_SPLIT), 0, h->stream.get(),
                        s.planes, s.ts, s.ntb, s.count, s.q.qp, s.q.qsum, s.nq, s.nqc, h->dCtr.get(), out, s.rank,
                        s.nranks, list);
 }
@@ -539,7 +542,7 @@ int vt_ensure_prune_buffers(rs_vt* h, int ntb, int nq) {
         vt_plan::parity_grown(grown, ntb);
         h->cntPar = vt_plan::ParityCounters{};
         RS_TRY(h->dCntPar.reserve(2 * (size_t)grown.cap));
-        RS_HIP(hipMemsetAsync(h->dCntPar.get(), 0, sizeof(unsigned) * 2 * (size_t)grown.cap, h->stream));
+        RS_HIP(hipMemsetAsync(h->dCntPar.get(), 0, sizeof(unsigned) * 2 * (size_t)grown.cap, h->stream.get()));
         grown.par = 0;
         h->cntPar = grown;
     }
@@ -547,12 +550,12 @@ int vt_ensure_prune_buffers(rs_vt* h, int ntb, int nq) {
         const int cap = std::max(ntb, 2 * h->listCntCap);
         h->listCntCap = 0;
         RS_TRY(h->dListCnt.reserve(2 * (size_t)cap + 1));
-        RS_HIP(hipMemsetAsync(h->dListCnt.get(), 0, sizeof(unsigned) * (2 * (size_t)cap + 1), h->stream));
+        RS_HIP(hipMemsetAsync(h->dListCnt.get(), 0, sizeof(unsigned) * (2 * (size_t)cap + 1), h->stream.get()));
         h->listCntCap = cap;
     }
     if (!h->dPruneStat.get()) {
         RS_TRY(h->dPruneStat.reserve(3));
-        RS_HIP(hipMemsetAsync(h->dPruneStat.get(), 0, 3 * sizeof(unsigned long long), h->stream));
+        RS_HIP(hipMemsetAsync(h->dPruneStat.get(), 0, 3 * sizeof(unsigned long long), h->stream.get()));
     }
     return RS_OK;
 }
@@ -565,7 +568,7 @@ int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
     const QueryForms& q = s.q;
     const int ntb = s.ntb, nq = s.nq;
     if (!h->qcValid) {   // the build before did not expect this scan to prune
-        hipLaunchKernelGGL(vt_qcompact_kernel, dim3((unsigned)nq), dim3(128), 0, h->stream,
+        hipLaunchKernelGGL(vt_qcompact_kernel, dim3((unsigned)nq), dim3(128), 0, h->stream.get(),
                            reinterpret_cast<const uint4*>(q.qp), reinterpret_cast<uint4*>(q.qc));
         h->qcValid = true;
     }
@@ -584,16 +587,16 @@ int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
     }
     if (h->front == 2 || (h->front == 1 && vt_plan::front_fused(ntb, PF_WAVES * PF_TPW))) {
         const vt_plan::Grid2 fg = vt_plan::front_grid(nq, PF_NB, VT_PF_GRID_CAP);
-        hipLaunchKernelGGL(vt_front_kernel, dim3((unsigned)fg.x, (unsigned)fg.y), dim3(64 * PF_WAVES), 0, h->stream,
+        hipLaunchKernelGGL(vt_front_kernel, dim3((unsigned)fg.x, (unsigned)fg.y), dim3(64 * PF_WAVES), 0, h->stream.get(),
                            s.planes, ntb, s.count, reinterpret_cast<const uint4*>(q.qc), q.qsj, nq, h->dMinLB.get(),
                            s.ts, reinterpret_cast<uint4*>(q.qp), q.qsum, out.best, s.rank, s.nranks,
                            h->dTbStar.get(), fl);
     } else {
         const vt_plan::Grid2 pf = vt_plan::prefilter_grid(ntb, nq, PF_WAVES * PF_TPW, PF_NB, VT_PF_GRID_CAP);
         hipLaunchKernelGGL(vt_prefilter_kernel, dim3((unsigned)pf.x, (unsigned)pf.y), dim3(64 * PF_WAVES), 0,
-                           h->stream, s.planes, ntb, s.count, reinterpret_cast<const uint4*>(q.qc), q.qsj, nq,
+                           h->stream.get(), s.planes, ntb, s.count, reinterpret_cast<const uint4*>(q.qc), q.qsj, nq,
                            h->dMinLB.get(), h->dSecond.get(), fl);
-        hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream, h->dMinLB.get(),
+        hipLaunchKernelGGL(vt_prune_verify_kernel, dim3((unsigned)nq), dim3(64), 0, h->stream.get(), h->dMinLB.get(),
                            h->dSecond.get(), ntb, nq, s.planes, s.ts, reinterpret_cast<const uint4*>(q.qc),
                            reinterpret_cast<uint4*>(q.qp), q.qsum, out.best, s.rank, s.nranks, h->dTbStar.get(), fl);
     }
@@ -625,11 +628,11 @@ int vt_launch_pruned(rs_vt* h, const PlaneScan& s, const ScanOut& out) {
         return RS_OK;
     }
     const dim3 lgrid((unsigned)((nq + VT_LIST_T - 1) / VT_LIST_T), (unsigned)ntb);
-    hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, nq, h->dTbStar.get(), cnt1,
+    hipLaunchKernelGGL(vt_prune_first_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream.get(), nq, h->dTbStar.get(), cnt1,
                        list1, verified, cnt2, ntb);
     vt_launch_plane_scan<64, false, true>(h, s, po,
                                           PlaneListU{{list1, cnt1, nq, (uint32_t)VT_LIST_PER_B1, lnb, 1u, fill}});
-    hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream, h->dMinLB.get(), nq,
+    hipLaunchKernelGGL(vt_prune_rest_kernel, lgrid, dim3(VT_LIST_T), 0, h->stream.get(), h->dMinLB.get(), nq,
                        h->dTbStar.get(), out.best, cnt2, list2, cnt1, verified, ntb, h->dPruneStat.get());
     vt_launch_plane_scan<64, false, true>(h, s, po, PlaneListU{{list2, cnt2, nq, (uint32_t)per2, lnb, 0u, fill}});
     if (out.host) vt_launch_keys_export(h, out.best, nq, out.host, vt_plan::VT_EXPORT_BLOCKS);
@@ -646,7 +649,7 @@ int vt_launch_plane(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int
     if (8 * (size_t)ntb > h->dCtr.capacity()) {  // counters start at zero and every scan leaves them at zero
         const size_t cap = std::max(8 * (size_t)ntb, 2 * h->dCtr.capacity());
         RS_TRY(h->dCtr.reserve(cap));
-        RS_HIP(hipMemsetAsync(h->dCtr.get(), 0, sizeof(unsigned) * cap, h->stream));
+        RS_HIP(hipMemsetAsync(h->dCtr.get(), 0, sizeof(unsigned) * cap, h->stream.get()));
     }
     RS_CHECK((int64_t)ntb * nqc < (1ll << 31), RS_ERR_ARG, "scan grid too large");
     const uint4* planes = reinterpret_cast<const uint4*>(
@@ -656,7 +659,7 @@ int vt_launch_plane(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int
     if constexpr (!MATRIX)
         if (vt_prunes(h, q, cand, tb0, count, nq)) return vt_launch_pruned(h, s, out);
     if (!h->qpFull) {   // a compact build, and a scan that reads every query's planes
-        hipLaunchKernelGGL(vt_qexpand_kernel, dim3((unsigned)nq), dim3(256), 0, h->stream,
+        hipLaunchKernelGGL(vt_qexpand_kernel, dim3((unsigned)nq), dim3(256), 0, h->stream.get(),
                            reinterpret_cast<const uint4*>(q.qc), reinterpret_cast<uint4*>(q.qp));
         h->qpFull = true;
     }
@@ -674,11 +677,11 @@ int vt_launch_sad(rs_vt* h, const uint4* lib, int ntb, int64_t count, int nq, Sc
         RS_CHECK((int64_t)ntb * nqc < (1ll << 31), RS_ERR_ARG, "scan grid too large (%d x %d)", ntb, nqc);
         vt_by_h(h, [&](auto H) {
             hipLaunchKernelGGL((vt_scan_sad_kernel<decltype(H)::value, MATRIX>), dim3((unsigned)(ntb * nqc)),
-                               dim3(64 * vt_plan::sad_waves(h->WD)), 0, h->stream, lib, ntb, count, h->WD, qd, nq,
+                               dim3(64 * vt_plan::sad_waves(h->WD)), 0, h->stream.get(), lib, ntb, count, h->WD, qd, nq,
                                nqc, out, rank, nranks);
         });
     } else {
-        hipLaunchKernelGGL((vt_scan_sad_generic_kernel<MATRIX>), dim3((unsigned)(ntb * nq)), dim3(64), 0, h->stream,
+        hipLaunchKernelGGL((vt_scan_sad_generic_kernel<MATRIX>), dim3((unsigned)(ntb * nq)), dim3(64), 0, h->stream.get(),
                            lib, ntb, count, h->H, h->M, h->WD, qd, nq, out, rank, nranks);
     }
     RS_HIP(hipGetLastError());
@@ -701,7 +704,7 @@ int vt_launch_scan(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int 
         // few waves of work: spread each template over 8 column lanes
         const dim3 grid((unsigned)((count + 7) / 8), nq);
         vt_by_h(h, [&](auto H) {
-            hipLaunchKernelGGL((vt_scan_carry_col_kernel<decltype(H)::value, 1>), grid, dim3(64), 0, h->stream, lib,
+            hipLaunchKernelGGL((vt_scan_carry_col_kernel<decltype(H)::value, 1>), grid, dim3(64), 0, h->stream.get(), lib,
                                count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out, rank, nranks);
         });
     } else if (fast) {
@@ -709,12 +712,12 @@ int vt_launch_scan(rs_vt* h, const QueryForms& q, bool cand, int64_t count, int 
         const int nqg = (nq + NQ - 1) / NQ;
         const dim3 grid((unsigned)(ntb * ((nqg + 7) / 8) * 8));
         vt_by_h(h, [&](auto H) {
-            hipLaunchKernelGGL((vt_scan_carry_kernel<decltype(H)::value, NQ, MATRIX>), grid, dim3(64), 0, h->stream,
+            hipLaunchKernelGGL((vt_scan_carry_kernel<decltype(H)::value, NQ, MATRIX>), grid, dim3(64), 0, h->stream.get(),
                                lib, ntb, count, h->WD, h->dQf.get(), h->dQsum.get(), nq, out, rank, nranks);
         });
     } else {
         hipLaunchKernelGGL((vt_scan_generic_kernel<MATRIX>), dim3((unsigned)(ntb * nq)), dim3(64),
-                           0, h->stream, lib, ntb, count, h->H, h->M, h->WD, h->dQf.get(), nq, out, rank,
+                           0, h->stream.get(), lib, ntb, count, h->H, h->M, h->WD, h->dQf.get(), nq, out, rank,
                            nranks);
     }
     RS_HIP(hipGetLastError());
@@ -738,7 +741,7 @@ bool vt_poll_keys(const unsigned long long* w_, int n) {
 // before the host writes or reallocates them again, those copies must have run.
 int vt_staging_idle(rs_vt* h) {
     if (h->stagingBusy) {
-        RS_HIP(hipStreamSynchronize(h->stream));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
         h->stagingBusy = false;
     }
     return RS_OK;
@@ -755,9 +758,9 @@ int vt_allreduce_min(rs_vt* h, unsigned long long* buf, size_t n, hipStream_t st
 // stream has run); timedScan says whether the last scan was.
 template <class Run>
 int vt_timed_scan(rs_vt* h, bool timed, Run run) {
-    if (timed) RS_HIP(hipEventRecord(h->ev0, h->stream));
+    if (timed) RS_HIP(hipEventRecord(h->ev0.get(), h->stream.get()));
     RS_TRY(run());
-    if (timed) RS_HIP(hipEventRecord(h->ev1, h->stream));
+    if (timed) RS_HIP(hipEventRecord(h->ev1.get(), h->stream.get()));
     h->timedScan = timed;
     return RS_OK;
 }
@@ -807,7 +810,7 @@ int vt_scan_local_impl(rs_vt* h, int nq, const uint8_t* queries, bool frames = f
                  h->stagedQ);
     }
     if (h->bestClean < nq) {  // vt_keys_export resets the keys it hands over
-        RS_HIP(hipMemsetAsync(h->dBest.get(), 0xFF, sizeof(unsigned long long) * nq, h->stream));
+        RS_HIP(hipMemsetAsync(h->dBest.get(), 0xFF, sizeof(unsigned long long) * nq, h->stream.get()));
         h->bestClean = nq;
     }
     h->bestPending = h->bestClean;  // [0, nq) is dirty until exported; the rest stays clean
@@ -819,7 +822,7 @@ int vt_scan_local_impl(rs_vt* h, int nq, const uint8_t* queries, bool frames = f
     if (h->keysFolded) {
         if (!h->dDone.get()) {
             RS_TRY(h->dDone.reserve(1));
-            RS_HIP(hipMemsetAsync(h->dDone.get(), 0, sizeof(unsigned), h->stream));
+            RS_HIP(hipMemsetAsync(h->dDone.get(), 0, sizeof(unsigned), h->stream.get()));
         }
         for (int i = 0; i < nq; ++i) h->hBest.get()[i] = KEY_PENDING;
         out.host = h->hBest.dev();
@@ -873,8 +876,8 @@ int vt_resolve_impl(rs_vt* h, int nq, const unsigned long long* keys, int mode,
         ScanOut mo{nullptr, h->dMat.get(), ldm};
         RS_TRY(vt_launch_scan<true>(h, vt_batch_view(h), true, C, nq, mo, 0, 1));
         RS_HIP(hipMemcpyAsync(h->hMat.get(), h->dMat.get(), sizeof(uint32_t) * ldm * nq, hipMemcpyDeviceToHost,
-                              h->stream));
-        RS_HIP(hipStreamSynchronize(h->stream));
+                              h->stream.get()));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
         h->stagingBusy = false;
     }
     std::vector<std::pair<int, int64_t>> news;
@@ -906,7 +909,7 @@ int vt_fetch_keys(rs_vt* h, int nq, bool allreduce) {
     if (allreduce && h->nranks > 1) {
         RS_CHECK(h->comm, RS_ERR_STATE, "sharded handle without a communicator: use "
                  "rs_vt_scan_local + an external min-reduction + rs_vt_resolve");
-        RS_TRY(vt_allreduce_min(h, h->dBest.get(), (size_t)nq, h->stream));
+        RS_TRY(vt_allreduce_min(h, h->dBest.get(), (size_t)nq, h->stream.get()));
     }
     const bool poll = vt_plan::polls_keys(vt_poll_env(), h->timedScan, nq);
     if (h->keysFolded) {   // the scan's last block exports them (vt_scan_local_impl)
@@ -918,14 +921,14 @@ int vt_fetch_keys(rs_vt* h, int nq, bool allreduce) {
         RS_HIP(hipGetLastError());
     }
     if (!(poll && vt_poll_keys(h->hBest.get(), nq))) {
-        RS_HIP(hipStreamSynchronize(h->stream));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
         h->stagingBusy = false;
     }
     // the keys are the call's last work: everything queued before them has run,
     // the readers of hQraw included (not the staging copies vt_store queues after them)
     h->qrawBusy = false;
     h->bestClean = h->bestPending;
-    if (h->timedScan) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
+    if (h->timedScan) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0.get(), h->ev1.get()));
     return RS_OK;
 }
 
@@ -960,7 +963,40 @@ int vt_stream_fused(rs_vt* h, size_t total, const uint8_t* queries, int64_t lc) 
     RS_TRY(vt_timed_scan(h, h->timing, [&] {
         return vt_launch_scan<false>(h, q, false, lc, (int)total, out, h->rank, h->nranks);
     }));
-    if (h->comm) RS_TRY(vt_allreduce_min(h, h->dStream.get(), total, h->stream));
+    if (h->comm) RS_TRY(vt_allreduce_min(h, h->dStream.get(), total, h->stream.get()));
+    return RS_OK;
+}
+
+// The two groups rs_vt_match_stream creates on first use: a stream and the events recorded
+// for it, built into locals and moved into the handle once every one exists.  After a refused
+// creation the group is absent and the next call creates it again.
+int vt_ensure_upload_stream(rs_vt* h) {
+    if (h->ustream.get()) return RS_OK;
+    rs::Stream st;
+    rs::Event up[2], used[2];
+    RS_TRY(st.create());
+    for (int i = 0; i < 2; ++i) {
+        RS_TRY(up[i].create(hipEventDisableTiming));
+        RS_TRY(used[i].create(hipEventDisableTiming));
+    }
+    for (int i = 0; i < 2; ++i) {
+        h->evUp[i] = std::move(up[i]);
+        h->evUsed[i] = std::move(used[i]);
+    }
+    h->ustream = std::move(st);
+    return RS_OK;
+}
+
+int vt_ensure_comm_stream(rs_vt* h) {
+    if (h->cstream.get()) return RS_OK;
+    rs::Stream st;
+    rs::Event scan, comm;
+    RS_TRY(st.create());
+    RS_TRY(scan.create(hipEventDisableTiming));
+    RS_TRY(comm.create(hipEventDisableTiming));
+    h->evScan = std::move(scan);
+    h->evComm = std::move(comm);
+    h->cstream = std::move(st);
     return RS_OK;
 }
 
@@ -972,15 +1008,9 @@ int vt_stream_host_groups(rs_vt* h, int nb, int nq, const uint8_t* queries, int6
     RS_TRY(vt_grow_stream_forms(h, total));
     const vt_plan::HostGroups plan = vt_plan::host_groups(nb);
     if (h->radius > 0) RS_TRY(h->dNormStream.reserve(qb * nb));
-    if (!h->ustream) {
-        RS_HIP(hipStreamCreateWithFlags(&h->ustream, hipStreamNonBlocking));
-        for (int i = 0; i < 2; ++i) {
-            RS_HIP(hipEventCreateWithFlags(&h->evUp[i], hipEventDisableTiming));
-            RS_HIP(hipEventCreateWithFlags(&h->evUsed[i], hipEventDisableTiming));
-        }
-    }
+    RS_TRY(vt_ensure_upload_stream(h));
     if (qb * plan.gb > h->upCap) {
-        RS_HIP(hipStreamSynchronize(h->ustream));
+        RS_HIP(hipStreamSynchronize(h->ustream.get()));
         h->upCap = 0;
         for (int i = 0; i < 2; ++i) RS_TRY(h->dUp[i].reserve(qb * plan.gb));
         h->upCap = qb * plan.gb;
@@ -989,10 +1019,10 @@ int vt_stream_host_groups(rs_vt* h, int nb, int nq, const uint8_t* queries, int6
         const vt_plan::HostGroup grp = plan.group(g);
         if (grp.n == 0) break;
         const int bi = grp.buf;
-        if (grp.waits) RS_HIP(hipStreamWaitEvent(h->ustream, h->evUsed[bi], 0));
-        RS_HIP(hipMemcpyAsync(h->dUp[bi].get(), queries + qb * grp.b0, qb * grp.n, hipMemcpyHostToDevice, h->ustream));
-        RS_HIP(hipEventRecord(h->evUp[bi], h->ustream));
-        RS_HIP(hipStreamWaitEvent(h->stream, h->evUp[bi], 0));
+        if (grp.waits) RS_HIP(hipStreamWaitEvent(h->ustream.get(), h->evUsed[bi].get(), 0));
+        RS_HIP(hipMemcpyAsync(h->dUp[bi].get(), queries + qb * grp.b0, qb * grp.n, hipMemcpyHostToDevice, h->ustream.get()));
+        RS_HIP(hipEventRecord(h->evUp[bi].get(), h->ustream.get()));
+        RS_HIP(hipStreamWaitEvent(h->stream.get(), h->evUp[bi].get(), 0));
         const QueryForms q = vt_stream_view(h, (size_t)grp.b0 * nq);
         const uint8_t* src = h->dUp[bi].get();
         if (h->radius > 0) {   // each group into its own part of dNormStream
@@ -1001,11 +1031,11 @@ int vt_stream_host_groups(rs_vt* h, int nb, int nq, const uint8_t* queries, int6
             src = dn;
         }
         RS_TRY(vt_build_forms(h, q, grp.n * nq, src));
-        RS_HIP(hipEventRecord(h->evUsed[bi], h->stream));
+        RS_HIP(hipEventRecord(h->evUsed[bi].get(), h->stream.get()));
         const ScanOut out{h->dStream.get() + (size_t)grp.b0 * nq, nullptr, 0};
         RS_TRY(vt_launch_scan<false>(h, q, false, lc, grp.n * nq, out, h->rank, h->nranks));
     }
-    if (h->comm) RS_TRY(vt_allreduce_min(h, h->dStream.get(), total, h->stream));
+    if (h->comm) RS_TRY(vt_allreduce_min(h, h->dStream.get(), total, h->stream.get()));
     return RS_OK;
 }
 
@@ -1021,7 +1051,7 @@ int vt_stream_per_batch(rs_vt* h, int nb, int nq, const uint8_t* queries, bool o
         const uint8_t* src = queries + qb * b;
         if (!on_device) {
             uint8_t* const up = h->radius > 0 ? h->dNormRaw.get() : h->dQraw.get();
-            RS_HIP(hipMemcpyAsync(up, src, qb, hipMemcpyHostToDevice, h->stream));
+            RS_HIP(hipMemcpyAsync(up, src, qb, hipMemcpyHostToDevice, h->stream.get()));
             src = up;
         }
         if (h->radius > 0) {   // (a device batch is read where it is and left as it is)
@@ -1031,14 +1061,14 @@ int vt_stream_per_batch(rs_vt* h, int nb, int nq, const uint8_t* queries, bool o
         RS_TRY(vt_build_forms(h, vt_batch_view(h), nq, src));
         RS_TRY(vt_launch_scan<false>(h, vt_batch_view(h), false, lc, nq, out, h->rank, h->nranks));
         if (h->comm) {
-            RS_HIP(hipEventRecord(h->evScan, h->stream));
-            RS_HIP(hipStreamWaitEvent(h->cstream, h->evScan, 0));
-            RS_TRY(vt_allreduce_min(h, keys, (size_t)nq, h->cstream));
+            RS_HIP(hipEventRecord(h->evScan.get(), h->stream.get()));
+            RS_HIP(hipStreamWaitEvent(h->cstream.get(), h->evScan.get(), 0));
+            RS_TRY(vt_allreduce_min(h, keys, (size_t)nq, h->cstream.get()));
         }
     }
     if (h->comm) {
-        RS_HIP(hipEventRecord(h->evComm, h->cstream));
-        RS_HIP(hipStreamWaitEvent(h->stream, h->evComm, 0));
+        RS_HIP(hipEventRecord(h->evComm.get(), h->cstream.get()));
+        RS_HIP(hipStreamWaitEvent(h->stream.get(), h->evComm.get(), 0));
     }
     return RS_OK;
 }
@@ -1052,12 +1082,8 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
     RS_CHECK(queries, RS_ERR_ARG, "null queries");
     RS_CHECK(h->nranks == 1 || h->comm, RS_ERR_STATE, "sharded handle without a communicator: "
              "rs_vt_match_stream needs the RCCL reduction (rs_vt_attach_comm)");
-    if (h->comm && !h->cstream) {
-        RS_HIP(hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking));
-        RS_HIP(hipEventCreateWithFlags(&h->evScan, hipEventDisableTiming));
-        RS_HIP(hipEventCreateWithFlags(&h->evComm, hipEventDisableTiming));
-    }
     RS_HIP(hipSetDevice(h->device));
+    if (h->comm) RS_TRY(vt_ensure_comm_stream(h));
     RS_TRY(vt_grow_queries(h, nq));
     const size_t total = (size_t)nb * nq;
     RS_CHECK(total <= INT32_MAX, RS_ERR_ARG, "too many queries in one stream");
@@ -1074,7 +1100,7 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
     // the keys start at UINT64_MAX: the export of the previous call reset them
     // (one memset after allocation, or after a call that did not reach its export)
     if (!h->streamClean)
-        RS_HIP(hipMemsetAsync(h->dStream.get(), 0xFF, sizeof(unsigned long long) * h->streamCap, h->stream));
+        RS_HIP(hipMemsetAsync(h->dStream.get(), 0xFF, sizeof(unsigned long long) * h->streamCap, h->stream.get()));
     h->streamClean = false;
     h->stagedQ = 0;  // the forms no longer match dQraw
     h->timedScan = false;  // (only the fused path's one scan is timed)
@@ -1089,9 +1115,9 @@ int vt_match_stream_impl(rs_vt* h, int nb, int nq, const uint8_t* queries, uint6
     // (in place of a device-to-host blit and a memset)
     vt_launch_keys_export(h, h->dStream.get(), (int)total, h->hStream.dev(), vt_plan::VT_EXPORT_BLOCKS_STREAM);
     RS_HIP(hipGetLastError());
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     h->streamClean = true;
-    if (h->timedScan) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
+    if (h->timedScan) RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0.get(), h->ev1.get()));
     vt_decode_keys(h->hStream.get(), total, best_score, best_index);
     return RS_OK;
 }
@@ -1126,11 +1152,8 @@ int rs_vt_create_metric(int H, int W, int max_offset, uint64_t thr, int64_t capa
     RS_CHECK(capacity >= 0, RS_ERR_ARG, "negative capacity");
     // max score H*W*255 must fit the 32-bit half of the packed key
     RS_CHECK((uint64_t)H * W * 255u < 0xFFFFFFFFull, RS_ERR_ARG, "template too large");
-    int ndev = 0;
-    RS_HIP(hipGetDeviceCount(&ndev));
-    RS_CHECK(device >= 0 && device < ndev, RS_ERR_ARG, "device %d not in [0, %d)", device, ndev);
-    RS_HIP(hipSetDevice(device));
-    // one failure exit: rs_vt_destroy takes a handle at any stage (null streams and events)
+    RS_TRY(rs::use_device(device));
+    // one failure exit: rs_vt_destroy takes a handle at any stage
     std::unique_ptr<rs_vt, int (*)(rs_vt*)> owner(new rs_vt(), rs_vt_destroy);
     rs_vt* const h = owner.get();
     h->H = H; h->W = W; h->M = max_offset; h->thr = (double)thr; h->device = device;
@@ -1185,10 +1208,9 @@ int rs_vt_create_metric(int H, int W, int max_offset, uint64_t thr, int64_t capa
         per_cu = std::max(1, std::min({api, by_vgpr, by_lds}));
         h->planeSlots = std::max(1, per_cu * cus);
     }
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&h->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-    RS_CHECK(e == hipSuccess, RS_ERR_HIP, "stream/event creation failed: %s", hipGetErrorString(e));
+    RS_TRY(h->stream.create());
+    RS_TRY(h->ev0.create());
+    RS_TRY(h->ev1.create());
     RS_TRY(vt_grow_lib(h, capacity > 0 ? capacity : 64));
     RS_TRY(vt_grow_queries(h, 64));
     RS_TRY(vt_grow_index(h, 64));
@@ -1201,25 +1223,9 @@ int rs_vt_destroy(rs_vt* h) {
     (void)hipSetDevice(h->device);
     // the handle's last queued work: a fault or launch error the early-returning calls
     // left on a stream is reported here instead of being dropped
-    hipError_t se = hipSuccess;
-    for (hipStream_t st : {h->stream, h->cstream, h->ustream})
-        if (st) {
-            const hipError_t e = hipStreamSynchronize(st);
-            if (se == hipSuccess) se = e;
-        }
+    const hipError_t se = rs::sync_streams({h->stream.get(), h->cstream.get(), h->ustream.get()});
     if (h->comm) (void)ncclCommDestroy(h->comm);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->evScan) (void)hipEventDestroy(h->evScan);
-    if (h->evComm) (void)hipEventDestroy(h->evComm);
-    if (h->cstream) (void)hipStreamDestroy(h->cstream);
-    for (int i = 0; i < 2; ++i) {
-        if (h->evUp[i]) (void)hipEventDestroy(h->evUp[i]);
-        if (h->evUsed[i]) (void)hipEventDestroy(h->evUsed[i]);
-    }
-    if (h->ustream) (void)hipStreamDestroy(h->ustream);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;  // (the buffers go with their members)
+    delete h;  // (the streams and events, then the buffers, go with their members)
     RS_CHECK(se == hipSuccess, RS_ERR_HIP, "work queued before rs_vt_destroy failed: %s", hipGetErrorString(se));
     return RS_OK;
 }
@@ -1251,7 +1257,7 @@ int rs_vt_add(rs_vt* h, int n, const uint8_t* templates, int64_t* first_index) {
     RS_HIP(hipMemcpyAsync(h->radius > 0 ? h->dNormRaw.get() : h->dQraw.get(), templates, qb,
                           attr.type == hipMemoryTypeDevice && direct_dma ? hipMemcpyDeviceToDevice
                                                                          : hipMemcpyHostToDevice,
-                          h->stream));
+                          h->stream.get()));
     int s = h->radius > 0 ? vt_normalise(h, h->dNormRaw.get(), h->dQraw.get(), (size_t)n) : RS_OK;
     h->stagedQ = 0;  // the staging buffer now holds templates, not a query batch
     std::vector<std::pair<int, int64_t>> news;
@@ -1260,7 +1266,7 @@ int rs_vt_add(rs_vt* h, int n, const uint8_t* templates, int64_t* first_index) {
     if (s == RS_OK) s = vt_append_staged(h, news);   // (its copies guarded by vt_staging_idle, not a sync)
     // (on the error path as well: the upload above is queued either way)
     if (direct_dma) {
-        const hipError_t e = hipStreamSynchronize(h->stream);
+        const hipError_t e = hipStreamSynchronize(h->stream.get());
         RS_CHECK(s != RS_OK || e == hipSuccess, RS_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
     }
     return s;
@@ -1281,8 +1287,8 @@ int rs_vt_read(rs_vt* h, int64_t index, uint8_t* out) {
         for (int q = 0; q < h->HQ; ++q)
             RS_HIP(hipMemcpyAsync(&chunks[(size_t)c * h->HQ + q],
                                   h->dLib.get() + ((tb * h->WD + c) * h->HQ + q) * 64 + tl, sizeof(uint4),
-                                  hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+                                  hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     for (int r = 0; r < h->H; ++r)
         for (int col = 0; col < h->W; ++col) {
             const uint4& ch = chunks[(size_t)(col / 4) * h->HQ + r / 4];
@@ -1325,8 +1331,8 @@ int rs_vt_set_subsample(rs_vt* h, int64_t frame_bytes, const int32_t* pixels) {
                  (long long)frame_bytes);
     RS_HIP(hipSetDevice(h->device));
     RS_TRY(h->dPix.reserve((size_t)npix));
-    RS_HIP(hipMemcpyAsync(h->dPix.get(), pixels, sizeof(int32_t) * npix, hipMemcpyHostToDevice, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipMemcpyAsync(h->dPix.get(), pixels, sizeof(int32_t) * npix, hipMemcpyHostToDevice, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     if (frame_bytes != h->frameBytes) {  // staging buffers are sized per frame
         h->frameCap = 0;
         h->dFrames.reset();
@@ -1385,7 +1391,7 @@ int rs_vt_set_normalise(rs_vt* h, int radius, int gain) {
     if (radius > 0) {
         RS_TRY(h->dNormRaw.reserve((size_t)h->H * h->W * h->qCap));
     } else {
-        RS_HIP(hipStreamSynchronize(h->stream));   // (queued work may still read them)
+        RS_HIP(hipStreamSynchronize(h->stream.get()));   // (queued work may still read them)
         h->dNormRaw.reset();
         h->dNormStream.reset();
         h->dOffRaw.reset();
@@ -1442,9 +1448,9 @@ int rs_vt_scores(rs_vt* h, int nq, const uint8_t* queries, int64_t t0, int64_t n
         return vt_launch_scan<true>(h, vt_batch_view(h), false, span, nq, mo, 0, 1, tb0);
     }));
     RS_HIP(hipMemcpy2DAsync(h->hMat.get(), sizeof(uint32_t) * nt, h->dMat.get() + lo, sizeof(uint32_t) * ld,
-                            sizeof(uint32_t) * nt, nq, hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
-    RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0, h->ev1));
+                            sizeof(uint32_t) * nt, nq, hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
+    RS_HIP(hipEventElapsedTime(&h->lastMs, h->ev0.get(), h->ev1.get()));
     for (size_t i = 0; i < (size_t)nq * nt; ++i) scores[i] = h->hMat.get()[i];
     return RS_OK;
 }
@@ -1475,7 +1481,7 @@ int rs_vt_offset_profile(rs_vt* h, int nq, const uint8_t* queries, const int64_t
         const uint8_t* raw = queries;
         if (!rs::on_device(queries)) {
             RS_TRY(h->dOffRaw.reserve(h->dOffQ.capacity()));
-            RS_HIP(hipMemcpyAsync(h->dOffRaw.get(), queries, qb, hipMemcpyHostToDevice, h->stream));
+            RS_HIP(hipMemcpyAsync(h->dOffRaw.get(), queries, qb, hipMemcpyHostToDevice, h->stream.get()));
             raw = h->dOffRaw.get();
         }
         RS_TRY(vt_normalise(h, raw, h->dOffQ.get(), n));
@@ -1484,13 +1490,13 @@ int rs_vt_offset_profile(rs_vt* h, int nq, const uint8_t* queries, const int64_t
         src = queries;   // read in place
     } else if (queries) {
         RS_TRY(h->dOffQ.reserve(offq));
-        RS_HIP(hipMemcpyAsync(h->dOffQ.get(), queries, qb, hipMemcpyHostToDevice, h->stream));
+        RS_HIP(hipMemcpyAsync(h->dOffQ.get(), queries, qb, hipMemcpyHostToDevice, h->stream.get()));
         src = h->dOffQ.get();
     }
     std::memcpy(h->hOffIdx.get(), index, sizeof(int64_t) * n);
     const bool sad = h->metric == RS_VT_METRIC_SAD, fast = h->M == FAST_M;
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(nq), dim3(64), 0, h->stream, h->dLib.get(), h->count, h->H, h->W,
+        hipLaunchKernelGGL(kernel, dim3(nq), dim3(64), 0, h->stream.get(), h->dLib.get(), h->count, h->H, h->W,
                            h->WD, h->HQ, h->M, src, h->hOffIdx.dev(), h->hOffProfile.dev(),
                            h->hOffOffset.dev());
     };
@@ -1501,7 +1507,7 @@ int rs_vt_offset_profile(rs_vt* h, int nq, const uint8_t* queries, const int64_t
     RS_HIP(hipGetLastError());
     // the results are the kernel's own stores: the call waits for the stream, and with it
     // for everything queued before (an append's staging copies, a reader of hQraw)
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     h->stagingBusy = false;
     h->qrawBusy = false;
     if (profile) std::memcpy(profile, h->hOffProfile.get(), sizeof(uint32_t) * n * no);
@@ -1547,13 +1553,13 @@ namespace {
 // acc[0] the pairs of the rule's second list, acc[1] the settled queries (vt_prune_count_kernel).
 int vt_prune_count(rs_vt* h, unsigned long long acc[2]) {
     if (!h->dCountAcc.get()) RS_TRY(h->dCountAcc.reserve(2));
-    RS_HIP(hipMemsetAsync(h->dCountAcc.get(), 0, 2 * sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(vt_prune_count_kernel, dim3((unsigned)((h->pruneNq + 255) / 256)), dim3(256), 0, h->stream,
+    RS_HIP(hipMemsetAsync(h->dCountAcc.get(), 0, 2 * sizeof(unsigned long long), h->stream.get()));
+    hipLaunchKernelGGL(vt_prune_count_kernel, dim3((unsigned)((h->pruneNq + 255) / 256)), dim3(256), 0, h->stream.get(),
                        h->dMinLB.get(), h->pruneNq, h->pruneNtb, h->dTbStar.get(), h->dUblk.get(),
                        h->dCountAcc.get());
     RS_HIP(hipGetLastError());
-    RS_HIP(hipMemcpyAsync(acc, h->dCountAcc.get(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipMemcpyAsync(acc, h->dCountAcc.get(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     return RS_OK;
 }
 }  // namespace
@@ -1576,10 +1582,10 @@ int rs_vt_prune_stats(rs_vt* h, int64_t out[4]) {
     // the pairs of B2: list2's counters, which stay until the next pruned launch's lists
     unsigned long long s0 = 0ull;
     std::vector<unsigned> c2((size_t)h->pruneNtb);
-    RS_HIP(hipMemcpyAsync(&s0, h->dPruneStat.get(), sizeof(s0), hipMemcpyDeviceToHost, h->stream));
+    RS_HIP(hipMemcpyAsync(&s0, h->dPruneStat.get(), sizeof(s0), hipMemcpyDeviceToHost, h->stream.get()));
     RS_HIP(hipMemcpyAsync(c2.data(), h->dListCnt.get() + h->listCntCap, sizeof(unsigned) * c2.size(), hipMemcpyDeviceToHost,
-                          h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+                          h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     out[0] = (int64_t)s0;
     for (const unsigned c : c2) out[1] += (int64_t)c;
     return RS_OK;
@@ -1594,8 +1600,8 @@ int rs_vt_prune_scanned(rs_vt* h, int64_t* out) {
     if (h->pruneMode == 1) {   // the one list's entries: the last call's parity of the counters
         std::vector<unsigned> c((size_t)h->pruneNtb);
         RS_HIP(hipMemcpyAsync(c.data(), h->dCntPar.get() + vt_plan::parity_last_offset(h->cntPar),
-                              sizeof(unsigned) * c.size(), hipMemcpyDeviceToHost, h->stream));
-        RS_HIP(hipStreamSynchronize(h->stream));
+                              sizeof(unsigned) * c.size(), hipMemcpyDeviceToHost, h->stream.get()));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
         for (const unsigned n : c) *out += (int64_t)n;
         return RS_OK;
     }
@@ -1603,8 +1609,8 @@ int rs_vt_prune_scanned(rs_vt* h, int64_t* out) {
     int64_t st[4];
     unsigned long long v = 0ull;
     RS_TRY(rs_vt_prune_stats(h, st));
-    RS_HIP(hipMemcpyAsync(&v, h->dPruneStat.get() + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipMemcpyAsync(&v, h->dPruneStat.get() + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     *out = st[0] - (int64_t)v + st[1];
     return RS_OK;
 }
@@ -1622,8 +1628,8 @@ int rs_vt_prune_verified(rs_vt* h, int64_t* out) {
         return RS_OK;
     }
     unsigned long long v = 0ull;
-    RS_HIP(hipMemcpyAsync(&v, h->dPruneStat.get() + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipMemcpyAsync(&v, h->dPruneStat.get() + 2, sizeof(v), hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     *out = (int64_t)v;
     return RS_OK;
 }

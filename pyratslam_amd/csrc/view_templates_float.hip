@@ -307,13 +307,13 @@ constexpr size_t LDS_BUDGET = 64 * 1024;
 // Host side
 // ===========================================================================
 // The buffers are rs::DevBuf members (rs_common.h; untyped ones count bytes, the element
-// being es wide).  Group capacities: qCap (dQ), scanCap (dIn, dBest, dBidx).
+// being es wide).  Group capacities: qCap (dQ), scanCap (dIn, dBest, dBidx).  The stream
+// and the events are rs::Stream / rs::Event owners.
 struct rs_vtf {
     int H = 0, W = 0, M = 0, dtype = 0, device = 0;
     size_t es = 0;            // element size
     int64_t count = 0, cap = 0;   // templates stored, and templates dLib holds
     rs::DevBuf<void> dLib;
-    hipStream_t stream = nullptr;
     SadPlan plan;
     rs::DevBuf<int2> dProg;
     // launch shape of the score kernel
@@ -327,8 +327,10 @@ struct rs_vtf {
     rs::DevBuf<int64_t> dBidx;   // [scanCap]
     rs::DevBuf<void> dScores;    // (its capacity in bytes)
     bool timing = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double lastMs = -1.0;
+    // the owners come after the buffers: members go in reverse order, streams and events first
+    rs::Stream stream;
+    rs::Event ev0, ev1;
 };
 
 namespace {
@@ -340,19 +342,6 @@ size_t lds_bytes(const rs_vtf* h, int threads, int qt, bool staged) {
     return el * h->es;
 }
 
-int free_handle(rs_vtf* h) {
-    int rc = RS_OK;
-    if (h->stream && hipStreamSynchronize(h->stream) != hipSuccess) {
-        rs::set_error("queued work of the float library failed");
-        rc = RS_ERR_HIP;
-    }
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return rc;
-}
-
 int ensure_lib(rs_vtf* h, int64_t want) {
     if (want <= h->cap) return RS_OK;
     const int64_t cap = rs::grown<int64_t>(h->cap, want, 1);
@@ -360,8 +349,8 @@ int ensure_lib(rs_vtf* h, int64_t want) {
     rs::DevBuf<void> nl;   // the library is copied: the new block before the old one goes
     RS_TRY(nl.reserve((size_t)cap * tb, "float template library"));
     if (h->count > 0) {
-        RS_HIP(hipMemcpyAsync(nl.get(), h->dLib.get(), (size_t)h->count * tb, hipMemcpyDeviceToDevice, h->stream));
-        RS_HIP(hipStreamSynchronize(h->stream));
+        RS_HIP(hipMemcpyAsync(nl.get(), h->dLib.get(), (size_t)h->count * tb, hipMemcpyDeviceToDevice, h->stream.get()));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
     }
     h->dLib = std::move(nl);
     h->cap = cap;
@@ -370,7 +359,7 @@ int ensure_lib(rs_vtf* h, int64_t want) {
 
 int ensure_queries(rs_vtf* h, int nq) {
     if (nq <= h->qCap) return RS_OK;
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     const int cap = rs::grown(h->qCap, nq, 1);
     h->qCap = 0;
     h->nqStaged = 0;
@@ -383,7 +372,7 @@ int ensure_queries(rs_vtf* h, int nq) {
 // allocates them
 int ensure_scan_results(rs_vtf* h, int nq) {
     if (nq <= h->scanCap) return RS_OK;
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     const int cap = rs::grown(h->scanCap, nq, 1);
     h->scanCap = 0;
     RS_TRY(h->dIn.reserve((size_t)cap * cap * h->es));
@@ -395,14 +384,14 @@ int ensure_scan_results(rs_vtf* h, int nq) {
 
 int ensure_scores(rs_vtf* h, size_t elems) {
     if (elems * h->es <= h->dScores.capacity()) return RS_OK;
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     return h->dScores.reserve(elems * h->es);
 }
 
 int stage_queries(rs_vtf* h, int nq, const void* queries) {
     RS_TRY(ensure_queries(h, nq));
     RS_HIP(hipMemcpyAsync(h->dQ.get(), queries, (size_t)nq * h->H * h->W * h->es, hipMemcpyHostToDevice,
-                          h->stream));
+                          h->stream.get()));
     h->nqStaged = nq;
     return RS_OK;
 }
@@ -428,12 +417,12 @@ int launch_scores(rs_vtf* h, const void* lib, int64_t nt, int nq, int lower, voi
     const dim3 grid((unsigned)nt, (unsigned)chunks);
     const int n_prog = (int)h->plan.prog.size();
     if (h->staged)
-        hipLaunchKernelGGL((vtf_score_kernel<T, true>), grid, dim3(threads), lds, h->stream,
+        hipLaunchKernelGGL((vtf_score_kernel<T, true>), grid, dim3(threads), lds, h->stream.get(),
                            static_cast<const T*>(lib), nt, static_cast<const T*>(h->dQ.get()), nq, qchunk,
                            h->H, h->W, h->M, h->tsize, qt, h->plan.depth, h->dProg.get(), n_prog, lower, nt,
                            static_cast<T*>(out));
     else
-        hipLaunchKernelGGL((vtf_score_kernel<T, false>), grid, dim3(threads), lds, h->stream,
+        hipLaunchKernelGGL((vtf_score_kernel<T, false>), grid, dim3(threads), lds, h->stream.get(),
                            static_cast<const T*>(lib), nt, static_cast<const T*>(h->dQ.get()), nq, qchunk,
                            h->H, h->W, h->M, 0, qt, h->plan.depth, h->dProg.get(), n_prog, lower, nt,
                            static_cast<T*>(out));
@@ -448,11 +437,11 @@ int launch_scores(rs_vtf* h, const void* lib, int64_t nt, int nq, int lower, voi
 
 int launch_argmin(rs_vtf* h, int nq, int64_t nt) {
     if (h->dtype == RS_DT_F32)
-        hipLaunchKernelGGL(vtf_argmin_kernel<float>, dim3(nq), dim3(256), 0, h->stream,
+        hipLaunchKernelGGL(vtf_argmin_kernel<float>, dim3(nq), dim3(256), 0, h->stream.get(),
                            static_cast<const float*>(h->dScores.get()), nt, static_cast<float*>(h->dBest.get()),
                            h->dBidx.get());
     else
-        hipLaunchKernelGGL(vtf_argmin_kernel<double>, dim3(nq), dim3(256), 0, h->stream,
+        hipLaunchKernelGGL(vtf_argmin_kernel<double>, dim3(nq), dim3(256), 0, h->stream.get(),
                            static_cast<const double*>(h->dScores.get()), nt,
                            static_cast<double*>(h->dBest.get()), h->dBidx.get());
     RS_HIP(hipGetLastError());
@@ -486,11 +475,10 @@ int rs_vtf_create(int H, int W, int max_offset, int dtype, int64_t capacity, int
     *out = nullptr;
     RS_TRY(check_geometry(dtype, H, W, max_offset));
     RS_CHECK(capacity >= 0, RS_ERR_ARG, "negative capacity");
-    int ndev = 0;
-    RS_HIP(hipGetDeviceCount(&ndev));
-    RS_CHECK(device >= 0 && device < ndev, RS_ERR_ARG, "device %d not in [0, %d)", device, ndev);
-    RS_HIP(hipSetDevice(device));
-    rs_vtf* h = new rs_vtf();
+    RS_TRY(rs::use_device(device));
+    // one failure exit: rs_vtf_destroy takes a handle at any stage
+    std::unique_ptr<rs_vtf, int (*)(rs_vtf*)> owner(new rs_vtf(), rs_vtf_destroy);
+    rs_vtf* const h = owner.get();
     h->H = H; h->W = W; h->M = max_offset; h->dtype = dtype; h->device = device;
     h->es = dtype == RS_DT_F32 ? 4 : 8;
     h->plan = make_plan((int64_t)(H - 2 * max_offset) * W);
@@ -499,32 +487,27 @@ int rs_vtf_create(int H, int W, int max_offset, int dtype, int64_t capacity, int
     const int64_t tsize = hw + ((hw >> (dtype == RS_DT_F32 ? 6 : 5)) << 3) + 8;
     h->tsize = (int)(tsize < (1 << 24) ? tsize : (1 << 24));
     h->staged = tsize < (1 << 24) && lds_bytes(h, 256, 2, true) <= LDS_BUDGET;
-    auto init = [&]() -> int {
-        RS_CHECK(lds_bytes(h, 256, 2, false) <= LDS_BUDGET, RS_ERR_ARG,
-                 "window too deep for the scan's LDS stack");
-        RS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        RS_TRY(h->dProg.reserve(h->plan.prog.size()));
-        RS_HIP(hipMemcpyAsync(h->dProg.get(), h->plan.prog.data(), sizeof(int2) * h->plan.prog.size(),
-                              hipMemcpyHostToDevice, h->stream));
-        RS_HIP(hipStreamSynchronize(h->stream));
-        RS_HIP(hipEventCreate(&h->ev0));
-        RS_HIP(hipEventCreate(&h->ev1));
-        return ensure_lib(h, capacity > 0 ? capacity : 1);
-    };
-    const int rc = init();
-    if (rc != RS_OK) {
-        (void)free_handle(h);
-        return rc;
-    }
-    *out = h;
+    RS_CHECK(lds_bytes(h, 256, 2, false) <= LDS_BUDGET, RS_ERR_ARG, "window too deep for the scan's LDS stack");
+    RS_TRY(h->stream.create());
+    RS_TRY(h->dProg.reserve(h->plan.prog.size()));
+    RS_HIP(hipMemcpyAsync(h->dProg.get(), h->plan.prog.data(), sizeof(int2) * h->plan.prog.size(),
+                          hipMemcpyHostToDevice, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
+    RS_TRY(h->ev0.create());
+    RS_TRY(h->ev1.create());
+    RS_TRY(ensure_lib(h, capacity > 0 ? capacity : 1));
+    *out = owner.release();
     return RS_OK;
 }
 
 int rs_vtf_destroy(rs_vtf* h) {
-    rs::clear_error();
     if (!h) return RS_OK;
     (void)hipSetDevice(h->device);
-    return free_handle(h);
+    // queued work that failed after a call returned is reported here, not dropped
+    const hipError_t se = rs::sync_streams({h->stream.get()});
+    delete h;  // (the streams and events, then the buffers, go with their members)
+    RS_CHECK(se == hipSuccess, RS_ERR_HIP, "work queued before rs_vtf_destroy failed: %s", hipGetErrorString(se));
+    return RS_OK;
 }
 
 int rs_vtf_count(const rs_vtf* h, int64_t* count) {
@@ -545,8 +528,8 @@ int rs_vtf_add(rs_vtf* h, int n, const void* templates, int64_t* first_index) {
     RS_TRY(ensure_lib(h, h->count + n));
     const size_t tb = (size_t)h->H * h->W * h->es;
     RS_HIP(hipMemcpyAsync(static_cast<char*>(h->dLib.get()) + (size_t)h->count * tb, templates,
-                          (size_t)n * tb, hipMemcpyHostToDevice, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+                          (size_t)n * tb, hipMemcpyHostToDevice, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     h->count += n;
     return RS_OK;
 }
@@ -559,8 +542,8 @@ int rs_vtf_read(rs_vtf* h, int64_t index, void* out) {
     RS_HIP(hipSetDevice(h->device));
     const size_t tb = (size_t)h->H * h->W * h->es;
     RS_HIP(hipMemcpyAsync(out, static_cast<char*>(h->dLib.get()) + (size_t)index * tb, tb,
-                          hipMemcpyDeviceToHost, h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+                          hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     return RS_OK;
 }
 
@@ -578,8 +561,8 @@ int rs_vtf_scores(rs_vtf* h, int nq, const void* queries, int64_t t0, int64_t nt
     const size_t tb = (size_t)h->H * h->W * h->es;
     RS_TRY(launch_scores(h, static_cast<char*>(h->dLib.get()) + (size_t)t0 * tb, nt, nq, 0, h->dScores.get()));
     RS_HIP(hipMemcpyAsync(scores, h->dScores.get(), (size_t)nq * nt * h->es, hipMemcpyDeviceToHost,
-                          h->stream));
-    RS_HIP(hipStreamSynchronize(h->stream));
+                          h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     return RS_OK;
 }
 
@@ -598,27 +581,27 @@ int rs_vtf_scan(rs_vtf* h, int nq, const void* queries, int want_inbatch, void* 
     const int64_t nt = h->count;
     if (nt > 0) {
         RS_TRY(ensure_scores(h, (size_t)nq * nt));
-        if (h->timing) RS_HIP(hipEventRecord(h->ev0, h->stream));
+        if (h->timing) RS_HIP(hipEventRecord(h->ev0.get(), h->stream.get()));
         RS_TRY(launch_scores(h, h->dLib.get(), nt, nq, 0, h->dScores.get()));
         RS_TRY(launch_argmin(h, nq, nt));
-        if (h->timing) RS_HIP(hipEventRecord(h->ev1, h->stream));
+        if (h->timing) RS_HIP(hipEventRecord(h->ev1.get(), h->stream.get()));
         RS_HIP(hipMemcpyAsync(best_score, h->dBest.get(), (size_t)nq * h->es, hipMemcpyDeviceToHost,
-                              h->stream));
+                              h->stream.get()));
         RS_HIP(hipMemcpyAsync(best_index, h->dBidx.get(), (size_t)nq * sizeof(int64_t),
-                              hipMemcpyDeviceToHost, h->stream));
+                              hipMemcpyDeviceToHost, h->stream.get()));
     }
     if (want_inbatch) {
         RS_TRY(launch_scores(h, h->dQ.get(), nq, nq, 1, h->dIn.get()));
         RS_HIP(hipMemcpyAsync(inbatch, h->dIn.get(), (size_t)nq * nq * h->es, hipMemcpyDeviceToHost,
-                              h->stream));
+                              h->stream.get()));
     }
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     if (nt == 0) {
         fill_inf(h->dtype, best_score, (size_t)nq);
         for (int i = 0; i < nq; ++i) best_index[i] = -1;
     } else if (h->timing) {
         float ms = 0.f;
-        RS_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        RS_HIP(hipEventElapsedTime(&ms, h->ev0.get(), h->ev1.get()));
         h->lastMs = ms;
     }
     return RS_OK;
@@ -642,10 +625,10 @@ int rs_vtf_append_staged(rs_vtf* h, int n, const int32_t* which, int64_t* first_
         while (i + run < n && which[i + run] == which[i] + run) ++run;
         RS_HIP(hipMemcpyAsync(static_cast<char*>(h->dLib.get()) + (size_t)(h->count + i) * tb,
                               static_cast<char*>(h->dQ.get()) + (size_t)which[i] * tb, (size_t)run * tb,
-                              hipMemcpyDeviceToDevice, h->stream));
+                              hipMemcpyDeviceToDevice, h->stream.get()));
         i += run;
     }
-    RS_HIP(hipStreamSynchronize(h->stream));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
     h->count += n;
     return RS_OK;
 }
@@ -679,7 +662,7 @@ int rs_sad_scores(int device, int dtype, int H, int W, int max_offset, int64_t n
     RS_TRY(rs_vtf_create(H, W, max_offset, dtype, nt, device, &h));
     int rc = rs_vtf_add(h, (int)nt, templates, nullptr);
     if (rc == RS_OK) rc = rs_vtf_scores(h, nq, queries, 0, nt, scores);
-    const int freed = free_handle(h);   // (not rs_vtf_destroy: a failure's message stays)
+    const int freed = rs_vtf_destroy(h);   // (a failure's message stays: destroy does not clear it)
     return rc != RS_OK ? rc : freed;
 }
 

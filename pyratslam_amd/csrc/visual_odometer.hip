@@ -230,15 +230,14 @@ int vo_check_params(int im_h, int im_w, const rs_vo_params* p) {
 }  // namespace
 
 // The buffers are rs::DevBuf / rs::PinnedBuf members (rs_common.h).  Group capacities, in
-// frames: cap (dProf, dTab, hTab) and frameCap (dFrames, hFrames).
+// frames: cap (dProf, dTab, hTab) and frameCap (dFrames, hFrames).  The stream and the events
+// are rs::Stream / rs::Event owners.
 struct rs_vo {
     int device = 0, H = 0, W = 0, S = 0;
     rs_vo_params p{};
     VoRegion reg[2]{};
     int wd[2]{}, rows[2]{};
     bool same = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     rs::DevBuf<uint8_t> dFrames;
     rs::PinnedBuf<uint8_t> hFrames;
     int frameCap = 0;
@@ -247,6 +246,9 @@ struct rs_vo {
     int cap = 0;
     bool hasCarry = false, timing = false, timed = false;
     float ms[2] = {0, 0};
+    // the owners come after the buffers: members go in reverse order, streams and events first
+    rs::Stream stream;
+    rs::Event ev[3];
 };
 
 namespace {
@@ -277,34 +279,34 @@ int vo_launch(rs_vo* h, int n, const uint8_t* src, bool timed) {
     const size_t fb = (size_t)h->H * h->W;
     const int ps = h->wd[0] + h->wd[1], nreg = h->same ? 1 : 2;
     const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0 && h->W % 16 == 0;
-    if (timed) RS_HIP(hipEventRecord(h->ev[0], h->stream));
+    if (timed) RS_HIP(hipEventRecord(h->ev[0].get(), h->stream.get()));
     if (vec) {
         int tiles = 1;
         for (int r = 0; r < nreg; ++r) {
             const int G = (h->reg[r].x1 - (h->reg[r].x0 & ~15) + 15) / 16;
             tiles = std::max(tiles, (G + VO_GROUPS - 1) / VO_GROUPS);
         }
-        hipLaunchKernelGGL(vo_profile_kernel, dim3(n, tiles, nreg), dim3(VO_THREADS), 0, h->stream, src,
+        hipLaunchKernelGGL(vo_profile_kernel, dim3(n, tiles, nreg), dim3(VO_THREADS), 0, h->stream.get(), src,
                            fb, h->W, h->reg[0], h->reg[1], (int)h->same, h->dProf.get(), ps);
     } else {
         const int wmax = std::max(h->wd[0], h->wd[1]);
         hipLaunchKernelGGL(vo_profile_bytes_kernel, dim3(n, (wmax + VO_THREADS - 1) / VO_THREADS, nreg),
-                           dim3(VO_THREADS), 0, h->stream, src, fb, h->W, h->reg[0], h->reg[1],
+                           dim3(VO_THREADS), 0, h->stream.get(), src, fb, h->W, h->reg[0], h->reg[1],
                            (int)h->same, h->dProf.get(), ps);
     }
     RS_HIP(hipGetLastError());
-    if (timed) RS_HIP(hipEventRecord(h->ev[1], h->stream));
+    if (timed) RS_HIP(hipEventRecord(h->ev[1].get(), h->stream.get()));
     const uint32_t* carry = h->hasCarry ? h->dCarry.get() : nullptr;
     const int wmax = std::max(h->wd[0], h->wd[1]);
     if (wmax <= VO_LDS_WIDTH)
         hipLaunchKernelGGL(vo_shift_kernel<true>, dim3(n, nreg), dim3(VO_THREADS),
-                           sizeof(uint32_t) * 2 * wmax, h->stream, h->dProf.get(), ps, carry, h->wd[0],
+                           sizeof(uint32_t) * 2 * wmax, h->stream.get(), h->dProf.get(), ps, carry, h->wd[0],
                            h->wd[1], h->S, (int)h->same, h->dTab.get());
     else
-        hipLaunchKernelGGL(vo_shift_kernel<false>, dim3(n, nreg), dim3(VO_THREADS), 0, h->stream,
+        hipLaunchKernelGGL(vo_shift_kernel<false>, dim3(n, nreg), dim3(VO_THREADS), 0, h->stream.get(),
                            h->dProf.get(), ps, carry, h->wd[0], h->wd[1], h->S, (int)h->same, h->dTab.get());
     RS_HIP(hipGetLastError());
-    if (timed) RS_HIP(hipEventRecord(h->ev[2], h->stream));
+    if (timed) RS_HIP(hipEventRecord(h->ev[2].get(), h->stream.get()));
     return RS_OK;
 }
 
@@ -328,11 +330,10 @@ int rs_vo_create(int im_h, int im_w, const rs_vo_params* params, int device, rs_
     RS_CHECK(out, RS_ERR_ARG, "null output handle pointer");
     *out = nullptr;
     RS_TRY(vo_check_params(im_h, im_w, params));  // (before any device call: checked without a GPU)
-    int ndev = 0;
-    RS_HIP(hipGetDeviceCount(&ndev));
-    RS_CHECK(device >= 0 && device < ndev, RS_ERR_ARG, "device %d not in [0, %d)", device, ndev);
-    RS_HIP(hipSetDevice(device));
-    rs_vo* h = new rs_vo();
+    RS_TRY(rs::use_device(device));
+    // one failure exit: rs_vo_destroy takes a handle at any stage
+    std::unique_ptr<rs_vo, int (*)(rs_vo*)> owner(new rs_vo(), rs_vo_destroy);
+    rs_vo* const h = owner.get();
     h->device = device; h->H = im_h; h->W = im_w; h->S = params->max_shift; h->p = *params;
     h->reg[0] = {params->trans_y0, params->trans_y1, params->trans_x0, params->trans_x1};
     h->reg[1] = {params->rot_y0, params->rot_y1, params->rot_x0, params->rot_x1};
@@ -341,20 +342,11 @@ int rs_vo_create(int im_h, int im_w, const rs_vo_params* params, int device, rs_
         h->rows[r] = h->reg[r].y1 - h->reg[r].y0;
     }
     h->same = std::memcmp(&h->reg[0], &h->reg[1], sizeof(VoRegion)) == 0;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&h->ev[i]);
-    if (e != hipSuccess) {
-        rs::set_error("odometer stream/event creation failed: %s", hipGetErrorString(e));
-        rs_vo_destroy(h);
-        return RS_ERR_HIP;
-    }
-    int s = h->dCarry.reserve((size_t)h->wd[0] + h->wd[1]);
-    if (s == RS_OK) s = vo_grow(h, 1, true);
-    if (s != RS_OK) {
-        rs_vo_destroy(h);
-        return s;
-    }
-    *out = h;
+    RS_TRY(h->stream.create());
+    for (rs::Event& e : h->ev) RS_TRY(e.create());
+    RS_TRY(h->dCarry.reserve((size_t)h->wd[0] + h->wd[1]));
+    RS_TRY(vo_grow(h, 1, true));
+    *out = owner.release();
     return RS_OK;
 }
 
@@ -362,11 +354,8 @@ int rs_vo_destroy(rs_vo* h) {
     if (!h) return RS_OK;
     (void)hipSetDevice(h->device);
     // queued work that failed after a call returned is reported here, not dropped
-    const hipError_t se = h->stream ? hipStreamSynchronize(h->stream) : hipSuccess;
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;  // (the buffers go with their members)
+    const hipError_t se = rs::sync_streams({h->stream.get()});
+    delete h;  // (the streams and events, then the buffers, go with their members)
     RS_CHECK(se == hipSuccess, RS_ERR_HIP, "work queued before rs_vo_destroy failed: %s", hipGetErrorString(se));
     return RS_OK;
 }
@@ -400,20 +389,20 @@ int rs_vo_run(rs_vo* h, int nf, const uint8_t* frames, double* deltas, uint32_t*
         const uint8_t* src = frames + fb * c0;
         if (!on_device) {
             std::memcpy(h->hFrames.get(), src, fb * n);
-            RS_HIP(hipMemcpyAsync(h->dFrames.get(), h->hFrames.get(), fb * n, hipMemcpyHostToDevice, h->stream));
+            RS_HIP(hipMemcpyAsync(h->dFrames.get(), h->hFrames.get(), fb * n, hipMemcpyHostToDevice, h->stream.get()));
             src = h->dFrames.get();
         }
         const bool first = !h->hasCarry;  // frame c0 has no predecessor
         RS_TRY(vo_launch(h, n, src, timed));
         RS_HIP(hipMemcpyAsync(h->dCarry.get(), h->dProf.get() + ps * (n - 1), sizeof(uint32_t) * ps,
-                              hipMemcpyDeviceToDevice, h->stream));
+                              hipMemcpyDeviceToDevice, h->stream.get()));
         h->hasCarry = true;
         RS_HIP(hipMemcpyAsync(h->hTab.get(), h->dTab.get(), sizeof(uint32_t) * 2 * nt * n, hipMemcpyDeviceToHost,
-                              h->stream));
-        RS_HIP(hipStreamSynchronize(h->stream));
+                              h->stream.get()));
+        RS_HIP(hipStreamSynchronize(h->stream.get()));
         if (timed) {
-            RS_HIP(hipEventElapsedTime(&h->ms[0], h->ev[0], h->ev[1]));
-            RS_HIP(hipEventElapsedTime(&h->ms[1], h->ev[1], h->ev[2]));
+            RS_HIP(hipEventElapsedTime(&h->ms[0], h->ev[0].get(), h->ev[1].get()));
+            RS_HIP(hipEventElapsedTime(&h->ms[1], h->ev[1].get(), h->ev[2].get()));
             h->timed = true;
         }
         if (profiles)

@@ -1,21 +1,25 @@
-// Stand-alone host test of rs::DevBuf / rs::PinnedBuf and rs::grown (rs_common.h) and of the
-// growth idiom the handles write with them.  It links its own definitions of the four allocation
-// functions -- malloc-backed, counting live blocks, able to refuse the k-th allocation --
-// in place of rs_common.cpp, so it needs no GPU; tests/test_host_buffers.py builds it with
-// -fsanitize=address,undefined and runs it.  Exit status 0: every check held.
+// Stand-alone host test of rs::DevBuf / rs::PinnedBuf, rs::Stream / rs::Event and rs::grown
+// (rs_common.h) and of the idioms the handles write with them: group growth, lazily created
+// stream groups, the event pool, a create's failure exit.  It links its own definitions of the
+// four allocation functions and of the four stream and event functions -- malloc-backed,
+// counting live blocks, able to refuse the k-th call -- in place of rs_common.cpp, so it needs
+// no GPU; tests/test_host_buffers.py builds it with -fsanitize=address,undefined and runs it.
+// Exit status 0: every check held.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
+#include <vector>
 
 #include "rs_common.h"
 
 namespace {
 
-int g_live = 0;       // blocks allocated and not yet released
-int g_allocs = 0;     // allocation calls so far
+int g_live = 0;       // blocks, streams and events created and not yet released
+int g_allocs = 0;     // allocation and creation calls so far
 int g_frees = 0;      // release calls so far
-int g_fail_at = -1;   // the allocation call (0-based, counted from arm()) to refuse
+int g_fail_at = -1;   // the allocation or creation call (0-based, counted from arm()) to refuse
 int g_checks = 0, g_failed = 0;
 char g_error[256] = {0};
 
@@ -35,6 +39,15 @@ hipError_t test_free(void* ptr) {
     --g_live;
     ++g_frees;
     return hipSuccess;
+}
+
+// A stream or an event: a one-byte block behind the opaque pointer, through the same counters.
+template <class T>
+hipError_t test_create(T* obj) {
+    void* p = nullptr;
+    const hipError_t e = test_alloc(&p, 1);
+    *obj = static_cast<T>(p);
+    return e == hipSuccess ? hipSuccess : hipErrorInvalidValue;
 }
 
 #define CHECK(cond)                                                        \
@@ -66,6 +79,11 @@ hipError_t pinned_alloc(void** ptr, void** dev, size_t bytes, unsigned) {
     return e;
 }
 hipError_t pinned_free(void* ptr) { return test_free(ptr); }
+
+hipError_t stream_create(hipStream_t* s) { return test_create(s); }
+hipError_t stream_destroy(hipStream_t s) { return test_free(s); }
+hipError_t event_create(hipEvent_t* e, unsigned) { return test_create(e); }
+hipError_t event_destroy(hipEvent_t e) { return test_free(e); }
 
 }  // namespace rs
 
@@ -242,6 +260,186 @@ void test_grown() {
     test_grown_as<size_t>();
 }
 
+// ---- rs::Stream / rs::Event ----
+
+void test_owner_create() {
+    arm(-1);
+    {
+        rs::Stream s;
+        rs::Event e;
+        CHECK(s.get() == nullptr && e.get() == nullptr);
+        CHECK(s.create() == RS_OK && s.get() && g_live == 1);
+        CHECK(e.create(hipEventDisableTiming) == RS_OK && e.get() && g_live == 2);
+        const hipStream_t ps = s.get();
+        const hipEvent_t pe = e.get();
+        const int allocs = g_allocs;
+        CHECK(s.create() == RS_OK && e.create() == RS_OK);   // on a full owner: nothing
+        CHECK(g_allocs == allocs && s.get() == ps && e.get() == pe && g_live == 2);
+        e.reset();
+        CHECK(e.get() == nullptr && g_live == 1);
+        e.reset();
+        CHECK(g_live == 1);
+    }
+    CHECK(g_live == 0);   // the destructors
+}
+
+void test_owner_refused() {
+    rs::Stream s;
+    rs::Event e;
+    arm(0);
+    rs::clear_error();
+    CHECK(s.create("test stream") == RS_ERR_HIP && s.get() == nullptr && g_live == 0);
+    CHECK(std::strstr(g_error, "test stream") != nullptr);
+    arm(0);
+    CHECK(e.create(hipEventDefault, "test event") == RS_ERR_HIP && e.get() == nullptr && g_live == 0);
+    CHECK(std::strstr(g_error, "test event") != nullptr);
+    arm(-1);
+    CHECK(s.create() == RS_OK && e.create() == RS_OK && g_live == 2);   // and creates again
+}
+
+void test_owner_move() {
+    arm(-1);
+    rs::Event a, b;
+    CHECK(a.create() == RS_OK && b.create() == RS_OK && g_live == 2);
+    const hipEvent_t pb = b.get();
+    const int frees = g_frees;
+    a = std::move(b);
+    CHECK(g_frees == frees + 1 && g_live == 1);   // the target's old event, exactly once
+    CHECK(a.get() == pb && b.get() == nullptr);
+    rs::Event& self = a;
+    a = std::move(self);
+    CHECK(a.get() == pb && g_live == 1);
+    {
+        rs::Event c(std::move(a));
+        CHECK(c.get() == pb && a.get() == nullptr && g_frees == frees + 1);
+    }   // c destroys it; a, moved from, does not (a second release is the sanitizer's to report)
+    CHECK(g_live == 0 && g_frees == frees + 2);
+    rs::Stream s, t;
+    CHECK(s.create() == RS_OK);
+    const hipStream_t ps = s.get();
+    t = std::move(s);
+    CHECK(t.get() == ps && s.get() == nullptr && g_live == 1);
+}
+
+// A stream and its four events, created on first use the way rs_vt_match_stream creates its
+// upload group: into locals, moved into the handle once every one exists.
+struct Lazy {
+    rs::Stream stream;
+    rs::Event up[2], used[2];
+};
+constexpr int LAZY_OBJECTS = 5;
+
+int ensure(Lazy* g) {
+    if (g->stream.get()) return RS_OK;
+    rs::Stream st;
+    rs::Event up[2], used[2];
+    RS_TRY(st.create());
+    for (int i = 0; i < 2; ++i) {
+        RS_TRY(up[i].create(hipEventDisableTiming));
+        RS_TRY(used[i].create(hipEventDisableTiming));
+    }
+    for (int i = 0; i < 2; ++i) {
+        g->up[i] = std::move(up[i]);
+        g->used[i] = std::move(used[i]);
+    }
+    g->stream = std::move(st);
+    return RS_OK;
+}
+
+bool lazy_absent(const Lazy& g) {
+    return !g.stream.get() && !g.up[0].get() && !g.up[1].get() && !g.used[0].get() && !g.used[1].get();
+}
+bool lazy_whole(const Lazy& g) {
+    return g.stream.get() && g.up[0].get() && g.up[1].get() && g.used[0].get() && g.used[1].get();
+}
+
+void test_lazy_group() {
+    for (int k = 0; k < LAZY_OBJECTS; ++k) {
+        Lazy g;
+        arm(k);
+        CHECK(ensure(&g) == RS_ERR_HIP);
+        CHECK(lazy_absent(g) && g_live == 0);   // whole or not at all
+        arm(-1);
+        CHECK(ensure(&g) == RS_OK && lazy_whole(g) && g_live == LAZY_OBJECTS);   // the retry builds it
+        const hipStream_t ps = g.stream.get();
+        const int allocs = g_allocs;
+        CHECK(ensure(&g) == RS_OK && g.stream.get() == ps && g_allocs == allocs);
+    }
+    CHECK(g_live == 0);
+}
+
+// The profiling-event pool of the pose cells (pc_ensure_events): the missing events whole or
+// not at all.
+int ensure_events(std::vector<rs::Event>* pool, size_t need) {
+    std::vector<rs::Event> fresh(need > pool->size() ? need - pool->size() : 0);
+    for (rs::Event& e : fresh) RS_TRY(e.create());
+    for (rs::Event& e : fresh) pool->push_back(std::move(e));
+    return RS_OK;
+}
+
+bool pool_valid(const std::vector<rs::Event>& pool) {
+    for (const rs::Event& e : pool) {
+        if (!e.get()) return false;
+        *reinterpret_cast<volatile char*>(e.get());   // still the test's block (the sanitizer checks)
+    }
+    return true;
+}
+
+void test_event_pool() {
+    for (int old = 0; old <= 4; old += 4)        // from empty, and from a pool of four
+        for (int k = 0; k < 8 - old; ++k) {
+            std::vector<rs::Event> pool;
+            arm(-1);
+            CHECK(ensure_events(&pool, (size_t)old) == RS_OK && (int)pool.size() == old && g_live == old);
+            arm(k);
+            CHECK(ensure_events(&pool, 8) == RS_ERR_HIP);
+            CHECK((int)pool.size() == old && g_live == old && pool_valid(pool));   // the old size, all valid
+            arm(-1);
+            CHECK(ensure_events(&pool, 8) == RS_OK && pool.size() == 8 && g_live == 8 && pool_valid(pool));
+            CHECK(ensure_events(&pool, 3) == RS_OK && pool.size() == 8 && g_live == 8);
+        }
+    CHECK(g_live == 0);
+}
+
+// A handle the way the library declares one -- buffers, then owners -- and its create: one
+// exit through a unique_ptr whose deleter is the destroy function.
+struct Handle {
+    rs::DevBuf<float> state;
+    rs::PinnedBuf<int> staging;
+    rs::Stream stream;
+    rs::Event ev[2];
+};
+constexpr int HANDLE_STAGES = 5;
+
+int handle_destroy(Handle* h) {
+    delete h;
+    return RS_OK;
+}
+
+int handle_create(Handle** out) {
+    *out = nullptr;
+    std::unique_ptr<Handle, int (*)(Handle*)> owner(new Handle(), handle_destroy);
+    Handle* const h = owner.get();
+    RS_TRY(h->stream.create());
+    for (rs::Event& e : h->ev) RS_TRY(e.create());
+    RS_TRY(h->state.reserve(100));
+    RS_TRY(h->staging.reserve(3, hipHostMallocDefault));
+    *out = owner.release();
+    return RS_OK;
+}
+
+void test_handle_create() {
+    for (int k = 0; k < HANDLE_STAGES; ++k) {
+        Handle* h = nullptr;
+        arm(k);
+        CHECK(handle_create(&h) != RS_OK && h == nullptr && g_live == 0);
+    }
+    Handle* h = nullptr;
+    arm(-1);
+    CHECK(handle_create(&h) == RS_OK && h && g_live == HANDLE_STAGES);
+    CHECK(handle_destroy(h) == RS_OK && g_live == 0);
+}
+
 }  // namespace
 
 int main() {
@@ -252,6 +450,15 @@ int main() {
     CHECK(g_live == 0);
     test_group_growth();
     test_move();
+    CHECK(g_live == 0);
+    test_owner_create();
+    test_owner_refused();
+    CHECK(g_live == 0);
+    test_owner_move();
+    CHECK(g_live == 0);
+    test_lazy_group();
+    test_event_pool();
+    test_handle_create();
     CHECK(g_live == 0);   // at exit nothing is live
     std::printf("%d checks, %d failed, %d live\n", g_checks, g_failed, g_live);
     return g_failed == 0 && g_live == 0 ? 0 : 1;

@@ -5,8 +5,10 @@ stream buffers by host and device-resident match_stream, its candidate, matrix a
 buffers by a sequential batch that appends; every index and score against the C oracle for
 the library as it stood at that call, and the batch matched before the streams matched
 again after them bit for bit (the streams read their own view of the query forms and leave
-the batch's alone).  Then every handle kind created and destroyed 20 times, and a library
-too large for the device refused with MemoryError, after which a fresh handle matches."""
+the batch's alone).  Then every handle kind created and destroyed 20 times (the view
+templates' upload stream and its events with it), the timing events of the kinds no other
+test times, and a library too large for the device refused with MemoryError, after which a
+fresh handle matches."""
 import os
 import subprocess
 import sys
@@ -119,16 +121,23 @@ def test_growth_across_capacities_and_the_stream_view(built, tmp_path, prune):
 def test_create_and_destroy_every_handle_kind_20_times(built):
     """close() raises unless rs_*_destroy returned RS_OK."""
     import pyratslam_amd.view_templates as vt
+    from pyratslam_amd.linked_experience_map import LinkedExperienceMap
+    from pyratslam_amd.pose_ensemble import PoseCellEnsemble
     from pyratslam_amd.posecell_network import PoseCellNetwork
     from pyratslam_amd.visual_odometer import SimpleVisualOdometer
     lib = V.synthetic_library(T, 64, 32, seed=301)
     q, _ = V.synthetic_queries(lib, 4, seed=306, hit_frac=1.0)
+    # five host batches: upload groups (1, 2, 2), so both upload buffers and every event of the group
+    qs, _ = V.synthetic_queries(lib, 20, seed=309, hit_frac=0.8)
     frames = np.random.default_rng(307).integers(0, 256, size=(3, 48, 64), dtype=np.uint8)
     for k in range(20):
         h = vt.ViewTemplates._from_shape((64, 32), THR)          # rs_vt
         h.add(lib)
         idx, _, new = h.match_templates(q, mode=0)
         assert not new.any() and idx.shape == (4,)
+        want_i, want_s, _ = h.match_templates(qs, mode=0)
+        got_i, got_s = h.match_stream(qs.reshape(5, 4, 64, 32))  # ... its upload stream and four events
+        assert np.array_equal(got_i.reshape(-1), want_i) and np.array_equal(got_s.reshape(-1), want_s)
         h.close()
         f = vt.ViewTemplates._from_shape((64, 32), 1e9)          # rs_vtf, made by the first float batch
         fq = q.astype(np.float32)
@@ -142,6 +151,54 @@ def test_create_and_destroy_every_handle_kind_20_times(built):
         pc.inject(1.0, (5, 6, 7))
         assert len(pc.update((0.2, 0.01))) == 3
         pc.close()
+        em = LinkedExperienceMap(capacity=2)                     # rs_em
+        for _ in range(3):
+            em.add_experience()
+        em.add_link(0, 1, 1.0, 0.5, -0.5)
+        em.iterate(1)
+        assert em.poses().shape == (3, 3)
+        em.close()
+        pce = PoseCellEnsemble(2, (8, 8, 8))                     # rs_pce
+        pce.inject(1.0, (3, 4, 5))
+        assert pce.run([(0.2, 0.01), (0.2, 0.01)]).shape == (2, 2, 3)
+        pce.close()
+
+
+def test_timing_events_of_the_float_library_the_pose_cells_and_the_ensemble(built):
+    """With timing on, one call, then a time that is finite and not negative.  (The other three
+    kinds: test_view_templates_gpu.py::test_untimed_scans, test_visual_odometer_gpu.py::
+    test_timing_is_off_by_default_and_per_call, test_linked_experience_map_gpu.py::
+    test_interleaved_calls_keep_their_order.)"""
+    import pyratslam_amd.view_templates as vt
+    from pyratslam_amd.pose_ensemble import PoseCellEnsemble
+    from pyratslam_amd.posecell_network import PoseCellNetwork
+
+    def is_time(ms):
+        return np.isfinite(ms) and ms >= 0
+
+    lib = V.synthetic_library(8, 64, 32, seed=310)
+    f = vt.ViewTemplates._from_shape((64, 32), 1e9)              # rs_vtf
+    f.set_timing(True)
+    f.match_templates(lib[:4].astype(np.float32))
+    assert f._vtf is not None
+    f.match_templates(lib[4:].astype(np.float32))                # (a scan of a library that is not empty)
+    print('rs_vtf device_ms', f.device_ms())
+    assert is_time(f.device_ms())
+    f.close()
+    pc = PoseCellNetwork((32, 32, 18))                           # rs_pc: the call's events and the pool's
+    pc.inject(1.0, (5, 6, 7))
+    pc.set_profiling(True, per_kernel=True)
+    assert pc.run([(0.2, 0.01)] * 3).shape == (3, 3)
+    print('rs_pc device_ms', pc.device_ms(), 'kernel_ms', pc.kernel_ms())
+    assert is_time(pc.device_ms()) and all(is_time(ms) for ms in pc.kernel_ms())
+    pc.close()
+    pce = PoseCellEnsemble(2, (8, 8, 8))                         # rs_pce
+    pce.inject(1.0, (3, 4, 5))
+    pce.set_timing(True)
+    pce.run([(0.2, 0.01), (0.2, 0.01)])
+    print('rs_pce device_ms', pce.device_ms())
+    assert is_time(pce.device_ms())
+    pce.close()
 
 
 def test_a_refused_allocation_is_a_memory_error(built):

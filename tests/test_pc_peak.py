@@ -5,18 +5,14 @@ refusals, and tests/pc_peak_main.cpp -- the header alone, built with the host co
 linked into the program; nothing is preloaded).  CPU only: no device call."""
 import ctypes
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import _host_program
 from pyratslam_amd import _build, _lib, numpy_peak_sums, peak_tables, pose_from_sums
 from pyratslam_amd import pc_peak
 
-CXX = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
 GRIDS = [(7, 7, 7), (9, 12, 8), (21, 21, 36), (50, 50, 10)]
 
 
@@ -128,17 +124,7 @@ def test_refusals(lib):
         assert st == _lib.RS_ERR_ARG
 
 
-@pytest.mark.skipif(not CXX, reason='host C++ compiler absent')
 def test_rule_header_alone_under_sanitizers(tmp_path):
-    exe = str(tmp_path / 'pc_peak')
-    # the sanitizer runtimes linked into the program (clang's default; gcc's is shared)
-    gcc = 'clang' not in subprocess.run([CXX, '--version'], stdout=subprocess.PIPE, text=True).stdout
-    static = ['-static-libasan', '-static-libubsan'] if gcc else []
-    subprocess.check_call([CXX, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', '-ffp-contract=off', *static,
-                           '-I' + os.path.join(ROOT, 'pyratslam_amd', 'csrc'),
-                           os.path.join(ROOT, 'tests', 'pc_peak_main.cpp'), '-o', exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
-    print(r.stdout)
+    r = _host_program.run(tmp_path, 'pc_peak_main.cpp', flags=('-ffp-contract=off',), timeout=60)
     assert r.returncode == 0, r.stdout
     assert ' 0 failed' in r.stdout

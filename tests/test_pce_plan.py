@@ -5,34 +5,19 @@ against its own restatement.  It is built with the host compiler and
 program, nothing is preloaded.  The second half goes through the library's C ABI without a
 device: rs_pce_fit against the plan, and rs_pce_create's refusals.  CPU only."""
 import ctypes
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+import _host_program
 from pyratslam_amd import _build, _lib
 from pyratslam_amd import filters as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
 LDS_BYTES = 160 * 1024
 
 
-@pytest.mark.skipif(not CXX, reason='host C++ compiler absent')
 def test_plan_record_and_chunks_under_sanitizers(tmp_path):
-    exe = str(tmp_path / 'pce_plan')
-    # the sanitizer runtimes linked into the program (clang's default; gcc's is shared)
-    gcc = 'clang' not in subprocess.run([CXX, '--version'], stdout=subprocess.PIPE, text=True).stdout
-    static = ['-static-libasan', '-static-libubsan'] if gcc else []
-    subprocess.check_call([CXX, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', *static,
-                           '-I' + os.path.join(ROOT, 'include'),
-                           '-I' + os.path.join(ROOT, 'pyratslam_amd', 'csrc'),
-                           os.path.join(ROOT, 'tests', 'pce_plan_main.cpp'), '-o', exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
-    print(r.stdout)
+    r = _host_program.run(tmp_path, 'pce_plan_main.cpp', include=('include',), timeout=60)
     assert r.returncode == 0, r.stdout
     assert ' 0 failed' in r.stdout
 

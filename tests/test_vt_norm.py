@@ -5,19 +5,15 @@ alone under -fsanitize=address,undefined (tests/vt_norm_main.cpp, run as a child
 sanitizer is linked into the program, nothing is preloaded); the exposure case the feature is
 for; and the arguments of the Python classes and of the replay's command line."""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import _host_program
 import _vt_norm_cases as C
 from pyratslam_amd import _lib, replay
 from pyratslam_amd import view_templates as VT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
 SHAPES = [(64, 32), (32, 32), (64, 48), (24, 10), (16, 5), (10, 7), (70, 130)]
 RADII = (1, 3, 7)
 GAINS = (1, 32, 127)
@@ -98,17 +94,8 @@ def test_host_rule_refuses_bad_arguments():
     assert lib.rs_version() == 100
 
 
-@pytest.mark.skipif(not CXX, reason='host C++ compiler absent')
 def test_norm_rule_header_under_sanitizers(tmp_path):
-    exe = str(tmp_path / 'vt_norm')
-    gcc = 'clang' not in subprocess.run([CXX, '--version'], stdout=subprocess.PIPE, text=True).stdout
-    static = ['-static-libasan', '-static-libubsan'] if gcc else []
-    subprocess.check_call([CXX, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', *static,
-                           '-I' + os.path.join(ROOT, 'pyratslam_amd', 'csrc'),
-                           os.path.join(ROOT, 'tests', 'vt_norm_main.cpp'), '-o', exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-    print(r.stdout)
+    r = _host_program.run(tmp_path, 'vt_norm_main.cpp', timeout=120)
     assert r.returncode == 0, r.stdout
     assert ' 0 failed' in r.stdout
 

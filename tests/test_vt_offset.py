@@ -5,21 +5,17 @@ here, with no tolerance; the header alone under -fsanitize=address,undefined
 nothing is preloaded); ``rel_rad`` in the linked map on NumpyLinkedExperienceMap; the host side
 of ``shift_axis='cols'``; ``refine_offset``; and the replay's command line."""
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import _em_graphs as G
+import _host_program
 from oracle import view_templates as V
 from pyratslam_amd import _lib, replay, synthetic
 from pyratslam_amd import linked_experience_map as M
 from pyratslam_amd import view_templates as VT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
 METRICS = ('wrapped', 'sad')
 
 
@@ -112,17 +108,8 @@ def test_host_rule_refuses_bad_arguments():
     assert lib.rs_version() == 100
 
 
-@pytest.mark.skipif(not CXX, reason='host C++ compiler absent')
 def test_offset_rule_header_under_sanitizers(tmp_path):
-    exe = str(tmp_path / 'vt_offset')
-    gcc = 'clang' not in subprocess.run([CXX, '--version'], stdout=subprocess.PIPE, text=True).stdout
-    static = ['-static-libasan', '-static-libubsan'] if gcc else []
-    subprocess.check_call([CXX, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', *static,
-                           '-I' + os.path.join(ROOT, 'pyratslam_amd', 'csrc'),
-                           os.path.join(ROOT, 'tests', 'vt_offset_main.cpp'), '-o', exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-    print(r.stdout)
+    r = _host_program.run(tmp_path, 'vt_offset_main.cpp', timeout=120)
     assert r.returncode == 0, r.stdout
     assert ' 0 failed' in r.stdout
 

@@ -4,20 +4,14 @@ wrapped metric that motivates it, the replay's command line, the refusal of an u
 before any device work, and the new dispatch rules of csrc/vt_plan.h (tests/vt_sad_plan_main.cpp,
 built with -fsanitize=address,undefined and run as a child process; the sanitizer is linked
 into the program, nothing is preloaded)."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import _host_program
 from oracle import view_templates as V
 from pyratslam_amd import replay, synthetic
 from pyratslam_amd.view_templates import (METRICS, ShardedViewTemplates, ViewTemplates,
                                           numpy_sad_u8_scores)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.environ.get('CXX') or shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
 
 
 def two_sided(library, q, seed, noise=3):
@@ -107,16 +101,7 @@ class _NoNetwork:
         pass
 
 
-@pytest.mark.skipif(not CXX, reason='host C++ compiler absent')
 def test_sad_plan_rules_under_sanitizers(tmp_path):
-    exe = str(tmp_path / 'vt_sad_plan')
-    gcc = 'clang' not in subprocess.run([CXX, '--version'], stdout=subprocess.PIPE, text=True).stdout
-    static = ['-static-libasan', '-static-libubsan'] if gcc else []
-    subprocess.check_call([CXX, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=undefined', *static,
-                           '-I' + os.path.join(ROOT, 'pyratslam_amd', 'csrc'),
-                           os.path.join(ROOT, 'tests', 'vt_sad_plan_main.cpp'), '-o', exe])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=60)
-    print(r.stdout)
+    r = _host_program.run(tmp_path, 'vt_sad_plan_main.cpp', timeout=60)
     assert r.returncode == 0, r.stdout
     assert ' 0 failed' in r.stdout

@@ -76,22 +76,22 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(h->dCtl.get(), h->hCtl.get(), h->ctlStride * n, hipMemcpyHostToDevice));
     hipGraph_t g;
     hipGraphExec_t ge;
-    CK(hipStreamBeginCapture(h->stream, hipStreamCaptureModeGlobal));
+    CK(hipStreamBeginCapture(h->stream.get(), hipStreamCaptureModeGlobal));
     for (int s = 0; s < n; ++s) {
         const PcCtlRing c = make_ctl_ring(h, s);
         if (pc_launch_step<float, PcCtlRing>(h, step_out(h, s), &c, -1) != RS_OK) return 1;
     }
-    hipLaunchKernelGGL(pc_res_export, dim3(n), dim3(64), 0, h->stream, h->dRes.get(), n, h->hRes.dev());
-    CK(hipStreamEndCapture(h->stream, &g));
+    hipLaunchKernelGGL(pc_res_export, dim3(n), dim3(64), 0, h->stream.get(), h->dRes.get(), n, h->hRes.dev());
+    CK(hipStreamEndCapture(h->stream.get(), &g));
     fprintf(stderr, "captured\n");
     double ti = now_us();
     CK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
     const double inst = now_us() - ti;
-    CK(hipGraphLaunch(ge, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    CK(hipGraphLaunch(ge, h->stream.get()));
+    CK(hipStreamSynchronize(h->stream.get()));
     t0 = now_us();
-    for (int rep = 0; rep < reps; ++rep) CK(hipGraphLaunch(ge, h->stream));
-    CK(hipStreamSynchronize(h->stream));
+    for (int rep = 0; rep < reps; ++rep) CK(hipGraphLaunch(ge, h->stream.get()));
+    CK(hipStreamSynchronize(h->stream.get()));
     const double graph = (now_us() - t0) / (reps * n);
     // the same with the ring form kernels launched directly (no inline control)
     t0 = now_us();
@@ -100,9 +100,9 @@ int main(int argc, char** argv) {
             const PcCtlRing c = make_ctl_ring(h, s);
             if (pc_launch_step<float, PcCtlRing>(h, step_out(h, s), &c, -1) != RS_OK) return 1;
         }
-        hipLaunchKernelGGL(pc_res_export, dim3(n), dim3(64), 0, h->stream, h->dRes.get(), n, h->hRes.dev());
+        hipLaunchKernelGGL(pc_res_export, dim3(n), dim3(64), 0, h->stream.get(), h->dRes.get(), n, h->hRes.dev());
     }
-    CK(hipStreamSynchronize(h->stream));
+    CK(hipStreamSynchronize(h->stream.get()));
     const double ring = (now_us() - t0) / (reps * n);
     printf("grid %dx%dx%d form %s: rs_pc_run %.2f us/step; ring launches %.2f us/step; "
            "one graph of all steps %.2f "

@@ -235,21 +235,21 @@ int main(int argc, char** argv) {
         const dim3 g(h->cgx * h->cgy), b(HF_NT);
         const int reps = 500;
         float t = 0;
-        CK(hipEventRecord(c0, h->stream));
-        for (int i = 0; i < reps; ++i) hipLaunchKernelGGL(empty_kernel, g, b, 0, h->stream, nullptr);
-        CK(hipEventRecord(c1, h->stream));
+        CK(hipEventRecord(c0, h->stream.get()));
+        for (int i = 0; i < reps; ++i) hipLaunchKernelGGL(empty_kernel, g, b, 0, h->stream.get(), nullptr);
+        CK(hipEventRecord(c1, h->stream.get()));
         CK(hipEventSynchronize(c1));
         CK(hipEventElapsedTime(&t, c0, c1));
         printf("empty kernel, same grid: %.2f us/launch\n", 1e3 * t / reps);
         PcCtlHalo c;
         make_ctl_halo(X, Y, h->TH, ox.data(), oy.data(), f.data(), zf.data(), &c);
-        CK(hipEventRecord(c0, h->stream));
+        CK(hipEventRecord(c0, h->stream.get()));
         for (int i = 0; i < reps; ++i)
-            hf_launch<false>(h->TH, g, h->stream, (const float*)h->dP.get(), hf_pack(X, Y),
+            hf_launch<false>(h->TH, g, h->stream.get(), (const float*)h->dP.get(), hf_pack(X, Y),
                                hf_pack(h->cgx, g.x), hf_pack(c.ux, c.uy), hf_pack(c.uw, c.uh), hf_magic(h->cgx),
                                hf_magic(c.uh), h->dPart.get(), h->nPart, (float*)h->dQ.get(), h->dPart.get() + h->nPart, h->dRes.get(), h->dRes.get() + RES_SLOTS,
                                (const float*)h->dFilt.get(), h->nf, c, h->kf, nullptr);
-        CK(hipEventRecord(c1, h->stream));
+        CK(hipEventRecord(c1, h->stream.get()));
         CK(hipEventSynchronize(c1));
         CK(hipEventElapsedTime(&t, c0, c1));
         printf("halo step alone: %.2f us/launch\n", 1e3 * t / reps);
@@ -270,29 +270,29 @@ int main(int argc, char** argv) {
         constexpr int THF = co_thmax<float>();
         const int reps = 500;
         float t = 0;
-        CK(hipEventRecord(c0, h->stream));
-        for (int i = 0; i < reps; ++i) hipLaunchKernelGGL(empty_kernel, g, b, 0, h->stream, nullptr);
-        CK(hipEventRecord(c1, h->stream));
+        CK(hipEventRecord(c0, h->stream.get()));
+        for (int i = 0; i < reps; ++i) hipLaunchKernelGGL(empty_kernel, g, b, 0, h->stream.get(), nullptr);
+        CK(hipEventRecord(c1, h->stream.get()));
         CK(hipEventSynchronize(c1));
         CK(hipEventElapsedTime(&t, c0, c1));
         printf("empty kernel, same grid: %.2f us/launch\n", 1e3 * t / reps);
         const PcCtlRing ctl = make_ctl_ring(h, 0);
-        CK(hipEventRecord(c0, h->stream));
+        CK(hipEventRecord(c0, h->stream.get()));
         for (int i = 0; i < reps; ++i)
-            hipLaunchKernelGGL((pc_excite_cols<float, CO_TX, CO_TY, CO_NW, THF, false>), g, b, 0, h->stream,
+            hipLaunchKernelGGL((pc_excite_cols<float, CO_TX, CO_TY, CO_NW, THF, false>), g, b, 0, h->stream.get(),
                                (const float*)h->dP.get(), X, Y, TH, h->cgx, h->cgy, (int)g.x, (float*)h->dQ.get(),
                                h->dPart.get(), h->dRes.get(), h->coKC, h->kf);
-        CK(hipEventRecord(c1, h->stream));
+        CK(hipEventRecord(c1, h->stream.get()));
         CK(hipEventSynchronize(c1));
         CK(hipEventElapsedTime(&t, c0, c1));
         printf("excite alone: %.2f us/launch\n", 1e3 * t / reps);
-        CK(hipEventRecord(c0, h->stream));
+        CK(hipEventRecord(c0, h->stream.get()));
         for (int i = 0; i < reps; ++i)
-            hipLaunchKernelGGL((pc_path_cols<float, CO_TX, CO_TY, CO_NW, THF, false, PcCtlRing>), g, bp, 0, h->stream,
+            hipLaunchKernelGGL((pc_path_cols<float, CO_TX, CO_TY, CO_NW, THF, false, PcCtlRing>), g, bp, 0, h->stream.get(),
                                (const float*)h->dQ.get(), X, Y, TH, h->cgx, h->cgy, (int)g.x, (float*)h->dP.get(), h->dPart.get(),
                                h->nPart, (const float*)h->dFilt.get(), h->nf, ctl, h->dRes.get(), (float*)nullptr,
                                (unsigned*)nullptr, h->coKC);
-        CK(hipEventRecord(c1, h->stream));
+        CK(hipEventRecord(c1, h->stream.get()));
         CK(hipEventSynchronize(c1));
         CK(hipEventElapsedTime(&t, c0, c1));
         printf("path alone: %.2f us/launch\n", 1e3 * t / reps);
@@ -314,29 +314,29 @@ int main(int argc, char** argv) {
     const dim3 g((X + RT_BX - 1) / RT_BX, (TH + RT_BK - 1) / RT_BK);
     const int reps = 500;
     float t = 0;
-    CK(hipEventRecord(e0, h->stream));
+    CK(hipEventRecord(e0, h->stream.get()));
     for (int i = 0; i < reps; ++i)
-        hipLaunchKernelGGL(empty_kernel, g, dim3(256), 0, h->stream, nullptr);
-    CK(hipEventRecord(e1, h->stream));
+        hipLaunchKernelGGL(empty_kernel, g, dim3(256), 0, h->stream.get(), nullptr);
+    CK(hipEventRecord(e1, h->stream.get()));
     CK(hipEventSynchronize(e1));
     CK(hipEventElapsedTime(&t, e0, e1));
     printf("empty kernel, same grid: %.2f us/launch\n", 1e3 * t / reps);
     const PcCtlRing ctl = make_ctl_ring(h, 0);
-    CK(hipEventRecord(e0, h->stream));
+    CK(hipEventRecord(e0, h->stream.get()));
     for (int i = 0; i < reps; ++i)
-        hipLaunchKernelGGL((pc_excite_rows<float, 64>), g, dim3(RT_NT), 0, h->stream,
+        hipLaunchKernelGGL((pc_excite_rows<float, 64>), g, dim3(RT_NT), 0, h->stream.get(),
                            (const float*)h->dP.get(), (float*)h->dQ.get(), h->dPart.get(), h->dRes.get(), X, Y, TH, h->kf);
-    CK(hipEventRecord(e1, h->stream));
+    CK(hipEventRecord(e1, h->stream.get()));
     CK(hipEventSynchronize(e1));
     CK(hipEventElapsedTime(&t, e0, e1));
     printf("excite alone: %.2f us/launch\n", 1e3 * t / reps);
-    CK(hipEventRecord(e0, h->stream));
+    CK(hipEventRecord(e0, h->stream.get()));
     for (int i = 0; i < reps; ++i)
-        hipLaunchKernelGGL((pc_path_rows<float, 64, PcCtlRing>), g, dim3(RT_NT), 0, h->stream,
+        hipLaunchKernelGGL((pc_path_rows<float, 64, PcCtlRing>), g, dim3(RT_NT), 0, h->stream.get(),
                            (const float*)h->dQ.get(), (float*)h->dP.get(), h->dPart.get(), h->nPart,
                            (const float*)h->dFilt.get(), h->nf, ctl, h->dRes.get(), (float*)nullptr,
                            (unsigned*)nullptr, X, Y, TH);
-    CK(hipEventRecord(e1, h->stream));
+    CK(hipEventRecord(e1, h->stream.get()));
     CK(hipEventSynchronize(e1));
     CK(hipEventElapsedTime(&t, e0, e1));
     printf("path alone: %.2f us/launch\n", 1e3 * t / reps);

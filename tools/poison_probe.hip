@@ -83,10 +83,10 @@ int main(int argc, char** argv) {
         }
         if (pc_grow_steps(h, steps) != RS_OK) return 1;   // the argmax slots exist now
         const size_t nres = sizeof(unsigned long long) * RES_SLOTS * h->resCap;
-        CK(hipMemsetAsync(h->dQ.get(), v == 1 ? 0xFF : 0, h->n * h->esz, h->stream));
-        CK(hipMemsetAsync(h->dPart.get(), v == 2 ? 0xFF : 0, sizeof(double) * h->nPart, h->stream));
-        CK(hipMemsetAsync(h->dRes.get(), v == 3 ? 0xFF : 0, nres, h->stream));
-        CK(hipStreamSynchronize(h->stream));
+        CK(hipMemsetAsync(h->dQ.get(), v == 1 ? 0xFF : 0, h->n * h->esz, h->stream.get()));
+        CK(hipMemsetAsync(h->dPart.get(), v == 2 ? 0xFF : 0, sizeof(double) * h->nPart, h->stream.get()));
+        CK(hipMemsetAsync(h->dRes.get(), v == 3 ? 0xFF : 0, nres, h->stream.get()));
+        CK(hipStreamSynchronize(h->stream.get()));
         rs_pc_inject(h, 1.0, X / 2, Y / 2, TH / 2);
         for (int s = 0; s < steps; ++s)
             if (rs_pc_update(h, &ox[s * TH], &oy[s * TH], &fi[s * TH], &zf[s * 7], &pk[3 * s]) != RS_OK) {
