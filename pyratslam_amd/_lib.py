@@ -5,6 +5,7 @@ The library is loaded from this package directory only (built in-tree by
 missing or no HIP device is visible, the drop-in classes raise.
 """
 import ctypes
+import math
 import os
 import threading
 
@@ -280,18 +281,76 @@ def as_c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-class DeviceBuffer:
+class Handle(ctypes.c_void_p):
+    """A handle of the library that knows how to destroy itself: a ``c_void_p``, so it is
+    passed to the rs_* functions as it is."""
+
+    _destroy = None
+
+    @classmethod
+    def create(cls, lib, create, destroy, *args):
+        """``lib.<create>(*args, &handle)``; the exception of ``check`` when it is refused
+        (nothing is then left to destroy)."""
+        h = cls()
+        check(getattr(lib, create)(*args, ctypes.byref(h)))
+        h._destroy = getattr(lib, destroy)
+        return h
+
+    def destroy(self):
+        """The status of the destroy call (it reports an error of queued work); RS_OK, and
+        no call, the second time."""
+        if not self.value:
+            return RS_OK
+        st = self._destroy(self)
+        self.value = None
+        return st
+
+
+class HandleOwner:
+    """``close()``, finalisation and ``with`` for a class that keeps Handles in the attributes
+    named by ``_handles``."""
+
+    _handles = ('_h',)
+
+    def _close_more(self):
+        """What else ``close()`` releases, after the handles."""
+
+    def _drop(self, name):
+        """Destroy the handle in attribute ``name`` and set it to None; the status."""
+        h = getattr(self, name, None)   # (absent when __init__ raised before it was set)
+        setattr(self, name, None)
+        return h.destroy() if h is not None else RS_OK
+
+    def close(self):
+        status = [self._drop(name) for name in self._handles]
+        self._close_more()
+        check(next((st for st in status if st != RS_OK), RS_OK))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class DeviceBuffer(HandleOwner):
     """A block of HBM owned by the caller (rs_dev_malloc); ``ptr`` is the device
     address, usable wherever the C ABI accepts device-resident inputs."""
 
+    _handles = ('ptr',)
+
     def __init__(self, nbytes, device=0):
         self._lib = require_device()
-        p = ctypes.c_void_p()
-        check(self._lib.rs_dev_malloc(int(device), int(nbytes), ctypes.byref(p)))
-        self.ptr, self.nbytes = p, int(nbytes)
+        self.ptr = Handle.create(self._lib, 'rs_dev_malloc', 'rs_dev_free', int(device), int(nbytes))
+        self.nbytes = int(nbytes)
 
     def upload(self, array):
-        import numpy as np
         a = np.ascontiguousarray(array)
         if a.nbytes > self.nbytes:
             raise ValueError('%d bytes do not fit a %d-byte buffer' % (a.nbytes, self.nbytes))
@@ -305,16 +364,21 @@ class DeviceBuffer:
             raise ValueError('offset %d outside the %d-byte buffer' % (byte_offset, self.nbytes))
         return DeviceView(self, int(byte_offset))
 
-    def close(self):
-        if getattr(self, 'ptr', None) is not None and self.ptr.value:
-            self._lib.rs_dev_free(self.ptr)
-        self.ptr = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def device_or_host(arg, item_bytes, host, too_big):
+    """An input of uint8 images, as a host array or as ``(count, ..., DeviceBuffer)`` for images
+    of ``item_bytes`` each already in HBM back to back: ``(pointer, counts, keep)``, the
+    counts a tuple of ints and ``keep`` the object that owns the memory (hold it across the
+    call).  A buffer too small for the counts is a ValueError of the text ``too_big %
+    (counts + (buffer bytes,))``; a host input goes through ``host(arg)``, which returns the
+    checked C-contiguous array (count, ..., H, W)."""
+    if isinstance(arg, tuple):
+        counts, buf = tuple(map(int, arg[:-1])), arg[-1]
+        if math.prod(counts) * item_bytes > buf.nbytes:
+            raise ValueError(too_big % (counts + (buf.nbytes,)))
+        return buf.ptr, counts, buf
+    a = host(arg)
+    return ctypes.c_void_p(a.ctypes.data), a.shape[:-2], a
 
 
 class DeviceView:

@@ -329,7 +329,7 @@ class NumpyLinkedExperienceMap(_LinkedMapBase):
         return self._poses[i]
 
 
-class LinkedExperienceMap(_LinkedMapBase):
+class LinkedExperienceMap(_lib.HandleOwner, _LinkedMapBase):
     """The linked map with its poses on the GPU (``rs_em_*``).  New poses are computed on
     the device from the relaxed pose they start at, ``iterate`` is queued and does not wait;
     ``poses`` / ``get_current_point`` read after everything queued before them.
@@ -340,11 +340,9 @@ class LinkedExperienceMap(_LinkedMapBase):
     def __init__(self, exp_loops=EXP_LOOPS, exp_correction=EXP_CORRECTION, capacity=1024, device=0):
         super().__init__(exp_loops, exp_correction)
         self.device = int(device)
-        self._h = None
         self._lib = _lib.require_device()
-        h = ctypes.c_void_p()
-        _lib.check(self._lib.rs_em_create(int(capacity), self.exp_correction, self.device, ctypes.byref(h)))
-        self._h = h
+        self._h = _lib.Handle.create(self._lib, 'rs_em_create', 'rs_em_destroy', int(capacity),
+                                     self.exp_correction, self.device)
 
     def _add_experience(self, src, d, h, f):
         out = ctypes.c_int(-1)
@@ -391,16 +389,3 @@ class LinkedExperienceMap(_LinkedMapBase):
         ms = ctypes.c_double(-1.0)
         _lib.check(self._lib.rs_em_last_ms(self._h, ctypes.byref(ms)))
         return ms.value
-
-    def close(self):
-        st = 0
-        if getattr(self, '_h', None) is not None and self._h.value:
-            st = self._lib.rs_em_destroy(self._h)   # (reports an error of queued work)
-        self._h = None
-        _lib.check(st)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

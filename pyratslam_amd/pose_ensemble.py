@@ -21,9 +21,10 @@ import numpy as np
 
 from . import _lib
 from . import filters as F
+from .posecell_network import grid_cell, pc_params
 
 
-class PoseCellEnsemble:
+class PoseCellEnsemble(_lib.HandleOwner):
     """B float32 pose-cell networks of shape (X, Y, TH) on one GPU.
 
     ``global_inhibition``: None (the reference's 0.2), a scalar, or one value per member.
@@ -39,7 +40,6 @@ class PoseCellEnsemble:
         self.device = int(device)
         self.max_pc = None
         self._mutex = threading.Lock()
-        self._h = None
         if precision not in ('float32', np.float32):
             raise ValueError('PoseCellEnsemble is float32 only, got precision %r' % (precision,))
         if self._b < 1:
@@ -57,19 +57,9 @@ class PoseCellEnsemble:
         self.filter_table = F.FilterTable()
         self._table = np.ascontiguousarray(self.filter_table.filters, dtype=np.float64)
         self._odo_tables = F.odometry_tables(self.shape[2], self.filter_table)
-        ge, gi, scale = F.separable_factors()
-        params = _lib.PcParams()
-        params.precision = _lib.RS_PREC_F32
-        params.global_inhibition = F.PC_GLOBAL_INHIB
-        params.ge[:] = list(ge)
-        params.gi[:] = list(gi)
-        params.k_scale = scale
-        params.nfilters = self._table.shape[0]
-        params.xy_filters = _lib.ptr(self._table, ctypes.c_double)
-        h = ctypes.c_void_p()
-        _lib.check(self._lib.rs_pce_create(self._b, *self.shape, ctypes.byref(params),
-                                           _lib.ptr(inhib, ctypes.c_double), self.device, ctypes.byref(h)))
-        self._h = h
+        params = pc_params(_lib.RS_PREC_F32, F.PC_GLOBAL_INHIB, self._table)
+        self._h = _lib.Handle.create(self._lib, 'rs_pce_create', 'rs_pce_destroy', self._b, *self.shape,
+                                     ctypes.byref(params), _lib.ptr(inhib, ctypes.c_double), self.device)
 
     @staticmethod
     def fits(shape):
@@ -84,26 +74,6 @@ class PoseCellEnsemble:
         n = ctypes.c_size_t()
         _lib.load().rs_pce_fit(x, y, th, ctypes.byref(n))
         return n.value
-
-    # -- lifetime ---------------------------------------------------------------
-    def close(self):
-        st = 0
-        if self._h is not None and self._h.value:
-            st = self._lib.rs_pce_destroy(self._h)   # (reports an error of queued work)
-        self._h = None
-        _lib.check(st)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def __len__(self):
         return self._b
@@ -129,13 +99,7 @@ class PoseCellEnsemble:
 
     def inject(self, energy, loc, members=None):
         """posecells[m][loc] += energy for every member, or for those of ``members``."""
-        if isinstance(loc, list):
-            raise TypeError('inject expects a tuple (x, y, th)')
-        x, y, th = (int(v) for v in loc)
-        X, Y, TH = self.shape
-        x, y, th = x + X if x < 0 else x, y + Y if y < 0 else y, th + TH if th < 0 else th
-        if not (0 <= x < X and 0 <= y < Y and 0 <= th < TH):
-            raise IndexError('inject location %r outside grid %r' % (loc, self.shape))
+        x, y, th = grid_cell(loc, self.shape, 'inject', 'inject expects a tuple (x, y, th)')
         who = [-1] if members is None else [int(m) for m in members]
         for m in who:
             if members is not None and not 0 <= m < self._b:

@@ -102,7 +102,37 @@ def round_up(x):  # posecell_network.py:19-20
     return math.ceil(x) if x > 0 else math.floor(x)
 
 
-class PoseCellNetwork:
+def grid_cell(loc, shape, what, not_a_tuple):
+    """The cell ``(x, y, th)`` of a grid that ``loc`` names: a tuple only (TypeError
+    ``not_a_tuple`` for a list, which the reference would fancy-index whole planes with,
+    posecell_network.py:324), indexed as numpy indexes -- negative indices count from the
+    end -- and an IndexError '<what> location ... outside grid ...' outside the grid."""
+    if isinstance(loc, list):
+        raise TypeError(not_a_tuple)
+    x, y, th = (int(v) for v in loc)
+    X, Y, TH = shape
+    x, y, th = x + X if x < 0 else x, y + Y if y < 0 else y, th + TH if th < 0 else th
+    if not (0 <= x < X and 0 <= y < Y and 0 <= th < TH):
+        raise IndexError('%s location %r outside grid %r' % (what, loc, shape))
+    return x, y, th
+
+
+def pc_params(precision, global_inhibition, table):
+    """``rs_pc_params`` of the separable kernel factors and the filter table ``table``
+    (float64, C order; the caller keeps it alive until the create call has returned)."""
+    ge, gi, scale = F.separable_factors()
+    params = _lib.PcParams()
+    params.precision = precision
+    params.global_inhibition = global_inhibition
+    params.ge[:] = list(ge)
+    params.gi[:] = list(gi)
+    params.k_scale = scale
+    params.nfilters = table.shape[0]
+    params.xy_filters = _lib.ptr(table, ctypes.c_double)
+    return params
+
+
+class PoseCellNetwork(_lib.HandleOwner):
     """Continuous-attractor pose-cell network on one GPU.
 
     ``precision``: 'float32' (default; activations within 1e-5 of the float64
@@ -152,23 +182,12 @@ class PoseCellNetwork:
         self.max_pc = None
         self._max_valid = False
         self._mutex = threading.Lock()
-        self._h = None
         self._pinned = None
         self._lib = _lib.require_device()
-        ge, gi, scale = F.separable_factors()
         self._table = np.ascontiguousarray(self.filter_table.filters, dtype=np.float64)
-        params = _lib.PcParams()
-        params.precision = _PRECISIONS[precision]
-        params.global_inhibition = self.global_inhibition
-        params.ge[:] = list(ge)
-        params.gi[:] = list(gi)
-        params.k_scale = scale
-        params.nfilters = self._table.shape[0]
-        params.xy_filters = _lib.ptr(self._table, ctypes.c_double)
-        h = ctypes.c_void_p()
-        _lib.check(self._lib.rs_pc_create(*self.shape, ctypes.byref(params), self.device,
-                                          ctypes.byref(h)))
-        self._h = h
+        params = pc_params(_PRECISIONS[precision], self.global_inhibition, self._table)
+        self._h = _lib.Handle.create(self._lib, 'rs_pc_create', 'rs_pc_destroy', *self.shape,
+                                     ctypes.byref(params), self.device)
         # fast path of update(): raw addresses, preallocated output
         self._update = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -189,27 +208,10 @@ class PoseCellNetwork:
         _lib.check(self._lib.rs_pc_set_odometry_tables(self._h, *F.table_args(self._odo_tables)))
 
     # -- lifetime ---------------------------------------------------------------
-    def close(self):
-        st = 0
-        if self._h is not None and self._h.value:
-            st = self._lib.rs_pc_destroy(self._h)   # (reports an error of queued work)
-        self._h = None
+    def _close_more(self):
         if getattr(self, '_pinned', None) is not None:
             self._pinned.close()
             self._pinned = None
-        _lib.check(st)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     # -- state ------------------------------------------------------------------
     @property
@@ -255,15 +257,9 @@ class PoseCellNetwork:
     # -- reference API ----------------------------------------------------------
     def inject(self, energy, loc):
         """posecells[loc] += energy for one cell ``loc = (x, y, th)`` (posecell_network.py:322-324)."""
-        if isinstance(loc, list):
-            raise TypeError('inject expects a tuple (x, y, th); the reference would fancy-index '
-                            'whole planes with a list (posecell_network.py:324)')
-        x, y, th = (int(v) for v in loc)
-        X, Y, TH = self.shape
-        # numpy indexing semantics: negative indices count from the end
-        x, y, th = x + X if x < 0 else x, y + Y if y < 0 else y, th + TH if th < 0 else th
-        if not (0 <= x < X and 0 <= y < Y and 0 <= th < TH):
-            raise IndexError('inject location %r outside grid %r' % (loc, self.shape))
+        x, y, th = grid_cell(loc, self.shape, 'inject',
+                             'inject expects a tuple (x, y, th); the reference would fancy-index '
+                             'whole planes with a list (posecell_network.py:324)')
         with self._mutex:
             self._fresh = None
             _lib.check(self._lib.rs_pc_inject(self._h, float(energy), x, y, th))
@@ -309,28 +305,62 @@ class PoseCellNetwork:
     def update_pose(self, v=(0.0, 0.0)):
         """``update(v)`` that returns the sub-cell pose after the step (and sets ``max_pc``):
         the centroid is taken on the GPU behind the step, one host round trip."""
-        vtrans, vrot = float(v[0]), float(v[1])
+        od = np.array([[float(v[0]), float(v[1])]])
         with self._mutex:
             self._peak_tables()
             self._fresh = None
-            st = self._lib.rs_pc_update_odom_peak(self._h, vtrans, vrot, _lib.ptr(self._out3, ctypes.c_int32),
+            st = self._lib.rs_pc_update_odom_peak(self._h, od[0, 0], od[0, 1], _lib.ptr(self._out3, ctypes.c_int32),
                                                   _lib.ptr(self._peak_sums, ctypes.c_double))
-            if st == _lib.RS_OK:
-                self.max_pc = tuple(int(x) for x in self._out3)
-                self._max_valid = True
-                return pc_peak.pose_from_sums(self._peak_sums, self.max_pc, self.shape)
-            if st == _lib.RS_ERR_LUT_KEY:
-                self._max_valid = False
-                F.step_control(vtrans, vrot, self.shape[2], self.filter_table)
-                raise KeyError('path-integration LUT miss')  # pragma: no cover
             if st != _lib.RS_ERR_CTL_RANGE:
-                _lib.check(st)
-        _, poses = self._run_host_control(np.array([[vtrans, vrot]]), poses=True)
+                self._settle(st, od, self._out3.reshape(1, 3))
+                return pc_peak.pose_from_sums(self._peak_sums, self.max_pc, self.shape)
+        _, poses = self._run_host_control(od, poses=True)
         return tuple(float(x) for x in poses[0])
 
     def _poses(self, maxes, sums):
         return np.array([pc_peak.pose_from_sums(s, m, self.shape) for m, s in zip(maxes, sums)],
                         dtype=np.float64).reshape(-1, 3)
+
+    def _settle(self, st, od, out, miss=0, sums=None, behind=False, launch=None, launch_empty=False):
+        """What the status ``st`` of an odometry call means, for every entry point (call with
+        the mutex held).  The call ran the rows of ``od`` and wrote each finished step's
+        max_pc to ``out`` (and its six sums to ``sums``, where poses were asked for).
+
+        RS_OK: every step counts.  RS_ERR_LUT_KEY at step ``miss``: the steps before it count
+        (steps 1-4 of the failing one ran too), and the reference's KeyError((k, k)) is
+        raised by deriving that row's control here; ``last_poses`` keeps the poses of the
+        steps that count.  RS_ERR_CTL_RANGE, odometry outside the library's control tables:
+        the control is computed here in NumPy (filters.batch_control) and handed to the
+        control-taking entry point, ``launch(steps, ox, oy, rows, zf)`` -> status (not called
+        for no steps unless ``launch_empty``); after a LUT miss of that control, the steps
+        before it and rs_pc_excite, then as for RS_ERR_LUT_KEY.  Anything else raises through
+        ``_lib.check``, the state as it was.
+
+        ``max_pc`` is that of the last step that counts; the cached maximum is valid only if
+        a step ran, none missed and nothing was injected ``behind`` the last one."""
+        if st == _lib.RS_OK:
+            miss = None
+        elif st == _lib.RS_ERR_CTL_RANGE:
+            ox, oy, rows, zf, miss = F.batch_control(od, self.shape[2], self.filter_table)
+            todo = len(od) if miss is None else miss
+            if todo > 0 or launch_empty:
+                i32 = ctypes.c_int32
+                _lib.check(launch(todo, _lib.ptr(ox, i32), _lib.ptr(oy, i32), _lib.ptr(rows, i32),
+                                  _lib.ptr(zf, ctypes.c_double)))
+            if miss is not None:
+                # the reference raises inside path_integration, after steps 1-4 ran
+                _lib.check(self._lib.rs_pc_excite(self._h))
+        elif st != _lib.RS_ERR_LUT_KEY:
+            _lib.check(st)
+        done = len(od) if miss is None else miss
+        if done > 0:
+            self.max_pc = tuple(int(v) for v in out[done - 1])
+        self._max_valid = miss is None and done > 0 and not behind
+        if miss is not None:
+            if sums is not None:
+                self.last_poses = self._poses(out[:done], sums[:done])
+            F.step_control(od[miss, 0], od[miss, 1], self.shape[2], self.filter_table)
+            raise KeyError('LUT miss at step %d' % miss)  # pragma: no cover
 
     def update(self, v=(0.0, 0.0)):
         """One network step (posecell_network.py:326-353); returns and stores max_pc.
@@ -352,35 +382,20 @@ class PoseCellNetwork:
                 self.max_pc = (int(out[0]), int(out[1]), int(out[2]))
                 self._max_valid = True
                 return self.max_pc
-            if st == _lib.RS_ERR_LUT_KEY:
-                # steps 1-4 ran in the library; raise the reference's KeyError((k, k))
-                self._max_valid = False
-                F.step_control(vtrans, vrot, self.shape[2], self.filter_table)
-                raise KeyError('path-integration LUT miss')  # pragma: no cover
-            if st != _lib.RS_ERR_CTL_RANGE:
-                _lib.check(st)
-        return self._update_host_control(vtrans, vrot)
+            return self._update_settle(st, vtrans, vrot)
+
+    def _update_settle(self, st, vtrans, vrot):
+        """update() after a status other than RS_OK: _settle, with rs_pc_update for the
+        control computed here."""
+        self._settle(st, np.array([[vtrans, vrot]]), self._out3.reshape(1, 3),
+                     launch=lambda _, *ctl: self._update(self._h, *ctl, self._out3_addr))
+        return self.max_pc
 
     def _update_host_control(self, vtrans, vrot):
         """update() with the control computed here in NumPy (filters.step_control) and
         handed to rs_pc_update: for odometry outside the library's control tables."""
-        try:
-            ox, oy, rows, zf, _ = F.step_control(vtrans, vrot, self.shape[2], self.filter_table)
-        except KeyError:
-            # the reference raises inside path_integration, after steps 1-4 ran
-            with self._mutex:
-                _lib.check(self._lib.rs_pc_excite(self._h))
-                self._max_valid = False
-            raise
-        out = self._out3
         with self._mutex:
-            st = self._update(self._h, ox.ctypes.data, oy.ctypes.data, rows.ctypes.data,
-                              zf.ctypes.data, self._out3_addr)
-            if st:
-                _lib.check(st)
-            self.max_pc = (int(out[0]), int(out[1]), int(out[2]))
-            self._max_valid = True
-        return self.max_pc
+            return self._update_settle(_lib.RS_ERR_CTL_RANGE, vtrans, vrot)
 
     step = update
 
@@ -417,24 +432,11 @@ class PoseCellNetwork:
             self._fresh = None
             st = self._lib.rs_pc_run_odom(self._h, n, _lib.ptr(od, ctypes.c_double),
                                           _lib.ptr(out, ctypes.c_int32), ctypes.byref(bad))
-            if st in (_lib.RS_OK, _lib.RS_ERR_LUT_KEY):
-                todo = n if st == _lib.RS_OK else bad.value
-                if todo > 0:
-                    self.max_pc = tuple(int(v) for v in out[todo - 1])
-                    self._max_valid = True
-                if st == _lib.RS_ERR_LUT_KEY:
-                    self._max_valid = False
-            elif st != _lib.RS_ERR_CTL_RANGE:
-                _lib.check(st)
-        if st == _lib.RS_ERR_CTL_RANGE:
-            return self._run_host_control(od)
-        if st == _lib.RS_ERR_LUT_KEY:
-            F.step_control(od[bad.value, 0], od[bad.value, 1], self.shape[2], self.filter_table)
-            raise KeyError('LUT miss at step %d' % bad.value)  # pragma: no cover
+            self._settle(st, od, out, bad.value, launch=self._host_run(out))
         return out
 
     def _run_poses(self, od):
-        """run(poses=True): rs_pc_run_odom_peaks, with run()'s KeyError and host-control paths."""
+        """run(poses=True): rs_pc_run_odom_peaks."""
         n = od.shape[0]
         out = np.empty((n, 3), dtype=np.int32)
         sums = np.empty((n, 6), dtype=np.float64)
@@ -445,20 +447,8 @@ class PoseCellNetwork:
             st = self._lib.rs_pc_run_odom_peaks(self._h, n, _lib.ptr(od, ctypes.c_double),
                                                 _lib.ptr(out, ctypes.c_int32), _lib.ptr(sums, ctypes.c_double),
                                                 ctypes.byref(bad))
-            if st in (_lib.RS_OK, _lib.RS_ERR_LUT_KEY):
-                todo = n if st == _lib.RS_OK else bad.value
-                if todo > 0:
-                    self.max_pc = tuple(int(v) for v in out[todo - 1])
-                self._max_valid = st == _lib.RS_OK and todo > 0
-            elif st != _lib.RS_ERR_CTL_RANGE:
-                _lib.check(st)
-        if st == _lib.RS_ERR_CTL_RANGE:
-            return self._run_host_control(od, poses=True)
-        if st == _lib.RS_ERR_LUT_KEY:
-            # (the poses of the steps before the failing one stay readable)
-            self.last_poses = self._poses(out[:bad.value], sums[:bad.value])
-            F.step_control(od[bad.value, 0], od[bad.value, 1], self.shape[2], self.filter_table)
-            raise KeyError('LUT miss at step %d' % bad.value)  # pragma: no cover
+            # (after a LUT miss the poses of the steps before it stay readable: last_poses)
+            self._settle(st, od, out, bad.value, sums, launch=self._host_run(out, sums))
         return out, self._poses(out, sums)
 
     def _injection_arrays(self, n, injections):
@@ -468,7 +458,6 @@ class PoseCellNetwork:
         step = np.empty(len(inj), dtype=np.int32)
         energy = np.empty(len(inj), dtype=np.float64)
         loc = np.zeros((len(inj), 3), dtype=np.int32)
-        X, Y, TH = self.shape
         for i, (st, e, where) in enumerate(inj):
             if int(st) != st or not 0 <= st <= n:
                 raise ValueError('injection %d: step %r outside 0 .. %d' % (i, st, n))
@@ -483,18 +472,12 @@ class PoseCellNetwork:
                     raise ValueError("injection %d: ('same', %r) is no earlier injection" % (i, k))
                 loc[i, :2] = _lib.RS_PC_INJ_SAME_AS, k
             else:
-                if isinstance(where, list):
-                    raise TypeError('an injection location is a tuple (x, y, th)')
-                x, y, th = (int(v) for v in where)
-                x, y, th = x + X if x < 0 else x, y + Y if y < 0 else y, th + TH if th < 0 else th
-                if not (0 <= x < X and 0 <= y < Y and 0 <= th < TH):
-                    raise IndexError('injection %d: location %r outside grid %r' % (i, where, self.shape))
-                loc[i] = x, y, th
+                loc[i] = grid_cell(where, self.shape, 'injection %d:' % i,
+                                   'an injection location is a tuple (x, y, th)')
         return step, energy, loc
 
     def _run_inject(self, od, poses, injections):
-        """run(injections=...): rs_pc_run_odom_inject, with run()'s KeyError and host-control
-        paths (rs_pc_run_inject)."""
+        """run(injections=...): rs_pc_run_odom_inject, rs_pc_run_inject with host control."""
         n = od.shape[0]
         step, energy, loc = self._injection_arrays(n, injections)
         ni = len(step)
@@ -507,69 +490,41 @@ class PoseCellNetwork:
                     _lib.ptr(sums, ctypes.c_double) if poses else None)
         bad = ctypes.c_int(-1)
         self.last_injection_cells = cells
+
+        def host(todo, *ctl):
+            # (a LUT miss: the steps before it with the injections up to it, then steps 1-4)
+            keep = int(np.searchsorted(step, todo, side='right'))
+            return self._lib.rs_pc_run_inject(self._h, todo, *ctl, keep, *inj_args[1:], *out_args)
+
         with self._mutex:
             if poses:
                 self._peak_tables()
             self._fresh = None
             st = self._lib.rs_pc_run_odom_inject(self._h, n, _lib.ptr(od, ctypes.c_double), *inj_args, *out_args,
                                                  ctypes.byref(bad))
-            first_bad = bad.value if st == _lib.RS_ERR_LUT_KEY else None
-            if st == _lib.RS_ERR_CTL_RANGE:
-                ox, oy, rows, zf, first_bad = F.batch_control(od, self.shape[2], self.filter_table)
-                todo = n if first_bad is None else first_bad
-                # (a LUT miss: the steps before it with the injections up to it, then steps 1-4)
-                keep = int(np.searchsorted(step, todo, side='right'))
-                _lib.check(self._lib.rs_pc_run_inject(
-                    self._h, todo, _lib.ptr(ox, ctypes.c_int32), _lib.ptr(oy, ctypes.c_int32),
-                    _lib.ptr(rows, ctypes.c_int32), _lib.ptr(zf, ctypes.c_double), keep, *inj_args[1:], *out_args))
-                if first_bad is not None:
-                    _lib.check(self._lib.rs_pc_excite(self._h))
-            elif st not in (_lib.RS_OK, _lib.RS_ERR_LUT_KEY):
-                _lib.check(st)
-            todo = n if first_bad is None else first_bad
-            if todo > 0:
-                self.max_pc = tuple(int(v) for v in out[todo - 1])
             # (an injection behind the last step has changed the state since its peak was taken)
-            self._max_valid = first_bad is None and todo > 0 and not (ni and step[-1] == n)
-        if first_bad is not None:
-            if poses:
-                self.last_poses = self._poses(out[:todo], sums[:todo])
-            F.step_control(od[first_bad, 0], od[first_bad, 1], self.shape[2], self.filter_table)
-            raise KeyError('LUT miss at step %d' % first_bad)  # pragma: no cover
+            self._settle(st, od, out, bad.value, sums, behind=bool(ni and step[-1] == n),
+                         launch=host, launch_empty=True)
         return (out, self._poses(out, sums), cells) if poses else (out, cells)
+
+    def _host_run(self, out, sums=None):
+        """_settle's ``launch`` of run(): rs_pc_run, or rs_pc_run_peaks into ``sums``."""
+        def launch(todo, *ctl):
+            if sums is None:
+                return self._lib.rs_pc_run(self._h, todo, *ctl, _lib.ptr(out, ctypes.c_int32))
+            self._peak_tables()
+            return self._lib.rs_pc_run_peaks(self._h, todo, *ctl, _lib.ptr(out, ctypes.c_int32),
+                                             _lib.ptr(sums, ctypes.c_double))
+        return launch
 
     def _run_host_control(self, od, poses=False):
         """run() with the control computed here (filters.batch_control) and handed to
         rs_pc_run (rs_pc_run_peaks with ``poses``): for odometry outside the library's
         control tables."""
-        n = od.shape[0]
-        ox, oy, rows, zf, first_bad = F.batch_control(od, self.shape[2], self.filter_table)
-        todo = n if first_bad is None else first_bad
-        out = np.empty((n, 3), dtype=np.int32)
-        sums = np.empty((n, 6), dtype=np.float64) if poses else None
+        out = np.empty((od.shape[0], 3), dtype=np.int32)
+        sums = np.empty((od.shape[0], 6), dtype=np.float64) if poses else None
         with self._mutex:
-            if todo > 0 and poses:
-                self._peak_tables()
-                _lib.check(self._lib.rs_pc_run_peaks(
-                    self._h, todo, _lib.ptr(ox, ctypes.c_int32), _lib.ptr(oy, ctypes.c_int32),
-                    _lib.ptr(rows, ctypes.c_int32), _lib.ptr(zf, ctypes.c_double),
-                    _lib.ptr(out, ctypes.c_int32), _lib.ptr(sums, ctypes.c_double)))
-            elif todo > 0:
-                _lib.check(self._lib.rs_pc_run(
-                    self._h, todo, _lib.ptr(ox, ctypes.c_int32), _lib.ptr(oy, ctypes.c_int32),
-                    _lib.ptr(rows, ctypes.c_int32), _lib.ptr(zf, ctypes.c_double),
-                    _lib.ptr(out, ctypes.c_int32)))
-            if todo > 0:
-                self.max_pc = tuple(int(v) for v in out[todo - 1])
-                self._max_valid = True
-            if first_bad is not None:
-                _lib.check(self._lib.rs_pc_excite(self._h))
-                self._max_valid = False
-        if first_bad is not None:
-            if poses:
-                self.last_poses = self._poses(out[:todo], sums[:todo])
-            F.step_control(od[first_bad, 0], od[first_bad, 1], self.shape[2], self.filter_table)
-            raise KeyError('LUT miss at step %d' % first_bad)  # pragma: no cover
+            self._settle(_lib.RS_ERR_CTL_RANGE, od, out, sums=sums, launch=self._host_run(out, sums))
         return (out, self._poses(out, sums)) if poses else out
 
     def device_ms(self):

@@ -285,8 +285,10 @@ class ViewTemplate:
         return self.index
 
 
-class ViewTemplates:
+class ViewTemplates(_lib.HandleOwner):
     """Library of view templates on one GPU (view_templates.py:40-75)."""
+
+    _handles = ('_h', '_vtf')
 
     def __init__(self, x_range, y_range, x_step, y_step, im_x, im_y, match_threshold,
                  device=0, capacity=1024, metric='wrapped', offsets=False, shift_axis='rows', normalise=None):
@@ -342,37 +344,16 @@ class ViewTemplates:
         self._capacity = int(capacity)
         self._timing = False
         self._mutex = threading.Lock()
-        self._h = None
         self._lib = _lib.require_device()
-        h = ctypes.c_void_p()
-        if code == _lib.RS_VT_METRIC_WRAPPED:
-            _lib.check(self._lib.rs_vt_create(self.shape[0], self.shape[1], MAX_OFFSET, 0,
-                                              int(capacity), self.device, ctypes.byref(h)))
-        else:
-            _lib.check(self._lib.rs_vt_create_metric(self.shape[0], self.shape[1], MAX_OFFSET, 0,
-                                                     int(capacity), self.device, code, ctypes.byref(h)))
-        self._h = h
+        create = ('rs_vt_create',) if code == _lib.RS_VT_METRIC_WRAPPED else ('rs_vt_create_metric', code)
+        self._h = h = _lib.Handle.create(self._lib, create[0], 'rs_vt_destroy', self.shape[0], self.shape[1],
+                                         MAX_OFFSET, 0, int(capacity), self.device, *create[1:])
         # `min(match_val) > match_threshold` (view_templates.py:67), compared in float64 as
         # numpy compares the uint64 score with a Python number (inf: never, < 0: always)
         _lib.check(self._lib.rs_vt_set_threshold(h, float(match_threshold)))
         if normalise is not None:
             _lib.check(self._lib.rs_vt_set_normalise(h, normalise[0], normalise[1]))
         self.normalise = normalise
-
-    # -- lifetime ---------------------------------------------------------------
-    def close(self):
-        st = 0
-        if getattr(self, '_h', None) is not None and self._h.value:
-            st = self._lib.rs_vt_destroy(self._h)   # (reports an error of queued work)
-        self._h = None
-        sf = self._drop_resident()
-        _lib.check(st or sf)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self):
         return len(self.templates)
@@ -426,6 +407,17 @@ class ViewTemplates:
             _lib.check(self._lib.rs_vt_count(self._h, ctypes.byref(c)))
         return c.value
 
+    def _append(self, index, template, pcs=None, i=0, raw=False):
+        """One more entry of ``templates``: ``index`` (what the device library numbered it) is
+        the list's length, ``pcs[i]`` its pose cell ((0, 0, 0) without ``pcs``), and ``raw``
+        uint8 bytes are kept as the library keeps them (``_stored``)."""
+        assert index == len(self.templates), (index, len(self.templates))
+        pc = pcs[i] if pcs is not None else (0, 0, 0)
+        new = ViewTemplate(pc[0], pc[1], pc[2], int(index), self._stored(template) if raw else template,
+                           _owner=self)
+        self.templates.append(new)
+        return new
+
     def _normalise_take(self, arrays):
         # a normalising library compares normalised bytes: a float frame would leave the
         # uint8 device path (module doc), so it is refused before that path is chosen
@@ -460,10 +452,8 @@ class ViewTemplates:
                 return dtype == self._fdtype
             if not self._resident_ok or self.nranks != 1 or self.templates:
                 return False
-            h = ctypes.c_void_p()
-            _lib.check(self._lib.rs_vtf_create(self.shape[0], self.shape[1], MAX_OFFSET,
-                                               _FLOAT_CODES[dtype], int(self._capacity), self.device,
-                                               ctypes.byref(h)))
+            h = _lib.Handle.create(self._lib, 'rs_vtf_create', 'rs_vtf_destroy', self.shape[0], self.shape[1],
+                                   MAX_OFFSET, _FLOAT_CODES[dtype], int(self._capacity), self.device)
             if self._timing:
                 _lib.check(self._lib.rs_vtf_set_timing(h, 1))
             self._vtf, self._fdtype = h, dtype
@@ -473,13 +463,6 @@ class ViewTemplates:
         # add() / scores() / match_templates(): on a float-resident library always (a wrong
         # dtype is then a TypeError), and float arrays create one on an empty library
         return self._vtf is not None or self._resident_for(np.asarray(arrays).dtype)
-
-    def _drop_resident(self):
-        st = 0
-        if getattr(self, '_vtf', None) is not None and self._vtf.value:
-            st = self._lib.rs_vtf_destroy(self._vtf)
-        self._vtf = None
-        return st
 
     def _check_float(self, t, what):
         t = np.asarray(t)
@@ -527,38 +510,29 @@ class ViewTemplates:
             which = np.asarray(added, dtype=np.int32)
             _lib.check(self._lib.rs_vtf_append_staged(self._vtf, len(added), _lib.ptr(which, ctypes.c_int32),
                                                       ctypes.byref(first)))
-            assert first.value == base, (first.value, base)
             for k, i in enumerate(added):
-                p = pcs[i]
-                self.templates.append(ViewTemplate(p[0], p[1], p[2], base + k, q[i].copy(), _owner=self))
+                self._append(first.value + k, q[i].copy(), pcs, i)
         return idx, score, new
 
     def add(self, templates, locations=None):
         """Append templates unconditionally (indices len .. len+n-1)."""
         self._offsets_take(templates)
         self._normalise_take(templates)
-        if self._use_resident(templates):
-            t = self._check_float(templates, 'add()')
-            first = ctypes.c_int64()
-            with self._mutex:
-                _lib.check(self._lib.rs_vtf_add(self._vtf, t.shape[0], ctypes.c_void_p(t.ctypes.data),
-                                                ctypes.byref(first)))
-                for i in range(t.shape[0]):
-                    loc = locations[i] if locations is not None else (0, 0, 0)
-                    self.templates.append(ViewTemplate(loc[0], loc[1], loc[2], first.value + i, t[i],
-                                                       _owner=self))
-            return first.value
-        self._refuse_float('add()')
-        t = self._check_templates(templates)
+        resident = self._use_resident(templates)
+        if not resident:
+            self._refuse_float('add()')
+        t = self._check_float(templates, 'add()') if resident else self._check_templates(templates)
         first = ctypes.c_int64()
         with self._mutex:
-            _lib.check(self._lib.rs_vt_add(self._h, t.shape[0], _lib.ptr(t, ctypes.c_uint8),
-                                           ctypes.byref(first)))
-            t = self._stored(t)
+            if resident:
+                _lib.check(self._lib.rs_vtf_add(self._vtf, t.shape[0], ctypes.c_void_p(t.ctypes.data),
+                                                ctypes.byref(first)))
+            else:
+                _lib.check(self._lib.rs_vt_add(self._h, t.shape[0], _lib.ptr(t, ctypes.c_uint8),
+                                               ctypes.byref(first)))
+                t = self._stored(t)
             for i in range(t.shape[0]):
-                loc = locations[i] if locations is not None else (0, 0, 0)
-                self.templates.append(ViewTemplate(loc[0], loc[1], loc[2], first.value + i, t[i],
-                                                   _owner=self))
+                self._append(first.value + i, t[i], locations, i)
         return first.value
 
     def scores(self, queries, t0=0, nt=None):
@@ -611,21 +585,12 @@ class ViewTemplates:
         UINT32_MAX."""
         self._refuse_offsets('offset_profile()')
         index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
-        keep = None
-        if queries is None:
-            qptr = None
-        elif isinstance(queries, tuple):
-            n, keep = int(queries[0]), queries[1]
+        qptr = keep = None
+        if queries is not None:
+            qptr, (n,), keep = _lib.device_or_host(queries, self.shape[0] * self.shape[1], self._check_templates,
+                                                   '%d queries exceed the %d-byte device buffer')
             if n != index.shape[0]:
                 raise ValueError('%d queries for %d indices' % (n, index.shape[0]))
-            if n * self.shape[0] * self.shape[1] > keep.nbytes:
-                raise ValueError('%d queries exceed the %d-byte device buffer' % (n, keep.nbytes))
-            qptr = keep.ptr
-        else:
-            keep = self._check_templates(queries)
-            if keep.shape[0] != index.shape[0]:
-                raise ValueError('%d queries for %d indices' % (keep.shape[0], index.shape[0]))
-            qptr = ctypes.c_void_p(keep.ctypes.data)
         with self._mutex:
             out = self._offset_profile(index, qptr)
         del keep
@@ -646,10 +611,7 @@ class ViewTemplates:
     def _record(self, q, pcs, idx, new):
         for i in range(q.shape[0]):
             if new[i]:
-                assert idx[i] == len(self.templates), (idx[i], len(self.templates))
-                p = pcs[i]
-                self.templates.append(ViewTemplate(p[0], p[1], p[2], int(idx[i]), self._stored(q[i]).copy(),
-                                                   _owner=self))
+                self._append(idx[i], q[i].copy(), pcs, i, raw=True)
         return [self.templates[int(j)] for j in idx]
 
     def match_templates(self, queries, pcs=None, mode=_lib.RS_VT_SEQUENTIAL):
@@ -663,7 +625,7 @@ class ViewTemplates:
             n = q.shape[0]
             with self._mutex:
                 if mode == _lib.RS_VT_SEQUENTIAL:
-                    return self._resident_match(q, pcs if pcs is not None else [(0, 0, 0)] * n)
+                    return self._resident_match(q, pcs)
                 score = np.empty(n, dtype=self._fdtype)
                 idx = np.empty(n, dtype=np.int64)
                 _lib.check(self._lib.rs_vtf_scan(self._vtf, n, ctypes.c_void_p(q.ctypes.data), 0,
@@ -681,9 +643,15 @@ class ViewTemplates:
                 self._h, n, _lib.ptr(q, ctypes.c_uint8), mode, _lib.ptr(score, ctypes.c_uint64),
                 _lib.ptr(idx, ctypes.c_int64), _lib.ptr(new, ctypes.c_uint8)))
             if mode == _lib.RS_VT_SEQUENTIAL:
-                self._record(q, pcs if pcs is not None else [(0, 0, 0)] * n, idx, new)
+                self._record(q, pcs, idx, new)
             self._record_offsets(idx, new)
         return idx, score, new.astype(bool)
+
+    def _check_batches(self, queries):
+        q = np.asarray(queries)
+        if q.ndim != 4:
+            raise ValueError('match_stream takes (nb, nq, H, W) queries, got %r' % (q.shape,))
+        return self._check_templates(q.reshape((-1,) + q.shape[2:])).reshape(q.shape)
 
     def match_stream(self, queries, nq=None):
         """Frozen-library matching of many batches with one host synchronisation
@@ -691,20 +659,8 @@ class ViewTemplates:
         ``(nb, nq, _lib.DeviceBuffer)`` for batches already in HBM.  Returns
         ``(index, score)`` shaped (nb, nq); nothing is appended."""
         self._refuse_float('match_stream()')
-        if isinstance(queries, tuple):
-            nb, nq, buf = int(queries[0]), int(queries[1]), queries[2]
-            if nb * nq * self.shape[0] * self.shape[1] > buf.nbytes:
-                raise ValueError('%d x %d queries exceed the %d-byte device buffer'
-                                 % (nb, nq, buf.nbytes))
-            qptr, keep = buf.ptr, buf
-        else:
-            q = np.asarray(queries)
-            if q.ndim != 4:
-                raise ValueError('match_stream takes (nb, nq, H, W) queries, got %r' % (q.shape,))
-            nb = q.shape[0]
-            q = self._check_templates(q.reshape((-1,) + q.shape[2:])).reshape(q.shape)
-            nq = q.shape[1]
-            qptr, keep = ctypes.c_void_p(q.ctypes.data), q
+        qptr, (nb, nq), keep = _lib.device_or_host(queries, self.shape[0] * self.shape[1], self._check_batches,
+                                                   '%d x %d queries exceed the %d-byte device buffer')
         idx = np.empty((nb, nq), dtype=np.int64)
         score = np.empty((nb, nq), dtype=np.uint64)
         with self._mutex:
@@ -761,7 +717,7 @@ class ViewTemplates:
             raise TypeError('float frames are not supported by a sharded library')
         with self._mutex:
             self._float = True
-            _lib.check(self._drop_resident())   # mixed dtypes: the host's list is the library
+            _lib.check(self._drop('_vtf'))   # mixed dtypes: the host's list is the library
             match_val = [None] * len(self.templates)
             groups = {}
             for i, tm in enumerate(self.templates):
@@ -775,10 +731,7 @@ class ViewTemplates:
                 for i, v in zip(ids, sc):
                     match_val[i] = v
             if len(match_val) == 0 or min(match_val) > self.match_threshold:
-                new = ViewTemplate(pc[0], pc[1], pc[2], len(self.templates), np.array(template),
-                                   _owner=self)
-                self.templates.append(new)
-                return new
+                return self._append(len(self.templates), np.array(template), [pc])
             return self.templates[int(np.argmin(match_val))]
 
     # -- on-device subsampling --------------------------------------------------
@@ -801,23 +754,18 @@ class ViewTemplates:
         """
         self._refuse_float('match_frames()')
         self._ensure_gather()
-        dev = isinstance(frames, tuple)
-        if dev:
-            n, buf = int(frames[0]), frames[1]
-            if n * self.mask.size > buf.nbytes:
-                raise ValueError('%d frames of %d bytes exceed the %d-byte device buffer'
-                                 % (n, self.mask.size, buf.nbytes))
-            fptr = buf.ptr
-        else:
+        def host(frames):
             f = np.asarray(frames)
             if f.dtype != np.uint8:
                 raise TypeError('ViewTemplates matches uint8 frames (mono8, ros_simulate.py:100-101); '
                                 'got %s' % f.dtype)
             if f.shape[1:] != self.mask.shape:
                 raise ValueError('frame shape %r does not match the mask %r' % (f.shape[1:], self.mask.shape))
-            f = np.ascontiguousarray(f)
-            n = f.shape[0]
-            fptr = ctypes.c_void_p(f.ctypes.data)
+            return np.ascontiguousarray(f)
+
+        fptr, (n,), f = _lib.device_or_host(
+            frames, self.mask.size, host,
+            '%%d frames of %d bytes exceed the %%d-byte device buffer' % self.mask.size)
         idx = np.empty(n, dtype=np.int64)
         score = np.empty(n, dtype=np.uint64)
         new = np.zeros(n, dtype=np.uint8)
@@ -826,23 +774,15 @@ class ViewTemplates:
                                                     _lib.ptr(score, ctypes.c_uint64),
                                                     _lib.ptr(idx, ctypes.c_int64),
                                                     _lib.ptr(new, ctypes.c_uint8)))
-            if mode == _lib.RS_VT_SEQUENTIAL:
-                pcs = pcs if pcs is not None else [(0, 0, 0)] * n
-                for i in range(n):
-                    if new[i]:
-                        if dev:  # the gathered bytes: read back from the owning rank
-                            t = np.empty(self.shape, dtype=np.uint8)
-                            if int(idx[i]) % self.nranks == self.rank:
-                                _lib.check(self._lib.rs_vt_read(self._h, int(idx[i]),
-                                                                _lib.ptr(t, ctypes.c_uint8)))
-                            else:
-                                t = None
-                        else:
-                            t = self._stored(self.subsample(f[i]))
-                        p = pcs[i]
-                        assert idx[i] == len(self.templates), (idx[i], len(self.templates))
-                        self.templates.append(ViewTemplate(p[0], p[1], p[2], int(idx[i]), t,
-                                                           _owner=self))
+            for i in np.flatnonzero(new) if mode == _lib.RS_VT_SEQUENTIAL else ():
+                if not isinstance(frames, tuple):
+                    self._append(idx[i], self.subsample(f[i]), pcs, i, raw=True)
+                    continue
+                t = None   # the gathered bytes: read back from the owning rank
+                if int(idx[i]) % self.nranks == self.rank:
+                    t = np.empty(self.shape, dtype=np.uint8)
+                    _lib.check(self._lib.rs_vt_read(self._h, int(idx[i]), _lib.ptr(t, ctypes.c_uint8)))
+                self._append(idx[i], t, pcs, i)
             self._record_offsets(idx, new)
         return idx, score, new.astype(bool)
 
@@ -978,7 +918,7 @@ class ShardedViewTemplates(ViewTemplates):
                 self._h, n, _lib.ptr(glob, ctypes.c_uint64), mode, _lib.ptr(score, ctypes.c_uint64),
                 _lib.ptr(idx, ctypes.c_int64), _lib.ptr(new, ctypes.c_uint8)))
             if mode == _lib.RS_VT_SEQUENTIAL:
-                self._record(q, pcs if pcs is not None else [(0, 0, 0)] * n, idx, new)
+                self._record(q, pcs, idx, new)
         return idx, score, new.astype(bool)
 
     def add(self, templates, locations=None):

@@ -197,7 +197,7 @@ class NumpyVisualOdometer(_OdometerBase):
         pass
 
 
-class SimpleVisualOdometer(_OdometerBase):
+class SimpleVisualOdometer(_lib.HandleOwner, _OdometerBase):
     """The odometer on the GPU (``rs_vo_*``).  ``SimpleVisualOdometer()`` as the node
     constructs it; the handle is created at the first frame, from that frame's shape.
 
@@ -214,13 +214,12 @@ class SimpleVisualOdometer(_OdometerBase):
 
     def _setup(self, shape):
         params = _Params(shape, **self._kw)
-        h = ctypes.c_void_p()
         cp = params.c_struct()
-        _lib.check(self._lib.rs_vo_create(params.im_h, params.im_w, ctypes.byref(cp), self.device,
-                                          ctypes.byref(h)))
-        self._h, self.params = h, params
+        self._h = _lib.Handle.create(self._lib, 'rs_vo_create', 'rs_vo_destroy', params.im_h, params.im_w,
+                                     ctypes.byref(cp), self.device)
+        self.params = params
         if self._timing:
-            _lib.check(self._lib.rs_vo_set_timing(h, 1))
+            _lib.check(self._lib.rs_vo_set_timing(self._h, 1))
 
     def setup(self, shape):
         """Create the handle for ``(im_h, im_w)`` frames before the first frame (needed
@@ -240,19 +239,16 @@ class SimpleVisualOdometer(_OdometerBase):
         ``tables`` / ``profiles`` a tuple that also holds the ``(n, 2, 2S-1)`` uint32
         tables and / or the ``(n, Wd_trans + Wd_rot)`` uint32 profiles."""
         with self._mutex:
-            if isinstance(frames, tuple):
-                n, buf = int(frames[0]), frames[1]
-                if self.params is None:
-                    raise ValueError('frame shape unknown: call setup((im_h, im_w)) before the '
-                                     'first device-resident frames')
-                if n < 0 or n * self.params.im_h * self.params.im_w > buf.nbytes:
-                    raise ValueError('%d frames of %d bytes exceed the %d-byte device buffer'
-                                     % (n, self.params.im_h * self.params.im_w, buf.nbytes))
-                fptr, keep = buf.ptr, buf
-            else:
-                keep = self._check(frames)
-                n = keep.shape[0]
-                fptr = ctypes.c_void_p(keep.ctypes.data)
+            dev = isinstance(frames, tuple)
+            if dev and self.params is None:
+                raise ValueError('frame shape unknown: call setup((im_h, im_w)) before the '
+                                 'first device-resident frames')
+            # (a host array goes through _check, where the first frame fixes the shape)
+            item = self.params.im_h * self.params.im_w if dev else 0
+            too_big = '%%d frames of %d bytes exceed the %%d-byte device buffer' % item
+            fptr, (n,), keep = _lib.device_or_host(frames, item, self._check, too_big)
+            if n < 0:
+                raise ValueError(too_big % (n, keep.nbytes))
             p = self.params
             out = np.zeros((n, 2), dtype=np.float64)
             tab = np.zeros((n, 2, 2 * p.S - 1), dtype=np.uint32) if tables else None
@@ -281,16 +277,3 @@ class SimpleVisualOdometer(_OdometerBase):
         if self._h is not None:
             _lib.check(self._lib.rs_vo_last_ms(self._h, ms))
         return ms[0], ms[1]
-
-    def close(self):
-        st = 0
-        if getattr(self, '_h', None) is not None and self._h.value:
-            st = self._lib.rs_vo_destroy(self._h)   # (reports an error of queued work)
-        self._h = None
-        _lib.check(st)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -130,38 +130,54 @@ def test_create_and_destroy_every_handle_kind_20_times(built):
     # five host batches: upload groups (1, 2, 2), so both upload buffers and every event of the group
     qs, _ = V.synthetic_queries(lib, 20, seed=309, hit_frac=0.8)
     frames = np.random.default_rng(307).integers(0, 256, size=(3, 48, 64), dtype=np.uint8)
-    for k in range(20):
-        h = vt.ViewTemplates._from_shape((64, 32), THR)          # rs_vt
+    def use_vt(h):                                               # rs_vt
         h.add(lib)
         idx, _, new = h.match_templates(q, mode=0)
         assert not new.any() and idx.shape == (4,)
         want_i, want_s, _ = h.match_templates(qs, mode=0)
         got_i, got_s = h.match_stream(qs.reshape(5, 4, 64, 32))  # ... its upload stream and four events
         assert np.array_equal(got_i.reshape(-1), want_i) and np.array_equal(got_s.reshape(-1), want_s)
-        h.close()
-        f = vt.ViewTemplates._from_shape((64, 32), 1e9)          # rs_vtf, made by the first float batch
+
+    def use_vtf(f):                                              # rs_vtf, made by the first float batch
         fq = q.astype(np.float32)
         fi, _, fn = f.match_templates(fq)
         assert f._vtf is not None and fn[0] and f.count() == int(fn.sum())
-        f.close()
-        vo = SimpleVisualOdometer()                              # rs_vo
+
+    def use_vo(vo):                                              # rs_vo
         assert vo.run(frames).shape == (3, 2)
-        vo.close()
-        pc = PoseCellNetwork((32, 32, 18), precision='float32' if k % 2 == 0 else 'float64')   # rs_pc
+
+    def use_pc(pc):                                              # rs_pc
         pc.inject(1.0, (5, 6, 7))
         assert len(pc.update((0.2, 0.01))) == 3
-        pc.close()
-        em = LinkedExperienceMap(capacity=2)                     # rs_em
+
+    def use_em(em):                                              # rs_em
         for _ in range(3):
             em.add_experience()
         em.add_link(0, 1, 1.0, 0.5, -0.5)
         em.iterate(1)
         assert em.poses().shape == (3, 3)
-        em.close()
-        pce = PoseCellEnsemble(2, (8, 8, 8))                     # rs_pce
+
+    def use_pce(pce):                                            # rs_pce
         pce.inject(1.0, (3, 4, 5))
         assert pce.run([(0.2, 0.01), (0.2, 0.01)]).shape == (2, 2, 3)
-        pce.close()
+
+    for k in range(20):
+        kinds = [(lambda: vt.ViewTemplates._from_shape((64, 32), THR), use_vt),
+                 (lambda: vt.ViewTemplates._from_shape((64, 32), 1e9), use_vtf),
+                 (SimpleVisualOdometer, use_vo),
+                 (lambda: PoseCellNetwork((32, 32, 18), precision='float32' if k % 2 == 0 else 'float64'), use_pc),
+                 (lambda: LinkedExperienceMap(capacity=2), use_em),
+                 (lambda: PoseCellEnsemble(2, (8, 8, 8)), use_pce)]
+        for make, use in kinds:
+            if k == 0:      # the first round: a with block closes, and a second close() is no call
+                with make() as h:
+                    use(h)
+                assert h._h is None
+                h.close()
+            else:
+                h = make()
+                use(h)
+                h.close()
 
 
 def test_timing_events_of_the_float_library_the_pose_cells_and_the_ensemble(built):
