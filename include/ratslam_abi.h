@@ -682,7 +682,47 @@ int rs_em_relax_host(int nexp, int nlinks, const int32_t* from, const int32_t* t
  *                   (member, X, Y, TH); a value that is not a finite float32 is refused
  *                   (RS_ERR_ARG, nothing written)
  *   rs_pce_set_timing, rs_pce_last_ms   HIP events around the launches of every later
- *                   rs_pce_run; the last run's device time in ms, -1 when it ran untimed */
+ *                   rs_pce_run or rs_pce_run_inject; the last run's device time in ms, -1 when
+ *                   it ran untimed
+ *
+ * Injections and the sub-cell pose inside a run: rs_pc_run_inject's rule,
+ * per member.
+ *   rs_pce_set_peak_tables   as rs_pc_set_peak_tables: r in 1 .. 3 with 2r+1 <= min(X, Y, TH)
+ *                   (else RS_ERR_ARG, before any device call), sc_a[2 N_a] the axis's sin then
+ *                   cos weights.  The sums below return RS_ERR_STATE before it.
+ *   rs_pce_get_peak out_xyz[B * 3], out_sums[B * 6]: each member's stored first maximum (as
+ *                   rs_pce_get_max) and the six sums (S_x, C_x, S_y, C_y, S_th, C_th) of
+ *                   csrc/pc_peak_rule.h over the box round it; one host synchronisation.
+ *   rs_pce_run_inject   rs_pce_run with ni injections; injection i is (inj_member[i],
+ *                   inj_step[i], inj_energy[i], inj_loc[3i .. 3i+2]) with 0 <= member < B,
+ *                   0 <= step <= n, the steps non-decreasing within each member in list order
+ *                   (the order across members is free), and a location that is one of
+ *                     (x, y, th)                 an explicit cell inside the grid;
+ *                     (RS_PC_INJ_AT_PEAK, ., .)  the first maximum in C order of that member's
+ *                                                state as it stands when the injection is
+ *                                                applied: what rs_pce_get_max would return there;
+ *                     (RS_PC_INJ_SAME_AS, k, .)  k < i and inj_member[k] == inj_member[i]: the
+ *                                                cell injection k resolved to.
+ *                   The call is defined, for every member m, as this sequence:
+ *                     for s in 0 .. n-1:
+ *                         for each i of member m with inj_step[i] == s, in order:
+ *                             rs_pce_inject(m, energy_i, cell_i)
+ *                         one step of member m with step s's control
+ *                     for each i of member m with inj_step[i] == n, in order:
+ *                             rs_pce_inject(m, energy_i, cell_i)
+ *                   and gives the peaks (out_xyz), the resolved cells (out_inj_xyz[ni * 3], in the
+ *                   caller's order) and the stored volumes of that sequence made call by call,
+ *                   bit for bit, whatever B, the member's place and the cut into launches.  An
+ *                   injection is rs_pce_inject's float32 += of (float)energy.  With out_sums
+ *                   (may be NULL; [(m * n + s) * 6]) step s's six sums are over the box round
+ *                   step s's peak, of the state before any injection with step s + 1; the
+ *                   ensemble stores the normalised state, so they are exactly the rule's, with
+ *                   no common factor.  RS_ERR_ARG before any device work, the state untouched:
+ *                   a member outside [0, B), steps out of order within a member, a step
+ *                   outside [0, n], an explicit cell outside the grid, a same-as k >= i or of
+ *                   another member, an energy that is not a finite float32.  n == 0 with
+ *                   ni > 0 applies the injections alone.  With ni == 0 and out_sums NULL it is
+ *                   rs_pce_run: the same launches, one host synchronisation either way. */
 typedef struct rs_pce rs_pce;
 int rs_pce_fit(int X, int Y, int TH, size_t* lds_bytes);
 int rs_pce_create(int B, int X, int Y, int TH, const rs_pc_params* params,
@@ -697,6 +737,12 @@ int rs_pce_read(rs_pce* h, int first, int count, double* volumes);
 int rs_pce_write(rs_pce* h, int first, int count, const double* volumes);
 int rs_pce_set_timing(rs_pce* h, int enable);
 int rs_pce_last_ms(rs_pce* h, double* ms);
+int rs_pce_set_peak_tables(rs_pce* h, int r, const double* sc_x, const double* sc_y, const double* sc_th);
+int rs_pce_get_peak(rs_pce* h, int32_t* out_xyz, double* out_sums);
+int rs_pce_run_inject(rs_pce* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx,
+                      const double* zf, int ni, const int32_t* inj_member, const int32_t* inj_step,
+                      const double* inj_energy, const int32_t* inj_loc, int32_t* out_xyz,
+                      int32_t* out_inj_xyz, double* out_sums);
 
 /* Multi-GPU: one process per GPU, library sharded round-robin (template g lives
  * on rank g % nranks at slot g / nranks); per query the local first-argmin keys

@@ -202,6 +202,10 @@ SIGNATURES = {
     'rs_pce_write': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _f64p]),
     'rs_pce_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
     'rs_pce_last_ms': (ctypes.c_int, [_vp, _f64p]),
+    'rs_pce_set_peak_tables': (ctypes.c_int, [_vp, ctypes.c_int, _f64p, _f64p, _f64p]),
+    'rs_pce_get_peak': (ctypes.c_int, [_vp, _i32p, _f64p]),
+    'rs_pce_run_inject': (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, _i32p, _f64p, ctypes.c_int, _i32p, _i32p,
+                                         _f64p, _i32p, _i32p, _i32p, _f64p]),
     'rs_comm_unique_id': (ctypes.c_int, [_u8p]),
     'rs_vt_attach_comm': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _u8p]),
     'rs_vt_set_shard': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),

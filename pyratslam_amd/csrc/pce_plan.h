@@ -1,5 +1,6 @@
-// The pose-cell ensemble's host rules: the LDS plan of one member's
-// workgroup, the compact control record of one step and the split of a run into launches.
+// The pose-cell ensemble's host rules (DESIGN sections 35 and 36): the LDS plan of one member's
+// workgroup, the compact control record of one step, the split of a run into launches, the
+// rule and the device form of a run's injections and the pose stage's scratch.
 // Pure functions of integers and small arrays, shared by pose_ensemble.hip (host side and
 // kernel: the kernel takes its offsets from the same PceFit the host computed) and by
 // tests/pce_plan_main.cpp (built with the plain host compiler: no HIP runtime call here).
@@ -19,9 +20,13 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <vector>
+
+#include "ratslam_abi.h"
 
 namespace rs {
 
@@ -148,6 +153,105 @@ inline int pce_chunk_count(int n, int K) { return n <= 0 ? 0 : (n + K - 1) / K; 
 inline void pce_chunk(int n, int K, int c, int* first, int* count) {
     *first = c * K;
     *count = std::min(K, n - c * K);
+}
+
+// ---- injections inside a run (rs_pce_run_inject) ----
+// The rule of a run's injections: B members, n steps, ni injections (member[ni], step[ni],
+// energy[ni], loc[3 ni]).  The index of the first injection that breaks it with the reason in
+// *why, or -1.  It is pc_ctl.h's pc_inj_first_bad per member: a member in [0, B); a step in
+// [0, n] and not below the step of the member's injection before it in list order (the order
+// across members is free); a location that is a cell inside the grid, (RS_PC_INJ_AT_PEAK, ., .),
+// or (RS_PC_INJ_SAME_AS, k, .) with 0 <= k < i and member[k] == member[i]; an energy that is
+// a finite float32.  The reasons are tried in that order.  Reads [0, ni) of each array only.
+enum PceInjBad {
+    PCE_INJ_OK = 0,
+    PCE_INJ_BAD_MEMBER,
+    PCE_INJ_BAD_STEP,
+    PCE_INJ_BAD_ORDER,
+    PCE_INJ_BAD_SAME,
+    PCE_INJ_BAD_CELL,
+    PCE_INJ_BAD_ENERGY
+};
+
+// |e| rounds to a finite float32: below the midpoint of FLT_MAX and 2^128 (the tie goes to 2^128)
+inline bool pce_finite_f32(double e) { return std::fabs(e) < 0x1.ffffffp127; }
+
+inline int pce_inj_first_bad(int B, int X, int Y, int TH, int n, int ni, const int32_t* member, const int32_t* step,
+                             const double* energy, const int32_t* loc, PceInjBad* why) {
+    // by[0 .. ni): the injections ordered by member, list order inside a member, so that the
+    // one before injection i of its member is its neighbour there
+    std::vector<int> by((size_t)std::max(ni, 0)), before((size_t)std::max(ni, 0), -1);
+    for (int i = 0; i < ni; ++i) by[i] = i;
+    std::stable_sort(by.begin(), by.end(), [&](int a, int b) { return member[a] < member[b]; });
+    for (int g = 1; g < ni; ++g)
+        if (member[by[g]] == member[by[g - 1]]) before[by[g]] = by[g - 1];
+    for (int i = 0; i < ni; ++i) {
+        const int32_t* l = loc + 3 * (size_t)i;
+        PceInjBad bad = PCE_INJ_OK;
+        if (member[i] < 0 || member[i] >= B) bad = PCE_INJ_BAD_MEMBER;
+        else if (step[i] < 0 || step[i] > n) bad = PCE_INJ_BAD_STEP;
+        else if (before[i] >= 0 && step[i] < step[before[i]]) bad = PCE_INJ_BAD_ORDER;
+        else if (l[0] == RS_PC_INJ_AT_PEAK) bad = PCE_INJ_OK;
+        else if (l[0] == RS_PC_INJ_SAME_AS)
+            bad = l[1] >= 0 && l[1] < i && member[l[1]] == member[i] ? PCE_INJ_OK : PCE_INJ_BAD_SAME;
+        else if (!(l[0] >= 0 && l[0] < X && l[1] >= 0 && l[1] < Y && l[2] >= 0 && l[2] < TH)) bad = PCE_INJ_BAD_CELL;
+        if (bad == PCE_INJ_OK && !pce_finite_f32(energy[i])) bad = PCE_INJ_BAD_ENERGY;
+        if (bad != PCE_INJ_OK) {
+            *why = bad;
+            return i;
+        }
+    }
+    *why = PCE_INJ_OK;
+    return -1;
+}
+
+// An injection as the kernel reads it, 16 bytes: the step it stands in front of, the kind of
+// its location, the cell's C-order linear index (explicit) or the grouped index of the
+// injection it repeats (same-as), and the energy as the float32 that is added.
+enum { PCE_INJ_EXPLICIT = 0, PCE_INJ_PEAK = 1, PCE_INJ_SAME = 2 };
+struct PceInjRec {
+    int32_t step;
+    int32_t kind;
+    uint32_t arg;
+    float energy;
+};
+static_assert(sizeof(PceInjRec) == 16, "the device form of an injection");
+
+// A list that pce_inj_first_bad accepts in its device form: member m's records are
+// rec[off[m] .. off[m + 1]), in list order (off[B + 1], rec[ni]); grouped[i] is the place of
+// the caller's injection i among them, which is also where the kernel leaves its resolved
+// cell, and a same-as k has become grouped[k].
+inline void pce_inj_group(int B, int Y, int TH, int ni, const int32_t* member, const int32_t* step,
+                          const double* energy, const int32_t* loc, uint32_t* off, PceInjRec* rec, int32_t* grouped) {
+    for (int m = 0; m <= B; ++m) off[m] = 0;
+    for (int i = 0; i < ni; ++i) ++off[member[i] + 1];
+    for (int m = 0; m < B; ++m) off[m + 1] += off[m];
+    std::vector<uint32_t> next(off, off + B);
+    for (int i = 0; i < ni; ++i) grouped[i] = (int32_t)next[member[i]]++;
+    for (int i = 0; i < ni; ++i) {
+        const int32_t* l = loc + 3 * (size_t)i;
+        PceInjRec& r = rec[grouped[i]];
+        r.step = step[i];
+        r.energy = (float)energy[i];
+        if (l[0] == RS_PC_INJ_AT_PEAK) r.kind = PCE_INJ_PEAK, r.arg = 0;
+        else if (l[0] == RS_PC_INJ_SAME_AS) r.kind = PCE_INJ_SAME, r.arg = (uint32_t)grouped[l[1]];
+        else r.kind = PCE_INJ_EXPLICIT, r.arg = ((uint32_t)l[0] * Y + l[1]) * TH + l[2];
+    }
+}
+
+// ---- the sub-cell pose inside a run ----
+// The pose stage's scratch for a radius r, w = 2r + 1, all float64: the box (w^3), R and C
+// (w^2 each), the three marginals (3w) and the six rows of weights (6w); 4,032 bytes at r = 3.
+// It lies at the head of temp + ring, which are dead between a step's theta pass and the next
+// step's excitation: the pose adds no LDS region and pce_fit's total does not change.
+inline size_t pce_pose_scratch_bytes(int r) {
+    const size_t w = 2 * (size_t)r + 1;
+    return 8 * (w * w * w + 2 * w * w + 3 * w + 6 * w);
+}
+// Whether a plan's scratch holds it (every shape pce_fit accepts does, at every radius whose
+// box the grid holds: the smallest, 7 x 7 x 7, has 4,312 bytes there).
+inline bool pce_pose_fits(const PceFit& f, int r) {
+    return r >= 1 && r <= 3 && f.temp_off % 8 == 0 && pce_pose_scratch_bytes(r) <= f.temp_bytes + f.ring_bytes;
 }
 
 }  // namespace rs

@@ -18,6 +18,15 @@
 //            registers, in place; the clamp and the first maximum in C order ride along
 // The next step's control record is fetched from HBM at the head of a step and stored into
 // LDS at its end.  Offsets and sizes come from pce_plan.h's PceFit, computed on the host.
+//
+// The kernel is a template on two flags; rs_pce_run launches <false, false>,
+// which is the code above and nothing else.
+//   INJ   a run's injections (rs_pce_run_inject): at the head of a step, and behind the last
+//         step of a run's last launch, the workgroup walks its member's records of that
+//         boundary; thread 0 resolves the cell and adds to the state in LDS
+//   POSE  the sub-cell pose: behind a step's theta pass the box round the step's first maximum
+//         is gathered from the state into the scratch that temp and ring are then, and the
+//         stage functions of pc_peak_rule.h give the step's six sums
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +36,7 @@
 #include <cstring>
 #include <vector>
 
+#include "pc_peak_rule.h"
 #include "pce_plan.h"
 #include "rs_common.h"
 
@@ -50,6 +60,14 @@ __device__ __forceinline__ unsigned long long pce_key(float v, unsigned lin) {
     return ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)~lin;
 }
 
+// The order of finite floats of either sign, -0 as +0, in front of ~lin: the largest key is the
+// first maximum in C order (pce_key's order holds for values >= +0 only, what a step leaves)
+__device__ __forceinline__ unsigned long long pce_ord_key(float v, unsigned lin) {
+    const unsigned u = v == 0.f ? 0u : __float_as_uint(v);   // -0 == +0: the first of them
+    const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)ord << 32) | (unsigned)~lin;
+}
+
 __device__ __forceinline__ unsigned long long pce_wave_max(unsigned long long k) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -66,9 +84,69 @@ __device__ __forceinline__ void pce_store_cell(int32_t* out, unsigned long long 
     out[2] = (int)(lin % (unsigned)TH);
 }
 
+// The largest key of the block's `waves` waves, in every thread (red: a word per wave).
+__device__ __forceinline__ unsigned long long pce_block_max(unsigned long long best, unsigned long long* red, int waves) {
+    best = pce_wave_max(best);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    __syncthreads();
+    unsigned long long k = red[0];
+    for (int w = 1; w < waves; ++w) k = red[w] > k ? red[w] : k;
+    return k;
+}
+
+// The six sums of the wrapped box round cell `lin` (pc_peak_rule.h), by the whole block: every
+// thread calls it, the stages run on at most 49 threads each, three barriers apart.  sc: a
+// scratch of pce_pose_scratch_bytes(r), in use until the caller's next barrier; cell(x, y, th)
+// reads the state; tabs: the weights of x, y and theta, sin then cos of each.  Six plain
+// 8-byte stores.
+template <class Cell>
+__device__ __forceinline__ void pce_peak_sums(double* sc, int r, int X, int Y, int TH, unsigned lin,
+                                              const double* __restrict__ tabs, double* __restrict__ out, Cell cell) {
+    const int tid = threadIdx.x, w = 2 * r + 1, w2 = w * w;
+    if (lin >= (unsigned)(X * Y * TH)) lin = 0u;   // (never an address outside the state)
+    double* const v = sc;
+    double* const bR = v + w * w2;
+    double* const bC = bR + w2;
+    double* const mg = bC + w2;
+    double* const tw = mg + 3 * w;
+    const int pth = (int)(lin % (unsigned)TH);
+    const unsigned xy = lin / (unsigned)TH;
+    const int py = (int)(xy % (unsigned)Y), px = (int)(xy / (unsigned)Y);
+    if (tid < 6 * w) {   // row q of the weights: axis q / 2, sin then cos
+        const int q = tid / w, ax = q >> 1;
+        const int nn = ax == 0 ? X : ax == 1 ? Y : TH, p = ax == 0 ? px : ax == 1 ? py : pth;
+        tw[tid] = tabs[(ax == 0 ? 0 : ax == 1 ? 2 * X : 2 * (X + Y)) + (q & 1) * nn + rs::pc_peak_wrap(p, tid % w, r, nn)];
+    }
+    for (int e = tid; e < w * w2; e += (int)blockDim.x) {
+        const int k = e % w, ij = e / w, j = ij % w, i = ij / w;
+        v[e] = (double)cell(rs::pc_peak_wrap(px, i, r, X), rs::pc_peak_wrap(py, j, r, Y), rs::pc_peak_wrap(pth, k, r, TH));
+    }
+    __syncthreads();
+    if (tid < w2) {
+        bR[tid] = rs::pc_peak_R(v, w, tid / w, tid % w);
+        bC[tid] = rs::pc_peak_C(v, w, tid / w, tid % w);
+    }
+    __syncthreads();
+    if (tid < 3 * w) mg[tid] = rs::pc_peak_marginal(bR, bC, w, tid / w, tid % w);
+    __syncthreads();
+    if (tid < 6) out[tid] = rs::pc_peak_dot_w(mg + (tid >> 1) * w, tw + tid * w, w);
+}
+
+// What the INJ and POSE instantiations take besides the plain arguments (all zero for the plain one).
+struct PceFb {
+    const unsigned* inj_off;        // [B + 1]: member m's records are inj_rec[inj_off[m] .. inj_off[m + 1])
+    const rs::PceInjRec* inj_rec;   // (pce_plan.h: pce_inj_group)
+    unsigned* inj_cell;             // each record's resolved cell, as a C-order linear index
+    const double* tabs;             // the pose weights (rs_pce_set_peak_tables)
+    double* sums;                   // [(m * ntotal + s) * 6]
+    int r;                          // the pose radius
+    int last;                       // the run's last launch: the records of step ntotal follow its last step
+};
+
+template <bool INJ, bool POSE>
 __global__ __launch_bounds__(PCE_THREADS) void pce_run_kernel(
     const PceArgs a, float* __restrict__ state, const float* __restrict__ ginh, const float* __restrict__ filt,
-    const unsigned char* __restrict__ ctl, int n, int ntotal, int s0, int32_t* __restrict__ out) {
+    const unsigned char* __restrict__ ctl, int n, int ntotal, int s0, int32_t* __restrict__ out, const PceFb fb) {
     extern __shared__ __align__(16) unsigned char pce_lds[];
     const int tid = threadIdx.x, m = blockIdx.x;
     const int X = a.X, Y = a.Y, TH = a.TH, TP = a.TP, PS = a.PS, XY = X * Y;
@@ -87,11 +165,51 @@ __global__ __launch_bounds__(PCE_THREADS) void pce_run_kernel(
         S[col * TP + (c - col * TH)] = gs[c];
     }
     for (int i = tid; i < a.nf * PCE_TAPS * PCE_TAPS; i += PCE_THREADS) Fl[i] = filt[i];
-    if (tid < rw) reinterpret_cast<unsigned*>(pce_lds + a.ctl_off)[tid] = grec[tid];
+    if ((!INJ || n > 0) && tid < rw) reinterpret_cast<unsigned*>(pce_lds + a.ctl_off)[tid] = grec[tid];
     const float g = ginh[m];
     __syncthreads();
 
+    // ---- the member's injections of one boundary (INJ): uniform in the block ----
+    unsigned cur = 0, end = 0;        // the records not yet applied
+    bool fresh = false;               // `peak` is the state's first maximum: this launch's last step wrote it,
+    unsigned long long peak = 0ull;   // and nothing was injected since (thread 0 holds the key)
+    if constexpr (INJ) {
+        cur = fb.inj_off[m], end = fb.inj_off[m + 1];
+        while (cur < end && fb.inj_rec[cur].step < s0) ++cur;   // (applied by the launches before)
+    }
+    auto inject_at = [&](int step) {
+        while (cur < end && fb.inj_rec[cur].step == step) {
+            const rs::PceInjRec rc = fb.inj_rec[cur];
+            unsigned long long k = peak;
+            if (rc.kind == rs::PCE_INJ_PEAK && !fresh) {
+                // the state may hold a negative cell or -0 (a launch's head, an injection of
+                // this boundary): pce_argmax_kernel's order over the state in LDS
+                __syncthreads();   // (thread 0 has read the last step's redK)
+                unsigned long long best = 0ull;
+                for (int c = tid; c < a.N; c += PCE_THREADS) {
+                    const int col = c / TH;
+                    const unsigned long long key = pce_ord_key(S[col * TP + (c - col * TH)], (unsigned)c);
+                    best = key > best ? key : best;
+                }
+                k = pce_block_max(best, redK, PCE_WAVES);
+            }
+            if (tid == 0) {
+                unsigned lin = rc.kind == rs::PCE_INJ_EXPLICIT ? rc.arg
+                               : rc.kind == rs::PCE_INJ_SAME   ? fb.inj_cell[rc.arg]
+                                                               : ~(unsigned)k;
+                if (lin >= (unsigned)a.N) lin = 0u;   // (never an address outside the state)
+                const unsigned col = lin / (unsigned)TH;
+                S[col * TP + (lin - col * TH)] += rc.energy;
+                fb.inj_cell[cur] = lin;
+            }
+            fresh = false;
+            ++cur;
+            __syncthreads();   // the next record's maximum, or the excitation, reads the state
+        }
+    };
+
     for (int s = 0; s < n; ++s) {
+        if constexpr (INJ) inject_at(s0 + s);
         const unsigned char* const rec = pce_lds + a.ctl_off + (size_t)(s & 1) * a.rec_bytes;
         const bool fetch = tid < rw && s + 1 < n;
         unsigned next_word = 0;
@@ -253,12 +371,24 @@ __global__ __launch_bounds__(PCE_THREADS) void pce_run_kernel(
         if ((tid & 63) == 0) redK[tid >> 6] = best;
         if (fetch) reinterpret_cast<unsigned*>(pce_lds + a.ctl_off + (size_t)((s + 1) & 1) * a.rec_bytes)[tid] = next_word;
         __syncthreads();
-        if (tid == 0) {
-            unsigned long long k = redK[0];
+        unsigned long long k = 0ull;
+        if (POSE || tid == 0) {   // (the pose: every thread decodes the cell)
+            k = redK[0];
 #pragma unroll
             for (int w = 1; w < PCE_WAVES; ++w) k = redK[w] > k ? redK[w] : k;
-            pce_store_cell(out + ((size_t)m * ntotal + s0 + s) * 3, k, Y, TH);
         }
+        if (tid == 0) pce_store_cell(out + ((size_t)m * ntotal + s0 + s) * 3, k, Y, TH);
+        if constexpr (INJ) peak = k, fresh = true;
+        if constexpr (POSE) {
+            // temp and ring are dead until the next excitation: the pose's scratch
+            pce_peak_sums(reinterpret_cast<double*>(T), fb.r, X, Y, TH, ~(unsigned)k, fb.tabs,
+                          fb.sums + ((size_t)m * ntotal + s0 + s) * 6,
+                          [&](int cx, int cy, int ck) { return S[(cx * Y + cy) * TP + ck]; });
+            __syncthreads();   // before the next excitation writes temp
+        }
+    }
+    if constexpr (INJ) {
+        if (fb.last) inject_at(ntotal);
     }
     __syncthreads();
     for (int c = tid; c < a.N; c += PCE_THREADS) {
@@ -274,11 +404,8 @@ __global__ __launch_bounds__(PCE_ARGMAX_THREADS) void pce_argmax_kernel(const fl
     const float* gs = state + (size_t)blockIdx.x * N;
     unsigned long long best = 0ull;
     for (int c = threadIdx.x; c < N; c += PCE_ARGMAX_THREADS) {
-        const float v = gs[c];
-        // (a stored volume is finite; negative values, which only rs_pce_write can bring, order below +0)
-        const unsigned u = v == 0.f ? 0u : __float_as_uint(v);   // -0 == +0: the first of them
-        const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-        const unsigned long long key = ((unsigned long long)ord << 32) | (unsigned)~(unsigned)c;
+        // (a stored volume is finite; negative values, which a write or an injection can bring, order below +0)
+        const unsigned long long key = pce_ord_key(gs[c], (unsigned)c);
         best = key > best ? key : best;
     }
     best = pce_wave_max(best);
@@ -291,10 +418,38 @@ __global__ __launch_bounds__(PCE_ARGMAX_THREADS) void pce_argmax_kernel(const fl
     }
 }
 
+// The stored state's first maximum and the six sums of the box round it: a block per member,
+// pce_argmax_kernel's maximum, then the box from HBM (rs_pce_get_peak).
+__global__ __launch_bounds__(PCE_ARGMAX_THREADS) void pce_peak_kernel(const float* __restrict__ state, int N, int X, int Y,
+                                                                     int TH, int r, const double* __restrict__ tabs,
+                                                                     int32_t* __restrict__ out, double* __restrict__ sums) {
+    constexpr int W = rs::PC_PEAK_WMAX;
+    __shared__ unsigned long long red[PCE_ARGMAX_THREADS / 64];
+    __shared__ double sc[W * W * W + 2 * W * W + 9 * W];   // pce_pose_scratch_bytes(3)
+    const float* gs = state + (size_t)blockIdx.x * N;
+    unsigned long long best = 0ull;
+    for (int c = threadIdx.x; c < N; c += PCE_ARGMAX_THREADS) {
+        const unsigned long long key = pce_ord_key(gs[c], (unsigned)c);
+        best = key > best ? key : best;
+    }
+    const unsigned long long k = pce_block_max(best, red, PCE_ARGMAX_THREADS / 64);
+    if (threadIdx.x == 0) pce_store_cell(out + 3 * (size_t)blockIdx.x, k, Y, TH);
+    pce_peak_sums(sc, r, X, Y, TH, ~(unsigned)k, tabs, sums + 6 * (size_t)blockIdx.x,
+                  [&](int cx, int cy, int ck) { return gs[((size_t)cx * Y + cy) * TH + ck]; });
+}
+
 // state[m][lin] += e for member `member`, or for every member (member < 0)
 __global__ void pce_inject_kernel(float* state, int B, int N, int member, int lin, float e) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m < B && (member < 0 || m == member)) state[(size_t)m * N + lin] += e;
+}
+
+// The instantiation a run launches: the plain one unless it has injections or wants sums.
+using PceRunKernel = void (*)(const PceArgs, float*, const float*, const float*, const unsigned char*, int, int, int,
+                              int32_t*, const PceFb);
+PceRunKernel pce_run_form(bool inj, bool pose) {
+    return inj ? (pose ? pce_run_kernel<true, true> : pce_run_kernel<true, false>)
+               : (pose ? pce_run_kernel<false, true> : pce_run_kernel<false, false>);
 }
 
 }  // namespace
@@ -315,6 +470,15 @@ struct rs_pce {
     rs::PinnedBuf<unsigned char> hCtl;     // a run's records, launch after launch
     rs::PinnedBuf<int32_t> hOut;
     rs::PinnedBuf<float> hState;           // staging of rs_pce_read / rs_pce_write
+    // a run's injections: the offsets and the records (pce_inj_group) in one block, the resolved cells
+    rs::DevBuf<unsigned char> dInj;
+    rs::PinnedBuf<unsigned char> hInj;
+    rs::DevBuf<unsigned> dInjCell;
+    rs::PinnedBuf<unsigned> hInjCell;
+    // the pose: the radius (0 before rs_pce_set_peak_tables), the weights, six sums per member and step
+    int peak_r = 0;
+    rs::DevBuf<double> dTabs, dSums;
+    rs::PinnedBuf<double> hSums;
     bool timing = false, timed = false;
     // the owners come after the buffers: members go in reverse order, streams and events first
     rs::Stream stream;
@@ -379,8 +543,9 @@ int rs_pce_create(int B, int X, int Y, int TH, const rs_pc_params* p, const doub
 
     RS_TRY(h->stream.create());
     for (rs::Event& e : h->ev) RS_TRY(e.create());
-    RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pce_run_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)fit.total));
+    for (int v = 0; v < 4; ++v)
+        RS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pce_run_form(v & 1, v & 2)),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)fit.total));
     const size_t nft = (size_t)p->nfilters * PCE_TAPS * PCE_TAPS;
     RS_TRY(h->dState.reserve((size_t)B * N, "ensemble volumes"));
     RS_TRY(h->dInhib.reserve(B, "ensemble inhibitions"));
@@ -422,12 +587,22 @@ int rs_pce_shape(const rs_pce* h, int* B, int* X, int* Y, int* TH) {
 
 int rs_pce_run(rs_pce* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx, const double* zf,
                int32_t* out_xyz) {
+    return rs_pce_run_inject(h, n, ox, oy, fidx, zf, 0, nullptr, nullptr, nullptr, nullptr, out_xyz, nullptr, nullptr);
+}
+
+// rs_pce_run is this call without injections and sums: one path for both, which launches the
+// plain instantiation then.
+int rs_pce_run_inject(rs_pce* h, int n, const int32_t* ox, const int32_t* oy, const int32_t* fidx, const double* zf,
+                      int ni, const int32_t* inj_member, const int32_t* inj_step, const double* inj_energy,
+                      const int32_t* inj_loc, int32_t* out_xyz, int32_t* out_inj_xyz, double* out_sums) {
     rs::clear_error();
     RS_CHECK(h, RS_ERR_STATE, "null ensemble handle");
     RS_CHECK(n >= 0, RS_ERR_ARG, "negative step count");
+    RS_CHECK(ni >= 0, RS_ERR_ARG, "negative injection count");
     h->timed = false;
-    if (n == 0) return RS_OK;
-    RS_CHECK(ox && oy && fidx && zf && out_xyz, RS_ERR_ARG, "null argument");
+    if (n == 0 && ni == 0) return RS_OK;
+    RS_CHECK(n == 0 || (ox && oy && fidx && zf && out_xyz), RS_ERR_ARG, "null argument");
+    RS_CHECK(ni == 0 || (inj_member && inj_step && inj_energy && inj_loc && out_inj_xyz), RS_ERR_ARG, "null argument");
     const int B = h->B, TH = h->TH;
     const size_t steps = (size_t)B * n;
     RS_CHECK(steps < (1ull << 31) / 4, RS_ERR_ARG, "%d members x %d steps: too many for one run", B, n);
@@ -437,17 +612,64 @@ int rs_pce_run(rs_pce* h, int n, const int32_t* ox, const int32_t* oy, const int
                           fidx[i], h->nfilters);
             return RS_ERR_ARG;
         }
+    rs::PceInjBad why = rs::PCE_INJ_OK;
+    const int bad = rs::pce_inj_first_bad(B, h->X, h->Y, TH, n, ni, inj_member, inj_step, inj_energy, inj_loc, &why);
+    if (bad >= 0) {
+        const int32_t* l = inj_loc + 3 * (size_t)bad;
+        switch (why) {
+        case rs::PCE_INJ_BAD_MEMBER: rs::set_error("injection %d: member %d outside [0, %d)", bad, inj_member[bad], B); break;
+        case rs::PCE_INJ_BAD_STEP: rs::set_error("injection %d: step %d outside [0, %d]", bad, inj_step[bad], n); break;
+        case rs::PCE_INJ_BAD_ORDER:
+            rs::set_error("injection %d: step %d below an earlier injection's of member %d", bad, inj_step[bad], inj_member[bad]);
+            break;
+        case rs::PCE_INJ_BAD_SAME:
+            rs::set_error("injection %d: same-as %d is no earlier injection of member %d", bad, l[1], inj_member[bad]);
+            break;
+        case rs::PCE_INJ_BAD_ENERGY: rs::set_error("injection %d: energy %g is not a finite float32", bad, inj_energy[bad]); break;
+        default:
+            rs::set_error("injection %d: cell (%d, %d, %d) outside grid (%d, %d, %d)", bad, l[0], l[1], l[2], h->X, h->Y, TH);
+        }
+        return RS_ERR_ARG;
+    }
+    const bool pose = out_sums && n > 0;
+    RS_CHECK(!pose || h->peak_r > 0, RS_ERR_STATE, "sums asked for before rs_pce_set_peak_tables");
     RS_HIP(hipSetDevice(h->device));
     const size_t rb = rs::pce_rec_bytes(TH);
-    const int K = std::min(n, rs::pce_chunk_len(B, TH, h->forced_chunk));
+    const int K = std::max(1, std::min(n, rs::pce_chunk_len(B, TH, h->forced_chunk)));
     const int nchunks = rs::pce_chunk_count(n, K);
+    const size_t inj_recs = rs::pce_align(sizeof(uint32_t) * ((size_t)B + 1));   // the records' place behind the offsets
+    const size_t inj_bytes = ni ? inj_recs + sizeof(rs::PceInjRec) * (size_t)ni : 0;
     // (queued launches of an earlier call may still read the blocks a growth would free)
-    if (steps * rb > h->hCtl.capacity() || (size_t)B * K * rb > h->dCtl[0].capacity() || 3 * steps > h->dOut.capacity())
+    if (steps * rb > h->hCtl.capacity() || (size_t)B * K * rb > h->dCtl[0].capacity() || 3 * steps > h->dOut.capacity() ||
+        inj_bytes > h->dInj.capacity() || (size_t)ni > h->dInjCell.capacity() || (pose && 6 * steps > h->dSums.capacity()))
         RS_HIP(hipStreamSynchronize(h->stream.get()));
     RS_TRY(h->hCtl.reserve(steps * rb, hipHostMallocDefault, "ensemble control"));
-    for (auto& d : h->dCtl) RS_TRY(d.reserve((size_t)B * K * rb, "ensemble control"));
+    if (n > 0)
+        for (auto& d : h->dCtl) RS_TRY(d.reserve((size_t)B * K * rb, "ensemble control"));
     RS_TRY(h->dOut.reserve(3 * steps, "ensemble peaks"));
     RS_TRY(h->hOut.reserve(3 * steps, hipHostMallocDefault, "ensemble peaks"));
+    std::vector<int32_t> grouped((size_t)ni);
+    PceFb fb{};
+    if (ni > 0) {
+        RS_TRY(h->dInj.reserve(inj_bytes, "ensemble injections"));
+        RS_TRY(h->hInj.reserve(inj_bytes, hipHostMallocDefault, "ensemble injections"));
+        RS_TRY(h->dInjCell.reserve(ni, "ensemble injection cells"));
+        RS_TRY(h->hInjCell.reserve(ni, hipHostMallocDefault, "ensemble injection cells"));
+        rs::pce_inj_group(B, h->Y, TH, ni, inj_member, inj_step, inj_energy, inj_loc,
+                          reinterpret_cast<uint32_t*>(h->hInj.get()),
+                          reinterpret_cast<rs::PceInjRec*>(h->hInj.get() + inj_recs), grouped.data());
+        fb.inj_off = reinterpret_cast<const unsigned*>(h->dInj.get());
+        fb.inj_rec = reinterpret_cast<const rs::PceInjRec*>(h->dInj.get() + inj_recs);
+        fb.inj_cell = h->dInjCell.get();
+    }
+    if (pose) {
+        RS_TRY(h->dSums.reserve(6 * steps, "ensemble sums"));
+        RS_TRY(h->hSums.reserve(6 * steps, hipHostMallocDefault, "ensemble sums"));
+        fb.tabs = h->dTabs.get();
+        fb.sums = h->dSums.get();
+        fb.r = h->peak_r;
+    }
+    const PceRunKernel kernel = pce_run_form(ni > 0, pose);
     // the records launch after launch, member-major inside a launch
     unsigned char* rec = h->hCtl.get();
     for (int c = 0; c < nchunks; ++c) {
@@ -459,6 +681,8 @@ int rs_pce_run(rs_pce* h, int n, const int32_t* ox, const int32_t* oy, const int
                 rs::pce_pack(h->X, h->Y, TH, ox + i * TH, oy + i * TH, fidx + i * TH, zf + i * PCE_TAPS, rec);
             }
     }
+    if (ni > 0)
+        RS_HIP(hipMemcpyAsync(h->dInj.get(), h->hInj.get(), inj_bytes, hipMemcpyHostToDevice, h->stream.get()));
     const bool timed = h->timing;
     if (timed) RS_HIP(hipEventRecord(h->ev[0].get(), h->stream.get()));
     size_t off = 0;
@@ -469,17 +693,77 @@ int rs_pce_run(rs_pce* h, int n, const int32_t* ox, const int32_t* oy, const int
         unsigned char* d = h->dCtl[c & 1].get();
         RS_HIP(hipMemcpyAsync(d, h->hCtl.get() + off, bytes, hipMemcpyHostToDevice, h->stream.get()));
         off += bytes;
-        hipLaunchKernelGGL(pce_run_kernel, dim3(B), dim3(PCE_THREADS), h->fit.total, h->stream.get(), h->args,
-                           h->dState.get(), h->dInhib.get(), h->dFilt.get(), d, count, n, first, h->dOut.get());
+        fb.last = c == nchunks - 1;
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(PCE_THREADS), h->fit.total, h->stream.get(), h->args, h->dState.get(),
+                           h->dInhib.get(), h->dFilt.get(), d, count, n, first, h->dOut.get(), fb);
+        RS_HIP(hipGetLastError());
+    }
+    if (n == 0) {   // the injections alone: a launch of no steps
+        fb.last = 1;
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(PCE_THREADS), h->fit.total, h->stream.get(), h->args, h->dState.get(),
+                           h->dInhib.get(), h->dFilt.get(), nullptr, 0, 0, 0, h->dOut.get(), fb);
         RS_HIP(hipGetLastError());
     }
     if (timed) {
         RS_HIP(hipEventRecord(h->ev[1].get(), h->stream.get()));
         h->timed = true;
     }
-    RS_HIP(hipMemcpyAsync(h->hOut.get(), h->dOut.get(), sizeof(int32_t) * 3 * steps, hipMemcpyDeviceToHost, h->stream.get()));
+    if (n > 0)
+        RS_HIP(hipMemcpyAsync(h->hOut.get(), h->dOut.get(), sizeof(int32_t) * 3 * steps, hipMemcpyDeviceToHost, h->stream.get()));
+    if (ni > 0)
+        RS_HIP(hipMemcpyAsync(h->hInjCell.get(), h->dInjCell.get(), sizeof(unsigned) * ni, hipMemcpyDeviceToHost, h->stream.get()));
+    if (pose)
+        RS_HIP(hipMemcpyAsync(h->hSums.get(), h->dSums.get(), sizeof(double) * 6 * steps, hipMemcpyDeviceToHost, h->stream.get()));
     RS_HIP(hipStreamSynchronize(h->stream.get()));
-    std::memcpy(out_xyz, h->hOut.get(), sizeof(int32_t) * 3 * steps);
+    if (n > 0) std::memcpy(out_xyz, h->hOut.get(), sizeof(int32_t) * 3 * steps);
+    if (pose) std::memcpy(out_sums, h->hSums.get(), sizeof(double) * 6 * steps);
+    for (int i = 0; i < ni; ++i) {
+        const unsigned lin = h->hInjCell.get()[grouped[i]];
+        out_inj_xyz[3 * (size_t)i] = (int32_t)(lin / (unsigned)(h->Y * TH));
+        out_inj_xyz[3 * (size_t)i + 1] = (int32_t)(lin / (unsigned)TH % (unsigned)h->Y);
+        out_inj_xyz[3 * (size_t)i + 2] = (int32_t)(lin % (unsigned)TH);
+    }
+    return RS_OK;
+}
+
+int rs_pce_set_peak_tables(rs_pce* h, int r, const double* sc_x, const double* sc_y, const double* sc_th) {
+    rs::clear_error();
+    RS_CHECK(h, RS_ERR_STATE, "null ensemble handle");
+    RS_CHECK(sc_x && sc_y && sc_th, RS_ERR_ARG, "null argument");
+    RS_CHECK(rs::pc_peak_fits(h->X, h->Y, h->TH, r), RS_ERR_ARG,
+             "cells_to_avg %d: expected 1 .. %d and a box of 2r+1 cells that grid (%d, %d, %d) holds", r,
+             rs::PC_PEAK_RMAX, h->X, h->Y, h->TH);
+    RS_CHECK(rs::pce_pose_fits(h->fit, r), RS_ERR_ARG, "the pose scratch of radius %d does not fit the plan", r);
+    RS_HIP(hipSetDevice(h->device));
+    const size_t nx = 2 * (size_t)h->X, ny = 2 * (size_t)h->Y, nth = 2 * (size_t)h->TH;
+    RS_HIP(hipStreamSynchronize(h->stream.get()));   // the staging is free, no queued launch reads the tables
+    RS_TRY(h->dTabs.reserve(nx + ny + nth, "pose weights"));
+    RS_TRY(h->hSums.reserve(std::max(nx + ny + nth, 6 * (size_t)h->B), hipHostMallocDefault, "ensemble sums"));
+    RS_TRY(h->dSums.reserve(6 * (size_t)h->B, "ensemble sums"));
+    double* st = h->hSums.get();
+    std::memcpy(st, sc_x, sizeof(double) * nx);
+    std::memcpy(st + nx, sc_y, sizeof(double) * ny);
+    std::memcpy(st + nx + ny, sc_th, sizeof(double) * nth);
+    RS_HIP(hipMemcpyAsync(h->dTabs.get(), st, sizeof(double) * (nx + ny + nth), hipMemcpyHostToDevice, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
+    h->peak_r = r;
+    return RS_OK;
+}
+
+int rs_pce_get_peak(rs_pce* h, int32_t* out_xyz, double* out_sums) {
+    rs::clear_error();
+    RS_CHECK(h, RS_ERR_STATE, "null ensemble handle");
+    RS_CHECK(out_xyz && out_sums, RS_ERR_ARG, "null argument");
+    RS_CHECK(h->peak_r > 0, RS_ERR_STATE, "rs_pce_get_peak before rs_pce_set_peak_tables");
+    RS_HIP(hipSetDevice(h->device));
+    hipLaunchKernelGGL(pce_peak_kernel, dim3(h->B), dim3(PCE_ARGMAX_THREADS), 0, h->stream.get(), h->dState.get(),
+                       (int)h->N, h->X, h->Y, h->TH, h->peak_r, h->dTabs.get(), h->dOut.get(), h->dSums.get());
+    RS_HIP(hipGetLastError());
+    RS_HIP(hipMemcpyAsync(h->hOut.get(), h->dOut.get(), sizeof(int32_t) * 3 * h->B, hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipMemcpyAsync(h->hSums.get(), h->dSums.get(), sizeof(double) * 6 * h->B, hipMemcpyDeviceToHost, h->stream.get()));
+    RS_HIP(hipStreamSynchronize(h->stream.get()));
+    std::memcpy(out_xyz, h->hOut.get(), sizeof(int32_t) * 3 * h->B);
+    std::memcpy(out_sums, h->hSums.get(), sizeof(double) * 6 * h->B);
     return RS_OK;
 }
 

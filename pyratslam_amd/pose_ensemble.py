@@ -6,6 +6,11 @@ section 35).
     ens.inject(1.0, (10, 10, 18))
     peaks = ens.run(od)            # od (B, n, 2) or (n, 2) -> int32 (B, n, 3)
 
+With ``cells_to_avg`` the ensemble also gives the sub-cell pose (``get_pc_pose``,
+``run(od, poses=True)``), and ``run(od, injections=[(member, step, energy, loc), ...])`` applies
+view-template feedback inside the batch: both stay in LDS, neither adds a
+launch or a host round trip.
+
 A member computes what a float32 ``PoseCellNetwork`` of that shape computes (within 1e-5 of
 the float64 oracle, the same peaks), whatever the size of the ensemble, its place in it and
 the way a run is cut into launches.  The per-step control is the library's
@@ -21,24 +26,34 @@ import numpy as np
 
 from . import _lib
 from . import filters as F
+from . import pc_peak
 from .posecell_network import grid_cell, pc_params
+
+
+F32_ROUNDS_TO_INF = float.fromhex('0x1.ffffffp127')   # the midpoint of float32's largest value and 2^128
 
 
 class PoseCellEnsemble(_lib.HandleOwner):
     """B float32 pose-cell networks of shape (X, Y, TH) on one GPU.
 
     ``global_inhibition``: None (the reference's 0.2), a scalar, or one value per member.
+    ``cells_to_avg``: None, or the radius (1 .. 3) of the wrapped box the sub-cell pose is
+    averaged over (``get_pc_pose``, ``run(poses=True)``); its weights are uploaded at create.
     A new ensemble is all zeros.  Shapes whose LDS plan does not fit a compute unit, a
-    dimension below 7 and ``precision='float64'`` raise ValueError before any device call.
+    dimension below 7, ``precision='float64'`` and a ``cells_to_avg`` whose box the grid does
+    not hold raise ValueError before any device call.
     """
 
-    def __init__(self, members, shape, global_inhibition=None, device=0, precision='float32'):
+    AT_PEAK = 'peak'   # run(injections=...): the member's first maximum at that point
+
+    def __init__(self, members, shape, global_inhibition=None, device=0, precision='float32', cells_to_avg=None):
         if len(shape) != 3:
             raise TypeError('PoseCellEnsemble shape must be (X, Y, TH), got %r' % (shape,))
         self.shape = tuple(int(s) for s in shape)
         self._b = int(members)
         self.device = int(device)
         self.max_pc = None
+        self.last_sums = None
         self._mutex = threading.Lock()
         if precision not in ('float32', np.float32):
             raise ValueError('PoseCellEnsemble is float32 only, got precision %r' % (precision,))
@@ -53,6 +68,7 @@ class PoseCellEnsemble(_lib.HandleOwner):
         self.global_inhibition = inhib
         lib = _lib.load()
         _lib.check(lib.rs_pce_fit(*self.shape, None))     # ValueError with the bytes needed
+        self.cells_to_avg = None if cells_to_avg is None else pc_peak.check_radius(self.shape, cells_to_avg)
         self._lib = _lib.require_device()
         self.filter_table = F.FilterTable()
         self._table = np.ascontiguousarray(self.filter_table.filters, dtype=np.float64)
@@ -60,6 +76,10 @@ class PoseCellEnsemble(_lib.HandleOwner):
         params = pc_params(_lib.RS_PREC_F32, F.PC_GLOBAL_INHIB, self._table)
         self._h = _lib.Handle.create(self._lib, 'rs_pce_create', 'rs_pce_destroy', self._b, *self.shape,
                                      ctypes.byref(params), _lib.ptr(inhib, ctypes.c_double), self.device)
+        if self.cells_to_avg is not None:
+            tabs = pc_peak.peak_tables(self.shape)
+            _lib.check(self._lib.rs_pce_set_peak_tables(self._h, self.cells_to_avg,
+                                                        *(_lib.ptr(t, ctypes.c_double) for t in tabs)))
 
     @staticmethod
     def fits(shape):
@@ -115,6 +135,29 @@ class PoseCellEnsemble(_lib.HandleOwner):
             _lib.check(self._lib.rs_pce_get_max(self._h, _lib.ptr(out, ctypes.c_int32)))
         return out
 
+    def _need_tables(self):
+        if self.cells_to_avg is None:
+            raise ValueError('the sub-cell pose needs PoseCellEnsemble(..., cells_to_avg=r)')
+
+    def _poses(self, cells, sums):
+        flat = [pc_peak.pose_from_sums(s, c, self.shape) for c, s in zip(cells.reshape(-1, 3), sums.reshape(-1, 6))]
+        return np.array(flat, dtype=np.float64).reshape(cells.shape)
+
+    def get_pc_peak(self):
+        """``(cells, sums)``: each member's stored first maximum, int32 (B, 3), and the rule's
+        six sums of the box round it, float64 (B, 6) (rs_pce_get_peak)."""
+        self._need_tables()
+        out = np.empty((self._b, 3), dtype=np.int32)
+        sums = np.empty((self._b, 6), dtype=np.float64)
+        with self._mutex:
+            _lib.check(self._lib.rs_pce_get_peak(self._h, _lib.ptr(out, ctypes.c_int32), _lib.ptr(sums, ctypes.c_double)))
+        return out, sums
+
+    def get_pc_pose(self):
+        """Each member's sub-cell pose ``(x, y, th)`` in cell units, float64 (B, 3): the circular
+        centroid of the activity within ``cells_to_avg`` cells of its first maximum."""
+        return self._poses(*self.get_pc_peak())
+
     # -- stepping ---------------------------------------------------------------
     def _control(self, od, shared):
         """Control arrays of ``od`` (members, n, 2): the library's rs_pc_odom_control, with
@@ -149,13 +192,73 @@ class PoseCellEnsemble(_lib.HandleOwner):
             _lib.check(int(status[i]))
         return ox, oy, fidx, zf
 
-    def run(self, odometry):
+    @classmethod
+    def injection_arrays(cls, members, shape, n, injections):
+        """``injections`` of ``run`` as rs_pce_run_inject's arrays ``(member, step, energy, loc)``,
+        a ``None`` member expanded to one entry per member (ValueError / IndexError as
+        ``PoseCellNetwork.run`` words them; no device needed)."""
+        inj = [tuple(e) for e in injections]
+        first = np.cumsum([0] + [members if e[0] is None else 1 for e in inj])   # entry j's first expanded index
+        member = np.empty(first[-1], dtype=np.int32)
+        step = np.empty(first[-1], dtype=np.int32)
+        energy = np.empty(first[-1], dtype=np.float64)
+        loc = np.zeros((first[-1], 3), dtype=np.int32)
+        last = np.zeros(members, dtype=np.int64)   # each member's latest step so far
+        everyone = np.arange(members)
+        for j, (who, st, e, where) in enumerate(inj):
+            if who is not None and (int(who) != who or not 0 <= who < members):
+                raise IndexError('injection %d: member %r outside the ensemble of %d' % (j, who, members))
+            if int(st) != st or not 0 <= st <= n:
+                raise ValueError('injection %d: step %r outside 0 .. %d' % (j, st, n))
+            if not abs(float(e)) < F32_ROUNDS_TO_INF:
+                raise ValueError('injection %d: energy %r is not a finite float32' % (j, e))
+            same = None
+            if isinstance(where, str) and where == cls.AT_PEAK:
+                cell = (_lib.RS_PC_INJ_AT_PEAK, 0, 0)
+            elif isinstance(where, tuple) and len(where) == 2 and where[0] == 'same':
+                same = where[1]
+                if int(same) != same or not 0 <= same < j:
+                    raise ValueError("injection %d: ('same', %r) is no earlier injection" % (j, same))
+            else:
+                cell = grid_cell(where, shape, 'injection %d:' % j, 'an injection location is a tuple (x, y, th)')
+            ms = everyone if who is None else everyone[int(who):int(who) + 1]   # (an array at a time: B may be large)
+            late = ms[last[ms] > st]
+            if late.size:
+                raise ValueError('injection %d: step %d after step %d of member %d' % (j, st, last[late[0]], late[0]))
+            last[ms] = st
+            at = slice(first[j], first[j + 1])
+            member[at], step[at], energy[at] = ms, st, float(e)
+            if same is None:
+                loc[at] = cell
+            else:
+                other = ms if inj[same][0] is None else ms[ms != inj[same][0]]
+                if inj[same][0] is not None and other.size:
+                    raise ValueError("injection %d: ('same', %d) is an injection of another member" % (j, same))
+                loc[at, 0] = _lib.RS_PC_INJ_SAME_AS
+                loc[at, 1] = first[same] + (ms if inj[same][0] is None else 0)
+        return member, step, energy, loc
+
+    def run(self, odometry, poses=False, injections=None):
         """``n`` updates of every member with one host round trip.
 
         ``odometry``: (B, n, 2) rows (vtrans, vrot) per member, or (n, 2) for all members
         alike.  Returns int32 (B, n, 3), each step's max_pc; the last step's are kept in
         ``max_pc``.  A LUT miss in any member's step raises KeyError (naming member and
-        step) and non-finite odometry ValueError, both before anything has run."""
+        step) and non-finite odometry ValueError, both before anything has run.
+
+        ``poses=True`` (needs ``cells_to_avg``): also each step's sub-cell pose, float64
+        (B, n, 3), taken on the GPU behind the step; the raw sums stay in ``last_sums``.
+
+        ``injections``: a sequence of ``(member, step, energy, loc)``; ``member`` an index, or
+        None for every member (one entry per member, in member order); the steps in ``0 .. n``
+        and non-decreasing within each member.  An injection is applied in front of step
+        ``step`` (``n``: behind the last one) exactly as ``inject(energy, cell, members=[m])``
+        between two ``run`` calls would be.  ``loc`` is a tuple ``(x, y, th)`` (``inject``'s
+        rules), ``PoseCellEnsemble.AT_PEAK`` (what ``get_pc_max()`` would return for the member
+        at that point) or ``('same', k)``, k an earlier entry of this list for the same member
+        (of a None entry: the same member's copy).  The resolved cells come back as an int32
+        array, a row per expanded entry.  Returns ``peaks``, then ``poses`` if asked for, then
+        the resolved cells if ``injections`` was given."""
         od = np.asarray(odometry, dtype=np.float64)
         if od.ndim == 2 and od.shape[1] == 2:
             shared = True
@@ -167,19 +270,40 @@ class PoseCellEnsemble(_lib.HandleOwner):
         if not np.isfinite(od).all():
             raise ValueError('odometry must be finite')
         n = od.shape[1]
+        if poses:
+            self._need_tables()
+        inj = None if injections is None else self.injection_arrays(self._b, self.shape, n, injections)
+        ni = 0 if inj is None else len(inj[0])
         out = np.empty((self._b, n, 3), dtype=np.int32)
-        if n == 0:
-            return out
-        ctl = self._control(od, shared)
-        if shared:
-            ctl = [np.ascontiguousarray(np.broadcast_to(a[None], (self._b,) + a.shape)) for a in ctl]
+        sums = np.empty((self._b, n, 6), dtype=np.float64) if poses else None
+        cells = np.empty((ni, 3), dtype=np.int32)
+        i32, f64 = ctypes.c_int32, ctypes.c_double
+        ctl = [None] * 4
+        if n > 0:
+            ctl = self._control(od, shared)
+            if shared:
+                ctl = [np.ascontiguousarray(np.broadcast_to(a[None], (self._b,) + a.shape)) for a in ctl]
         ox, oy, fidx, zf = ctl
-        i32 = ctypes.c_int32
-        with self._mutex:
-            _lib.check(self._lib.rs_pce_run(self._h, n, _lib.ptr(ox, i32), _lib.ptr(oy, i32), _lib.ptr(fidx, i32),
-                                            _lib.ptr(zf, ctypes.c_double), _lib.ptr(out, i32)))
-            self.max_pc = out[:, -1].copy()
-        return out
+        if n > 0 or ni > 0:
+            with self._mutex:
+                if inj is None and not poses:
+                    _lib.check(self._lib.rs_pce_run(self._h, n, _lib.ptr(ox, i32), _lib.ptr(oy, i32), _lib.ptr(fidx, i32),
+                                                    _lib.ptr(zf, f64), _lib.ptr(out, i32)))
+                else:
+                    member, step, energy, loc = inj if ni else (None,) * 4
+                    _lib.check(self._lib.rs_pce_run_inject(
+                        self._h, n, _lib.ptr(ox, i32), _lib.ptr(oy, i32), _lib.ptr(fidx, i32), _lib.ptr(zf, f64), ni,
+                        _lib.ptr(member, i32), _lib.ptr(step, i32), _lib.ptr(energy, f64), _lib.ptr(loc, i32),
+                        _lib.ptr(out, i32), _lib.ptr(cells, i32), _lib.ptr(sums, f64)))
+                if n > 0:
+                    self.max_pc = out[:, -1].copy()
+        result = (out,)
+        if poses:
+            self.last_sums = sums
+            result += (self._poses(out, sums),)
+        if inj is not None:
+            result += (cells,)
+        return result[0] if len(result) == 1 else result
 
     def set_timing(self, enable=True):
         """HIP events around the launches of every later run() (device_ms)."""
